@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training samples/sec of the MFM_KL_EF step (MOSI shape, T=20, 3 modalities).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,21 @@ Adam, train mode with the canonical dropouts.  Workload (BASELINE.json configs[1
 MOSI sizes (mfm_mosi.py:1239-1286), B=32 per GPU, T=20 (configs/mosi.json seqlength), D=325,
 fp32.  N>1 is weak scaling: every rank processes its own B=32 shard.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, timed inside the timed region by
-two HIP events that carry the dispatch's own begin / end timestamps (hipExtLaunchKernelGGL on the
-launch stream: what rocprofv3 --kernel-trace reports, no bracket overhead to subtract);
-`cpu_baseline` times the CPU oracle (a restatement of the reference's PyTorch-CPU path) on this host
-for a bounded number of steps.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value` samples/s, `ms_per_step`).  --full adds what takes work of its own: `roofline` for the dominant
+kernel (found by an untimed breakdown pass, then timed inside the timed region by two HIP events that
+carry the dispatch's own begin / end timestamps: hipExtLaunchKernelGGL on the launch stream, what
+rocprofv3 --kernel-trace reports, no bracket overhead to subtract); `cpu_baseline`, the CPU oracle (a
+restatement of the reference's PyTorch-CPU path) on this host for a bounded number of steps; and with
+N > 1 the replica check, the collectives' own cost and the per-rank diagnosis.
+
+--dump-outputs DIR writes what the last timed step computed as float32 .npy files: `losses` (the loss
+slots the step returns), `params` (the parameters after its Adam update) and `grads` (its gradient), the
+last two as the named tensors in state_dict order, concatenated: at most ~6 MB on every shape.  Weights,
+data and seeds are fixed, and the last timed step starts again from the state set up before the warm-up
+(the loaded weights, zero Adam moments, step 0; three device copies inside the timed region), so with the
+same arguments its inputs, and its outputs up to the rounding of the float atomics, are the same on every
+run, however many steps came before.
 """
 import argparse
 import json
@@ -23,11 +33,13 @@ import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-FP32_MATRIX_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 peak
-BF16_MATRIX_PEAK_TFLOPS = 2500.0  # same guide: dense bf16 MFMA peak (2:1-sparsity figures are never used)
+FP32_MATRIX_PEAK_TFLOPS = 157.3   # MI355X: v_mfma_f32_16x16x4_f32 peak
+BF16_MATRIX_PEAK_TFLOPS = 2500.0  # MI355X: dense bf16 MFMA peak (2:1-sparsity figures are never used)
 HBM_PEAK_GBS = 8000.0
 MODEL_NAME = {"kl_ef": "MFM_KL_EF", "kl": "MFM_KL (MFN encoder, KLD)", "mmd": "MFM (MFN encoder, MMD)"}
 
@@ -46,9 +58,18 @@ def main():
     ap.add_argument("--model", default="kl_ef", choices=["kl_ef", "kl", "mmd"],
                     help="kl_ef = MFM_KL_EF (the headline workload); kl / mmd = MFM_KL / MFM with the Memory Fusion Network "
                          "encoder, the classes train_mfm picks by config['type'] (reference mfm_mosi.py:398-401)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--breakdown", action="store_true", help="also print a per-kernel time table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline of the dominant kernel, CPU baseline, and "
+                         "with N > 1 the replica check, the collectives' own cost and the per-rank diagnosis")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's losses, parameters and gradients as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--breakdown", action="store_true", help="with --full: also print a per-kernel time table to stderr")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full (it reads the untimed breakdown pass)")
 
     import torch
     from factorized_amd import configs as C
@@ -88,6 +109,19 @@ def main():
     e = engine.MFMEngine(cfgs, device="cuda:%d" % local_rank, precision=args.dtype, variant=args.model)
     e.load_weights(synth.make_weights(e.layout.shapes, seed=1234))
     train.broadcast_params(e, world)
+    torch.manual_seed(1234)                       # the MMD variant draws its N(0,1) sample per step from torch's generator
+    # --dump-outputs: the last timed step starts again from this state (the loaded weights, zero Adam moments, step 0).  The
+    # kernels' float atomics make a step reproducible only to rounding, and over thousands of steps two runs drift apart far
+    # beyond it; from this state the dumped step's inputs are the same on every run.
+    start_state = [t.clone() for t in (e.params, e.adam_m, e.adam_v)] if args.dump_outputs else None
+
+    def restart():
+        for t, s in zip((e.params, e.adam_m, e.adam_v), start_state):
+            t.copy_(s)
+        e.step_count = 0
+        for g in e.group_steps:
+            e.group_steps[g] = 0
+
     n_samples = max(1280, B * world * 8)          # MOSI-scale split (1,284 train utterances)
     data = train.DeviceDataset(cfg, n_samples, T, B, e.device, seed=11)
     my_batches = train.shard_batches(data.nb, rank, world)
@@ -96,9 +130,11 @@ def main():
     stepper = train.DataParallelStep(e, world, lr=1e-3, allreduce=allreduce, rank=rank)
 
     def run(n, first=0):
+        losses = None
         for i in range(n):
             x, y = data.batch(my_batches[(first + i) % len(my_batches)])
-            stepper.step(x, y)
+            losses = stepper.step(x, y)
+        return losses
 
     def barrier():
         if world > 1:
@@ -106,7 +142,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up (untimed) + a per-kernel breakdown pass (untimed) to find the dominant kernel
+    # ---- warm-up (untimed); --full: a per-kernel breakdown pass (untimed) to find the dominant kernel
     dbg = os.environ.get("MFM_BENCH_DEBUG")
     if dbg:
         sys.stderr.write("setup done, warmup...\n"); sys.stderr.flush()
@@ -114,31 +150,40 @@ def main():
     barrier()
     if dbg:
         sys.stderr.write("warmup done\n"); sys.stderr.flush()
-    e.set_timing(T, B, (1 << 30) - 1)
-    run(10, args.warmup)
-    barrier()
-    table = e.collect_timing(T, B)
-    dom = max(table, key=lambda k: table[k]["ms"])
-    if args.breakdown and rank == 0:
-        tot = sum(v["ms"] for v in table.values()) / 10
-        for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms"]):
-            if v["count"]:
-                sys.stderr.write("%-14s %8.2f us/launch  %5.1f%%\n" % (k, 1e3 * v["ms"] / v["count"],
-                                                                      100 * v["ms"] / 10 / tot))
-    # inside the timed region the dominant kernel is timed on every 8th step only (its two events are extra work for the
-    # runtime on the steps they are active on)
-    TIMING_EVERY = max(1, min(8, args.steps // 4))
-    e.set_timing(T, B, 1 << table[dom]["kid"], every=TIMING_EVERY)
+    first = args.warmup                                  # batch index of the first timed step
+    if args.full:
+        e.set_timing(T, B, (1 << 30) - 1)
+        run(10, args.warmup)
+        barrier()
+        first += 10
+        table = e.collect_timing(T, B)
+        dom = max(table, key=lambda k: table[k]["ms"])
+        if args.breakdown and rank == 0:
+            tot = sum(v["ms"] for v in table.values()) / 10
+            for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms"]):
+                if v["count"]:
+                    sys.stderr.write("%-14s %8.2f us/launch  %5.1f%%\n" % (k, 1e3 * v["ms"] / v["count"],
+                                                                          100 * v["ms"] / 10 / tot))
+        # inside the timed region the dominant kernel is timed on every 8th step only (its two events are extra work for the
+        # runtime on the steps they are active on)
+        TIMING_EVERY = max(1, min(8, args.steps // 4))
+        e.set_timing(T, B, 1 << table[dom]["kid"], every=TIMING_EVERY)
 
     # ---- timed region: EXACTLY K steps, barrier + synchronize on both sides, max over ranks
     rank_dt = [0.0]
+    last_losses = [None]                                 # what the last timed step returned
 
     def timed_region():
         barrier()
         if world > 1 and hasattr(allreduce, "wait_stats"):
             allreduce.wait_stats(reset=True)
         t0 = time.perf_counter()
-        run(args.steps, args.warmup + 10)
+        if start_state is None:
+            last_losses[0] = run(args.steps, first)
+        else:
+            run(args.steps - 1, first)
+            restart()
+            last_losses[0] = run(1, first + args.steps - 1)
         torch.cuda.synchronize()
         rank_dt[0] = time.perf_counter() - t0          # this rank's own K steps (before the closing barrier)
         barrier()
@@ -167,10 +212,11 @@ def main():
             sys.stderr.write("[bench] an in-launch hand-over timed out during the run: repeating the timed region on separate launches\n")
         if world > 1:
             train.broadcast_params(e, world)
-        e.collect_timing(T, B)
+        if args.full:
+            e.collect_timing(T, B)
         dt = timed_region()
-    in_sync = None
-    flag_wait = allreduce.wait_stats(reset=True) if (world > 1 and hasattr(allreduce, "wait_stats")) else None
+    in_sync = coll_us = exposed_us = per_rank = None
+    flag_wait = allreduce.wait_stats(reset=True) if (args.full and world > 1 and hasattr(allreduce, "wait_stats")) else None
     if world > 1:
         import torch.distributed as dist
         # a P2P wait that gave up on any rank invalidates the measurement: switch every rank to RCCL,
@@ -181,9 +227,21 @@ def main():
             allreduce.close()
             allreduce = stepper.allreduce = comm.TorchAllReduce()
             train.broadcast_params(e, world)
-            e.collect_timing(T, B)
+            if args.full:
+                e.collect_timing(T, B)
             dt = timed_region()
             flag_wait = None
+    if args.dump_outputs and rank == 0:
+        # before the --full measurements below: they run steps of their own.  params / grads: the named tensors in state_dict
+        # order, concatenated (independent of the flat buffer's physical placement and padding)
+        def named(buf):
+            return np.concatenate([v.numpy().reshape(-1) for v in e.layout.views(buf.detach().cpu()).values()])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("losses", last_losses[0].detach().float().cpu().numpy()), ("params", named(e.params)),
+                        ("grads", named(e.grads))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    if args.full and world > 1:
+        import torch.distributed as dist
         # replicas must still hold identical parameters (same reduced gradients on every rank)
         lo, hi = e.params.clone(), e.params.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -209,8 +267,6 @@ def main():
             tt = torch.tensor([coll_rank[name]], dtype=torch.float64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             coll_us[name] = round(float(tt.item()), 1)
-    exposed_us = None
-    if world > 1:
         # what the exchange ADDS to a step: the same K steps without it (fwd + bwd + Adam on the local gradients), timed the
         # same way.  Last: the replicas diverge from here on.
         def run_local(n, first=0):
@@ -247,31 +303,13 @@ def main():
                 "handover_failures": e.handover_failures}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
-    timed = e.collect_timing(T, B)[dom]
-    e.set_timing(T, B, 0)
+    if args.full:
+        timed = e.collect_timing(T, B)[dom]
+        e.set_timing(T, B, 0)
 
     if rank == 0:
         ms = 1e3 * dt / args.steps
         value = B * world * args.steps / dt
-        # the dominant kernel's own dispatch timestamps (csrc/common.h, MFM_LAUNCH_TIMED): nothing to subtract.  Round 5
-        # subtracted the cost of an empty event bracket from a bracket around the launch and landed below rocprofv3's fastest
-        # sample; the bracket's cost is still reported (empty_bracket_us) for kernels that share a timer with other launches
-        k_ms = timed["ms"] / max(timed["count"], 1)
-        ev_ms = e.bracket_overhead_ms()
-        k_flops = timed["flops"]
-        achieved = (k_flops / (k_ms * 1e-3)) / 1e12 if k_ms > 0 and k_flops > 0 else 0.0
-        work = e.work_per_step(T, B)
-        peak = FP32_MATRIX_PEAK_TFLOPS if args.dtype == "fp32" else BF16_MATRIX_PEAK_TFLOPS
-        # HBM bytes per launch of the dominant kernel: measured in a SEPARATE rocprofv3 --pmc pass of this
-        # command (scripts/profile_round6.sh -> profiles/r06_traffic_B*.json); only valid for the workload it
-        # was measured on, otherwise null.
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "r06_traffic_B%d%s.json" % (B, "" if args.dtype == "fp32" else "_bf16"))
-        if os.path.exists(tpath) and args.shape == "mosi" and T == 20 and args.model == "kl_ef":
-            try:
-                traffic = json.load(open(tpath)).get(dom, {}).get("total_bytes")
-            except Exception:
-                traffic = None
         out = {
             "metric": "training samples/sec (MOSI-shape, T=%d, 3 modalities)" % T,
             "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -286,24 +324,46 @@ def main():
                        "handover_failures": e.handover_failures, "role_workgroups": bool(e.handover),
                        "collective": allreduce.name if allreduce is not None else None,
                        "replicas_in_sync": in_sync,
-                       "collective_us_per_call": coll_us if world > 1 else None,
+                       "collective_us_per_call": coll_us,
                        "exposed_collective_us": exposed_us,
-                       "per_rank": per_rank if world > 1 else None},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 4),
-                         "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 6), "traffic": traffic,
-                         "note": ("fp32 matrix peak == fp32 vector peak on gfx950 (157.3 TF); at B<=512 the "
-                                  "recurrent products run on the VALU small-tile kernels, above on the MFMA")
-                         if args.dtype == "fp32" else
-                         ("dense bf16 MFMA peak; GEMMs and, from B=128, the recurrences feed v_mfma_f32_16x16x32_bf16 (below: fp32 one-row "
-                          "VALU recurrences; decoder fc1 up to 5120 rows: bf16-rounded operands on the fp32 MFMA)"),
-                         "kernel_us": round(1e3 * k_ms, 2), "kernel_time_source": "dispatch begin/end timestamps (hipExtLaunchKernelGGL events)",
-                         "empty_bracket_us": round(1e3 * ev_ms, 2), "kernel_launches_timed": timed["count"],
-                         "timed_every_nth_step": TIMING_EVERY, "kernel_flops": k_flops,
-                         "step_flops": work["flops"], "step_bytes": work["bytes"],
-                         "step_tflops": round(work["flops"] / (ms * 1e-3) / 1e12, 4)},
+                       "per_rank": per_rank},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            # the dominant kernel's own dispatch timestamps (csrc/common.h, MFM_LAUNCH_TIMED): nothing to subtract.  Round 5
+            # subtracted the cost of an empty event bracket from a bracket around the launch and landed below rocprofv3's
+            # fastest sample; the bracket's cost is still reported (empty_bracket_us) for kernels that share a timer with
+            # other launches
+            k_ms = timed["ms"] / max(timed["count"], 1)
+            ev_ms = e.bracket_overhead_ms()
+            k_flops = timed["flops"]
+            achieved = (k_flops / (k_ms * 1e-3)) / 1e12 if k_ms > 0 and k_flops > 0 else 0.0
+            work = e.work_per_step(T, B)
+            peak = FP32_MATRIX_PEAK_TFLOPS if args.dtype == "fp32" else BF16_MATRIX_PEAK_TFLOPS
+            # HBM bytes per launch of the dominant kernel: measured in a SEPARATE rocprofv3 --pmc pass of this
+            # command (scripts/profile_round6.sh -> profiles/r06_traffic_B*.json); only valid for the workload it
+            # was measured on, otherwise null.
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "r06_traffic_B%d%s.json" % (B, "" if args.dtype == "fp32" else "_bf16"))
+            if os.path.exists(tpath) and args.shape == "mosi" and T == 20 and args.model == "kl_ef":
+                try:
+                    traffic = json.load(open(tpath)).get(dom, {}).get("total_bytes")
+                except Exception:
+                    traffic = None
+            out["roofline"] = {
+                "bound": "mfma", "kernel": dom, "achieved": round(achieved, 4),
+                "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 6), "traffic": traffic,
+                "note": ("fp32 matrix peak == fp32 vector peak on gfx950 (157.3 TF); at B<=512 the "
+                         "recurrent products run on the VALU small-tile kernels, above on the MFMA")
+                if args.dtype == "fp32" else
+                ("dense bf16 MFMA peak; GEMMs and, from B=128, the recurrences feed v_mfma_f32_16x16x32_bf16 (below: fp32 one-row "
+                 "VALU recurrences; decoder fc1 up to 5120 rows: bf16-rounded operands on the fp32 MFMA)"),
+                "kernel_us": round(1e3 * k_ms, 2), "kernel_time_source": "dispatch begin/end timestamps (hipExtLaunchKernelGGL events)",
+                "empty_bracket_us": round(1e3 * ev_ms, 2), "kernel_launches_timed": timed["count"],
+                "timed_every_nth_step": TIMING_EVERY, "kernel_flops": k_flops,
+                "step_flops": work["flops"], "step_bytes": work["bytes"],
+                "step_tflops": round(work["flops"] / (ms * 1e-3) / 1e12, 4)}
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import mfm_oracle as O
             import torch as _t
             cores = os.cpu_count() or 1

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-prof_r05}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-NB="--no-cpu-baseline"
+NB="--full --no-cpu-baseline"
 PMC_SQ="SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS"
 d=h32
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/$d -o ktrace -- python $R/bench.py --steps 200 --warmup 10 $NB > $O/bench_under_rocprof_$d.json 2>/dev/null
@@ -30,7 +30,7 @@ done
 python scripts/make_traffic_json.py $(ls $O/h32/pmc_fetch*.db | head -1) $(ls $O/h32/pmc_write*.db | head -1) > $O/traffic_B32.json
 python scripts/roofline_table.py $O/h32 > $O/roofline_table_h32.txt 2>&1
 python scripts/roofline_table.py $O/l_bf16 > $O/roofline_table_l_bf16.txt 2>&1
-python bench.py > $O/bench_B32.json 2> $O/bench_B32.err
+python bench.py --full > $O/bench_B32.json 2> $O/bench_B32.err
 python bench.py --steps 400 --warmup 40 $NB > $O/bench_B32_400.json 2>/dev/null
 python bench.py --dtype bf16 --steps 400 --warmup 40 $NB > $O/bench_B32_bf16.json 2>/dev/null
 for m in kl mmd; do python bench.py --model $m --steps 400 --warmup 40 $NB > $O/bench_B32_$m.json 2>/dev/null; done

@@ -275,7 +275,7 @@ def test_bench_ranks_on_one_device_stay_in_sync(n, extra):
     env.update(MFM_BENCH_ONE_DEVICE="1", MFM_P2P_TIMEOUT_MS="20000", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps",
-           "20", "--warmup", "5", "--no-cpu-baseline"] + extra
+           "20", "--warmup", "5", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -289,6 +289,27 @@ def test_bench_ranks_on_one_device_stay_in_sync(n, extra):
     # the exchange's cost inside a step: the timed K steps minus the same K steps on local gradients (a float; on one
     # shared device it also contains the ranks' queueing behind each other, so only its presence is checked here)
     assert isinstance(out["config"]["exposed_collective_us"], float)
+
+
+def test_bench_plain_run_on_ranks(tmp_path):
+    """The same command without --full: the headline only (no replica check, no per-rank diagnosis), and --dump-outputs
+    written once, by rank 0."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = dict(os.environ)
+    env.update(MFM_BENCH_ONE_DEVICE="1", MFM_P2P_TIMEOUT_MS="20000", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
+           "20", "--warmup", "5", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 20 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert "roofline" not in out and out["config"]["replicas_in_sync"] is None and out["config"]["per_rank"] is None
+    assert sorted(os.listdir(tmp_path)) == ["grads.npy", "losses.npy", "params.npy"]
+    assert np.isfinite(np.load(tmp_path / "params.npy")).all()
 
 
 def _nccl_world1(q):
