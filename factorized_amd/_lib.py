@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("MFM_LIB_PATH") or os.path.join(_HERE, "libmfm_hip.so"
 MFM_KLEF_NPARAM = 78
 MFM_LOSS_SLOTS = 8
 MFM_MAX_SEQ = 6
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class MfmError(RuntimeError):
@@ -132,7 +132,6 @@ _SIGS = {
                                   C.POINTER(C.c_void_p)]),
     "mfm_plan_destroy": (None, [C.c_void_p]),
     "mfm_plan_workspace_bytes": (C.c_int64, [C.c_void_p]),
-    "mfm_plan_debug_offset": (C.c_int64, [C.c_void_p]),
     "mfm_plan_init_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mfm_plan_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

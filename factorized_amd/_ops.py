@@ -2,7 +2,6 @@
 grouped forms, Linear layers on the HIP GEMM (single / grouped), the MFN memory recurrence, the MMD kernel.  `mfm_model.py` builds the
 reference's classes from them; the ablation / missing-modality classes (`mfm_extra.py`) are compositions of exactly these."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -267,7 +266,7 @@ class _DecoderGroupFn(torch.autograd.Function):
 
 def decoder_group(pairs, t):
     """[(hT, decoderLSTM), ...] -> [x_hat, ...] in shared launches (all on the same batch size)."""
-    if os.environ.get("MFM_NO_SEQ_GROUP") or len({p[0].shape[0] for p in pairs}) != 1:
+    if len({p[0].shape[0] for p in pairs}) != 1:
         return [m.forward(hT, t) for hT, m in pairs]
     args = []
     for hT, m in pairs:
@@ -455,8 +454,6 @@ class _GroupLinearFn(torch.autograd.Function):
 
 def linear_group(pairs):
     """[(x, HipLinear), ...] -> [y, ...] in one launch."""
-    if os.environ.get("MFM_NO_GROUP_LINEAR"):          # A/B timing only
-        return [l(x) for x, l in pairs]
     n = len(pairs)
     xs = [x for x, _ in pairs]
     return list(_GroupLinearFn.apply(n, *xs, *[l.weight for _, l in pairs], *[l.bias for _, l in pairs]))

@@ -20,6 +20,7 @@ int hip_fail(hipError_t e, const char* what);
 // changed since -- no getenv on the launch path, and two plans of one process can run with different switches.  Outside a
 // plan call (the granular C entry points: GEMM, recurrences, ...) it reads the environment.
 const char* opt_get(const char* name);
+bool opt_disabled(const char* name);           // the switch is set to 0 (switches that turn a default form off)
 struct OptTable;                               // name -> value
 OptTable* opt_table_from_env();                // snapshot of every MFM_* variable
 void opt_table_set(OptTable* t, const char* name, const char* value /* null: remove */);

@@ -215,11 +215,9 @@ int dec_fc1_launch(DecFc1Launch& L, bool dhs_zeroed, hipStream_t stream) {
     // partial dH tiles of a row tile's column groups are added with memory-side atomics, and those, not the products, end the
     // launch: the single-group tiles of the narrow decoders leave 2.4 us after their first product, the four-group tiles 3.9
     // (median) to 5.4 us.  Step time against fragments per group: 3 0.1484, 4 0.1467, 5 0.1454, 7 0.1453, 8 0.1442 ms; ten waves
-    // with groups of 10 were built and are slower, 0.1467.  MFM_FC1_FPG overrides.)
-    int fpg = FC1_MAXF;
-    if (const char* e = opt_get("MFM_FC1_FPG")) { const int v = atoi(e); if (v >= 1 && v <= FC1_MAXF && dhs_zeroed) fpg = v; }
-    if (NF1 > fpg && !(dhs_zeroed || !L.with_bwd)) return MFM_ERR_UNSUPPORTED;      // several groups add into dH
-    I.frags_per_group = std::min(fpg, NF1);
+    // with groups of 10 were built and are slower, 0.1467.)
+    if (NF1 > FC1_MAXF && !(dhs_zeroed || !L.with_bwd)) return MFM_ERR_UNSUPPORTED;      // several groups add into dH
+    I.frags_per_group = std::min(FC1_MAXF, NF1);
     I.col_groups = (NF1 + I.frags_per_group - 1) / I.frags_per_group;
     I.tile_begin = tiles;
     tiles += row_tiles * I.col_groups;

@@ -370,7 +370,7 @@ __device__ __forceinline__ void fc1_large64_body(const DecFc1LargeLaunch& L, con
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt) request_x(wg, i, rt);
 
-  for (int tile = wg; tile < ((L.dbg & 4) ? 0 : n_tiles); tile += nwg) {
+  for (int tile = wg; tile < n_tiles; tile += nwg) {
     const int row0 = tile * FL_R64;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -378,83 +378,77 @@ __device__ __forceinline__ void fc1_large64_body(const DecFc1LargeLaunch& L, con
     request_h(tile + nwg);
     lds_barrier();                                  // the H tile is in place; everybody is done with the previous tile's dx_hat
     // ---- product 1
-    if (!(L.dbg & 1)) {
-      bf16x8 wf[FL_MAXF][KB1];
+    bf16x8 wf[FL_MAXF][KB1];
 #pragma unroll
-      for (int i = 0; i < FL_MAXF; ++i)
+    for (int i = 0; i < FL_MAXF; ++i)
 #pragma unroll
-        for (int kb = 0; kb < KB1; ++kb)
-          wf[i][kb] = (wave + FL_WAVES * i < NF1)
-                          ? *reinterpret_cast<const bf16x8*>(Wb + (size_t)((wave + FL_WAVES * i) * 16 + bi) * FL_LDW + kb * 32 + 8 * q)
-                          : bf16x8{};
+      for (int kb = 0; kb < KB1; ++kb)
+        wf[i][kb] = (wave + FL_WAVES * i < NF1)
+                        ? *reinterpret_cast<const bf16x8*>(Wb + (size_t)((wave + FL_WAVES * i) * 16 + bi) * FL_LDW + kb * 32 + 8 * q)
+                        : bf16x8{};
 #pragma unroll
-      for (int rt = 0; rt < 4; ++rt) {
-        bf16x8 hf[KB1];
+    for (int rt = 0; rt < 4; ++rt) {
+      bf16x8 hf[KB1];
 #pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) hf[kb] = *reinterpret_cast<const bf16x8*>(Ht + (rt * 16 + bi) * FL_LDW + kb * 32 + 8 * q);
-        const int row = row0 + rt * 16 + bi;
+      for (int kb = 0; kb < KB1; ++kb) hf[kb] = *reinterpret_cast<const bf16x8*>(Ht + (rt * 16 + bi) * FL_LDW + kb * 32 + 8 * q);
+      const int row = row0 + rt * 16 + bi;
 #pragma unroll
-        for (int i = 0; i < FL_MAXF; ++i) {
-          if (wave + FL_WAVES * i < NF1) {          // wave-uniform
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = 0; i < FL_MAXF; ++i) {
+        if (wave + FL_WAVES * i < NF1) {          // wave-uniform
+          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int kb = 0; kb < KB1; ++kb) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i][kb], hf[kb], acc, 0, 0, 0);
-            // accumulator lane (bi, q): x_hat[row][n0 + r]
-            const f32x4 xt = xv[i][rt];
-            f32x4 dx;
+          for (int kb = 0; kb < KB1; ++kb) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i][kb], hf[kb], acc, 0, 0, 0);
+          // accumulator lane (bi, q): x_hat[row][n0 + r]
+          const f32x4 xt = xv[i][rt];
+          f32x4 dx;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const bool ok = n0[i] + r < d && row < L.rows;
-              const float diff = ok ? acc[r] + bv[i][r] - xt[r] : 0.0f;
-              lsum = fmaf(diff, diff, lsum);
-              dx[r] = I.grad_scale * diff;
-            }
-            request_x(tile + nwg, i, rt);           // (the register is free again: the next tile's target)
-            const bf16x4 dxb = __builtin_convertvector(dx, bf16x4);
-            *reinterpret_cast<bf16x4*>(Dx + (rt * 16 + bi) * LDX + n0[i]) = dxb;
+          for (int r = 0; r < 4; ++r) {
+            const bool ok = n0[i] + r < d && row < L.rows;
+            const float diff = ok ? acc[r] + bv[i][r] - xt[r] : 0.0f;
+            lsum = fmaf(diff, diff, lsum);
+            dx[r] = I.grad_scale * diff;
           }
+          request_x(tile + nwg, i, rt);           // (the register is free again: the next tile's target)
+          const bf16x4 dxb = __builtin_convertvector(dx, bf16x4);
+          *reinterpret_cast<bf16x4*>(Dx + (rt * 16 + bi) * LDX + n0[i]) = dxb;
         }
       }
     }
     lds_barrier();
     // the tile's d x_hat to memory (the next tile's product 1 overwrites Dx only behind the next barrier)
-    if (!(L.dbg & 1)) {
-      u32x4 pv[FL_DXP];
+    u32x4 pv[FL_DXP];
 #pragma unroll
-      for (int j = 0; j < FL_DXP; ++j) pv[j] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(Dx) + dxp_lds[j]);
+    for (int j = 0; j < FL_DXP; ++j) pv[j] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(Dx) + dxp_lds[j]);
 #pragma unroll
-      for (int j = 0; j < FL_DXP; ++j)
-        __builtin_amdgcn_raw_buffer_store_b128(pv[j], dxres, (row0 + dxp_row[j] < L.rows) ? (unsigned)(row0 * I.ld_dxhat * 2 + dxp_g[j]) : FL_OOB, 0, 0);
-    }
+    for (int j = 0; j < FL_DXP; ++j)
+      __builtin_amdgcn_raw_buffer_store_b128(pv[j], dxres, (row0 + dxp_row[j] < L.rows) ? (unsigned)(row0 * I.ld_dxhat * 2 + dxp_g[j]) : FL_OOB, 0, 0);
     // ---- product 2: wave (rt, half) owns dH fragments rows 16 rt .., hidden fragments half * JH .. of the tile
-    if (!(L.dbg & 2)) {
-      const int rt = wave & 3, half = wave >> 2;
-      f32x4 acc2[JH];
+    const int rt = wave & 3, half = wave >> 2;
+    f32x4 acc2[JH];
 #pragma unroll
-      for (int j = 0; j < JH; ++j) acc2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int nb = 0; nb < NB2; ++nb) {
-        const __bf16* ap = Dx + (rt * 16 + bi) * LDX + nb * 32 + 4 * q;
-        const bf16x8 a = cat8(*reinterpret_cast<const bf16x4*>(ap), *reinterpret_cast<const bf16x4*>(ap + 16));
-#pragma unroll
-        for (int j = 0; j < JH; ++j)
-          if (half * JH + j < J2) {          // wave-uniform (odd fragment counts: the second half has one less)
-            const __bf16* bp = Wb + (size_t)(nb * 32 + rrow) * FL_LDW + (half * JH + j) * 16 + rcol;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)bp);
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(bp + 16 * FL_LDW));
-            const bf16x8 b = cat8(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi));
-            acc2[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, acc2[j], 0, 0, 0);
-          }
-      }
-      // accumulator lane (bi, q): dH[row0 + 16 rt + bi][16 f2 + 4q + r]; pad units (>= h) come out as exact zeros
-      const int row = row0 + rt * 16 + bi;
+    for (int j = 0; j < JH; ++j) acc2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int nb = 0; nb < NB2; ++nb) {
+      const __bf16* ap = Dx + (rt * 16 + bi) * LDX + nb * 32 + 4 * q;
+      const bf16x8 a = cat8(*reinterpret_cast<const bf16x4*>(ap), *reinterpret_cast<const bf16x4*>(ap + 16));
 #pragma unroll
       for (int j = 0; j < JH; ++j)
-        if (half * JH + j < J2) {
-          const bf16x4 o = __builtin_convertvector(acc2[j], bf16x4);
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), dhres,
-                                                row < L.rows ? (unsigned)((row * Hp + (half * JH + j) * 16 + 4 * q) * 2) : FL_OOB, 0, 0);
+        if (half * JH + j < J2) {          // wave-uniform (odd fragment counts: the second half has one less)
+          const __bf16* bp = Wb + (size_t)(nb * 32 + rrow) * FL_LDW + (half * JH + j) * 16 + rcol;
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)bp);
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(bp + 16 * FL_LDW));
+          const bf16x8 b = cat8(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi));
+          acc2[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, acc2[j], 0, 0, 0);
         }
     }
+    // accumulator lane (bi, q): dH[row0 + 16 rt + bi][16 f2 + 4q + r]; pad units (>= h) come out as exact zeros
+    const int row = row0 + rt * 16 + bi;
+#pragma unroll
+    for (int j = 0; j < JH; ++j)
+      if (half * JH + j < J2) {
+        const bf16x4 o = __builtin_convertvector(acc2[j], bf16x4);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), dhres,
+                                              row < L.rows ? (unsigned)((row * Hp + (half * JH + j) * 16 + 4 * q) * 2) : FL_OOB, 0, 0);
+      }
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
@@ -556,12 +550,10 @@ int dec_fc1_large_launch(DecFc1LargeLaunch& L, hipStream_t stream) {
                          (int64_t)L.rows * L.it[i].ldx >= ((int64_t)1 << 29)))
       RT = FL_ROWS;
   }
-  L.dbg = opt_get("MFM_FC1_LARGE_DBG") ? atoi(opt_get("MFM_FC1_LARGE_DBG")) : 0;
   const int n_tiles = (L.rows + RT - 1) / RT;
   // one workgroup per CU; workgroups per decoder in proportion to its cost per row tile: a fixed part (barriers, the
   // tile's loads) plus the matrix part
-  const double c0_def = RT == FL_R64 ? 0.25 : 0.5;      // 16-row tiles, measured at B = 2048: 0.25 -> 124, 0.5 -> 93, 1 -> 94, 2 -> 106, 8 -> 119 us
-  const double c0 = opt_get("MFM_FC1_LARGE_C0") ? atof(opt_get("MFM_FC1_LARGE_C0")) : c0_def;      // tuning override
+  const double c0 = RT == FL_R64 ? 0.25 : 0.5;      // 16-row tiles, measured at B = 2048: 0.25 -> 124, 0.5 -> 93, 1 -> 94, 2 -> 106, 8 -> 119 us
   auto cost = [c0](const DecFc1LargeItem& I) { return c0 + (double)I.d * I.h / 31200.0; };
   double wsum = 0.0;
   size_t smem = 0;

@@ -384,7 +384,6 @@ __device__ __forceinline__ void dw_stream_body(const DwbLaunch& L, const DwbItem
 #endif
 
   // ---- add the tile into the gradient buffers.  Accumulator lane: rows (A columns) 4q + r, column bi of fragment j.
-  if (L.debug_no_epilogue == 1) return;     // (tuning aid: MFM_DWB_NOEPI=1 measures the streaming part alone)
   if (L.slabs) {
     // slab form: the partial tile [MT][npad] of this (M-tile, row range) leaves with plain stores; column npad - 16 holds the
     // column sums of A (bias gradients).  dw_reduce_kernel adds the row ranges up.
@@ -621,9 +620,7 @@ static double chunk_cost(int mt, int N, bool wide, int kpc = 1) {
 // rows per chunk of an item (128-column forms): what costs least per row, as long as a row range keeps >= 8 chunks
 static int best_kpc(int mt, int N, bool wide, int rows) {
   int best = 1;
-  const char* e = opt_get("MFM_DWB_KPC");
-  const int cap = e ? atoi(e) : 4;
-  for (int k = 2; k <= cap && wide; k *= 2)
+  for (int k = 2; k <= 4 && wide; k *= 2)
     if (chunk_cost(mt, N, wide, k) < chunk_cost(mt, N, wide, best) && rows >= 8 * DWB_KC * k) best = k;
   return best;
 }
@@ -631,7 +628,6 @@ static int best_kpc(int mt, int N, bool wide, int rows) {
 int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
   MFM_REQUIRE(Lu.n_items >= 1 && Lu.n_items <= MFM_DWB_MAXI && Lu.rows >= 1, "dw bf16: bad launch");
   if (!Lu.zeros) Lu.zeros = zero_block();
-  Lu.debug_no_epilogue = opt_get("MFM_DWB_NOEPI") ? atoi(opt_get("MFM_DWB_NOEPI")) : 0;
   MFM_REQUIRE(Lu.zeros, "dw bf16: no zero block");
   DwbLaunch L = Lu;                       // working copy: entries may be split into column parts below
   for (int i = 0; i < L.n_items; ++i) { L.it[i].parts = 1; L.it[i].part = 0; }
@@ -650,9 +646,8 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
   // the wide form from 65536 rows on; MFM_DWB_MF=4 / 3 forces one)
   const int mf_env = opt_get("MFM_DWB_MF") ? atoi(opt_get("MFM_DWB_MF")) : 0;
   // (slab form: the 128-column tiles' larger partial tiles cost plain stores, not atomics -> wide from 8192 rows on)
-  // measured (profiles/r04_bf16_large_batch.txt): ahead up to T*B = 40960 rows, behind from 81920 (MFM_DWB_SLABS=1 / 0 forces)
-  const char* slab_env = opt_get("MFM_DWB_SLABS");
-  const bool slab_req = L.slabs != nullptr && !L.f32 && (slab_env ? atoi(slab_env) != 0 : L.rows <= 65536);
+  // measured (profiles/r04_bf16_large_batch.txt): ahead up to T*B = 40960 rows, behind from 81920
+  const bool slab_req = L.slabs != nullptr && !L.f32 && L.rows <= 65536;
   // (round 5, with the per-item shapes / 64-128-row chunks / cost model below: ahead from the smallest bf16-resident plan on,
   // bench.py --dtype bf16, ms per step, 128-column form forced vs 96-column form: B = 128 0.2717 vs 0.2752, 192 0.2827 vs 0.2853,
   // 256 0.2925 vs 0.2975, 384 0.3151 vs 0.3276 -> from 2048 rows)
@@ -665,53 +660,50 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
     if (N > 16 * 4 * 8) wide9 = true;              // right-hand sides of 513-576 columns: the (4, 9) instantiation
   }
   for (int i = 0; i < L.n_items; ++i) L.it[i].mt = wide ? 128 : DWB_MT;
-  // Tile shape per item (round 5, 128-column form only; MFM_DWB_MIXED=0 keeps one shape): the main loop is bound by the bytes a
+  // Tile shape per item (round 5, 128-column form only): the main loop is bound by the bytes a
   // CU takes in, (MT + N) x 2 per row and tile -- a 256 x <= 256 tile (8 x 4 fragments per wave, the same 32-36 accumulator
   // tiles) moves fewer columns than 128 x N when the item is tall and wide: the early-fusion encoder, M = 512 N = 480: 4 x 608
   // -> 2 M-tiles x 2 column parts x 496; a decoder, M = 448 N = 112: 4 x 240 -> 2 x 368.  Taken when it saves >= 5 %.
   bool mixed = false;
-  {
-    const char* me = opt_get("MFM_DWB_MIXED");
-    if (wide && !(me && atoi(me) == 0)) {
-      DwbLaunch X = L;
-      X.n_items = 0;
-      for (int i = 0; i < L.n_items; ++i) {
-        const DwbItem& I = L.it[i];
-        const int n0 = I.seg[0].ncols, n1 = I.nseg > 1 ? I.seg[1].ncols : 0, N = n0 + n1;
-        const int k = (N + 255) / 256, nf = N / 16;
-        const double c128 = (I.M + 127) / 128 * chunk_cost(128, N, true, best_kpc(128, N, true, L.rows));
-        double c256 = 0.0;
-        for (int p = 0; p < k; ++p) {
-          const int np = 16 * (nf / k + (p < nf % k ? 1 : 0));
-          c256 += (I.M + 255) / 256 * chunk_cost(256, np, true, best_kpc(256, np, true, L.rows));
-        }
-        const int left = L.n_items - i - 1;
-        const bool take = I.M > 128 && c256 <= c128 * 0.95 && X.n_items + k + left <= MFM_DWB_MAXI;
-        if (!take) { X.it[X.n_items++] = I; continue; }
-        mixed = true;
-        int cs = 0;
-        for (int p = 0; p < k; ++p) {
-          const int ce = cs + 16 * (nf / k + (p < nf % k ? 1 : 0));
-          DwbItem& J = X.it[X.n_items++];
-          J = I;
-          J.mt = 256; J.parts = k; J.part = p;
-          if (p > 0) { J.cb = nullptr; J.cb2 = nullptr; }          // the column sums of A: the first part's
-          J.nseg = 0; J.nout = 0;
-          if (cs < n0) { DwbSeg& S = J.seg[J.nseg++]; S = I.seg[0]; S.col0 += cs; S.ncols = std::min(ce, n0) - cs; }
-          if (ce > n0) { DwbSeg& S = J.seg[J.nseg++]; S = I.seg[1]; S.col0 += std::max(cs, n0) - n0; S.ncols = ce - std::max(cs, n0); }
-          for (int o = 0; o < I.nout; ++o) {
-            const int lo = std::max(I.out[o].n0, cs), hi = std::min(I.out[o].n0 + I.out[o].nvalid, ce);
-            if (lo >= hi) continue;
-            DwbOut& O = J.out[J.nout++];
-            O = I.out[o];
-            O.n0 = lo - cs; O.nvalid = hi - lo; O.c = I.out[o].c + (lo - I.out[o].n0);
-            O.c2 = I.out[o].c2 ? I.out[o].c2 + (lo - I.out[o].n0) : nullptr;
-          }
-          cs = ce;
-        }
+  if (wide) {
+    DwbLaunch X = L;
+    X.n_items = 0;
+    for (int i = 0; i < L.n_items; ++i) {
+      const DwbItem& I = L.it[i];
+      const int n0 = I.seg[0].ncols, n1 = I.nseg > 1 ? I.seg[1].ncols : 0, N = n0 + n1;
+      const int k = (N + 255) / 256, nf = N / 16;
+      const double c128 = (I.M + 127) / 128 * chunk_cost(128, N, true, best_kpc(128, N, true, L.rows));
+      double c256 = 0.0;
+      for (int p = 0; p < k; ++p) {
+        const int np = 16 * (nf / k + (p < nf % k ? 1 : 0));
+        c256 += (I.M + 255) / 256 * chunk_cost(256, np, true, best_kpc(256, np, true, L.rows));
       }
-      if (mixed) L = X;
+      const int left = L.n_items - i - 1;
+      const bool take = I.M > 128 && c256 <= c128 * 0.95 && X.n_items + k + left <= MFM_DWB_MAXI;
+      if (!take) { X.it[X.n_items++] = I; continue; }
+      mixed = true;
+      int cs = 0;
+      for (int p = 0; p < k; ++p) {
+        const int ce = cs + 16 * (nf / k + (p < nf % k ? 1 : 0));
+        DwbItem& J = X.it[X.n_items++];
+        J = I;
+        J.mt = 256; J.parts = k; J.part = p;
+        if (p > 0) { J.cb = nullptr; J.cb2 = nullptr; }          // the column sums of A: the first part's
+        J.nseg = 0; J.nout = 0;
+        if (cs < n0) { DwbSeg& S = J.seg[J.nseg++]; S = I.seg[0]; S.col0 += cs; S.ncols = std::min(ce, n0) - cs; }
+        if (ce > n0) { DwbSeg& S = J.seg[J.nseg++]; S = I.seg[1]; S.col0 += std::max(cs, n0) - n0; S.ncols = ce - std::max(cs, n0); }
+        for (int o = 0; o < I.nout; ++o) {
+          const int lo = std::max(I.out[o].n0, cs), hi = std::min(I.out[o].n0 + I.out[o].nvalid, ce);
+          if (lo >= hi) continue;
+          DwbOut& O = J.out[J.nout++];
+          O = I.out[o];
+          O.n0 = lo - cs; O.nvalid = hi - lo; O.c = I.out[o].c + (lo - I.out[o].n0);
+          O.c2 = I.out[o].c2 ? I.out[o].c2 + (lo - I.out[o].n0) : nullptr;
+        }
+        cs = ce;
+      }
     }
+    if (mixed) L = X;
   }
   for (int i = 0; i < L.n_items; i += L.it[i].parts) {       // rows per chunk: one value per item (the parts share the row ranges)
     int kpc = 4;
@@ -729,20 +721,19 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
   // (profiles/r02_dw_onepass.txt).  One round up to 32768 rows, two above: every workgroup ends with its partial tile's
   // atomics, so few long ranges win while the rows are few (measured, MOSI sizes, T*B = 5120 / 10240 / 20480 / 40960 rows,
   // us at 0.5 / 0.75 / 1 / 2 x CUs workgroups: 56 / 59 / 89 / 99, 94 / 73 / 106 / 107, 175 / 122 / 145 / 125, 335 / 229 / 267 / 173:
-  // "1 x CUs" came out at a few workgroups more than CUs and ran two rounds).  MFM_DWB_TARGET = workgroups / CUs (no fitting).
+  // "1 x CUs" came out at a few workgroups more than CUs and ran two rounds).
   const int cus = device_cus();
-  // Round 5 (after the recurrences got shorter the launch was measured again, MFM_DWB_TARGET sweep, ms per step, 1 / 2 / 3 rounds):
+  // Round 5 (after the recurrences got shorter the launch was measured again, ms per step, 1 / 2 / 3 rounds):
   // 128-column tiles (MOSI sizes):  T*B = 40960: 0.5646 / 0.5870 / 0.5833,  81920: 0.9817 / 1.0073 / 1.0238 -> ONE round
   // (half the partial tiles: 35 instead of 71 MB of slabs written and read back).  The MOSEI / YouTube sizes (right-hand sides of
   // 544 columns) then got a (4, 9) instantiation of the 128-column form -- 232 VGPRs, no spills -- instead of 96-column tiles in
   // two rounds: MOSEI T = 50 B = 1024 0.833 -> 0.811 ms, YouTube T = 50 B = 2048 1.300 -> 1.258 ms, MOSEI T = 20 B = 2048
   // 0.656 -> 0.631 ms.  96-column tiles (right-hand sides beyond 576 columns) keep two rounds above 32768 rows.
   const int rounds = (L.rows <= 32768 || wide) ? 1 : 2;                 // (81920 rows run the atomics form: measured with it)
-  const char* tenv = opt_get("MFM_DWB_TARGET");
   int tiles = 0;
   size_t smem = 0;
   for (double fill = 0.98; ; fill -= 0.04) {
-    const double target = tenv ? atof(tenv) * cus : fill * rounds * cus;
+    const double target = fill * rounds * cus;
     tiles = 0;
     for (int i = 0; i < L.n_items; i += L.it[i].parts) {         // an item = `parts` consecutive entries with one set of row ranges
       const int k = L.it[i].parts;
@@ -761,7 +752,7 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
       }
       tiles += k * L.it[i].m_tiles * L.it[i].splits;
     }
-    if (tenv || tiles <= rounds * cus || fill < 0.3) break;
+    if (tiles <= rounds * cus || fill < 0.3) break;
   }
   for (int i = 0; i < L.n_items; ++i) {
     DwbItem& I = L.it[i];
@@ -770,15 +761,14 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
     const int P = DWB_KC * I.kpc * (I.mt + N) / 8;
     const int NI = (P + DWB_THREADS - 1) / DWB_THREADS;
     MFM_REQUIRE(NI <= DWB_MAXNI, "dw one-pass: %d DMA instructions per chunk", NI);
-    // stages: as many as fit ~144 KB, the counted wait and the cap (MFM_DWB_STAGES forces a count, clamped)
+    // stages: as many as fit ~144 KB, the counted wait and the cap
     int S = (int)((144 * 1024) / ((size_t)NI * DWB_THREADS * 16));
     S = std::min(S, DWB_MAX_WAIT / NI + 2);
-    if (const char* e = opt_get("MFM_DWB_STAGES")) S = std::min(S, atoi(e));
     S = std::max(DWB_MIN_STAGES, std::min(S, DWB_MAX_STAGES));
     I.stages = S;
     smem = std::max(smem, (size_t)S * NI * DWB_THREADS * 16);
   }
-  // slab form: partial tiles into the caller's scratch, summed by a second launch (bf16 form; MFM_DWB_SLABS=0 keeps the atomics)
+  // slab form: partial tiles into the caller's scratch, summed by a second launch (bf16 form)
   bool slabs = slab_req;
   if (slabs) {
     int64_t off = 0;
@@ -793,7 +783,7 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
       I.red_begin = red;
       red += I.m_tiles * I.mt;
     }
-    if (off > L.slab_floats) slabs = false;           // (scratch sized for fewer workgroups than a forced MFM_DWB_TARGET asks for)
+    if (off > L.slab_floats) slabs = false;           // (scratch sized for fewer workgroups: the atomics)
     else L.red_rows = red;
   }
   if (!slabs) L.slabs = nullptr;
@@ -818,7 +808,7 @@ int dw_bf16_launch(DwbLaunch& Lu, hipStream_t stream) {
   else if (wide) MFM_LAUNCH_TIMED((dw_stream_kernel<false, 4, 8>), dim3(tiles), dim3(DWB_THREADS), smem, stream, L);
   else MFM_LAUNCH_TIMED((dw_stream_kernel<false, 3, 9>), dim3(tiles), dim3(DWB_THREADS), smem, stream, L);
   MFM_LAUNCH_CHECK("dw_stream_kernel");
-  if (L.slabs && L.debug_no_epilogue != 1) {
+  if (L.slabs) {
     MFM_LAUNCH_TIMED(dw_reduce_kernel, dim3((L.red_rows + 1) / 2), dim3(256), 0, stream, L);
     MFM_LAUNCH_CHECK("dw_reduce_kernel");
   }

@@ -38,6 +38,10 @@ const char* opt_get(const char* name) {
   }
   return ::getenv(name);
 }
+bool opt_disabled(const char* name) {
+  const char* v = opt_get(name);
+  return v && atoi(v) == 0;
+}
 OptTable* opt_table_from_env() {
   OptTable* t = new OptTable();
   for (char** e = environ; e && *e; ++e) {

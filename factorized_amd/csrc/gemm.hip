@@ -341,8 +341,7 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
   long base_blocks = 0;
   for (int i = 0; i < count; ++i)
     base_blocks += (long)cdiv(descs[i].m, BT) * cdiv(descs[i].n, BT) * descs[i].batch;
-  long kdepth = 2048;      // K elements one workgroup walks at most (accumulating problems; measured 256..4096 at B=512/2048)
-  if (const char* e = opt_get("MFM_GEMM_KDEPTH")) { const long v = atol(e); if (v >= 64) kdepth = v; }   // tuning override
+  const long kdepth = 2048;      // K elements one workgroup walks at most (accumulating problems; measured 256..4096 at B=512/2048)
   bool vec = true;
   for (int i = 0; i < count; ++i) {
     const MfmGemmDesc& d = descs[i];

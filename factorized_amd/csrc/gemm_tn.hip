@@ -181,29 +181,22 @@ bool gemm_tn_supported(const MfmGemmDesc* descs, int count, int max_rows, bool c
   if (count < 1 || count > MFM_TN_MAXP) return false;
   for (int i = 0; i < count; ++i) {
     const MfmGemmDesc& d = descs[i];
-    const bool dbg = opt_get("MFM_PLAN_DEBUG") != nullptr;
-    auto no = [&](const char* why) {
-      if (dbg) fprintf(stderr, "[mfm gemm_tn] problem %d of %d declined: %s (m %d n %d k %d batch %d a_sm %lld a_sk %lld b_sk %lld b_sn %lld acc %d)\n", i, count, why,
-                       d.m, d.n, d.k, d.batch, (long long)d.a_sm, (long long)d.a_sk, (long long)d.b_sk, (long long)d.b_sn, d.accumulate);
-      return false;
-    };
-    if (!d.a || !d.b || !d.c || d.m < 1 || d.n < 1 || d.k < 1 || d.batch < 1) return no("empty");
+    if (!d.a || !d.b || !d.c || d.m < 1 || d.n < 1 || d.k < 1 || d.batch < 1) return false;   // empty
     // a non-accumulating product (C = ...) is taken when the caller vouches that C holds zeros: 0 + v is v exactly
-    if (d.a_sm != 1 || d.b_sn != 1 || (!d.accumulate && !c_is_zero) || d.bias || d.bias2) return no("not an accumulating TN product");
-    if (d.k > max_rows) return no("too many rows");
-    if (d.a_bf16 && ((d.a_sk & 3) || (d.a_sz & 3) || (reinterpret_cast<uintptr_t>(d.a) & 7))) return no("bf16 A not 8-byte shaped");
-    if (d.c_bf16) return no("bf16 output");
+    if (d.a_sm != 1 || d.b_sn != 1 || (!d.accumulate && !c_is_zero) || d.bias || d.bias2) return false;   // not an accumulating TN product
+    if (d.k > max_rows) return false;   // too many rows
+    if (d.a_bf16 && ((d.a_sk & 3) || (d.a_sz & 3) || (reinterpret_cast<uintptr_t>(d.a) & 7))) return false;   // bf16 A not 8-byte shaped
+    if (d.c_bf16) return false;   // bf16 output
     const int64_t lim = (int64_t)1 << 29;
     if ((int64_t)(d.k - 1) * d.a_sk + d.m >= lim || (int64_t)(d.k - 1) * d.b_sk + d.n >= lim) return false;
-    if (d.a_sz >= lim || d.b_sz >= lim || d.c_sz >= lim || d.ldc >= lim) return no("strides beyond 2^29");
+    if (d.a_sz >= lim || d.b_sz >= lim || d.c_sz >= lim || d.ldc >= lim) return false;   // strides beyond 2^29
   }
   return true;
 }
 
 int gemm_tn_launch(const MfmGemmDesc* descs, int count, int max_rows, bool c_is_zero, hipStream_t stream) {
   MFM_REQUIRE(gemm_tn_supported(descs, count, max_rows, c_is_zero), "gemm tn: unsupported group (count %d)", count);
-  int KC = 160;                                   // rows per chunk; MFM_GEMM_TN_KC=80|160|320 (tuning)
-  if (const char* e = opt_get("MFM_GEMM_TN_KC")) { const int v = atoi(e); if (v == 80 || v == 160 || v == 320) KC = v; }
+  constexpr int KC = 160;                         // rows per chunk
   TnGroup g;
   memset(&g, 0, sizeof(g));
   g.count = count;
@@ -227,17 +220,9 @@ int gemm_tn_launch(const MfmGemmDesc* descs, int count, int max_rows, bool c_is_
     total += P.tiles_m * P.tiles_n * s.batch * split;
   }
   for (int i = count; i < MFM_TN_MAXP; ++i) g.begins[i] = 0x7fffffff;
-  const size_t lds = (size_t)2 * KC * TN_T * sizeof(float);
-#define MFM_TN_GO(KC_)                                                                                             \
-  do {                                                                                                             \
-    auto* fn = gemm_tn_kernel<KC_>;                                                                                \
-    if (lds > 64 * 1024) MFM_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    MFM_LAUNCH_TIMED(fn, dim3(total), dim3(256), lds, stream, g);                                                \
-  } while (0)
-  if (KC == 80) MFM_TN_GO(80);
-  else if (KC == 320) MFM_TN_GO(320);
-  else MFM_TN_GO(160);
-#undef MFM_TN_GO
+  constexpr size_t lds = (size_t)2 * KC * TN_T * sizeof(float);
+  static_assert(lds <= 64 * 1024, "gemm tn: beyond the default LDS limit");
+  MFM_LAUNCH_TIMED(gemm_tn_kernel<KC>, dim3(total), dim3(256), lds, stream, g);
   MFM_LAUNCH_CHECK("gemm_tn_kernel");
   return MFM_OK;
 }

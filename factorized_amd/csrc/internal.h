@@ -104,7 +104,7 @@ struct DecFc1LargeItem {
   int wg_begin, wg_count;                                                // filled by dec_fc1_large_launch
   void* wimg;     // optional scratch, dec_fc1_large_wimg_bytes(): the bf16 image of Wfc, packed once per launch instead of once per workgroup
 };
-struct DecFc1LargeLaunch { DecFc1LargeItem it[3]; int n_items, rows, dbg, packed; };   // dbg: tuning aid (MFM_FC1_LARGE_DBG); packed: the weight images are already built
+struct DecFc1LargeLaunch { DecFc1LargeItem it[3]; int n_items, rows, packed; };   // packed: the weight images are already built
 bool dec_fc1_large_uses_wimg(const DecFc1LargeLaunch& L);
 int dec_fc1_large_supported(const DecFc1LargeItem& I);
 size_t dec_fc1_large_wimg_bytes(int d);
@@ -130,7 +130,7 @@ struct DwbItem {
   int parts, part;
   int kpc, pad2_;                       // 32-row k-blocks per chunk (filled by dw_bf16_launch: narrow items take 64 / 128 rows per chunk)
 };
-struct DwbLaunch { DwbItem it[MFM_DWB_MAXI]; int n_items, rows; const void* zeros; int debug_no_epilogue; int f32;
+struct DwbLaunch { DwbItem it[MFM_DWB_MAXI]; int n_items, rows; const void* zeros; int f32;
                    // optional scratch (dw_bf16_scratch_floats()): every workgroup leaves its partial tile there with plain stores and a
                    // second launch sums the row ranges of each M-tile and adds the result once -- instead of ~7 M atomicAdds into
                    // the same few hundred KB (round 4); null: the atomics
@@ -232,7 +232,6 @@ struct LatentDev {
   float seed_w; const float* seed_w_ptr;   // weight of grd_seed (device scalar when set: the caller's upstream gradient wrt the regulariser)
   const float* grd_seed;               // optional [B, rec_size]: gradients injected into the record before the backward
                                        // walks the stages (the MMD regulariser's d reg / d z of the non-KL MFM)
-  unsigned long long* dbg;             // optional: block 0 / thread 0 writes s_memtime at phase marks
   int B, rows_per_wg, rows_fwd, train, has_logvar;     // rows per workgroup of the staged kernels: backward / forward
   int skip_bias;                       // staged backward: leave the bias gradients to the weight-gradient launch (gemm_tn column sums)
   int mfma;                            // staged kernels: the layers' products on v_mfma_f32_16x16x4_f32 (rows per workgroup <= 16, every K % 4 == 0)

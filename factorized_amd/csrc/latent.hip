@@ -113,9 +113,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatentDev
   }
   f32x4 pre[PRE_U];
   if (staged) span_load(params + L.span_off[0], L.span_len[0] >> 2, tid, nt, pre);
-  mark(L, 0);
   lds_barrier();     // record inputs + LDS op table
-  mark(L, 1);
 
   for (int s = 0; s < L.nstages; ++s) {
     const int ob = L.stage_begin[s], oe = L.stage_begin[s + 1];
@@ -125,7 +123,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatentDev
       lds_barrier();     // LDS-only barrier: __syncthreads() would also drain the prefetch below (vmcnt(0))
       if (s + 1 < L.nstages) span_load(params + L.span_off[s + 1], L.span_len[s + 1] >> 2, tid, nt, pre);
     }
-    mark(L, 2 + 2 * s);
     // one work item = (output column n of one op, k-quarter q, chunk of 4 batch rows): the four lanes of
     // a quad split the reduction dim in interleaved 16-byte chunks (ds_read_b128 for the weight row
     // and for each of the 4 activation rows: 5 LDS reads per 16 FMAs), all-reduce with two DPP adds,
@@ -192,7 +189,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatentDev
         }
       }
       lds_barrier();
-      mark(L, 3 + 2 * s);
       continue;
     }
     const int nch = (nrows + 3) >> 2;
@@ -261,7 +257,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatentDev
       }
     }
     lds_barrier();
-    mark(L, 3 + 2 * s);
   }
 
   // ---- losses (partials per workgroup, one atomic each)
@@ -334,7 +329,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_fwd_kernel(const LatentDev
     const f32x4* s4 = reinterpret_cast<const f32x4*>(rec);
     for (int idx = tid; idx < n4; idx += nt) d4[idx] = s4[idx];
   }
-  mark(L, 20);
 }
 
 template <bool STAGED>
@@ -437,7 +431,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_kernel(const LatentDev
   f32x4 pre[PRE_U];
   if (staged) span_load(params + L.span_off[L.nstages - 1], L.span_len[L.nstages - 1] >> 2, tid, nt, pre);
   lds_barrier();
-  mark(L, 24);
 
   for (int s = L.nstages - 1; s >= 0; --s) {
     const int ob = L.stage_begin[s], oe = L.stage_begin[s + 1];
@@ -460,7 +453,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_kernel(const LatentDev
       grd[r * RS + op.out_off + n] = gv;
     }
     lds_barrier();       // also publishes the weight panel; LDS-only, the span prefetch stays in flight
-    mark(L, 25 + 3 * s);
     // pass 2a: grad wrt the input segment (LDS atomics: several ops may share an input).
     // work item = (input column k of one op, n-quarter q, chunk of 4 rows): the quad splits the output
     // dim in interleaved chunks of 4, all-reduces with DPP, lane q adds batch row q.
@@ -550,7 +542,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_kernel(const LatentDev
       if (live && r0 + q < nrows) atomicAdd(&grd[(r0 + q) * RS + op.in_off + k], v);
     }
     }
-    mark(L, 26 + 3 * s);
     // pass 2b: bias gradients (column sums over this workgroup's rows).  The WEIGHT gradients
     // dW = G^T X are left to a grouped MFMA GEMM over the two records (plan.hip): writing 57k
     // floats per workgroup from here is store-issue bound (~7 B/clk/CU: 25 us at B=32), and
@@ -565,7 +556,6 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_bwd_kernel(const LatentDev
       atomicAdd(grads + op.b_off + n, a0);
     }
     lds_barrier();       // LDS-only: the bias atomics retire in the background (a full barrier waited ~4 us per stage for them)
-    mark(L, 27 + 3 * s);
   }
 
   for (int m = 0; m < 4; ++m) {

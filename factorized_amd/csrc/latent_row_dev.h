@@ -17,12 +17,6 @@ __device__ __forceinline__ float dpp_quad(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
 }
 
-
-// debug: phase timestamps of workgroup 0 (shader clock), enabled with MFM_LATENT_DBG=1
-__device__ __forceinline__ void mark(const LatentDev& L, int slot) {
-  if (L.dbg && blockIdx.x == 0 && threadIdx.x == 0) L.dbg[slot] = __builtin_readcyclecounter();
-}
-
 __device__ __forceinline__ int find_op(const int* pfx, int ob, int oe, int x, int mult) {
   int o = ob;
 #pragma unroll
@@ -202,9 +196,7 @@ __device__ __forceinline__ void latent_fwd_row_body(const LatentDev& L, const fl
     }
     t.bias = params[(unsigned)t.e[1]];
   };
-  mark(L, 0);
   lds_barrier();
-  mark(L, 1);
   LSTAMP(LST_KF, 16);
   auto stage = [&](int s, Slot& cur, Slot& nxt) {
     // A wave with no item in this stage nor in the next skips the body.  Inside the body every load is
@@ -225,7 +217,6 @@ __device__ __forceinline__ void latent_fwd_row_body(const LatentDev& L, const fl
       if (s == 2 && threadIdx.x < 64) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); LSTAMP(LST_KF, 27); }
 #endif
       if constexpr (!PRE) fetch(sn, nxt);
-      mark(L, 2 + 2 * s);
 #if MFM_LAUNCH_STAMP
       if (s == 2 && threadIdx.x < 64) { LSTAMP(LST_KF, 28); asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); LSTAMP(LST_KF, 29); }
 #endif
@@ -267,7 +258,6 @@ __device__ __forceinline__ void latent_fwd_row_body(const LatentDev& L, const fl
     if (s == 2) LSTAMP(LST_KF, 30);
 #endif
     lds_barrier();
-    mark(L, 3 + 2 * s);
     LSTAMP(LST_KF, 17 + s);
   };
   if constexpr (PRE) {
@@ -354,7 +344,6 @@ __device__ __forceinline__ void latent_fwd_row_body(const LatentDev& L, const fl
     const f32x4* s4 = reinterpret_cast<const f32x4*>(rec);
     for (int idx = lo4 + tid; idx < hi4; idx += nt) d4[idx] = s4[idx];
   }
-  mark(L, 20);
 }
 
 // `mode` (round 6, the launch clock: 3.1 us of stores and atomics between the last stage and the BPTT that only needs d h_T):
@@ -563,12 +552,10 @@ __device__ __forceinline__ void latent_bwd_row_body(const LatentDev& L, const fl
       }
   }
   lds_barrier();
-  mark(L, 24);
   LSTAMP(LST_KB, 17);
 
   auto stage = [&](int s, Slot& cur, Slot& nxt) {
     const int sn = max(s - 1, 0);
-    mark(L, 25 + 3 * s);
     // ---- pass 2a: dX[k] += sum_n g[n] W[n][k]   (per-wave skip and unconditional loads as in the forward)
     if (wave0 < (PRE ? nib[s] : max(nib[s], nib[sn]))) {
       const int N = (cur.e[1] >> 8) & 0xFF;
@@ -605,9 +592,7 @@ __device__ __forceinline__ void latent_bwd_row_body(const LatentDev& L, const fl
         }
       }
     }
-    mark(L, 26 + 3 * s);
     lds_barrier();
-    mark(L, 27 + 3 * s);
     LSTAMP(LST_KB, 18 + s);
   };
   if constexpr (PRE) {

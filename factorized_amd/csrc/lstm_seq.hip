@@ -416,7 +416,7 @@ static int seq_launch(const MfmSeqDesc* descs_in, int count_in, int T, int B, bo
   // (B=2048: encoder recurrences 154 -> 132 us forward, 163 -> 151 us backward).  While everything is
   // resident at once the caller's order is kept: widest-first measured 0.8 % slower per step at B=32.
   bool sorted = false;
-  if ((long)count * B > (long)device_cus() && !opt_get("MFM_SEQ_KEEP_ORDER")) {
+  if ((long)count * B > (long)device_cus()) {
     std::stable_sort(descs, descs + count, [](const MfmSeqDesc& a, const MfmSeqDesc& b) { return a.h > b.h; });
     sorted = true;
   }

@@ -373,10 +373,8 @@ int seq_small_launch(SeqLaunch& L, bool bwd, hipStream_t stream) {
     // forward, one-row tiles, idle CUs left: a few more blocks write this step's transposed-weight images
     const int rows_total = total;
     L.n_img_blocks = 0;
-    // (no idle CU left: the writers still pay -- they run in the launch's last round, ~2 us, against ~9 us of staging saved;
-    //  MFM_WT_IMG_FULL=0: only with idle CUs)
-    const bool img_full = !(opt_get("MFM_WT_IMG_FULL") && atoi(opt_get("MFM_WT_IMG_FULL")) == 0);
-    if (!bwd && R == 1 && L.n_img > 0 && (cus - total >= 8 || img_full)) {
+    // (no idle CU left: the writers still pay -- they run in the launch's last round, ~2 us, against ~9 us of staging saved)
+    if (!bwd && R == 1 && L.n_img > 0) {
       L.img_begin = total; L.n_img_blocks = cus - total >= 8 ? std::min(cus - total, 64) : 32; total += L.n_img_blocks;
     }
     // backward, one-row tiles: MFM_SEQ_KS=8 selects 8 k-slices per unit pair (half the threads, twice the FMAs each).
@@ -459,7 +457,7 @@ int seq_small_folddw_launch(SeqLaunch& L, const LatentDev& LD, DwRole& DR, const
   // the chain's gradient record must survive into the BPTT's prologue: it has to lie behind everything the BPTT keeps in LDS, and
   // every encoder must take its transposed weights from this step's images (no staging panel)
   DR.lat_split = 0;
-  if (!(opt_get("MFM_LATENT_SPLIT") && atoi(opt_get("MFM_LATENT_SPLIT")) == 0)) {
+  if (!opt_disabled("MFM_LATENT_SPLIT")) {
     bool imgs = true;
     for (int i = 0; i < 4; ++i) imgs = imgs && L.d[i].wt_img != nullptr;
     if (imgs && lds_bytes <= (size_t)latent_bwd_grd_floats(LD.rec_size) * sizeof(float)) DR.lat_split = 1;
@@ -581,7 +579,7 @@ int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, c
   lds_bytes = std::max(lds_bytes, std::max(lat, role));
   // chain tables preloaded in front of the time loop: chain region + recurrence buffers side by side (lstm_seq_small_foldproj_kernel)
   PR.lat_pre = 0;
-  if (!(opt_get("MFM_LATENT_PRELOAD") && atoi(opt_get("MFM_LATENT_PRELOAD")) == 0)) {
+  if (!opt_disabled("MFM_LATENT_PRELOAD")) {
     bool direct = true;
     for (int i = 0; i < 4; ++i) direct = direct && (L.d[i].h & 3) == 0;
     const size_t side = (size_t)latent_fwd_lds_floats(LD.rec_size) * sizeof(float) + small_lds_bytes(L, false, 1, true);
@@ -610,11 +608,9 @@ int seq_small_fold_launch(SeqLaunch& L, bool bwd, const LatentDev& LD, const flo
   }
   if (max_threads < 1024) max_threads = 1024;       // the chain's work items are tabulated for up to 1024 threads
   L.n_img_blocks = 0;
-  const bool img_full = !(opt_get("MFM_WT_IMG_FULL") && atoi(opt_get("MFM_WT_IMG_FULL")) == 0);
-  if (!bwd && L.n_img > 0 && (device_cus() - total >= 8 || img_full)) {
+  if (!bwd && L.n_img > 0) {
     L.img_begin = total; L.n_img_blocks = device_cus() - total >= 8 ? std::min(device_cus() - total, 64) : 32; total += L.n_img_blocks;
   }
-  else L.n_img = 0;
   size_t lds_bytes = small_lds_bytes(L, bwd, 1);
   const size_t lat = ((size_t)MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4 + (bwd ? 2 : 1) * (size_t)LD.rec_size) * sizeof(float);
   if (lat > lds_bytes) lds_bytes = lat;

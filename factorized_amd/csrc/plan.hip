@@ -70,8 +70,6 @@ extern "C" void mfm_plan_destroy(MfmPlan* P) {
   delete P;
 }
 
-extern "C" int64_t mfm_plan_debug_offset(const MfmPlan* P) { return P ? P->dbg_off * (int64_t)sizeof(float) : -1; }
-
 extern "C" int64_t mfm_plan_workspace_bytes(const MfmPlan* P) { return P ? P->ws_floats * (int64_t)sizeof(float) : 0; }
 
 extern "C" int mfm_plan_init_workspace(MfmPlan* P, void* workspace, void* stream) {
@@ -442,7 +440,7 @@ extern "C" double mfm_plan_kernel_flops(const MfmPlan* P, int kid) {
       // the fused kernel (dec_fc1.hip; the plan's default up to 5120 rows) also forms dH = dx_hat Wfc in the same launch
       long fc1_max_rows = 5120;
       if (const char* e = opt_get("MFM_FC1_FUSED_MAXROWS")) fc1_max_rows = atol(e);
-      const bool on = !(opt_get("MFM_FC1_FUSED") && atoi(opt_get("MFM_FC1_FUSED")) == 0);
+      const bool on = !opt_disabled("MFM_FC1_FUSED");
       if (on && TB <= (double)fc1_max_rows) f *= 2.0;
       break;
     }

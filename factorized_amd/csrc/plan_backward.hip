@@ -88,7 +88,6 @@ int dw_role_build(MfmPlan* P, const std::vector<MfmGemmDesc>& all, float* W, int
     const int split = cdiv(q.k, DWR_KC);
     q.kps = round_up(cdiv(q.k, split), 4);
     if (d.a >= W + P->lat_grd && d.a < W + P->lat_grd + (int64_t)B * P->lat.rec_size) dep[i] = DWR_DEP_LATENT;
-    if (opt_get("MFM_DW_FOLD_NODEP")) dep[i] = DWR_DEP_NONE;       // timing experiment only (wrong gradients): nothing waits
   }
   int n_role = device_cus() - 4 * B;
   if (const char* e = opt_get("MFM_DW_FOLD_ROLES")) { const int v = atoi(e); if (v >= 1 && v <= n_role) n_role = v; }
@@ -163,7 +162,6 @@ int dw_role_build(MfmPlan* P, const std::vector<MfmGemmDesc>& all, float* W, int
     };
     for (size_t u = 0; u < ua.size(); ++u)
       put((int)(u / n_role), (int)(u % n_role), ua[u], ua[u].chunk, groups[ua[u].grp].dep | DWR_FIRST | DWR_LAST);
-    const bool store_ok = !opt_get("MFM_DW_FOLD_ATOMICS");           // (A/B timing: MFM_DW_FOLD_ATOMICS=1 keeps the atomics)
     for (size_t j = 0; j < te.size(); ++j) {
       const Group& g = groups[te[j].grp];
       const int split = cdiv(g.k, g.kps);
@@ -171,7 +169,7 @@ int dw_role_build(MfmPlan* P, const std::vector<MfmGemmDesc>& all, float* W, int
       for (int c = 0; c < split; ++c) {            // c-th block of this tile set: chunk split - 1 - c
         const int sp = split - 1 - c;
         const int t0 = g.tbase + (sp * g.kps) / B;
-        int w = g.dep | (t0 << 8) | (acc ? DWR_ACC1 : 0) | (store_ok ? DWR_STORE : 0);
+        int w = g.dep | (t0 << 8) | (acc ? DWR_ACC1 : 0) | DWR_STORE;
         if (c == 0) w |= DWR_FIRST;
         if (c == split - 1) w |= DWR_LAST;
         put(rows_a + (max_split - split + c) * nacc + acc, wg, te[j], sp, w);
@@ -231,7 +229,6 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
     L.ops = reinterpret_cast<const LatOp*>(W + P->lat_ops_off);
     L.items_fwd = reinterpret_cast<const int*>(W + P->lat_items_off);
     L.items_bwd = L.items_fwd + (size_t)4 * MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4;
-    if (opt_get("MFM_LATENT_DBG")) L.dbg = reinterpret_cast<unsigned long long*>(W + P->dbg_off);
     for (int m = 0; m < 3; ++m) {
       L.d_dec_init[m] = gen_on ? W + P->dec_dinit[m] : nullptr;
       L.dec_ld[m] = P->dec_h[m];
@@ -365,7 +362,7 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
                               imgs_on ? W + P->wt_img[2] : nullptr, imgs_on ? W + P->wt_img[3] : nullptr};
       // B <= 32: the idle CUs of this launch run every weight-gradient product of the step (dw_role_dev.h); B5 disappears
       if (!st16 && P->dwfold_state >= 0 && P->dw_table >= 0 && P->opt_handover && seq_small_folddw_supported(T, B) &&
-          !opt_get("MFM_DW_F32_MINROWS") && !(opt_get("MFM_GEMM_TN") && atoi(opt_get("MFM_GEMM_TN")) == 0)) {
+          !opt_get("MFM_DW_F32_MINROWS") && !opt_disabled("MFM_GEMM_TN")) {
         std::vector<MfmGemmDesc> all = tail;
         latent_products(all, false);
         for (int e = 0; e < 4; ++e) dA_gemms(P, P->enc[e], P->enc_p[e], W, grads, all, x + P->enc_xoff[e], P->D, P->enc_d[e], false);
@@ -403,14 +400,11 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
     }
     // bf16 plans from B = 192 send the latent weight gradients to gemm_tn_kernel (end of this function): the staged backward
     // then leaves the bias gradients to that launch's column sums instead of adding 1180 words per workgroup into the same
-    // addresses (10 of its 60 us at B = 2048, profiles/r03_latent_mfma.txt); MFM_LATENT_BIAS_TN=0 keeps the atomics
+    // addresses (10 of its 60 us at B = 2048, profiles/r03_latent_mfma.txt)
     bool bias_in_tail = false;
-    if (!enc_bwd_done && !L.row_path && c.precision && B <= 8192 && !(opt_get("MFM_GEMM_TN") && atoi(opt_get("MFM_GEMM_TN")) == 0) &&
-        !(opt_get("MFM_LATENT_BIAS_TN") && atoi(opt_get("MFM_LATENT_BIAS_TN")) == 0)) {
+    if (!enc_bwd_done && !L.row_path && c.precision && B <= 8192 && !opt_disabled("MFM_GEMM_TN")) {
       const long minb = opt_get("MFM_GEMM_TN_BF16_MINB") ? atol(opt_get("MFM_GEMM_TN_BF16_MINB")) : 192;
-      long rows16 = 8192;
-      if (const char* e = opt_get("MFM_GEMM_TN_MAXROWS_BF16")) rows16 = atol(e);
-      bias_in_tail = B >= minb && B <= rows16;
+      bias_in_tail = B >= minb;
     }
     L.skip_bias = bias_in_tail ? 1 : 0;
     if (!enc_bwd_done) RUN(K_LAT_BWD, latent_bwd_launch(L, params, grads, s));
@@ -553,7 +547,7 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
     // profiles/r02_gemm_tn.txt); MFM_GEMM_TN=0 / larger row counts / bf16 plans: the grouped GEMM
     long tn_rows = 1024;         // measured crossover: 640 rows 21.7 vs 24.8 us, 1280 rows equal, 2560 rows 67 vs 59 us
     if (const char* e = opt_get("MFM_GEMM_TN_MAXROWS")) tn_rows = atol(e);
-    const bool tn_on = !c.precision && !(opt_get("MFM_GEMM_TN") && atoi(opt_get("MFM_GEMM_TN")) == 0);
+    const bool tn_on = !c.precision && !opt_disabled("MFM_GEMM_TN");
     // bf16 plans: the products over B rows (the latent stack's 22 Linears on their fp32 records, the decoders' t = 0 products
     // on bf16-resident dA) go to the chunked fp32 kernel too -- 22 small outputs with K = B are all split-K prologue on the grouped kernel (48 us at
     // B = 2048) -- the rest (bf16-resident operands, sums over T*B rows) stays on the grouped bf16 GEMM
@@ -561,9 +555,8 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
     // 10.0 vs 12.9, 11.2 vs 16.2, 16.4 vs 23.8, 22.2 vs 48.5 us; fp32-stored bf16 plans, B < 192, keep the one grouped launch;
     // MFM_GEMM_TN_BF16_MINB moves the threshold)
     const long tn16_minb = opt_get("MFM_GEMM_TN_BF16_MINB") ? atol(opt_get("MFM_GEMM_TN_BF16_MINB")) : 192;
-    if (c.precision && B >= tn16_minb && !(opt_get("MFM_GEMM_TN") && atoi(opt_get("MFM_GEMM_TN")) == 0)) {
-      long tn_rows16 = 8192;
-      if (const char* e = opt_get("MFM_GEMM_TN_MAXROWS_BF16")) tn_rows16 = atol(e);
+    if (c.precision && B >= tn16_minb && !opt_disabled("MFM_GEMM_TN")) {
+      const long tn_rows16 = 8192;
       std::vector<MfmGemmDesc> small, rest;
       for (const MfmGemmDesc& d : tail)
         ((!d.c_bf16 && d.k <= tn_rows16 && d.k <= 4L * B && gemm_tn_supported(&d, 1, (int)tn_rows16, true)) ? small : rest).push_back(d);

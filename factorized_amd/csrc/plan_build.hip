@@ -72,9 +72,7 @@ int build(MfmPlan* P) {
     // 64-row decoder fc1 and whole rounds of workgroups in the one-pass weight-gradient launch); MFM_BF16_STORE=1 forces it
     // on for every size, =0 off
     const char* se = opt_get("MFM_BF16_STORE");
-    long st_minrows = 2560;
-    if (const char* e = opt_get("MFM_BF16_STORE_MINROWS")) st_minrows = atol(e);
-    bool ok = P->seq_bf16 && !opt_get("MFM_SEQ_STEPWISE") && (se ? atoi(se) != 0 : TB >= st_minrows);
+    bool ok = P->seq_bf16 && !opt_get("MFM_SEQ_STEPWISE") && (se ? atoi(se) != 0 : TB >= 2560);
     const int Dp = round_up(c.d_l, 16) + round_up(c.d_a, 16) + round_up(c.d_v, 16);
     int hmax = 0, np_max = 0;
     for (int e = 0; e < P->n_enc; ++e) {
@@ -89,7 +87,6 @@ int build(MfmPlan* P) {
     ok = ok && hmax <= MFM_SEQ_MAX_RESIDENT_H && np_max <= 576 && (32 * (96 + np_max) / 8 + 511) / 512 <= 6;
     ok = ok && TB * 4 * round_up(hmax, 16) * 2 < ((int64_t)1 << 31) && TB * Dp * 2 < ((int64_t)1 << 31);
     P->st16 = ok;
-    if (opt_get("MFM_PLAN_DEBUG")) fprintf(stderr, "[mfm plan] bf16: recurrences on the bf16 kernels %d, bf16-resident activations %d\n", (int)P->seq_bf16, (int)P->st16);
   }
   const int ESH = P->st16 ? 2 : 1;          // bf16-resident buffers take half the floats
   for (int e = 0; e < P->n_enc; ++e) {
@@ -148,7 +145,6 @@ int build(MfmPlan* P) {
       P->pj_wimg = carve(cur, (int64_t)P->pj.ntiles * 2048);
       P->pj_bimg = carve(cur, P->pj.nbias);
     }
-    if (opt_get("MFM_PLAN_DEBUG")) fprintf(stderr, "[mfm plan] bf16-resident projections: proj_bf16_kernel %d (%d tiles, %d-row panels, %d stages)\n", (int)P->proj16, P->pj.ntiles, P->pj.BM, P->pj.S);
   }
   // ---- Memory Fusion Network (variants 1, 2): every [T*B, .] tensor of the attention block and the memory recurrence
   P->tot = P->A2 = P->nzy = 0;
@@ -216,7 +212,7 @@ int build(MfmPlan* P) {
   // encoder fc1 (mfm_model.py:60-61).  Batches beyond the row kernels' range (staged kernels, latent.hip) give the
   // early-fusion encoder's fc1 a stage of its own: the four heads together are the largest weight span (89 KB at the MOSI
   // sizes), alone it is 58 KB, and the LDS that frees doubles the rows a workgroup carries (backward 4 -> 8).
-  const int lat_row_maxb = opt_get("MFM_LATENT_ROW_MAXB") ? atoi(opt_get("MFM_LATENT_ROW_MAXB")) : 256;   // tuning override
+  const int lat_row_maxb = 256;
   bool split0 = V == 0 && c.B > lat_row_maxb && c.B > 4 * device_cus();   // (up to 4 rows x CUs one round of 4-row workgroups does)
   if (const char* e = opt_get("MFM_LATENT_SPLIT0")) split0 = V == 0 && atoi(e) != 0;
   for (int e = 0; e < nfc; ++e) {
@@ -287,7 +283,6 @@ int build(MfmPlan* P) {
   // rows per workgroup: small batches want many workgroups, large ones fewer atomics
   const size_t LDS_BUDGET = 150 * 1024;
   int R = (c.B <= 64) ? 4 : ((c.B <= 1024) ? 8 : 16);
-  if (const char* e = opt_get("MFM_LATENT_ROWS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) R = v; }   // tuning override
   if (((size_t)panel + 2 * (size_t)rs) * sizeof(float) <= LDS_BUDGET) {
     L.wpanel = panel;
     while (R > 1 && (2 * (size_t)R * rs + panel) * sizeof(float) > LDS_BUDGET) R >>= 1;
@@ -310,11 +305,9 @@ int build(MfmPlan* P) {
     // (measured, profiles/r02_latent_rows.txt: a round of 4-row workgroups 31 us, of 8-row ones 43 us), so the rows double
     // while the launch would otherwise need more than one round of workgroups
     int Rf = R;
-    const int want = opt_get("MFM_LATENT_ROWS_FWD") ? atoi(opt_get("MFM_LATENT_ROWS_FWD")) : 0;   // tuning override
-    while (Rf < 16 && (want ? Rf < want : cdiv(c.B, Rf) > device_cus()) && ((size_t)2 * Rf * rs + L.wpanel) * sizeof(float) <= LDS_BUDGET)
+    while (Rf < 16 && cdiv(c.B, Rf) > device_cus() && ((size_t)2 * Rf * rs + L.wpanel) * sizeof(float) <= LDS_BUDGET)
       Rf <<= 1;
     L.rows_fwd = Rf;
-    if (opt_get("MFM_PLAN_DEBUG")) fprintf(stderr, "[mfm plan] latent: rec_size %d floats, weight panel %d floats, rows per workgroup bwd %d fwd %d\n", rs, L.wpanel, R, Rf);
   }
   // Latency path (latent.hip, row kernels): one row per workgroup while that still fits the chip in one
   // wave of workgroups and every layer meets the vector-load shape requirements.
@@ -450,7 +443,7 @@ int build(MfmPlan* P) {
         for (int st = 0; st < L.nstages; ++st) mx = std::max(mx, std::max(L.nitems_fwd_c[ch][st], L.nitems_bwd_c[ch][st]));
       int in_sum = 0;
       for (int e = 0; e < 4; ++e) in_sum += L.enc_n[e];
-      if (mx <= 512 && in_sum <= 512 && !(opt_get("MFM_LATENT_512") && atoi(opt_get("MFM_LATENT_512")) == 0)) L.row_threads = 512;
+      if (mx <= 512 && in_sum <= 512) L.row_threads = 512;
     }
     if (L.nch > 1)       // whole-stage counts (bias-gradient loops of the backward walk all layers of a stage)
       for (int st = 0; st < L.nstages; ++st) {
@@ -461,7 +454,6 @@ int build(MfmPlan* P) {
   }
 
   P->lat_ops_off = carve(cur, (int64_t)(sizeof(P->lat_ops) / (sizeof(float))));
-  P->dbg_off = carve(cur, 128);     // 64 x u64 debug timestamps
   P->pf_flags = (V == 0) ? carve(cur, (int64_t)4 * P->T * PROJ_ROLE_FLAGS) : -1;
   if ((long)(P->n_enc > 3 ? P->n_enc : 3) * c.B < 6L * device_cus() && !P->seq_bf16) {        // (one-row BPTT tiles)
     for (int i = 0; i < P->n_enc + 3; ++i) {

@@ -86,7 +86,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
   // up to 5120 rows: decoder fc1, the squared error AND (training) dH = dx_hat Wfc run as one launch (dec_fc1.hip) whose
   // column groups add into dH (bf16 plans: operands rounded to bf16 in the kernel); larger T*B, shapes it does not take and
   // MFM_FC1_FUSED=0 use the grouped GEMMs (F4, B0)
-  const bool fc1_env_on = !(opt_get("MFM_FC1_FUSED") && atoi(opt_get("MFM_FC1_FUSED")) == 0);
+  const bool fc1_env_on = !opt_disabled("MFM_FC1_FUSED");
   long fc1_max_rows = 5120;                        // measured crossover (profiles/r02_dec_fc1.txt)
   if (const char* e = opt_get("MFM_FC1_FUSED_MAXROWS")) fc1_max_rows = atol(e);
   const bool fc1_fused = fc1_env_on && TB <= fc1_max_rows && !P->st16;      // (the fused kernel reads fp32 hidden states)
@@ -125,8 +125,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
       if (rc0 != MFM_OK) return rc0;
       pjp = &PJD; P->pj_pack_call = P->calls;
     }
-    if (st16 && train && !(xhat_out && (xhat_out[0] || xhat_out[1] || xhat_out[2])) &&
-        !(opt_get("MFM_FC1_LARGE") && atoi(opt_get("MFM_FC1_LARGE")) == 0)) {
+    if (st16 && train && !(xhat_out && (xhat_out[0] || xhat_out[1] || xhat_out[2]))) {
       DecFc1LargeLaunch FLp;
       memset(&FLp, 0, sizeof(FLp));
       FLp.n_items = 3; FLp.rows = (int)TB;
@@ -207,7 +206,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
   // workgroups of the encoder recurrence launch
   WtImgItem wt_items[MFM_IMG_MAX];
   int n_wt_items = 0, n_wf_items = 0;
-  if (train && !seq_bf16 && !(opt_get("MFM_WT_IMG") && atoi(opt_get("MFM_WT_IMG")) == 0)) {
+  if (train && !seq_bf16 && !opt_disabled("MFM_WT_IMG")) {
     bool all = true;
     for (int i = 0; i < P->n_enc + 3; ++i) all = all && P->wt_img[i] >= 0;
     if (all) {
@@ -225,7 +224,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
       }
       // launches without projection role workgroups (MFM_KL / MFM, B > 32): the decoders' forward-order images (lstm_seq_dev.h)
       // ride on the same image-writer blocks, behind the transposed ones
-      if (T >= 2 && !(opt_get("MFM_WF_IMG") && atoi(opt_get("MFM_WF_IMG")) == 0) && (long)3 * B < 6L * device_cus()) {
+      if (T >= 2 && !opt_disabled("MFM_WF_IMG") && (long)3 * B < 6L * device_cus()) {
         bool ok = true;
         for (int k = 0; k < 6; ++k) ok = ok && P->wf_img[k] >= 0;
         for (int k = 0; k < 6 && ok; ++k) {
@@ -247,7 +246,6 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
     L.ops = reinterpret_cast<const LatOp*>(W + P->lat_ops_off);
     L.items_fwd = reinterpret_cast<const int*>(W + P->lat_items_off);
     L.items_bwd = L.items_fwd + (size_t)4 * MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4;
-    if (opt_get("MFM_LATENT_DBG")) L.dbg = reinterpret_cast<unsigned long long*>(W + P->dbg_off);
     for (int e = 0; e < 4; ++e) {
       if (e == 3 && V != 0) { L.enc_h[e] = W + P->zyin; L.enc_ld[e] = P->nzy; continue; }
       L.enc_h[e] = st16 ? W + P->h_last[e] : W + P->enc[e].hs + (int64_t)(T - 1) * B * P->enc[e].Hp;
@@ -282,7 +280,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
     // training steps: the BPTT launches of this step take their transposed weights from images the role workgroups write
     if (n_wt_items == 7) { for (int i = 0; i < 7; ++i) PR.wt[i] = wt_items[i]; PR.n_wt = 7; }
     // the decoders' steps >= 1 weights in the forward's register order: their launch reloads them with coalesced loads
-    if (!(opt_get("MFM_WF_IMG") && atoi(opt_get("MFM_WF_IMG")) == 0)) {
+    if (!opt_disabled("MFM_WF_IMG")) {
       for (int k = 0; k < 6; ++k) {           // W_ih (the step-0 weights) first: the decoder launch asks for them first
         const int m = k % 3;
         const bool sum = k >= 3;
@@ -418,9 +416,8 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
     }
     int rc = MFM_ERR_UNSUPPORTED;
     // bf16-resident training steps: fc1, the squared error, d x_hat and dH in one launch of persistent workgroups
-    // (dec_fc1_large.hip); MFM_FC1_LARGE=0 keeps the two grouped GEMMs
-    if (st16 && train && !(xhat_out && (xhat_out[0] || xhat_out[1] || xhat_out[2])) &&
-        !(opt_get("MFM_FC1_LARGE") && atoi(opt_get("MFM_FC1_LARGE")) == 0)) {
+    // (dec_fc1_large.hip)
+    if (st16 && train && !(xhat_out && (xhat_out[0] || xhat_out[1] || xhat_out[2]))) {
       DecFc1LargeLaunch FL;
       memset(&FL, 0, sizeof(FL));
       FL.n_items = 3; FL.rows = (int)TB;

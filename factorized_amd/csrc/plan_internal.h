@@ -80,7 +80,7 @@ struct MfmPlan {
   int64_t ws_floats;
   mfm::LatentDev lat;
   mfm::LatOp lat_ops[MFM_LAT_MAXOPS];
-  int64_t lat_ops_off, dbg_off, lat_grd, lat_items_off;
+  int64_t lat_ops_off, lat_grd, lat_items_off;
   int lay_f1[4], lay_m1[4], lay_c1, lay_mc;   // record offsets kept for mfm_plan_latent_layout
   std::vector<int> lat_items;       // row-path item tables: forward then backward, [MAXSTAGES][1024][4] each
   // timing

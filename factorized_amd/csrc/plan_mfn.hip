@@ -56,7 +56,7 @@ int mfn_forward(MfmPlan* P, const float* params, int train, uint64_t seed, float
     // profiles/r02_lin_rows.txt); bf16 plans, larger batches and MFM_LIN_ROWS=0 keep the grouped GEMM
     long lr_max = 5120;
     if (const char* e = opt_get("MFM_LIN_ROWS_MAXROWS")) lr_max = atol(e);
-    const bool lr_on = prec == 0 && TB <= lr_max && !(opt_get("MFM_LIN_ROWS") && atoi(opt_get("MFM_LIN_ROWS")) == 0);
+    const bool lr_on = prec == 0 && TB <= lr_max && !opt_disabled("MFM_LIN_ROWS");
     auto rows = [&](const MfmGemmDesc& d, int kind, float* aux, float p, unsigned op_id) {
       LinRowsItem it;
       memset(&it, 0, sizeof(it));
@@ -218,7 +218,7 @@ int mfn_backward(MfmPlan* P, const float* params, float* W, float* grads, hipStr
     // fp32 plans with few rows: the four input-gradient products as row-block launches too (lin_rows.hip, trans = 1)
     long lr_max = 5120;
     if (const char* e = opt_get("MFM_LIN_ROWS_MAXROWS")) lr_max = atol(e);
-    const bool lr_on = prec == 0 && TB <= lr_max && !(opt_get("MFM_LIN_ROWS") && atoi(opt_get("MFM_LIN_ROWS")) == 0);
+    const bool lr_on = prec == 0 && TB <= lr_max && !opt_disabled("MFM_LIN_ROWS");
     auto rows = [&](const MfmGemmDesc& d, int kind, float* aux) {
       LinRowsItem it;
       memset(&it, 0, sizeof(it));

@@ -19,7 +19,7 @@
 //     image in LDS) and one 16-byte store per row fragment.
 // Measured at B = 2048 (T*B = 40960 rows, MOSI sizes): 121 us (gemm_panel) + 28 us (x_to_bf16) -> 57 us.  What is left is the
 // per-CU traffic itself: 208 KB of x + 488 KB of tiles in, 307 KB of gates + 110 KB of x16 out = 1.1 MB per workgroup at
-// the ~10 B/clk a CU exchanges with the L2 (49 us); the tile stream alone (MFM_PROJ16_DBG=15) takes 22 us whatever the
+// the ~10 B/clk a CU exchanges with the L2 (49 us); the tile stream alone takes 22 us whatever the
 // pipeline depth (3, 4, 5 stages measured equal).
 #include <stdlib.h>
 #include <string.h>
@@ -45,7 +45,7 @@ struct PjDev {
   const float* x; int64_t lda; int M, K, KP;
   const __bf16* wimg; const float* bimg;
   __bf16* x16; int x16_ld; int xsrc0[3], xn[3], xdst0[3];
-  PjGroupDev g[PJ_MAXG]; int ngroups, ntiles, nbias, S, dbg;
+  PjGroupDev g[PJ_MAXG]; int ngroups, ntiles, nbias, S;
   int ns, tb[9];                 // column splits (few row panels): workgroup (panel, y) runs the jobs whose tiles are [tb[y], tb[y + 1])
   float* zero_ptr[MFM_GEMM_ZSPANS]; int64_t zero_n[MFM_GEMM_ZSPANS];
 };
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(PJ_THREADS + 64) void proj_bf16_kernel(const PjDev 
     const unsigned gmagic = (1u << 24) / (unsigned)gpr + 1u;
     auto div_gpr = [&](int idx) { return (int)(((unsigned)idx * gmagic) >> 24); };
     constexpr int U = 14;                         // 16-byte loads in flight per thread (HBM latency x 64 B/clk wants ~100 KB)
-    for (int base = tid; base < ((L.dbg & 8) ? 0 : total); base += PJ_THREADS * U) {
+    for (int base = tid; base < total; base += PJ_THREADS * U) {
       f32x4 v[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(PJ_THREADS + 64) void proj_bf16_kernel(const PjDev 
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   // ---- side output: the padded bf16 image of these rows (modality slices on 16-column boundaries, pads zero)
-  if (L.x16 && ysplit == 0 && !(L.dbg & 1)) {
+  if (L.x16 && ysplit == 0) {
     const int cpr = L.x16_ld >> 3;
     const unsigned cmagic = (1u << 24) / (unsigned)cpr + 1u;
     for (int idx = tid; idx < BM * cpr; idx += PJ_THREADS) {
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(PJ_THREADS + 64) void proj_bf16_kernel(const PjDev 
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int kt = G.kt0; kt < G.kt1; ++kt, ++t) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // tile t landed (the requesting wave waited for it)
-        if (wave_live && !(L.dbg & 4)) {
+        if (wave_live) {
           const unsigned char* B = Bt + ((t - tb) % S) * (PJ_TILE * 2);
           bf16x8 wf[FN], xf[FM];
 #pragma unroll
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(PJ_THREADS + 64) void proj_bf16_kernel(const PjDev 
       // the job's results.  Tile row 16 fn + i of this wave's 32 carries column 8 (i / 4) + 4 fn + i % 4 (proj_pack_kernel),
       // and accumulator register r of lane (bi, q) is [MFMA row 4q + r][x row bi]: the lane holds columns 8q .. 8q+7 of
       // row bi -- bias add, one 16-byte store per row fragment
-      if (wave_live && !(L.dbg & 2)) {
+      if (wave_live) {
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(Bias + G.bias_off + colw + 8 * q);
         const f32x4 b1 = *reinterpret_cast<const f32x4*>(Bias + G.bias_off + colw + 8 * q + 4);
 #pragma unroll
@@ -269,15 +269,13 @@ int proj_bf16_plan(const PanelLaunch& L, ProjPlan* out) {
     if (forced && cand[i] != forced) continue;
     const size_t a_lds = ((size_t)cand[i] * (KP + 8) * 2 + 1023) / 1024 * 1024;
     int S = 6;
-    if (const char* e = opt_get("MFM_PROJ16_STAGES")) S = std::max(3, std::min(6, atoi(e)));
     while (S >= 3 && a_lds + (size_t)S * PJ_TILE * 2 + (size_t)nb * 4 > 160 * 1024) --S;
     if (S < 3) continue;
     // column splits (round 5): with few row panels, ns workgroups share a panel and stream 1 / ns of the tiles each
     const long npanels = cdiv(std::max(L.M, 1), cand[i]);
     int jobs = 0;
     for (int g = 0; g < L.ngroups; ++g) jobs += out->nchunks[g];
-    int ns = (int)std::max<long>(1, std::min<long>(std::min(8, jobs), cus / npanels));
-    if (const char* e = opt_get("MFM_PROJ16_NS")) ns = std::max(1, std::min(std::min(8, jobs), atoi(e)));
+    const int ns = (int)std::max<long>(1, std::min<long>(std::min(8, jobs), cus / npanels));
     const long rounds = (npanels * ns + cus - 1) / cus;
     const double cost = (double)rounds * (100.0 / ns + cand[i]);
     if (out->BM == 0 || cost < best) { out->BM = cand[i]; out->S = S; out->ns = ns; out->lds = a_lds + (size_t)S * PJ_TILE * 2 + (size_t)nb * 4; best = cost; }
@@ -353,7 +351,6 @@ int proj_bf16_launch(const PanelLaunch& L, const ProjPlan& P, const void* wimg, 
     d.c = reinterpret_cast<__bf16*>(G.c); d.ldc = G.ldc; d.n = G.n; d.kt0 = P.kt0[i]; d.kt1 = P.kt0[i] + P.nkt[i]; d.bias_off = P.bias_off[i];
   }
   D.ngroups = L.ngroups; D.ntiles = P.ntiles; D.nbias = P.nbias; D.S = P.S;
-  D.dbg = opt_get("MFM_PROJ16_DBG") ? atoi(opt_get("MFM_PROJ16_DBG")) : 0;     // tuning aid: skip parts of the kernel
   if (zs) {
     for (int i = 0; i < MFM_GEMM_ZSPANS; ++i) {
       if (zs->n[i] <= 0) continue;
@@ -362,7 +359,7 @@ int proj_bf16_launch(const PanelLaunch& L, const ProjPlan& P, const void* wimg, 
     }
   }
   // column splits: the jobs (group, 128-column chunk) are dealt to `ns` workgroups per panel in contiguous ranges of about equal
-  // tile counts (MFM_PROJ16_NS forces a count when the plan is built, 1 = off)
+  // tile counts
   const int npanels = cdiv(L.M, P.BM);
   {
     int jobs = 0;

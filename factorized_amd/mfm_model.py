@@ -23,8 +23,6 @@ tensors or a missing library raise.  `.cuda()` calls inside the reference's forw
 The fastest way to train is not this autograd path but `factorized_amd.engine.MFMEngine.train_step`
 (one C call per step); `MFM_KL_EF.engine` exposes it on the same parameter storage.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -218,7 +216,7 @@ class MFN(nn.Module):
         w1m = self.gamma1_fc1.weight[:, na:].contiguous()
         w2m = self.gamma2_fc1.weight[:, na:].contiguous()
         H1, H2 = w1m.shape[0], w2m.shape[0]
-        if _MemFn.supported(self.mem_dim, H1, H2) and not os.environ.get("MFM_MFN_LOOP"):   # env: A/B timing only
+        if _MemFn.supported(self.mem_dim, H1, H2):
             # the sequential part (:177-181) as one persistent HIP kernel per direction
             mem = _MemFn.apply(g1_att, g2_att, cHat, w1m, w2m, self.gamma1_fc2.weight, self.gamma1_fc2.bias,
                                self.gamma2_fc2.weight, self.gamma2_fc2.bias,
@@ -319,17 +317,11 @@ class _FactorizedMFN(_FusedEngineMixin, nn.Module):
         x_a = x[:, :, self.d_l:self.d_l + self.d_a]
         x_v = x[:, :, self.d_l + self.d_a:]
         t = x.shape[0]
-        if os.environ.get("MFM_NO_SEQ_GROUP"):               # A/B timing only: one launch set per LSTM
-            zl_last = self.encoder_l.forward(x_l)
-            za_last = self.encoder_a.forward(x_a)
-            zv_last = self.encoder_v.forward(x_v)
-            mfn_last = self.mfn_encoder.forward(x)
-        else:
-            mfn = self.mfn_encoder
-            (zl_last, za_last, zv_last), states = seq_group(
-                [(x_l, self.encoder_l), (x_a, self.encoder_a), (x_v, self.encoder_v)],
-                [(x_l, mfn.lstm_l), (x_a, mfn.lstm_a), (x_v, mfn.lstm_v)])
-            mfn_last = mfn.forward(x, states)
+        mfn = self.mfn_encoder
+        (zl_last, za_last, zv_last), states = seq_group(
+            [(x_l, self.encoder_l), (x_a, self.encoder_a), (x_v, self.encoder_v)],
+            [(x_l, mfn.lstm_l), (x_a, mfn.lstm_a), (x_v, mfn.lstm_v)])
+        mfn_last = mfn.forward(x, states)
         if self._use_kl:
             zy, zl, za, zv, lvy, lvl, lva, lvv = linear_group([
                 (mfn_last, self.last_to_zy_fc1), (zl_last, self.last_to_zl_fc1), (za_last, self.last_to_za_fc1),

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Module-path (drop-in) step times of the three model classes on one GPU: reference-style driver loop
 (model.forward, torch losses, loss.backward(), torch.optim.Adam.step()), B=32, T=20, canonical sizes.
-MFM_KL_EF is also timed on the fused one-call path for comparison.  `MFM_MFN_LOOP=1` forces the
-step-by-step MFN memory loop (the pre-kernel implementation) for an A/B."""
+MFM_KL_EF is also timed on the fused one-call path for comparison."""
 import os
 import sys
 import time

@@ -27,9 +27,9 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.exported_names()) == names
 
 
-def test_abi_version_and_error_text():
+def test_abi_version_5_and_error_text():
     L = _lib.lib()
-    assert L.mfm_abi_version() == 4
+    assert L.mfm_abi_version() == 5
     rc = L.mfm_gemm_grouped_f32(None, 0, None)
     assert rc == -1
     assert b"no problems" in L.mfm_last_error()
