@@ -59,6 +59,15 @@ class AdamSpan(C.Structure):
 MFM_ADAM_MAX_SPANS = 8
 
 
+class SgdSpan(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float),
+                ("momentum", C.c_float), ("dampening", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+MFM_SGD_MAX_SPANS = 112
+MFM_SGD_NESTEROV, MFM_SGD_MAXIMIZE, MFM_SGD_FIRST = 1, 2, 4
+
+
 class LossWeights(C.Structure):
     _fields_ = [("disc", C.c_float), ("gen_l", C.c_float), ("gen_a", C.c_float), ("gen_v", C.c_float), ("reg", C.c_float),
                 ("write_disc_loss", C.c_int32)]
@@ -110,6 +119,9 @@ _SIGS = {
                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mfm_adam_flat_spans_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamSpan), C.c_int32,
                                               C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "mfm_sgd_flat_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SgdSpan), C.c_int32, C.c_float, C.c_void_p]),
+    "mfm_sgd_flat_spans_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SgdSpan), C.c_int32, C.c_float,
+                                             C.c_void_p, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -155,6 +155,10 @@ int adam_spans_launch(float* p, const float* g, float* m, float* v, const MfmAda
                       float beta1, float beta2, float eps, float grad_scale, hipStream_t stream, const float* guard = nullptr);
 int fill_launch(float* p, int64_t n, float val, hipStream_t stream);
 
+// sgd.hip -- momentum SGD over spans of a flat buffer (include/mfm_hip.h, mfm_sgd_flat_spans); guard as for adam_launch
+int sgd_spans_launch(float* p, const float* g, float* buf, const MfmSgdSpan* spans, int nspans, float grad_scale,
+                     hipStream_t stream, const float* guard);
+
 // mfn_att.hip -- row-wise glue of the MFN attention block (everything between its GEMMs)
 struct MfnCs { const float* cs[3]; float* dcx[3]; int h[3]; int T, B; };     // the three MFN LSTMs' cell states [T,B,Hp]
 int mfn_cstar_launch(const MfnCs& c, float* cstar, hipStream_t stream);

@@ -14,7 +14,9 @@ nn.Parameter is a view into ONE flat buffer) and whose `.grad`s are the views of
 tensors received no gradient: like torch.optim.Adam, a parameter without a gradient is skipped and step counts are kept
 per tensor.  Everything else (other modules, models on the composed autograd path) goes through a stock
 `torch.optim.Adam` with the same hyper-parameters.  `torch.optim.Adam` itself keeps working too -- it is just host-bound
-(78 tensors per step); see INTEGRATION.md for the measured step times.
+(78 tensors per step); see INTEGRATION.md for the measured step times.  `SGD` does the same for the reference's other optimizer
+line (`optim.SGD(model.parameters(), lr=config["lr"], momentum=config["momentum"])`, mfm_mosi.py:404): one launch of
+`mfm_sgd_flat_spans_guarded` per fused model and step, with torch.optim.SGD's arithmetic and per-group hyper-parameters.
 
 `zero_grad()` of this class clears a fused model's flat gradient buffer with one launch and marks every tensor "no gradient
 yet" (= torch's `set_to_none=True`: the next `step()` skips tensors the next backward does not reach) while leaving the
@@ -29,7 +31,6 @@ from . import _lib
 
 ReduceLROnPlateau = torch.optim.lr_scheduler.ReduceLROnPlateau      # convenience: `optim.lr_scheduler` users import torch's
 lr_scheduler = torch.optim.lr_scheduler
-SGD = torch.optim.SGD
 
 
 def _owner(p):
@@ -45,7 +46,7 @@ _FOREIGN = {}
 
 
 def _foreign_step_hook(opt, args, kwargs):
-    if isinstance(opt, Adam) or getattr(opt, "_mfm_inner", False):
+    if isinstance(opt, (Adam, SGD)) or getattr(opt, "_mfm_inner", False):
         return
     key = id(opt)
     n = sum(len(g["params"]) for g in opt.param_groups)
@@ -379,6 +380,384 @@ class Adam(torch.optim.Optimizer):
         for group in self.param_groups:
             for p in group["params"]:
                 if id(p) in handled or p.grad is None:
+                    continue
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.detach_()
+                    p.grad.zero_()
+
+
+_SGD_HYPER = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize")
+
+
+class SGD(torch.optim.Optimizer):
+    """torch.optim.SGD with momentum (same signature, validation and arithmetic) whose fused models are updated by ONE launch of
+    `mfm_sgd_flat_spans_guarded` per step: the reference's other optimizer line (mfm_mosi.py:404, commented out under the Adam
+    line in every driver).
+
+    A fused model (`MFM_KL_EF`, `MFM_KL`, `MFM`) takes the flat path when the optimizer's parameter groups together hold all of
+    its parameters -- one group or several: each tensor becomes a span of the launch with its group's hyper-parameters
+    (adjacent tensors with equal values merge).  Such a model keeps its in-launch hand-overs (the update honours the gradient
+    guard).  A tensor without a gradient is skipped, its momentum buffer included, as torch skips a parameter whose `.grad` is
+    None; `zero_grad(set_to_none=False)` keeps zero gradients in place, so a tensor that once had a gradient keeps moving on its
+    momentum (the reference's PyTorch 0.4).  Everything else -- other modules, a model only partly in the groups, frozen or
+    hooked parameters, `fast_grads = False` -- goes through an inner torch.optim.SGD; momentum buffers move between the two.
+
+    Momentum buffers are kept per model as ONE flat buffer plus a per-tensor "buffer exists" flag (torch's
+    `state[p]["momentum_buffer"] is not None`); the slot of a tensor whose flag is False always holds zeros (every place that
+    clears a flag clears the slot).  A step the gradient guard skipped writes nothing, yet the host has already marked the
+    buffers of that step's first-step tensors as existing.  With dampening 0 that is exact: the slot still holds zeros and
+    `momentum * 0 + d` is the first step's `d`.  With dampening != 0 it is not, so such a step also copies the guard word aside,
+    and the next step (or state_dict()) reads it -- one synchronisation, once per first step -- and, if the step was skipped,
+    marks those buffers as not existing again.
+
+    Which side holds a model's live buffers is tracked per model: a model that steps through the inner optimizer (from its
+    first step on, or after flat steps) is "away", and its next flat step takes the inner optimizer's buffers back."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 foreach=None, differentiable=False, fused=None):
+        # torch.optim.SGD's checks, in its order and with its messages
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if differentiable:
+            raise ValueError("factorized_amd.optim.SGD: differentiable=True is not built (the flat update is not part of the "
+                             "autograd graph); use torch.optim.SGD")
+        if fused:
+            raise ValueError("factorized_amd.optim.SGD: fused=True is torch's own fused kernel; this class fuses on its own "
+                             "(leave fused unset)")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=maximize, foreach=foreach, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        import weakref
+        # module -> flat momentum state of a fused model (weak keys: a model that is gone takes its state with it)
+        self._fused = weakref.WeakKeyDictionary()
+        self._fallback = None       # inner torch.optim.SGD over everything that is not fused
+        self._fallback_ids = None
+        self._fm_key = None
+        self._fm_list = []
+        self._pending_fused = None  # fused states of a load_state_dict() waiting for their models' first step
+        self._pending_fallback = None
+        # fused models whose live momentum buffers are in the inner optimizer (they stepped through it since their last flat step)
+        self._away = weakref.WeakSet()
+        self._fused_models()        # marks the models this optimizer owns (their hand-overs stay on)
+
+    # ------------------------------------------------------------------ helpers
+    def _fused_models(self):
+        """[(model, group index of every tensor)] for the fused models whose parameters all lie in this optimizer's groups;
+        cached while the groups hold the same lists of the same lengths"""
+        key = tuple((id(g["params"]), len(g["params"]), id(g["params"][0]) if g["params"] else 0) for g in self.param_groups)
+        if key == self._fm_key and all(r() is not None for r, _ in self._fm_list):
+            return [(r(), gi) for r, gi in self._fm_list]
+        import weakref
+        gid = {}
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                gid[id(p)] = k
+        seen, out = set(), []
+        for g in self.param_groups:
+            for p in g["params"]:
+                m = _owner(p)
+                if m is None or id(m) in seen:
+                    continue
+                seen.add(id(m))
+                if all(id(q) in gid for q in m._plist):
+                    out.append((weakref.ref(m), np.array([gid[id(q)] for q in m._plist], dtype=np.int64)))
+                    m._guarded = weakref.ref(self)
+        self._fm_key, self._fm_list = key, out
+        return [(r(), gi) for r, gi in out]
+
+    def _state_for(self, m, eng):
+        st = self._fused.get(m)
+        n = len(eng.layout.slots)
+        if st is None or st["total"] != eng.layout.total or (st["buf"] is not None and st["buf"].device != eng.params.device):
+            order = np.argsort([o for o, _, _ in eng.layout.slots], kind="stable")
+            starts = [eng.layout.slots[i][0] for i in order] + [eng.layout.guard]
+            st = dict(total=eng.layout.total, buf=None, have=np.zeros(n, dtype=bool), pending=None, gseen=None,
+                      order=order, starts=starts, spans={})
+            if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
+                saved = self._pending_fused.pop(0)
+                if saved["total"] != eng.layout.total or len(saved["have"]) != n:
+                    raise _lib.MfmError(
+                        "factorized_amd.optim.SGD.load_state_dict: the saved fused state (%d elements, %d tensors) does not fit "
+                        "this model's flat layout (%d elements, %d tensors) -- a checkpoint of another model / library version; "
+                        "refusing to restart the momentum silently" % (saved["total"], len(saved["have"]), eng.layout.total, n))
+                st["have"][:] = np.asarray(saved["have"], dtype=bool)
+                if saved["buf"] is not None:
+                    st["buf"] = saved["buf"].to(eng.params.device, copy=True)
+                    for i in np.flatnonzero(~st["have"]):
+                        o, k, _ = eng.layout.slots[i]
+                        st["buf"][o:o + k].zero_()       # (no buffer: a zero slot, whatever the checkpoint held there)
+            self._fused[m] = st
+        return st
+
+    @staticmethod
+    def _resolve_pending(st):
+        """a first step with dampening != 0 that the guard may have skipped: read the guard word it saw (see the class doc)"""
+        if st["pending"] is not None:
+            if not float(st["gseen"].item()) == 0.0:
+                st["have"][st["pending"]] = False
+            st["pending"] = None
+
+    def _buf(self, st, like):
+        if st["buf"] is None:
+            st["buf"] = torch.zeros_like(like)
+        return st["buf"]
+
+    def _migrate_back(self, m, st, eng):
+        """the model returns to the flat path after steps through the inner optimizer: its momentum buffers (the live ones) come
+        back into the flat state"""
+        fb = self._fallback
+        for i, p in enumerate(m._plist):
+            s = fb.state.get(p) if fb is not None else None
+            b = s.get("momentum_buffer") if s else None
+            o, n, shp = eng.layout.slots[i]
+            if b is not None:
+                self._buf(st, eng.params)[o:o + n].view(shp).copy_(b)
+            elif st["buf"] is not None:
+                st["buf"][o:o + n].zero_()
+            st["have"][i] = b is not None
+            if s is not None:
+                del fb.state[p]
+        st["spans"].clear()
+
+    def _migrate_out(self, m, st):
+        """the model steps through the inner optimizer (a parameter was frozen / got a hook): its momentum buffers move there --
+        on every such switch, so that freeze -> unfreeze -> freeze keeps the momentum"""
+        self._resolve_pending(st)
+        fb = self._fallback
+        for i, p in enumerate(m._plist):
+            if st["have"][i]:
+                o, n, shp = m.engine.layout.slots[i]
+                fb.state[p] = dict(momentum_buffer=st["buf"][o:o + n].view(shp).clone())
+            else:
+                fb.state.pop(p, None)
+
+    def _spans_of(self, st, present, gidx):
+        """ctypes span tables for this step (cached per pattern of present tensors, existing buffers and hyper-parameters)"""
+        hyper = tuple((float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), float(g["dampening"]),
+                       (_lib.MFM_SGD_NESTEROV if g["nesterov"] else 0) | (_lib.MFM_SGD_MAXIMIZE if g["maximize"] else 0))
+                      for g in self.param_groups)
+        have = st["have"]
+        key = (present.tobytes(), have.tobytes(), hyper)
+        hit = st["spans"].get(key)
+        if hit is not None:
+            return hit
+        starts, spans, first, first_damp = st["starts"], [], [], []
+        for k, i in enumerate(st["order"]):
+            if not present[i]:
+                continue
+            lr, wd, mom, damp, fl = hyper[gidx[i]]
+            if mom != 0.0 and not have[i]:
+                fl |= _lib.MFM_SGD_FIRST
+                first.append(i)
+                if damp != 0.0:
+                    first_damp.append(i)
+            b, e, h = starts[k], starts[k + 1], (lr, wd, mom, damp, fl)
+            if spans and spans[-1][1] == b and spans[-1][2] == h:
+                spans[-1] = (spans[-1][0], e, h)
+            else:
+                spans.append((b, e, h))
+        tables = []
+        for k in range(0, len(spans), _lib.MFM_SGD_MAX_SPANS):
+            part = spans[k:k + _lib.MFM_SGD_MAX_SPANS]
+            arr = (_lib.SgdSpan * len(part))()
+            for j, (b, e, (lr, wd, mom, damp, fl)) in enumerate(part):
+                arr[j].begin, arr[j].end, arr[j].flags = b, e, fl
+                arr[j].lr, arr[j].weight_decay, arr[j].momentum, arr[j].dampening = lr, wd, mom, damp
+            tables.append((arr, len(part)))
+        momentum = any(h[2] != 0.0 for _, _, h in spans)
+        hit = (tables, np.array(first, dtype=np.int64), np.array(first_damp, dtype=np.int64), momentum)
+        if len(st["spans"]) > 32:
+            st["spans"].clear()
+        st["spans"][key] = hit
+        return hit
+
+    def _fused_step(self, m, gidx):
+        eng = m.engine
+        import weakref
+        m._guarded = weakref.ref(self)          # (per step: the optimizer that steps the model answers for the guard)
+        gflat = getattr(m, "_grad_flat", None)
+        if gflat is None or not m._grad_views_attached():
+            return False                     # gradients are ordinary per-tensor tensors: the inner optimizer handles them
+        if not m._fast_last:
+            m._detach_grad_views()           # (Adam._fused_step: a parameter was frozen / got a hook after fast-path steps)
+            return False
+        if eng.poll_status():
+            import warnings
+            eng.check_status(raise_on_error=False)
+            warnings.warn(eng.status_message(), RuntimeWarning, stacklevel=3)
+        st = self._state_for(m, eng)
+        if m in self._away:
+            self._migrate_back(m, st, eng)
+            self._away.discard(m)
+        self._resolve_pending(st)
+        tables, first, first_damp, momentum = self._spans_of(st, m._grad_present, gidx)
+        if not tables:
+            return True                      # no tensor has a gradient: torch's step does nothing either
+        L = _lib.lib()
+        stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index))
+        buf = C.c_void_p(self._buf(st, eng.params).data_ptr()) if momentum else C.c_void_p(None)
+        # guard word of the flat gradient buffer (Adam._fused_step): a NaN there leaves parameters and buffers alone
+        guard = C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard)
+        for arr, n in tables:
+            _lib.check(L.mfm_sgd_flat_spans_guarded(C.c_void_p(eng.params.data_ptr()), C.c_void_p(gflat.data_ptr()), buf, arr, n,
+                                                    1.0, guard, stream), "mfm_sgd_flat_spans_guarded")
+        if len(first):
+            st["have"][first] = True
+            if len(first_damp):
+                if st["gseen"] is None:
+                    st["gseen"] = torch.zeros(1, dtype=torch.float32, device=eng.params.device)
+                g = eng.layout.guard
+                st["gseen"].copy_(gflat[g:g + 1])
+                st["pending"] = first_damp
+        return True
+
+    def _fallback_step(self, rest):
+        if not rest:
+            return
+        ids = tuple(id(p) for _, ps in rest for p in ps)
+        if self._fallback is None or self._fallback_ids != ids:
+            old = self._fallback
+            groups = [dict(params=ps, **{k: g[k] for k in _SGD_HYPER}) for g, ps in rest]
+            self._fallback = torch.optim.SGD(groups, foreach=self.defaults["foreach"])
+            self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
+            self._fallback_ids = ids
+            if old is not None:                     # buffers of tensors that stay with the inner optimizer stay too
+                idset = set(ids)
+                for p, s in old.state.items():
+                    if id(p) in idset:
+                        self._fallback.state[p] = s
+            if self._pending_fallback is not None:
+                self._fallback.load_state_dict(self._pending_fallback)
+                self._pending_fallback = None
+        idset = set(ids)
+        for m, _ in self._fused_models():
+            if m in self._away or id(m._plist[0]) not in idset or not m._plist[0].is_cuda:
+                continue
+            # a fused model starts stepping through the inner optimizer: its flat buffers (if it has any, or a checkpoint's
+            # waiting for it) go there, and its next flat step takes them back
+            st = self._fused.get(m)
+            if st is None and self._pending_fused:
+                st = self._state_for(m, m.engine)
+            if st is not None:
+                self._migrate_out(m, st)
+            self._away.add(m)
+        for fg, (g, _) in zip(self._fallback.param_groups, rest):
+            for k in _SGD_HYPER:
+                fg[k] = g[k]                        # schedulers act on OUR groups
+        self._fallback.step()
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """torch's dict plus, under "fused", the momentum state of every fused model (in the order the models appear in the
+        parameter groups): its flat buffer (None before any momentum step) and the per-tensor "buffer exists" flags; plus the
+        inner optimizer's state under "fallback"."""
+        sd = super().state_dict()
+        fused = []
+        for m, _ in self._fused_models():
+            st = self._fused.get(m)
+            away = m in self._away
+            if st is None and not away:
+                continue
+            if not away:
+                self._resolve_pending(st)
+                buf = st["buf"].detach().clone() if st["buf"] is not None else None
+                have = st["have"].tolist()
+            else:                            # stepping through the inner optimizer: its buffers are the live ones
+                eng = m.engine
+                buf, have = torch.zeros_like(eng.params), []
+                for i, p in enumerate(m._plist):
+                    b = self._fallback.state.get(p, {}).get("momentum_buffer")
+                    if b is not None:
+                        o, n, shp = eng.layout.slots[i]
+                        buf[o:o + n].view(shp).copy_(b)
+                    have.append(b is not None)
+            fused.append(dict(total=m.engine.layout.total, buf=buf, have=have))
+        if self._pending_fused:          # loaded, not stepped yet: what was loaded is still the state
+            fused += [dict(f) for f in self._pending_fused]
+        sd["fused"] = fused
+        if self._fallback is not None:
+            sd["fallback"] = self._fallback.state_dict()
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        fused = sd.pop("fused", None)
+        fb = sd.pop("fallback", None)
+        super().load_state_dict(sd)
+        self._fused.clear()
+        import weakref
+        self._away = weakref.WeakSet()      # (the loaded fused entries hold every model's live buffers)
+        self._pending_fused = [dict(total=int(f["total"]), buf=f["buf"], have=list(f["have"])) for f in fused] if fused else None
+        self._pending_fallback = fb
+        if self._fallback is not None and fb is not None:
+            self._fallback.load_state_dict(fb)
+            self._pending_fallback = None
+
+    # ------------------------------------------------------------------ Optimizer interface
+    def step(self, closure=None):
+        """(Adam.step: not wrapped by torch's profile_hook_step; step hooks are still honoured)"""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.MfmError("factorized_amd.optim.SGD.step() inside a stream capture: the SGD update is eager only "
+                                "(hipGraph capture of a training step: train.GraphedModuleStep with optim.Adam(capturable=True))")
+        hooks = self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(_GLOBAL_PRE) > 1 or _GLOBAL_POST
+        if hooks:
+            for h in list(_GLOBAL_PRE.values()) + list(self._optimizer_step_pre_hooks.values()):
+                if h is not _foreign_step_hook:
+                    h(self, (closure,) if closure is not None else (), {})
+        prev = torch.is_grad_enabled()
+        torch._C._set_grad_enabled(False)
+        try:
+            loss = self._step(closure)
+        finally:
+            torch._C._set_grad_enabled(prev)
+        if hooks:
+            for h in list(self._optimizer_step_post_hooks.values()) + list(_GLOBAL_POST.values()):
+                h(self, (closure,) if closure is not None else (), {})
+        return loss
+    step.hooked = True
+
+    def _step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        done, ndone = set(), 0
+        for m, gidx in self._fused_models():
+            if m._plist[0].is_cuda and self._fused_step(m, gidx):
+                done.add(id(m))
+                ndone += len(m._plist)
+        if ndone == sum(len(g["params"]) for g in self.param_groups):
+            return loss                               # (the reference's case: one model, nothing left)
+        rest = []
+        for group in self.param_groups:
+            left = [p for p in group["params"] if id(_owner(p)) not in done] if done else list(group["params"])
+            if left:
+                rest.append((group, left))
+        self._fallback_step(rest)
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        cleared, nh = set(), 0
+        for m, _ in self._fused_models():
+            if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
+                m._zero_flat_grads(set_to_none)
+                cleared.add(id(m))
+                nh += len(m._plist)
+        if nh == sum(len(g["params"]) for g in self.param_groups):
+            return
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None or (cleared and id(_owner(p)) in cleared):
                     continue
                 if set_to_none:
                     p.grad = None

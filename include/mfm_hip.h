@@ -241,6 +241,32 @@ int mfm_adam_flat_spans_guarded(float* p, const float* g, float* m, float* v, co
                                 float lr, float beta1, float beta2, float eps, float grad_scale, const float* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused momentum SGD on one flat parameter buffer (torch.optim.SGD semantics, the reference's commented-out optimizer line
+ * mfm_mosi.py:404): p and the momentum buffer `buf` updated in place over up to MFM_SGD_MAX_SPANS disjoint element ranges,
+ * given in ascending order; elements outside every span keep p and buf untouched (torch skips a parameter whose .grad is
+ * None; several parameter groups give one model several sets of hyper-parameters).  Per element of a span:
+ *   d = g * grad_scale;  maximize: d = -d;  d += weight_decay * p
+ *   momentum != 0:  buf = FIRST ? d : momentum * buf + (1 - dampening) * d;   d = NESTEROV ? d + momentum * buf : buf
+ *   p -= lr * d
+ * A span with momentum 0 neither reads nor writes buf (buf may be NULL when no span has momentum); FIRST is the step that
+ * creates a tensor's buffer (torch: a clone of d), its old contents are not read.  begin/end are multiples of 4; lr,
+ * weight_decay and momentum >= 0.  `guard`: as for mfm_adam_flat_guarded (NULL in the unguarded form). */
+#define MFM_SGD_MAX_SPANS 112
+#define MFM_SGD_NESTEROV 1
+#define MFM_SGD_MAXIMIZE 2
+#define MFM_SGD_FIRST 4
+typedef struct MfmSgdSpan {
+  int64_t begin, end;
+  float lr, weight_decay, momentum, dampening;
+  int32_t flags; /* MFM_SGD_NESTEROV | MFM_SGD_MAXIMIZE | MFM_SGD_FIRST */
+  int32_t reserved;
+} MfmSgdSpan;
+int mfm_sgd_flat_spans(float* p, const float* g, float* buf, const MfmSgdSpan* spans /*host*/, int32_t nspans, float grad_scale,
+                       void* stream);
+int mfm_sgd_flat_spans_guarded(float* p, const float* g, float* buf, const MfmSgdSpan* spans /*host*/, int32_t nspans,
+                               float grad_scale, const float* guard, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached

@@ -1,5 +1,6 @@
 """ms per step of the reference's UNCHANGED loop (mfm_mosi.py:427-441 incl. its per-step .item()) on MFM_KL_EF, B=32, T=20:
-stock torch.optim.Adam vs factorized_amd.optim.Adam, per-tensor autograd path vs flat gradients, and the fused engine call."""
+stock torch.optim.Adam vs factorized_amd.optim.Adam, per-tensor autograd path vs flat gradients, torch.optim.SGD vs
+factorized_amd.optim.SGD (lr 0.01, momentum 0.9), and the fused engine call."""
 import os, sys, time
 import torch, torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,6 +46,23 @@ for name, opt_cls, fast, item in (("torch.optim.Adam, per-tensor autograd (round
     model = MFM_KL_EF(*cfgs)
     model.fast_grads = fast
     optimizer = opt_cls(model.parameters())
+    model = model.to("cuda")
+    model.train()
+    loop(model, optimizer, 30, item)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loop(model, optimizer, 300, item)
+    torch.cuda.synchronize()
+    print("%-70s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
+# the reference's other optimizer line (mfm_mosi.py:404) at the canonical lr 0.01, momentum 0.9, flat gradients
+for name, opt_cls, item in (("torch.optim.SGD(lr=0.01, momentum=0.9), flat gradients", torch.optim.SGD, True),
+                            ("factorized_amd.optim.SGD(lr=0.01, momentum=0.9), flat gradients", optim.SGD, True),
+                            ("factorized_amd.optim.SGD(lr=0.01, momentum=0.9), no per-step .item()", optim.SGD, False)):
+    import gc
+    model = optimizer = None
+    gc.collect(); torch.cuda.empty_cache()
+    model = MFM_KL_EF(*cfgs)
+    optimizer = opt_cls(model.parameters(), lr=config["lr"], momentum=config["momentum"])
     model = model.to("cuda")
     model.train()
     loop(model, optimizer, 30, item)
