@@ -198,6 +198,10 @@ class _FusedEngineMixin:
             mk = dict(disc=sel("fy_to_y_"), l=sel("decoder_l.", "zl_to_fl_"), a=sel("decoder_a.", "za_to_fa_"),
                       v=sel("decoder_v.", "zv_to_fv_"))
             mk["shared"] = ~(mk["disc"] | mk["l"] | mk["a"] | mk["v"])
+            # tensors no forward uses (the MFN's out_fc1 / out_fc2, as in the reference): torch leaves their .grad None.  The
+            # flat backward hands them a zero gradient, which moves nothing under plain Adam or SGD; an update with weight
+            # decay has to skip them itself (optim.Adam._ext_step)
+            mk["unreached"] = sel("mfn_encoder.out_fc")
             self._masks = mk
         return mk
 

@@ -68,6 +68,16 @@ MFM_SGD_MAX_SPANS = 112
 MFM_SGD_NESTEROV, MFM_SGD_MAXIMIZE, MFM_SGD_FIRST = 1, 2, 4
 
 
+class AdamExtSpan(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("step", C.c_int32), ("flags", C.c_int32), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+MFM_ADAMX_MAX_SPANS = 88
+MFM_ADAMX_MAXIMIZE, MFM_ADAMX_AMSGRAD, MFM_ADAMX_DECOUPLED = 1, 2, 4
+
+
 class LossWeights(C.Structure):
     _fields_ = [("disc", C.c_float), ("gen_l", C.c_float), ("gen_a", C.c_float), ("gen_v", C.c_float), ("reg", C.c_float),
                 ("write_disc_loss", C.c_int32)]
@@ -122,6 +132,10 @@ _SIGS = {
     "mfm_sgd_flat_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SgdSpan), C.c_int32, C.c_float, C.c_void_p]),
     "mfm_sgd_flat_spans_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SgdSpan), C.c_int32, C.c_float,
                                              C.c_void_p, C.c_void_p]),
+    "mfm_adam_ext_flat_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamExtSpan),
+                                          C.c_int32, C.c_float, C.c_void_p]),
+    "mfm_adam_ext_flat_spans_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(AdamExtSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

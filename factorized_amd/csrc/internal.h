@@ -159,6 +159,11 @@ int fill_launch(float* p, int64_t n, float val, hipStream_t stream);
 int sgd_spans_launch(float* p, const float* g, float* buf, const MfmSgdSpan* spans, int nspans, float grad_scale,
                      hipStream_t stream, const float* guard);
 
+// adam_ext.hip -- Adam / AdamW / AMSGrad over spans of a flat buffer, hyper-parameters and step count per span
+// (include/mfm_hip.h, mfm_adam_ext_flat_spans); vmax may be NULL when no span has MFM_ADAMX_AMSGRAD; guard as for adam_launch
+int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* vmax, const MfmAdamExtSpan* spans, int nspans,
+                          float grad_scale, hipStream_t stream, const float* guard);
+
 // mfn_att.hip -- row-wise glue of the MFN attention block (everything between its GEMMs)
 struct MfnCs { const float* cs[3]; float* dcx[3]; int h[3]; int T, B; };     // the three MFN LSTMs' cell states [T,B,Hp]
 int mfn_cstar_launch(const MfnCs& c, float* cstar, hipStream_t stream);

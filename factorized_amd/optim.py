@@ -18,6 +18,10 @@ per tensor.  Everything else (other modules, models on the composed autograd pat
 line (`optim.SGD(model.parameters(), lr=config["lr"], momentum=config["momentum"])`, mfm_mosi.py:404): one launch of
 `mfm_sgd_flat_spans_guarded` per fused model and step, with torch.optim.SGD's arithmetic and per-group hyper-parameters.
 
+`Adam` takes every option of torch.optim.Adam (weight decay, decoupled decay, AMSGrad, maximize; several parameter groups with their own
+values) and `AdamW` derives from it as torch's does: a fused model stays on the flat path with all of them, on ONE launch of
+`mfm_adam_ext_flat_spans_guarded` per step (see the class).  The reference's call issues the launches it always did.
+
 `zero_grad()` of this class clears a fused model's flat gradient buffer with one launch and marks every tensor "no gradient
 yet" (= torch's `set_to_none=True`: the next `step()` skips tensors the next backward does not reach) while leaving the
 `.grad` views attached; `zero_grad(set_to_none=False)` keeps zero gradients in place, which is the reference's PyTorch-0.4
@@ -75,11 +79,64 @@ _OPT_MOD.register_optimizer_step_pre_hook(_foreign_step_hook)
 _GLOBAL_PRE, _GLOBAL_POST = _OPT_MOD._global_optimizer_pre_hooks, _OPT_MOD._global_optimizer_post_hooks
 
 
+_ADAM_HYPER = ("lr", "betas", "eps", "weight_decay", "amsgrad", "maximize", "decoupled_weight_decay")
+
+
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False):
-        if weight_decay != 0 or amsgrad:
-            raise ValueError("factorized_amd.optim.Adam: weight_decay / amsgrad are not used by the reference and not built")
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)
+    """torch.optim.Adam (same signature, validation and arithmetic: weight decay, decoupled decay, AMSGrad, maximize, several
+    parameter groups) whose fused models are updated by ONE launch per step.
+
+    A fused model (`MFM_KL_EF`, `MFM_KL`, `MFM`) takes the flat path when the optimizer's parameter groups together hold all of
+    its parameters.  A model that sits in one group with `weight_decay == 0`, `amsgrad` and `maximize` off -- the reference's
+    call -- is stepped by `mfm_adam_flat_guarded` (`mfm_adam_flat_spans_guarded` when some tensors have no gradient,
+    `mfm_adam_flat_dev` with `capturable=True`).  Any option, or a model spread over several groups, goes to
+    `mfm_adam_ext_flat_spans_guarded`: each tensor is a span of the launch with its group's hyper-parameters and its own step
+    count (adjacent tensors with equal values merge, so one group is one span).  Either way the model keeps its in-launch
+    hand-overs.  A tensor without a gradient is skipped with all its state, its step count and its decoupled decay, as torch
+    skips a parameter whose `.grad` is None.  Everything else -- other modules, a model only partly in the groups, frozen or
+    hooked parameters, `fast_grads = False` -- goes through an inner torch.optim.Adam built with the same per-group options;
+    moments, `max_exp_avg_sq` and step counts move between the two.
+
+    The AMSGrad maximum is a third flat buffer per model (`_fused[m]["vmax"]`), allocated zero-filled on first need.
+    `capturable=True` keeps the plain update only: an option or a second group per model is refused at construction."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        # torch.optim.Adam's checks, in its order and with its messages
+        if isinstance(lr, torch.Tensor):
+            if foreach and not capturable:
+                raise ValueError("lr as a Tensor is not supported for capturable=False and foreach=True")
+            if lr.numel() != 1:
+                raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not ((isinstance(betas[0], float) and isinstance(betas[1], float))
+                or (isinstance(betas[0], torch.Tensor) and isinstance(betas[1], torch.Tensor))):
+            raise ValueError("betas must be either both floats or both Tensors")
+        for k in (0, 1):
+            if isinstance(betas[k], torch.Tensor):
+                if not capturable and foreach:
+                    raise ValueError(f"betas[{k}] as a Tensor is not supported for capturable=False and foreach=True")
+                if betas[k].numel() != 1:
+                    raise ValueError(f"Tensor betas[{k}] must be 1-element")
+        betas = tuple(b.item() if isinstance(b, torch.Tensor) else b for b in betas)
+        name = "factorized_amd.optim.%s" % type(self).__name__
+        if differentiable:
+            raise ValueError(name + ": differentiable=True is not built (the flat update is not part of the autograd graph); "
+                             "use torch.optim." + type(self).__name__)
+        if fused:
+            raise ValueError(name + ": fused=True is torch's own fused kernel; this class fuses on its own (leave fused unset)")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                        foreach=foreach, capturable=capturable, differentiable=False, fused=None,
+                        decoupled_weight_decay=decoupled_weight_decay)
         super().__init__(params, defaults)
         import weakref
         # module -> state of a fused model: flat moments, per-tensor step counts (weak keys: a model that is gone takes its
@@ -87,49 +144,77 @@ class Adam(torch.optim.Optimizer):
         self._fused = weakref.WeakKeyDictionary()
         self._fallback = None       # stock torch.optim.Adam over everything that is not fused
         self._fallback_ids = None
-        self._fm_cache = {}
+        self._fm_key = None
+        self._fm_list = []
         self._pending_fused = None  # fused states of a load_state_dict() waiting for their models' first step
         # capturable=True (torch.optim.Adam's flag): step count and learning rate of the fused update live in device memory
         # (mfm_adam_flat_dev), so a whole training step can be captured into a hipGraph and replayed (train.GraphedModuleStep)
         self._capturable = bool(capturable)
         # this optimizer honours the gradient guard: the models it owns may run their in-launch hand-overs (a model under
         # any other optimizer stays on separate launches, mfm_model._FusedEngineMixin._guarded)
-        for group in self.param_groups:
-            self._fused_modules(group)
+        models = self._fused_models()
+        if self._capturable:
+            if any(self._has_option(g) for g in self.param_groups) or any(not self._one_group(gidx) for _, gidx in models):
+                raise ValueError(name + "(capturable=True): weight_decay, amsgrad, maximize and a model spread over several "
+                                 "parameter groups are not built for the capturable update (one device-side step counter and "
+                                 "learning rate per model); leave capturable off for them")
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:          # (a state saved before these options existed)
+            for k in ("weight_decay", "amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused",
+                      "decoupled_weight_decay"):
+                group.setdefault(k, self.defaults[k])
 
     # ------------------------------------------------------------------ helpers
-    def _fused_modules(self, group):
-        """models whose parameter list lies entirely inside `group` (the reference has one group: model.parameters());
-        cached per group while its parameter list is the same list of the same length"""
-        key = (id(group["params"]), len(group["params"]), id(group["params"][0]) if group["params"] else 0)
-        hit = self._fm_cache.get(id(group))
-        if hit is not None and hit[0] == key and all(r() is not None for r in hit[2]):
-            return hit[1]
+    @staticmethod
+    def _has_option(group):
+        """an option the plain flat update does not compute (decay style alone changes nothing while weight_decay is 0)"""
+        return group["weight_decay"] != 0 or bool(group["amsgrad"]) or bool(group["maximize"])
+
+    @staticmethod
+    def _one_group(gidx):
+        return bool((gidx == gidx[0]).all())
+
+    def _fused_models(self):
+        """[(model, group index of every tensor)] for the fused models whose parameters all lie in this optimizer's groups (the
+        reference has one group: model.parameters()); cached while the groups hold the same lists of the same lengths"""
+        key = tuple((id(g["params"]), len(g["params"]), id(g["params"][0]) if g["params"] else 0) for g in self.param_groups)
+        if key == self._fm_key and all(r() is not None for r, _ in self._fm_list):
+            return [(r(), gi) for r, gi in self._fm_list]
         import weakref
-        ids = {id(p) for p in group["params"]}
+        gid = {}
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                gid[id(p)] = k
         seen, out = set(), []
-        for p in group["params"]:
-            m = _owner(p)
-            if m is None or id(m) in seen:
-                continue
-            seen.add(id(m))
-            if all(id(q) in ids for q in m._plist):
-                out.append(m)
-                import weakref as _wr
-                m._guarded = _wr.ref(self)
-        self._fm_cache[id(group)] = (key, out, [weakref.ref(m) for m in out])
-        return out
+        for g in self.param_groups:
+            for p in g["params"]:
+                m = _owner(p)
+                if m is None or id(m) in seen:
+                    continue
+                seen.add(id(m))
+                if all(id(q) in gid for q in m._plist):
+                    out.append((weakref.ref(m), np.array([gid[id(q)] for q in m._plist], dtype=np.int64)))
+                    m._guarded = weakref.ref(self)
+        self._fm_key, self._fm_list = key, out
+        return [(r(), gi) for r, gi in out]
 
     def _state_for(self, m, eng):
         st = self._fused.get(m)
         if st is None or st["m"].numel() != eng.layout.total or st["m"].device != eng.params.device:
-            st = dict(m=torch.zeros_like(eng.params), v=torch.zeros_like(eng.params),
+            # vmax: the AMSGrad maximum of v, allocated on first need (_vmax)
+            st = dict(m=torch.zeros_like(eng.params), v=torch.zeros_like(eng.params), vmax=None,
                       steps=np.zeros(len(eng.layout.slots), dtype=np.int64))
             if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
                 saved = self._pending_fused.pop(0)
-                if saved["m"].numel() == eng.layout.total and len(saved["steps"]) == len(eng.layout.slots):
+                vmax = saved.get("vmax")
+                if saved["m"].numel() == eng.layout.total and len(saved["steps"]) == len(eng.layout.slots) and \
+                        (vmax is None or vmax.numel() == eng.layout.total):
                     st["m"].copy_(saved["m"]); st["v"].copy_(saved["v"])
                     st["steps"][:] = np.asarray(saved["steps"], dtype=np.int64)
+                    if vmax is not None:
+                        st["vmax"] = vmax.to(eng.params.device, copy=True)
                 else:
                     raise _lib.MfmError(
                         "factorized_amd.optim.Adam.load_state_dict: the saved fused state (%d elements, %d tensors) does not fit "
@@ -138,6 +223,12 @@ class Adam(torch.optim.Optimizer):
                                                                       len(eng.layout.slots)))
             self._fused[m] = st
         return st
+
+    @staticmethod
+    def _vmax(st):
+        if st["vmax"] is None:
+            st["vmax"] = torch.zeros_like(st["v"])
+        return st["vmax"]
 
     def _device_scalars(self, st, eng, lr):
         """capturable mode: the step counter and the learning rate as device words of this model's state"""
@@ -171,13 +262,20 @@ class Adam(torch.optim.Optimizer):
             o, n, shp = eng.layout.slots[i]
             st["m"][o:o + n].view(shp).copy_(s["exp_avg"])
             st["v"][o:o + n].view(shp).copy_(s["exp_avg_sq"])
+            if "max_exp_avg_sq" in s:
+                self._vmax(st)[o:o + n].view(shp).copy_(s["max_exp_avg_sq"])
             st["steps"][i] = int(float(s["step"]))
             del fb.state[p]
         if "step_dev" in st:
             st["step_dev"].fill_(int(st["steps"].max()))
 
-    def _fused_step(self, m, group):
+    def _fused_step(self, m, gidx):
         eng = m.engine
+        group = self.param_groups[gidx[0]]
+        plain = self._one_group(gidx) and not self._has_option(group)
+        if self._capturable and not plain:
+            raise _lib.MfmError("factorized_amd.optim.Adam(capturable=True): weight_decay, amsgrad, maximize and a model spread "
+                                "over several parameter groups are not built for the capturable update")
         import weakref
         m._guarded = weakref.ref(self)          # (per step: the optimizer that steps the model answers for the guard)
         gflat = getattr(m, "_grad_flat", None)
@@ -197,6 +295,8 @@ class Adam(torch.optim.Optimizer):
         st = self._state_for(m, eng)
         if self._fallback is not None and self._fallback.state:
             self._migrate_back(m, st, eng)
+        if not plain:
+            return self._ext_step(m, gidx, st, gflat)
         lr, (b1, b2), eps = group["lr"], group["betas"], group["eps"]
         if torch.is_tensor(lr) and not self._capturable:
             lr = float(lr)
@@ -245,13 +345,73 @@ class Adam(torch.optim.Optimizer):
                                                      b2, eps, 1.0, guard, stream), "mfm_adam_flat_spans_guarded")
         return True
 
+    def _ext_step(self, m, gidx, st, gflat):
+        """an option (weight decay, AMSGrad, maximize) or several groups: every tensor with a gradient is a span of ONE launch of
+        mfm_adam_ext_flat_spans_guarded with its group's hyper-parameters and its own step count; adjacent tensors whose values
+        and step counts agree merge (one group, every tensor present: one span)"""
+        eng = m.engine
+        hyper = []
+        for g in self.param_groups:
+            fl = ((_lib.MFM_ADAMX_MAXIMIZE if g["maximize"] else 0) | (_lib.MFM_ADAMX_AMSGRAD if g["amsgrad"] else 0)
+                  | (_lib.MFM_ADAMX_DECOUPLED if g["decoupled_weight_decay"] else 0))
+            hyper.append((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), fl))
+        # (layers no forward uses carry a zero gradient on the flat path; torch's .grad is None there: no decay, no step count)
+        present, steps = m._grad_present & ~m._group_masks()["unreached"], st["steps"]
+        if "runs" not in st or st["runs"][0] is not gidx:
+            # tensors in address order, and the runs of adjacent tensors of one group (tensor starts are 64-float aligned: span
+            # bounds are multiples of 4)
+            order = np.argsort([o for o, _, _ in eng.layout.slots], kind="stable")
+            starts = [eng.layout.slots[i][0] for i in order] + [eng.layout.guard]
+            runs = []
+            for k, i in enumerate(order):
+                if runs and runs[-1][2] == gidx[i]:
+                    runs[-1][1] = starts[k + 1]
+                else:
+                    runs.append([starts[k], starts[k + 1], int(gidx[i])])
+            st["runs"] = (gidx, order, starts, runs)
+        _, order, starts, runs = st["runs"]
+        if present.all() and (steps == steps[0]).all():
+            steps += 1
+            s_ = int(steps[0])
+            spans = [(b, e, gi, s_) for b, e, gi in runs]
+        else:
+            spans = []
+            for k, i in enumerate(order):
+                if not present[i]:
+                    continue             # no gradient: moments, vmax, step count and decoupled decay all stay (torch skips it)
+                steps[i] += 1
+                b, e, gi, s_ = starts[k], starts[k + 1], int(gidx[i]), int(steps[i])
+                if spans and spans[-1][1] == b and spans[-1][3] == s_ and hyper[spans[-1][2]] == hyper[gi]:
+                    spans[-1] = (spans[-1][0], e, spans[-1][2], s_)
+                else:
+                    spans.append((b, e, gi, s_))
+        if not spans:
+            return True                  # no tensor has a gradient: torch's step does nothing either
+        amsgrad = any(hyper[gi][5] & _lib.MFM_ADAMX_AMSGRAD for _, _, gi, _ in spans)
+        L = _lib.lib()
+        stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index))
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        vmax = ptr(self._vmax(st)) if amsgrad else C.c_void_p(None)
+        # guard word of the flat gradient buffer (_fused_step): a NaN there leaves parameters, moments and vmax alone
+        guard = C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard)
+        for k in range(0, len(spans), _lib.MFM_ADAMX_MAX_SPANS):
+            part = spans[k:k + _lib.MFM_ADAMX_MAX_SPANS]
+            arr = (_lib.AdamExtSpan * len(part))()
+            for j, (b, e, gi, s_) in enumerate(part):
+                a = arr[j]
+                a.begin, a.end, a.step = b, e, s_
+                a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.flags = hyper[gi]
+            _lib.check(L.mfm_adam_ext_flat_spans_guarded(ptr(eng.params), ptr(gflat), ptr(st["m"]), ptr(st["v"]), vmax, arr,
+                                                         len(part), 1.0, guard, stream), "mfm_adam_ext_flat_spans_guarded")
+        return True
+
     def _fallback_step(self, rest):
         if not rest:
             return
         ids = tuple(id(p) for _, ps in rest for p in ps)
         if self._fallback is None or self._fallback_ids != ids:
-            groups = [dict(params=ps, lr=g["lr"], betas=g["betas"], eps=g["eps"]) for g, ps in rest]
-            self._fallback = torch.optim.Adam(groups)
+            groups = [dict(params=ps, **{k: g[k] for k in _ADAM_HYPER}) for g, ps in rest]
+            self._fallback = torch.optim.Adam(groups, foreach=self.defaults["foreach"])
             self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
             self._fallback_ids = ids
             self._migrate_fused_state(rest)
@@ -260,13 +420,14 @@ class Adam(torch.optim.Optimizer):
                 self._fallback.load_state_dict(fb)
                 self._pending_fallback = None
         for fg, (g, _) in zip(self._fallback.param_groups, rest):
-            fg["lr"], fg["betas"], fg["eps"] = g["lr"], g["betas"], g["eps"]      # schedulers act on OUR groups
+            for k in _ADAM_HYPER:
+                fg[k] = g[k]                        # schedulers act on OUR groups
         self._fallback.step()
 
     def _migrate_fused_state(self, rest):
         """parameters of a fused model that now go through the stock optimizer (a parameter was frozen / got a hook after
         fast-path steps): their moments and step counts move along -- Adam must not restart"""
-        for _, ps in rest:
+        for g, ps in rest:
             for p in ps:
                 m = _owner(p)
                 st = self._fused.get(m) if m is not None else None
@@ -281,6 +442,8 @@ class Adam(torch.optim.Optimizer):
                     continue
                 self._fallback.state[p] = dict(step=torch.tensor(float(steps)), exp_avg=st["m"][o:o + n].view(shp).clone(),
                                                exp_avg_sq=st["v"][o:o + n].view(shp).clone())
+                if g["amsgrad"]:
+                    self._fallback.state[p]["max_exp_avg_sq"] = self._vmax(st)[o:o + n].view(shp).clone()
         # (the flat state stays: when the model returns to the flat path, _migrate_back brings the moments home instead of
         #  restarting them from zero)
 
@@ -288,6 +451,8 @@ class Adam(torch.optim.Optimizer):
         """moments and step counters of every fused model back to zero, in place (a captured graph keeps pointing at them)"""
         for st in self._fused.values():
             st["m"].zero_(); st["v"].zero_(); st["steps"][:] = 0
+            if st["vmax"] is not None:
+                st["vmax"].zero_()
             if "step_dev" in st:
                 st["step_dev"].zero_()
 
@@ -297,17 +462,18 @@ class Adam(torch.optim.Optimizer):
         parameter groups): first / second moments and per-tensor step counts (capturable mode: the device counter)."""
         sd = super().state_dict()
         fused = []
-        for group in self.param_groups:
-            for m in self._fused_modules(group):
-                st = self._fused.get(m)
-                if st is None:
-                    continue
-                steps = st["steps"].copy()
-                if "step_dev" in st:
-                    steps[:] = int(st["step_dev"].item())
-                fused.append(dict(m=st["m"].detach().clone(), v=st["v"].detach().clone(), steps=steps.tolist()))
+        for m, _ in self._fused_models():
+            st = self._fused.get(m)
+            if st is None:
+                continue
+            steps = st["steps"].copy()
+            if "step_dev" in st:
+                steps[:] = int(st["step_dev"].item())
+            fused.append(dict(m=st["m"].detach().clone(), v=st["v"].detach().clone(), steps=steps.tolist()))
+            if st["vmax"] is not None:       # (AMSGrad only: a state without it keeps the keys it always had)
+                fused[-1]["vmax"] = st["vmax"].detach().clone()
         if self._pending_fused:          # loaded, not stepped yet: what was loaded is still the state
-            fused += [dict(m=f["m"], v=f["v"], steps=list(f["steps"])) for f in self._pending_fused]
+            fused += [dict(f) for f in self._pending_fused]
         sd["fused"] = fused
         if self._fallback is not None:
             sd["fallback"] = self._fallback.state_dict()
@@ -319,7 +485,7 @@ class Adam(torch.optim.Optimizer):
         fb = sd.pop("fallback", None)
         super().load_state_dict(sd)
         self._fused.clear()
-        self._pending_fused = [dict(m=f["m"], v=f["v"], steps=list(f["steps"])) for f in fused] if fused else None
+        self._pending_fused = [dict(f, steps=list(f["steps"])) for f in fused] if fused else None
         self._pending_fallback = fb
 
     # ------------------------------------------------------------------ Optimizer interface
@@ -349,43 +515,49 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        done, ndone = set(), 0
+        for m, gidx in self._fused_models():
+            if m._plist[0].is_cuda and self._fused_step(m, gidx):
+                done.add(id(m))
+                ndone += len(m._plist)
+        if ndone == sum(len(g["params"]) for g in self.param_groups):
+            return loss                               # (the reference's case: one model, nothing left)
         rest = []
         for group in self.param_groups:
-            stepped, ndone = [], 0
-            for m in self._fused_modules(group):
-                if m._plist[0].is_cuda and self._fused_step(m, group):
-                    stepped.append(m)
-                    ndone += len(m._plist)
-            if ndone == len(group["params"]):
-                continue                              # (the reference's case: one model, one group, nothing left)
-            done = {id(p) for m in stepped for p in m._plist}
-            left = [p for p in group["params"] if id(p) not in done]
+            left = [p for p in group["params"] if id(_owner(p)) not in done] if done else list(group["params"])
             if left:
                 rest.append((group, left))
         self._fallback_step(rest)
         return loss
 
     def zero_grad(self, set_to_none=True):
-        cleared, nh, total = [], 0, 0
-        for group in self.param_groups:
-            total += len(group["params"])
-            for m in self._fused_modules(group):
-                if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
-                    m._zero_flat_grads(set_to_none)
-                    cleared.append(m)
-                    nh += len(m._plist)
-        if nh == total:
+        cleared, nh = set(), 0
+        for m, _ in self._fused_models():
+            if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
+                m._zero_flat_grads(set_to_none)
+                cleared.add(id(m))
+                nh += len(m._plist)
+        if nh == sum(len(g["params"]) for g in self.param_groups):
             return
-        handled = {id(p) for m in cleared for p in m._plist}
         for group in self.param_groups:
             for p in group["params"]:
-                if id(p) in handled or p.grad is None:
+                if p.grad is None or (cleared and id(_owner(p)) in cleared):
                     continue
                 if set_to_none:
                     p.grad = None
                 else:
                     p.grad.detach_()
                     p.grad.zero_()
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: `Adam` with torch's AdamW defaults and decoupled weight decay forced on (as torch.optim.AdamW derives
+    from torch.optim.Adam)"""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize,
+                         capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
 
 
 _SGD_HYPER = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize")

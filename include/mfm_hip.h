@@ -267,6 +267,37 @@ int mfm_sgd_flat_spans_guarded(float* p, const float* g, float* buf, const MfmSg
                                float grad_scale, const float* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused Adam with every option of torch.optim.Adam / AdamW (weight decay, decoupled decay, AMSGrad, maximize) on one flat
+ * parameter buffer: p, the moments m and v and the running maximum vmax updated in place over up to MFM_ADAMX_MAX_SPANS
+ * disjoint element ranges, given in ascending order, each with its own hyper-parameters and 1-based step count; elements
+ * outside every span keep p, m, v and vmax untouched (torch skips a parameter whose .grad is None; several parameter groups
+ * give one model several sets of hyper-parameters).  Per element of a span, in the order of torch's _single_tensor_adam:
+ *   d = g * grad_scale;  MAXIMIZE: d = -d
+ *   weight_decay != 0:  DECOUPLED ? p *= 1 - lr * weight_decay  :  d += weight_decay * p
+ *   m += (1 - beta1) * (d - m);   v = beta2 * v + (1 - beta2) * d * d
+ *   AMSGRAD: vmax = max(vmax, v);   denom = sqrt(AMSGRAD ? vmax : v) / sqrt(1 - beta2^step) + eps
+ *   p -= lr / (1 - beta1^step) * m / denom
+ * A span without AMSGRAD neither reads nor writes vmax (vmax may be NULL when no span has the flag).  A span with no flag and
+ * weight_decay 0 computes what mfm_adam_flat computes.  begin/end are multiples of 4; lr, eps and weight_decay >= 0;
+ * 0 <= beta < 1; step >= 1.  `guard`: as for mfm_adam_flat_guarded (NULL in the unguarded form). */
+#define MFM_ADAMX_MAX_SPANS 88
+#define MFM_ADAMX_MAXIMIZE 1
+#define MFM_ADAMX_AMSGRAD 2
+#define MFM_ADAMX_DECOUPLED 4
+typedef struct MfmAdamExtSpan {
+  int64_t begin, end;
+  int32_t step;  /* 1-based count of updates of this span, this one included */
+  int32_t flags; /* MFM_ADAMX_MAXIMIZE | MFM_ADAMX_AMSGRAD | MFM_ADAMX_DECOUPLED */
+  float lr, beta1, beta2, eps, weight_decay;
+  int32_t reserved;
+} MfmAdamExtSpan;
+int mfm_adam_ext_flat_spans(float* p, const float* g, float* m, float* v, float* vmax, const MfmAdamExtSpan* spans /*host*/,
+                            int32_t nspans, float grad_scale, void* stream);
+int mfm_adam_ext_flat_spans_guarded(float* p, const float* g, float* m, float* v, float* vmax,
+                                    const MfmAdamExtSpan* spans /*host*/, int32_t nspans, float grad_scale, const float* guard,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached

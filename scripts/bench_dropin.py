@@ -1,6 +1,7 @@
 """ms per step of the reference's UNCHANGED loop (mfm_mosi.py:427-441 incl. its per-step .item()) on MFM_KL_EF, B=32, T=20:
 stock torch.optim.Adam vs factorized_amd.optim.Adam, per-tensor autograd path vs flat gradients, torch.optim.SGD vs
-factorized_amd.optim.SGD (lr 0.01, momentum 0.9), and the fused engine call."""
+factorized_amd.optim.SGD (lr 0.01, momentum 0.9), torch.optim.AdamW vs factorized_amd.optim.AdamW (and AMSGrad, two parameter
+groups), and the fused engine call."""
 import os, sys, time
 import torch, torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -71,6 +72,35 @@ for name, opt_cls, item in (("torch.optim.SGD(lr=0.01, momentum=0.9), flat gradi
     loop(model, optimizer, 300, item)
     torch.cuda.synchronize()
     print("%-70s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
+# torch.optim.Adam's other options (span kernel mfm_adam_ext_flat_spans_guarded): AdamW with weight_decay 1e-2, AMSGrad, two
+# parameter groups; the plain Adam line repeated in between shows the spread of this run
+def two_groups(m):
+    enc = ("encoder_l.", "encoder_a.", "encoder_v.", "ef_encoder.")
+    return [{"params": [p for n, p in m.named_parameters() if n.startswith(enc)], "lr": 1e-4},
+            {"params": [p for n, p in m.named_parameters() if not n.startswith(enc)]}]
+
+
+for name, make, item in (("torch.optim.AdamW(weight_decay=1e-2), flat gradients", lambda m: torch.optim.AdamW(m.parameters(), weight_decay=1e-2), True),
+                         ("factorized_amd.optim.AdamW(weight_decay=1e-2), flat gradients", lambda m: optim.AdamW(m.parameters(), weight_decay=1e-2), True),
+                         ("factorized_amd.optim.Adam, flat gradients (again)", lambda m: optim.Adam(m.parameters()), True),
+                         ("factorized_amd.optim.AdamW(weight_decay=1e-2), no per-step .item()", lambda m: optim.AdamW(m.parameters(), weight_decay=1e-2), False),
+                         ("factorized_amd.optim.Adam, no per-step .item() (again)", lambda m: optim.Adam(m.parameters()), False),
+                         ("factorized_amd.optim.Adam(weight_decay=1e-4, amsgrad=True), flat gradients", lambda m: optim.Adam(m.parameters(), weight_decay=1e-4, amsgrad=True), True),
+                         ("factorized_amd.optim.AdamW, encoders in their own group", lambda m: optim.AdamW(two_groups(m)), True),
+                         ("factorized_amd.optim.Adam, flat gradients (a third time)", lambda m: optim.Adam(m.parameters()), True)):
+    import gc
+    model = optimizer = None
+    gc.collect(); torch.cuda.empty_cache()
+    model = MFM_KL_EF(*cfgs)
+    optimizer = make(model)
+    model = model.to("cuda")
+    model.train()
+    loop(model, optimizer, 30, item)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loop(model, optimizer, 300, item)
+    torch.cuda.synchronize()
+    print("%-78s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
 model = MFM_KL_EF(*cfgs).to("cuda")
 for _ in range(30):
     model.engine.train_step(X, y)
