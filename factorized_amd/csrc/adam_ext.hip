@@ -3,47 +3,44 @@
 //
 // Traffic per element of a span: p, m, v read and written, g read = 28 B; a span with MFM_ADAMX_AMSGRAD also reads and writes
 // vmax = 36 B.  A span without the flag neither reads nor writes vmax.
-#include "internal.h"
+#include "span_tiles.h"
 
 namespace mfm {
 
-// One span in kernel form: bounds in float4 units, the first 256-float4 tile of the span in the launch's tile numbering, the bias
-// corrections of its step count (formed on the host in double precision, as adam_launch does) and its hyper-parameters.
+// One span in kernel form: the common head, the bias corrections of its step count (formed on the host in double precision, as
+// adam_launch does) and its hyper-parameters.
 // `decay` is weight_decay for L2 decay (g += decay * p) and 1 - lr * weight_decay for decoupled decay (p *= decay).
 struct AdamxSpanDev {
-  int32_t b4, e4, tile0, flags;
+  SpanHead h;
   float step_size, bc2_sqrt, beta1, beta2, eps, decay;
 };
-// 88 x 40 bytes + 8 = 3528: well inside the 4 KiB a kernel argument block may hold (sgd.hip's table: 3592)
+// 88 x 40 bytes + 8 = 3528: well inside the 4 KiB a kernel argument block may hold
 struct AdamxSpansDev {
   AdamxSpanDev s[MFM_ADAMX_MAX_SPANS];
   int32_t count, tiles;
 };
 static_assert(sizeof(AdamxSpansDev) + 6 * sizeof(void*) + 8 <= 4096, "Adam span table exceeds the kernel argument limit");
 
-constexpr int kAdamxTile = 256;      // float4 per tile = threads per workgroup
 constexpr int kAdamxDecay = 1 << 30;  // (device table only) the span has weight_decay != 0
 
-// Work is dealt in tiles of 256 float4 as in sgd_spans_kernel: span k owns tiles [tile0_k, tile0_{k+1}), a workgroup walks its
-// tiles in ascending order and finds the span of a tile by advancing k -- once per tile, uniform over the workgroup.  The
-// element loop holds no span search and every hyper-parameter branch is uniform.  The m / v / p lines keep adam_kernel's
-// operation order: a span with no option set computes what adam_kernel computes.
-__global__ __launch_bounds__(kAdamxTile) void adam_ext_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                    float* __restrict__ m, float* __restrict__ v,
-                                                                    float* __restrict__ vmax, const AdamxSpansDev S,
-                                                                    float grad_scale, const float* __restrict__ guard) {
+// Work is dealt in tiles as span_tiles.h describes.  The m / v / p lines keep adam_kernel's operation order: a span with no
+// option set computes what adam_kernel computes.
+__global__ __launch_bounds__(kSpanTile) void adam_ext_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                   float* __restrict__ m, float* __restrict__ v,
+                                                                   float* __restrict__ vmax, const AdamxSpansDev S,
+                                                                   float grad_scale, const float* __restrict__ guard) {
   // guard word (mfm_adam_ext_flat_spans_guarded): anything but 0.0f leaves p, m, v and vmax as they are (adam_kernel)
   if (guard && !(guard[0] == 0.0f)) return;
   int k = 0;
   for (int t = blockIdx.x; t < S.tiles; t += gridDim.x) {
-    while (k + 1 < S.count && t >= S.s[k + 1].tile0) ++k;
+    k = span_of_tile(S, t, k);
     const AdamxSpanDev sp = S.s[k];
-    const int64_t i = (int64_t)sp.b4 + (int64_t)(t - sp.tile0) * kAdamxTile + threadIdx.x;
-    if (i >= sp.e4) continue;
-    const bool amsgrad = (sp.flags & MFM_ADAMX_AMSGRAD) != 0;
-    const bool decay = (sp.flags & kAdamxDecay) != 0;
-    const bool decoupled = (sp.flags & MFM_ADAMX_DECOUPLED) != 0;
-    const float gs = (sp.flags & MFM_ADAMX_MAXIMIZE) ? -grad_scale : grad_scale;
+    const int64_t i = span_tile_index(sp.h, t);
+    if (i >= sp.h.e4) continue;
+    const bool amsgrad = (sp.h.flags & MFM_ADAMX_AMSGRAD) != 0;
+    const bool decay = (sp.h.flags & kAdamxDecay) != 0;
+    const bool decoupled = (sp.h.flags & MFM_ADAMX_DECOUPLED) != 0;
+    const float gs = (sp.h.flags & MFM_ADAMX_MAXIMIZE) ? -grad_scale : grad_scale;
     const float beta1 = sp.beta1, beta2 = sp.beta2;
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
@@ -88,10 +85,8 @@ int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* v
   int64_t tiles = 0, prev_end = 0;
   for (int k = 0; k < nspans; ++k) {
     const MfmAdamExtSpan& sp = spans[k];
-    MFM_REQUIRE(sp.begin >= prev_end && sp.end > sp.begin && (sp.begin & 3) == 0 && (sp.end & 3) == 0 &&
-                    (sp.end >> 2) <= INT32_MAX,
-                "adam ext spans[%d]: [%lld,%lld) (ascending, disjoint, bounds multiples of 4 elements)", k, (long long)sp.begin,
-                (long long)sp.end);
+    AdamxSpanDev& d = S.s[k];
+    if (int rc = span_head_fill("adam ext spans", k, sp.begin, sp.end, &prev_end, &tiles, &d.h)) return rc;
     MFM_REQUIRE(sp.step >= 1, "adam ext spans[%d]: step %d (1-based, must be >= 1)", k, sp.step);
     MFM_REQUIRE(sp.lr >= 0.0f && sp.eps >= 0.0f && sp.weight_decay >= 0.0f,
                 "adam ext spans[%d]: lr %g, eps %g, weight_decay %g (each must be >= 0)", k, (double)sp.lr, (double)sp.eps,
@@ -103,24 +98,17 @@ int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* v
     MFM_REQUIRE(vmax || !(sp.flags & MFM_ADAMX_AMSGRAD), "adam ext spans[%d]: AMSGRAD needs a vmax buffer", k);
     const double bc1 = 1.0 - pow((double)sp.beta1, (double)sp.step);
     const double bc2 = 1.0 - pow((double)sp.beta2, (double)sp.step);
-    AdamxSpanDev& d = S.s[k];
-    d.b4 = (int32_t)(sp.begin >> 2);
-    d.e4 = (int32_t)(sp.end >> 2);
-    d.tile0 = (int32_t)tiles;
-    d.flags = sp.flags | (sp.weight_decay != 0.0f ? kAdamxDecay : 0);
+    d.h.flags = sp.flags | (sp.weight_decay != 0.0f ? kAdamxDecay : 0);
     d.step_size = (float)((double)sp.lr / bc1);
     d.bc2_sqrt = (float)sqrt(bc2);
     d.beta1 = sp.beta1;
     d.beta2 = sp.beta2;
     d.eps = sp.eps;
     d.decay = (sp.flags & MFM_ADAMX_DECOUPLED) ? (float)(1.0 - (double)sp.lr * (double)sp.weight_decay) : sp.weight_decay;
-    tiles += (d.e4 - d.b4 + kAdamxTile - 1) / kAdamxTile;
-    prev_end = sp.end;
   }
-  MFM_REQUIRE(tiles <= INT32_MAX, "adam ext spans: %lld tiles", (long long)tiles);
-  S.tiles = (int32_t)tiles;
-  const int nb = (int)(tiles < 2048 ? tiles : 2048);
-  MFM_LAUNCH_TIMED(adam_ext_spans_kernel, dim3(nb), dim3(kAdamxTile), 0, stream, p, g, m, v, vmax, S, grad_scale, guard);
+  int nb;
+  if (int rc = span_grid("adam ext spans", tiles, &S.tiles, &nb)) return rc;
+  MFM_LAUNCH_TIMED(adam_ext_spans_kernel, dim3(nb), dim3(kSpanTile), 0, stream, p, g, m, v, vmax, S, grad_scale, guard);
   MFM_LAUNCH_CHECK("adam_ext_spans_kernel");
   return MFM_OK;
 }

@@ -1,12 +1,12 @@
 // Fused momentum SGD over spans of one flat parameter buffer (torch.optim.SGD semantics; factorized_amd.optim.SGD).
-#include "internal.h"
+#include "span_tiles.h"
 
 namespace mfm {
 
-// One span in kernel form: bounds in float4 units, the first 256-float4 tile of the span in the launch's tile numbering, and the
-// hyper-parameters the update needs (1 - dampening formed on the host in double precision, as torch's Python scalar is).
+// One span in kernel form: the common head and the hyper-parameters the update needs (1 - dampening formed on the host in
+// double precision, as torch's Python scalar is).
 struct SgdSpanDev {
-  int32_t b4, e4, tile0, flags;
+  SpanHead h;
   float lr, wd, mom, omd;
 };
 // 112 x 32 bytes + 8: well inside the 4 KiB a kernel argument block may hold
@@ -16,29 +16,25 @@ struct SgdSpansDev {
 };
 static_assert(sizeof(SgdSpansDev) + 4 * sizeof(void*) + 8 <= 4096, "SGD span table exceeds the kernel argument limit");
 
-constexpr int kSgdTile = 256;      // float4 per tile = threads per workgroup
-
-// Work is dealt in tiles of 256 float4: span k owns tiles [tile0_k, tile0_{k+1}).  A workgroup walks its tiles in ascending order
-// (grid-stride), so the span of the next tile is found by advancing k -- once per tile, uniform over the workgroup; the element
-// loop holds no span search and every hyper-parameter branch is uniform.
-__global__ __launch_bounds__(kSgdTile) void sgd_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                             float* __restrict__ buf, const SgdSpansDev S, float grad_scale,
-                                                             const float* __restrict__ guard) {
+// Work is dealt in tiles as span_tiles.h describes.
+__global__ __launch_bounds__(kSpanTile) void sgd_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              float* __restrict__ buf, const SgdSpansDev S, float grad_scale,
+                                                              const float* __restrict__ guard) {
   // guard word (mfm_sgd_flat_spans_guarded): anything but 0.0f leaves p and buf as they are (adam_kernel)
   if (guard && !(guard[0] == 0.0f)) return;
   int k = 0;
   for (int t = blockIdx.x; t < S.tiles; t += gridDim.x) {
-    while (k + 1 < S.count && t >= S.s[k + 1].tile0) ++k;
+    k = span_of_tile(S, t, k);
     const SgdSpanDev sp = S.s[k];
-    const int64_t i = (int64_t)sp.b4 + (int64_t)(t - sp.tile0) * kSgdTile + threadIdx.x;
-    if (i >= sp.e4) continue;
-    const bool maximize = (sp.flags & MFM_SGD_MAXIMIZE) != 0;
+    const int64_t i = span_tile_index(sp.h, t);
+    if (i >= sp.h.e4) continue;
+    const bool maximize = (sp.h.flags & MFM_SGD_MAXIMIZE) != 0;
     const float gs = maximize ? -grad_scale : grad_scale;
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
     if (sp.mom != 0.0f) {
-      const bool first = (sp.flags & MFM_SGD_FIRST) != 0;
-      const bool nesterov = (sp.flags & MFM_SGD_NESTEROV) != 0;
+      const bool first = (sp.h.flags & MFM_SGD_FIRST) != 0;
+      const bool nesterov = (sp.h.flags & MFM_SGD_NESTEROV) != 0;
       // a first step creates the buffer (torch: clone of the gradient): the old contents are not read
       f32x4 bv = first ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : reinterpret_cast<const f32x4*>(buf)[i];
 #pragma unroll
@@ -74,32 +70,23 @@ int sgd_spans_launch(float* p, const float* g, float* buf, const MfmSgdSpan* spa
   int64_t tiles = 0, prev_end = 0;
   for (int k = 0; k < nspans; ++k) {
     const MfmSgdSpan& sp = spans[k];
-    MFM_REQUIRE(sp.begin >= prev_end && sp.end > sp.begin && (sp.begin & 3) == 0 && (sp.end & 3) == 0 &&
-                    (sp.end >> 2) <= INT32_MAX,
-                "sgd spans[%d]: [%lld,%lld) (ascending, disjoint, bounds multiples of 4 elements)", k, (long long)sp.begin,
-                (long long)sp.end);
+    SgdSpanDev& d = S.s[k];
+    if (int rc = span_head_fill("sgd spans", k, sp.begin, sp.end, &prev_end, &tiles, &d.h)) return rc;
     MFM_REQUIRE(sp.lr >= 0.0f && sp.weight_decay >= 0.0f && sp.momentum >= 0.0f,
                 "sgd spans[%d]: lr %g, weight_decay %g, momentum %g (each must be >= 0)", k, (double)sp.lr,
                 (double)sp.weight_decay, (double)sp.momentum);
     MFM_REQUIRE((sp.flags & ~(MFM_SGD_NESTEROV | MFM_SGD_MAXIMIZE | MFM_SGD_FIRST)) == 0, "sgd spans[%d]: unknown flags 0x%x", k,
                 (unsigned)sp.flags);
     MFM_REQUIRE(buf || sp.momentum == 0.0f, "sgd spans[%d]: momentum %g needs a momentum buffer", k, (double)sp.momentum);
-    SgdSpanDev& d = S.s[k];
-    d.b4 = (int32_t)(sp.begin >> 2);
-    d.e4 = (int32_t)(sp.end >> 2);
-    d.tile0 = (int32_t)tiles;
-    d.flags = sp.flags;
+    d.h.flags = sp.flags;
     d.lr = sp.lr;
     d.wd = sp.weight_decay;
     d.mom = sp.momentum;
     d.omd = (float)(1.0 - (double)sp.dampening);
-    tiles += (d.e4 - d.b4 + kSgdTile - 1) / kSgdTile;
-    prev_end = sp.end;
   }
-  MFM_REQUIRE(tiles <= INT32_MAX, "sgd spans: %lld tiles", (long long)tiles);
-  S.tiles = (int32_t)tiles;
-  const int nb = (int)(tiles < 2048 ? tiles : 2048);
-  MFM_LAUNCH_TIMED(sgd_spans_kernel, dim3(nb), dim3(kSgdTile), 0, stream, p, g, buf, S, grad_scale, guard);
+  int nb;
+  if (int rc = span_grid("sgd spans", tiles, &S.tiles, &nb)) return rc;
+  MFM_LAUNCH_TIMED(sgd_spans_kernel, dim3(nb), dim3(kSpanTile), 0, stream, p, g, buf, S, grad_scale, guard);
   MFM_LAUNCH_CHECK("sgd_spans_kernel");
   return MFM_OK;
 }

@@ -1,4 +1,5 @@
-"""Drop-in `optim.Adam` for the reference's UNCHANGED training loops (reference mfm_mosi.py:403, 427-441):
+"""Drop-in `optim.Adam` / `optim.AdamW` / `optim.SGD` for the reference's UNCHANGED training loops (reference
+mfm_mosi.py:403-404, 427-441):
 
     import factorized_amd.optim as optim                       # instead of: import torch.optim as optim
     from factorized_amd.mfm_model import MFM_KL_EF              # instead of: from mfm_model import MFM_KL_EF
@@ -7,26 +8,30 @@
     ...
     optimizer.zero_grad(); decoded, reg, missing = model.forward(batch_X); ...; loss.backward(); optimizer.step()
 
-`Adam` is a `torch.optim.Optimizer` (so `ReduceLROnPlateau(optimizer, 'min')`, `param_groups[0]['lr']`, `zero_grad()` work as
-in the reference).  Parameters that belong to a model with the fused engine (`MFM_KL_EF`, `MFM_KL`, `MFM`: every
-nn.Parameter is a view into ONE flat buffer) and whose `.grad`s are the views of the model's flat gradient buffer (what
-`MFM_KL_EF`'s backward leaves behind) are updated by ONE launch of `mfm_adam_flat` -- or `mfm_adam_flat_spans` when some
-tensors received no gradient: like torch.optim.Adam, a parameter without a gradient is skipped and step counts are kept
-per tensor.  Everything else (other modules, models on the composed autograd path) goes through a stock
-`torch.optim.Adam` with the same hyper-parameters.  `torch.optim.Adam` itself keeps working too -- it is just host-bound
-(78 tensors per step); see INTEGRATION.md for the measured step times.  `SGD` does the same for the reference's other optimizer
-line (`optim.SGD(model.parameters(), lr=config["lr"], momentum=config["momentum"])`, mfm_mosi.py:404): one launch of
-`mfm_sgd_flat_spans_guarded` per fused model and step, with torch.optim.SGD's arithmetic and per-group hyper-parameters.
+Every class here is a `torch.optim.Optimizer` (so `ReduceLROnPlateau(optimizer, 'min')`, `param_groups[0]['lr']`, `zero_grad()`
+work as in the reference) built on one base, `_FlatOptimizer`, which holds everything that does not depend on the update rule.
+Parameters that belong to a model with the fused engine (`MFM_KL_EF`, `MFM_KL`, `MFM`: every nn.Parameter is a view into ONE
+flat buffer) and whose `.grad`s are the views of the model's flat gradient buffer (what `MFM_KL_EF`'s backward leaves behind)
+take the flat path: ONE launch per model and step over the flat buffers.  Like torch, a parameter without a gradient is skipped
+with all its state; tensors with a gradient become spans of the launch (adjacent tensors whose hyper-parameters and step counts
+agree merge).  Everything else (other modules, models on the composed autograd path) goes through an inner stock torch
+optimizer with the same hyper-parameters, and state moves between the two.  `torch.optim.Adam` itself keeps working too -- it is
+just host-bound (78 tensors per step); see INTEGRATION.md for the measured step times.
 
-`Adam` takes every option of torch.optim.Adam (weight decay, decoupled decay, AMSGrad, maximize; several parameter groups with their own
-values) and `AdamW` derives from it as torch's does: a fused model stays on the flat path with all of them, on ONE launch of
-`mfm_adam_ext_flat_spans_guarded` per step (see the class).  The reference's call issues the launches it always did.
+`Adam` takes every option of torch.optim.Adam (weight decay, decoupled decay, AMSGrad, maximize; several parameter groups with
+their own values) and `AdamW` derives from it as torch's does.  The reference's call -- no option, one group -- is ONE launch of
+`mfm_adam_flat` (`mfm_adam_flat_spans` when some tensors received no gradient); any option goes to
+`mfm_adam_ext_flat_spans_guarded` (see the class).  `SGD` is the reference's other optimizer line
+(`optim.SGD(model.parameters(), lr=config["lr"], momentum=config["momentum"])`, mfm_mosi.py:404): `mfm_sgd_flat_spans_guarded`
+with torch.optim.SGD's arithmetic and per-group hyper-parameters.
 
-`zero_grad()` of this class clears a fused model's flat gradient buffer with one launch and marks every tensor "no gradient
-yet" (= torch's `set_to_none=True`: the next `step()` skips tensors the next backward does not reach) while leaving the
-`.grad` views attached; `zero_grad(set_to_none=False)` keeps zero gradients in place, which is the reference's PyTorch-0.4
-behaviour (a tensor that once had a gradient keeps moving on its decaying first moment)."""
+`zero_grad()` clears a fused model's flat gradient buffer with one launch and marks every tensor "no gradient yet" (= torch's
+`set_to_none=True`: the next `step()` skips tensors the next backward does not reach) while leaving the `.grad` views attached;
+`zero_grad(set_to_none=False)` keeps zero gradients in place, which is the reference's PyTorch-0.4 behaviour (a tensor that
+once had a gradient keeps moving on its decaying first moment)."""
 import ctypes as C
+import warnings
+import weakref
 
 import numpy as np
 import torch
@@ -42,21 +47,20 @@ def _owner(p):
     return _owner_of(p)
 
 
-# Who may keep the in-launch hand-overs on is decided PER STEP by the optimizer that actually steps the model: this class marks
-# the models it owns in every step(); any OTHER torch optimizer that steps parameters of a fused model -- an optimizer swap, an
-# LR finder, per-stage optimizers built while the first one is still referenced -- takes the permission away before its
+# Who may keep the in-launch hand-overs on is decided PER STEP by the optimizer that actually steps the model: a _FlatOptimizer
+# marks the models it owns in every step(); any OTHER torch optimizer that steps parameters of a fused model -- an optimizer
+# swap, an LR finder, per-stage optimizers built while the first one is still referenced -- takes the permission away before its
 # update (a global step pre-hook: it knows nothing of the gradient guard and would apply a step whose hand-over gave up).
 _FOREIGN = {}
 
 
 def _foreign_step_hook(opt, args, kwargs):
-    if isinstance(opt, (Adam, SGD)) or getattr(opt, "_mfm_inner", False):
+    if isinstance(opt, _FlatOptimizer) or getattr(opt, "_mfm_inner", False):
         return
     key = id(opt)
     n = sum(len(g["params"]) for g in opt.param_groups)
     hit = _FOREIGN.get(key)
     if hit is None or hit[0] != n or hit[1]() is not opt:
-        import weakref
         mods, seen = [], set()
         for g in opt.param_groups:
             for p in g["params"]:
@@ -79,10 +83,262 @@ _OPT_MOD.register_optimizer_step_pre_hook(_foreign_step_hook)
 _GLOBAL_PRE, _GLOBAL_POST = _OPT_MOD._global_optimizer_pre_hooks, _OPT_MOD._global_optimizer_post_hooks
 
 
-_ADAM_HYPER = ("lr", "betas", "eps", "weight_decay", "amsgrad", "maximize", "decoupled_weight_decay")
+# ---------------------------------------------------------------------- spans of a flat buffer
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
 
 
-class Adam(torch.optim.Optimizer):
+def _stream_and_guard(eng, gflat):
+    """the current stream, and the guard word of the flat gradient buffer: the plan's backward stores a NaN there when a
+    hand-over inside one of its launches gave up -- a guarded update then leaves parameters and optimizer state alone
+    (engine.check_status() reports it)"""
+    return (C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index)),
+            C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard))
+
+
+def _address_order(layout):
+    """the tensors of a flat layout in address order, and where each starts plus the end of the last (tensor starts are
+    64-float aligned: span bounds are multiples of 4)"""
+    order = np.argsort([o for o, _, _ in layout.slots], kind="stable")
+    return order, [layout.slots[i][0] for i in order] + [layout.guard]
+
+
+def _merge_spans(order, starts, present, keys):
+    """[(begin, end, key)]: walk the tensors in address order, skip tensor i unless present[i], merge adjacent ones whose
+    keys[i] agree"""
+    spans = []
+    for k, i in enumerate(order):
+        if not present[i]:
+            continue
+        b, e, h = starts[k], starts[k + 1], keys[i]
+        if spans and spans[-1][1] == b and spans[-1][2] == h:
+            spans[-1] = (spans[-1][0], e, h)
+        else:
+            spans.append((b, e, h))
+    return spans
+
+
+def _span_tables(spans, span_cls, max_spans, fields):
+    """[(ctypes array, length)]: the spans cut into chunks of at most max_spans (one launch each); a span's key is the tuple of
+    its `fields`"""
+    tables = []
+    for k in range(0, len(spans), max_spans):
+        part = spans[k:k + max_spans]
+        arr = (span_cls * len(part))()
+        for a, (b, e, key) in zip(arr, part):
+            a.begin, a.end = b, e
+            for name, val in zip(fields, key):
+                setattr(a, name, val)
+        tables.append((arr, len(part)))
+    return tables
+
+
+def _launch_tables(fn, name, head, tables, tail):
+    """one launch of the span entry point `fn(*head, spans, nspans, *tail)` per table"""
+    for arr, n in tables:
+        _lib.check(fn(*head, arr, n, *tail), name)
+
+
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What `Adam` and `SGD` share: which fused models this optimizer owns, the step / zero_grad shell around one
+    `_fused_step(model, group index of every tensor)` per owned model, the inner torch optimizer for everything that is not on
+    the flat path, and the checkpoint format (torch's dict plus "fused" and "fallback").  A subclass supplies the update rule:
+    its per-model state (`_stale`, `_new_state`, `_restore`, `_snapshot`, `_loaded_entry`), `_fused_step`, and how state moves
+    to and from the inner optimizer (`_inner_rebuilt`, `_inner_stepping`)."""
+
+    _inner_cls = None            # the stock torch optimizer behind _fallback, and the group keys it takes from ours
+    _hyper = ()
+    _state_word = "state"        # what the layout-mismatch error refuses to restart
+    _capture_refusal = None      # message of the error step() raises inside a stream capture (None: capture is supported)
+
+    def _init_flat(self):
+        """(after torch's __init__) the state of the flat path; returns the owned models"""
+        # module -> state of a fused model (weak keys: a model that is gone takes its optimizer state with it)
+        self._fused = weakref.WeakKeyDictionary()
+        self._fallback = None       # inner stock optimizer over everything that is not fused
+        self._fallback_ids = None
+        self._fm_key = None
+        self._fm_list = []
+        self._pending_fused = None  # fused states of a load_state_dict() waiting for their models' first step
+        self._pending_fallback = None
+        # this optimizer honours the gradient guard: the models it owns may run their in-launch hand-overs (a model under
+        # any other optimizer stays on separate launches, mfm_model._FusedEngineMixin._guarded)
+        return self._fused_models()
+
+    def _fused_models(self):
+        """[(model, group index of every tensor)] for the fused models whose parameters all lie in this optimizer's groups (the
+        reference has one group: model.parameters()); cached while the groups hold the same lists of the same lengths"""
+        key = tuple((id(g["params"]), len(g["params"]), id(g["params"][0]) if g["params"] else 0) for g in self.param_groups)
+        if key == self._fm_key and all(r() is not None for r, _ in self._fm_list):
+            return [(r(), gi) for r, gi in self._fm_list]
+        gid = {}
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                gid[id(p)] = k
+        seen, out = set(), []
+        for g in self.param_groups:
+            for p in g["params"]:
+                m = _owner(p)
+                if m is None or id(m) in seen:
+                    continue
+                seen.add(id(m))
+                if all(id(q) in gid for q in m._plist):
+                    out.append((weakref.ref(m), np.array([gid[id(q)] for q in m._plist], dtype=np.int64)))
+                    m._guarded = weakref.ref(self)
+        self._fm_key, self._fm_list = key, out
+        return [(r(), gi) for r, gi in out]
+
+    # ------------------------------------------------------------------ the flat path
+    def _flat_grads(self, m, eng):
+        """the model's flat gradient buffer when this step can take the flat path, else None (the inner optimizer steps it)"""
+        m._guarded = weakref.ref(self)          # (per step: the optimizer that steps the model answers for the guard)
+        gflat = getattr(m, "_grad_flat", None)
+        if gflat is None or not m._grad_views_attached():
+            return None                      # gradients are ordinary per-tensor tensors
+        if not m._fast_last:
+            # a parameter was frozen / got a hook after fast-path steps: the flat path would move it (or skip everything);
+            # hand the gradients back to per-tensor tensors and let the inner optimizer apply torch's rules
+            m._detach_grad_views()
+            return None
+        if eng.poll_status():
+            # a hand-over of this step (or an earlier one) gave up: its gradients carry the NaN guard, the guarded launch leaves
+            # the parameters alone.  Clear the status, fall back to separate launches for the rest of the run, say so.
+            eng.check_status(raise_on_error=False)
+            warnings.warn(eng.status_message(), RuntimeWarning, stacklevel=4)      # (attributed to step())
+        return gflat
+
+    def _state_for(self, m, eng):
+        st = self._fused.get(m)
+        if st is None or self._stale(st, eng):
+            st = self._new_state(eng)
+            st["order"], st["starts"] = _address_order(eng.layout)
+            if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
+                self._restore(st, self._pending_fused.pop(0), eng)
+            self._fused[m] = st
+        return st
+
+    def _require_fit(self, elements, tensors, eng, ok=True):
+        if not (ok and elements == eng.layout.total and tensors == len(eng.layout.slots)):
+            raise _lib.MfmError(
+                "factorized_amd.optim.%s.load_state_dict: the saved fused state (%d elements, %d tensors) does not fit this "
+                "model's flat layout (%d elements, %d tensors) -- a checkpoint of another model / library version; refusing to "
+                "restart the %s silently" % (self._inner_cls.__name__, elements, tensors, eng.layout.total, len(eng.layout.slots), self._state_word))
+
+    # ------------------------------------------------------------------ the inner optimizer
+    def _fallback_step(self, rest):
+        if not rest:
+            return
+        ids = tuple(id(p) for _, ps in rest for p in ps)
+        if self._fallback is None or self._fallback_ids != ids:
+            old = self._fallback
+            groups = [dict(params=ps, **{k: g[k] for k in self._hyper}) for g, ps in rest]
+            self._fallback = self._inner_cls(groups, foreach=self.defaults["foreach"])
+            self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
+            self._fallback_ids = ids
+            self._inner_rebuilt(rest, old)
+            if self._pending_fallback is not None:
+                self._fallback.load_state_dict(self._pending_fallback)
+                self._pending_fallback = None
+        self._inner_stepping(ids)
+        for fg, (g, _) in zip(self._fallback.param_groups, rest):
+            for k in self._hyper:
+                fg[k] = g[k]                        # schedulers act on OUR groups
+        self._fallback.step()
+
+    def _inner_stepping(self, ids):
+        pass
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """torch's dict plus, under "fused", the flat state of every fused model (in the order the models appear in the
+        parameter groups; the subclass's `_snapshot` says what an entry holds) and, under "fallback", the inner optimizer's"""
+        sd = super().state_dict()
+        fused = []
+        for m, _ in self._fused_models():
+            entry = self._snapshot(m, self._fused.get(m))
+            if entry is not None:
+                fused.append(entry)
+        if self._pending_fused:          # loaded, not stepped yet: what was loaded is still the state
+            fused += [dict(f) for f in self._pending_fused]
+        sd["fused"] = fused
+        if self._fallback is not None:
+            sd["fallback"] = self._fallback.state_dict()
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        fused = sd.pop("fused", None)
+        fb = sd.pop("fallback", None)
+        super().load_state_dict(sd)
+        self._fused.clear()
+        self._pending_fused = [self._loaded_entry(f) for f in fused] if fused else None
+        self._pending_fallback = fb
+
+    # ------------------------------------------------------------------ Optimizer interface
+    def step(self, closure=None):
+        """Not wrapped by torch's `profile_hook_step` (`step.hooked` below): that wrapper opens a record_function scope around
+        every step, ~10 us of host time against a 150 us device step the unchanged loop has to keep fed.  Step pre / post hooks
+        registered on this optimizer or globally are still honoured."""
+        if self._capture_refusal and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.MfmError(self._capture_refusal)
+        hooks = self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(_GLOBAL_PRE) > 1 or _GLOBAL_POST
+        if hooks:
+            for h in list(_GLOBAL_PRE.values()) + list(self._optimizer_step_pre_hooks.values()):
+                if h is not _foreign_step_hook:
+                    h(self, (closure,) if closure is not None else (), {})
+        prev = torch.is_grad_enabled()
+        torch._C._set_grad_enabled(False)
+        try:
+            loss = self._step(closure)
+        finally:
+            torch._C._set_grad_enabled(prev)
+        if hooks:
+            for h in list(self._optimizer_step_post_hooks.values()) + list(_GLOBAL_POST.values()):
+                h(self, (closure,) if closure is not None else (), {})
+        return loss
+    step.hooked = True
+
+    def _step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        done, ndone = set(), 0
+        for m, gidx in self._fused_models():
+            if m._plist[0].is_cuda and self._fused_step(m, gidx):
+                done.add(id(m))
+                ndone += len(m._plist)
+        if ndone == sum(len(g["params"]) for g in self.param_groups):
+            return loss                               # (the reference's case: one model, nothing left)
+        rest = []
+        for group in self.param_groups:
+            left = [p for p in group["params"] if id(_owner(p)) not in done] if done else list(group["params"])
+            if left:
+                rest.append((group, left))
+        self._fallback_step(rest)
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        cleared, nh = set(), 0
+        for m, _ in self._fused_models():
+            if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
+                m._zero_flat_grads(set_to_none)
+                cleared.add(id(m))
+                nh += len(m._plist)
+        if nh == sum(len(g["params"]) for g in self.param_groups):
+            return
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None or (cleared and id(_owner(p)) in cleared):
+                    continue
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.detach_()
+                    p.grad.zero_()
+
+
+class Adam(_FlatOptimizer):
     """torch.optim.Adam (same signature, validation and arithmetic: weight decay, decoupled decay, AMSGrad, maximize, several
     parameter groups) whose fused models are updated by ONE launch per step.
 
@@ -99,6 +355,10 @@ class Adam(torch.optim.Optimizer):
 
     The AMSGrad maximum is a third flat buffer per model (`_fused[m]["vmax"]`), allocated zero-filled on first need.
     `capturable=True` keeps the plain update only: an option or a second group per model is refused at construction."""
+
+    _inner_cls = torch.optim.Adam
+    _hyper = ("lr", "betas", "eps", "weight_decay", "amsgrad", "maximize", "decoupled_weight_decay")
+    _state_word = "moments"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
                  maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
@@ -138,21 +398,10 @@ class Adam(torch.optim.Optimizer):
                         foreach=foreach, capturable=capturable, differentiable=False, fused=None,
                         decoupled_weight_decay=decoupled_weight_decay)
         super().__init__(params, defaults)
-        import weakref
-        # module -> state of a fused model: flat moments, per-tensor step counts (weak keys: a model that is gone takes its
-        # optimizer state with it)
-        self._fused = weakref.WeakKeyDictionary()
-        self._fallback = None       # stock torch.optim.Adam over everything that is not fused
-        self._fallback_ids = None
-        self._fm_key = None
-        self._fm_list = []
-        self._pending_fused = None  # fused states of a load_state_dict() waiting for their models' first step
         # capturable=True (torch.optim.Adam's flag): step count and learning rate of the fused update live in device memory
         # (mfm_adam_flat_dev), so a whole training step can be captured into a hipGraph and replayed (train.GraphedModuleStep)
         self._capturable = bool(capturable)
-        # this optimizer honours the gradient guard: the models it owns may run their in-launch hand-overs (a model under
-        # any other optimizer stays on separate launches, mfm_model._FusedEngineMixin._guarded)
-        models = self._fused_models()
+        models = self._init_flat()
         if self._capturable:
             if any(self._has_option(g) for g in self.param_groups) or any(not self._one_group(gidx) for _, gidx in models):
                 raise ValueError(name + "(capturable=True): weight_decay, amsgrad, maximize and a model spread over several "
@@ -166,7 +415,7 @@ class Adam(torch.optim.Optimizer):
                       "decoupled_weight_decay"):
                 group.setdefault(k, self.defaults[k])
 
-    # ------------------------------------------------------------------ helpers
+    # ------------------------------------------------------------------ per-model state
     @staticmethod
     def _has_option(group):
         """an option the plain flat update does not compute (decay style alone changes nothing while weight_decay is 0)"""
@@ -176,53 +425,23 @@ class Adam(torch.optim.Optimizer):
     def _one_group(gidx):
         return bool((gidx == gidx[0]).all())
 
-    def _fused_models(self):
-        """[(model, group index of every tensor)] for the fused models whose parameters all lie in this optimizer's groups (the
-        reference has one group: model.parameters()); cached while the groups hold the same lists of the same lengths"""
-        key = tuple((id(g["params"]), len(g["params"]), id(g["params"][0]) if g["params"] else 0) for g in self.param_groups)
-        if key == self._fm_key and all(r() is not None for r, _ in self._fm_list):
-            return [(r(), gi) for r, gi in self._fm_list]
-        import weakref
-        gid = {}
-        for k, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                gid[id(p)] = k
-        seen, out = set(), []
-        for g in self.param_groups:
-            for p in g["params"]:
-                m = _owner(p)
-                if m is None or id(m) in seen:
-                    continue
-                seen.add(id(m))
-                if all(id(q) in gid for q in m._plist):
-                    out.append((weakref.ref(m), np.array([gid[id(q)] for q in m._plist], dtype=np.int64)))
-                    m._guarded = weakref.ref(self)
-        self._fm_key, self._fm_list = key, out
-        return [(r(), gi) for r, gi in out]
+    @staticmethod
+    def _stale(st, eng):
+        return st["m"].numel() != eng.layout.total or st["m"].device != eng.params.device
 
-    def _state_for(self, m, eng):
-        st = self._fused.get(m)
-        if st is None or st["m"].numel() != eng.layout.total or st["m"].device != eng.params.device:
-            # vmax: the AMSGrad maximum of v, allocated on first need (_vmax)
-            st = dict(m=torch.zeros_like(eng.params), v=torch.zeros_like(eng.params), vmax=None,
-                      steps=np.zeros(len(eng.layout.slots), dtype=np.int64))
-            if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
-                saved = self._pending_fused.pop(0)
-                vmax = saved.get("vmax")
-                if saved["m"].numel() == eng.layout.total and len(saved["steps"]) == len(eng.layout.slots) and \
-                        (vmax is None or vmax.numel() == eng.layout.total):
-                    st["m"].copy_(saved["m"]); st["v"].copy_(saved["v"])
-                    st["steps"][:] = np.asarray(saved["steps"], dtype=np.int64)
-                    if vmax is not None:
-                        st["vmax"] = vmax.to(eng.params.device, copy=True)
-                else:
-                    raise _lib.MfmError(
-                        "factorized_amd.optim.Adam.load_state_dict: the saved fused state (%d elements, %d tensors) does not fit "
-                        "this model's flat layout (%d elements, %d tensors) -- a checkpoint of another model / library version; "
-                        "refusing to restart the moments silently" % (saved["m"].numel(), len(saved["steps"]), eng.layout.total,
-                                                                      len(eng.layout.slots)))
-            self._fused[m] = st
-        return st
+    @staticmethod
+    def _new_state(eng):
+        """flat moments and per-tensor step counts; vmax: the AMSGrad maximum of v, allocated on first need (_vmax)"""
+        return dict(m=torch.zeros_like(eng.params), v=torch.zeros_like(eng.params), vmax=None,
+                    steps=np.zeros(len(eng.layout.slots), dtype=np.int64))
+
+    def _restore(self, st, saved, eng):
+        vmax = saved.get("vmax")
+        self._require_fit(saved["m"].numel(), len(saved["steps"]), eng, vmax is None or vmax.numel() == eng.layout.total)
+        st["m"].copy_(saved["m"]); st["v"].copy_(saved["v"])
+        st["steps"][:] = np.asarray(saved["steps"], dtype=np.int64)
+        if vmax is not None:
+            st["vmax"] = vmax.to(eng.params.device, copy=True)
 
     @staticmethod
     def _vmax(st):
@@ -269,6 +488,7 @@ class Adam(torch.optim.Optimizer):
         if "step_dev" in st:
             st["step_dev"].fill_(int(st["steps"].max()))
 
+    # ------------------------------------------------------------------ the update
     def _fused_step(self, m, gidx):
         eng = m.engine
         group = self.param_groups[gidx[0]]
@@ -276,22 +496,9 @@ class Adam(torch.optim.Optimizer):
         if self._capturable and not plain:
             raise _lib.MfmError("factorized_amd.optim.Adam(capturable=True): weight_decay, amsgrad, maximize and a model spread "
                                 "over several parameter groups are not built for the capturable update")
-        import weakref
-        m._guarded = weakref.ref(self)          # (per step: the optimizer that steps the model answers for the guard)
-        gflat = getattr(m, "_grad_flat", None)
-        if gflat is None or not m._grad_views_attached():
-            return False                     # gradients are ordinary per-tensor tensors: the stock optimizer handles them
-        if not m._fast_last:
-            # a parameter was frozen / got a hook after fast-path steps: the flat path would move it (or skip everything);
-            # hand the gradients back to per-tensor tensors and let the stock optimizer apply torch's rules
-            m._detach_grad_views()
+        gflat = self._flat_grads(m, eng)
+        if gflat is None:
             return False
-        if eng.poll_status():
-            # a hand-over of this step (or an earlier one) gave up: its gradients carry the NaN guard, the launch below leaves
-            # the parameters alone.  Clear the status, fall back to separate launches for the rest of the run, say so.
-            import warnings
-            eng.check_status(raise_on_error=False)
-            warnings.warn(eng.status_message(), RuntimeWarning, stacklevel=3)
         st = self._state_for(m, eng)
         if self._fallback is not None and self._fallback.state:
             self._migrate_back(m, st, eng)
@@ -302,48 +509,32 @@ class Adam(torch.optim.Optimizer):
             lr = float(lr)
         present = m._grad_present
         L = _lib.lib()
-        stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index))
-        ptr = lambda t: C.c_void_p(t.data_ptr())
+        stream, guard = _stream_and_guard(eng, gflat)
+        head = (_ptr(eng.params), _ptr(gflat), _ptr(st["m"]), _ptr(st["v"]))
         steps = st["steps"]
-        # guard word of the flat gradient buffer: the plan's backward stores a NaN there when a hand-over inside one of its
-        # launches gave up -- the launch below then leaves parameters and moments alone (engine.check_status() reports it)
-        guard = C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard)
         if self._capturable:
             if not (present.all() and (steps == steps[0]).all()):
                 raise _lib.MfmError("factorized_amd.optim.Adam(capturable=True): every tensor needs a gradient in every step (one "
                                     "device-side step counter); staged losses train through the eager optimizer")
             step_dev, lr_dev = self._device_scalars(st, eng, group["lr"])
-            _lib.check(L.mfm_adam_flat_dev(ptr(eng.params), ptr(gflat), ptr(st["m"]), ptr(st["v"]), eng.layout.total, ptr(step_dev),
-                                           ptr(lr_dev), b1, b2, eps, 1.0, guard, stream), "mfm_adam_flat_dev")
-            steps += 1           # (host mirror: exact in eager use, a lower bound under graph replay -- see state_dict())
+            _lib.check(L.mfm_adam_flat_dev(*head, eng.layout.total, _ptr(step_dev), _ptr(lr_dev), b1, b2, eps, 1.0, guard, stream),
+                       "mfm_adam_flat_dev")
+            steps += 1           # (host mirror: exact in eager use, a lower bound under graph replay -- see _snapshot())
             return True
         if present.all() and (steps == steps[0]).all():
             steps += 1
-            _lib.check(L.mfm_adam_flat_guarded(ptr(eng.params), ptr(gflat), ptr(st["m"]), ptr(st["v"]), eng.layout.total,
-                                               int(steps[0]), lr, b1, b2, eps, 1.0, guard, stream), "mfm_adam_flat_guarded")
+            _lib.check(L.mfm_adam_flat_guarded(*head, eng.layout.total, int(steps[0]), lr, b1, b2, eps, 1.0, guard, stream),
+                       "mfm_adam_flat_guarded")
             return True
         # some tensors have no gradient (stage losses, unused layers): contiguous runs of present tensors with equal
-        # step counts become spans (tensor starts are 64-float aligned: span bounds are multiples of 4)
-        order = np.argsort([o for o, _, _ in eng.layout.slots])
-        starts = [eng.layout.slots[i][0] for i in order] + [eng.layout.guard]
-        spans = []
-        for k, i in enumerate(order):
-            if not present[i]:
-                continue
-            steps[i] += 1
-            b, e_, s_ = starts[k], starts[k + 1], int(steps[i])
-            if spans and spans[-1][1] == b and spans[-1][2] == s_:
-                spans[-1] = (spans[-1][0], e_, s_)
-            else:
-                spans.append((b, e_, s_))
-        for k in range(0, len(spans), _lib.MFM_ADAM_MAX_SPANS):
-            part = spans[k:k + _lib.MFM_ADAM_MAX_SPANS]
-            arr = (_lib.AdamSpan * len(part))()
-            for j, (b, e_, s_) in enumerate(part):
-                arr[j].begin, arr[j].end, arr[j].step = b, e_, s_
-            _lib.check(L.mfm_adam_flat_spans_guarded(ptr(eng.params), ptr(gflat), ptr(st["m"]), ptr(st["v"]), arr, len(part), lr, b1,
-                                                     b2, eps, 1.0, guard, stream), "mfm_adam_flat_spans_guarded")
+        # step counts become spans
+        steps[present] += 1
+        spans = _merge_spans(st["order"], st["starts"], present, [(s,) for s in steps.tolist()])
+        _launch_tables(L.mfm_adam_flat_spans_guarded, "mfm_adam_flat_spans_guarded", head,
+                       _span_tables(spans, _lib.AdamSpan, _lib.MFM_ADAM_MAX_SPANS, ("step",)), (lr, b1, b2, eps, 1.0, guard, stream))
         return True
+
+    _EXT_FIELDS = ("lr", "beta1", "beta2", "eps", "weight_decay", "flags", "step")
 
     def _ext_step(self, m, gidx, st, gflat):
         """an option (weight decay, AMSGrad, maximize) or several groups: every tensor with a gradient is a span of ONE launch of
@@ -357,74 +548,29 @@ class Adam(torch.optim.Optimizer):
             hyper.append((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), fl))
         # (layers no forward uses carry a zero gradient on the flat path; torch's .grad is None there: no decay, no step count)
         present, steps = m._grad_present & ~m._group_masks()["unreached"], st["steps"]
+        order, starts = st["order"], st["starts"]
         if "runs" not in st or st["runs"][0] is not gidx:
-            # tensors in address order, and the runs of adjacent tensors of one group (tensor starts are 64-float aligned: span
-            # bounds are multiples of 4)
-            order = np.argsort([o for o, _, _ in eng.layout.slots], kind="stable")
-            starts = [eng.layout.slots[i][0] for i in order] + [eng.layout.guard]
-            runs = []
-            for k, i in enumerate(order):
-                if runs and runs[-1][2] == gidx[i]:
-                    runs[-1][1] = starts[k + 1]
-                else:
-                    runs.append([starts[k], starts[k + 1], int(gidx[i])])
-            st["runs"] = (gidx, order, starts, runs)
-        _, order, starts, runs = st["runs"]
+            # the runs (begin, end, group) of adjacent tensors of one group
+            st["runs"] = (gidx, order, starts, _merge_spans(order, starts, np.ones(len(order), dtype=bool), gidx.tolist()))
         if present.all() and (steps == steps[0]).all():
             steps += 1
             s_ = int(steps[0])
-            spans = [(b, e, gi, s_) for b, e, gi in runs]
+            spans = [(b, e, hyper[gi] + (s_,)) for b, e, gi in st["runs"][3]]
         else:
-            spans = []
-            for k, i in enumerate(order):
-                if not present[i]:
-                    continue             # no gradient: moments, vmax, step count and decoupled decay all stay (torch skips it)
-                steps[i] += 1
-                b, e, gi, s_ = starts[k], starts[k + 1], int(gidx[i]), int(steps[i])
-                if spans and spans[-1][1] == b and spans[-1][3] == s_ and hyper[spans[-1][2]] == hyper[gi]:
-                    spans[-1] = (spans[-1][0], e, spans[-1][2], s_)
-                else:
-                    spans.append((b, e, gi, s_))
+            # no gradient: moments, vmax, step count and decoupled decay all stay (torch skips it)
+            steps[present] += 1
+            spans = _merge_spans(order, starts, present, [hyper[gi] + (s,) for gi, s in zip(gidx.tolist(), steps.tolist())])
         if not spans:
             return True                  # no tensor has a gradient: torch's step does nothing either
-        amsgrad = any(hyper[gi][5] & _lib.MFM_ADAMX_AMSGRAD for _, _, gi, _ in spans)
-        L = _lib.lib()
-        stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index))
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        vmax = ptr(self._vmax(st)) if amsgrad else C.c_void_p(None)
-        # guard word of the flat gradient buffer (_fused_step): a NaN there leaves parameters, moments and vmax alone
-        guard = C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard)
-        for k in range(0, len(spans), _lib.MFM_ADAMX_MAX_SPANS):
-            part = spans[k:k + _lib.MFM_ADAMX_MAX_SPANS]
-            arr = (_lib.AdamExtSpan * len(part))()
-            for j, (b, e, gi, s_) in enumerate(part):
-                a = arr[j]
-                a.begin, a.end, a.step = b, e, s_
-                a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.flags = hyper[gi]
-            _lib.check(L.mfm_adam_ext_flat_spans_guarded(ptr(eng.params), ptr(gflat), ptr(st["m"]), ptr(st["v"]), vmax, arr,
-                                                         len(part), 1.0, guard, stream), "mfm_adam_ext_flat_spans_guarded")
+        amsgrad = any(key[5] & _lib.MFM_ADAMX_AMSGRAD for _, _, key in spans)
+        stream, guard = _stream_and_guard(eng, gflat)       # (a NaN guard leaves vmax alone too)
+        vmax = _ptr(self._vmax(st)) if amsgrad else C.c_void_p(None)
+        _launch_tables(_lib.lib().mfm_adam_ext_flat_spans_guarded, "mfm_adam_ext_flat_spans_guarded",
+                       (_ptr(eng.params), _ptr(gflat), _ptr(st["m"]), _ptr(st["v"]), vmax),
+                       _span_tables(spans, _lib.AdamExtSpan, _lib.MFM_ADAMX_MAX_SPANS, self._EXT_FIELDS), (1.0, guard, stream))
         return True
 
-    def _fallback_step(self, rest):
-        if not rest:
-            return
-        ids = tuple(id(p) for _, ps in rest for p in ps)
-        if self._fallback is None or self._fallback_ids != ids:
-            groups = [dict(params=ps, **{k: g[k] for k in _ADAM_HYPER}) for g, ps in rest]
-            self._fallback = torch.optim.Adam(groups, foreach=self.defaults["foreach"])
-            self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
-            self._fallback_ids = ids
-            self._migrate_fused_state(rest)
-            fb = getattr(self, "_pending_fallback", None)
-            if fb is not None:
-                self._fallback.load_state_dict(fb)
-                self._pending_fallback = None
-        for fg, (g, _) in zip(self._fallback.param_groups, rest):
-            for k in _ADAM_HYPER:
-                fg[k] = g[k]                        # schedulers act on OUR groups
-        self._fallback.step()
-
-    def _migrate_fused_state(self, rest):
+    def _inner_rebuilt(self, rest, old):
         """parameters of a fused model that now go through the stock optimizer (a parameter was frozen / got a hook after
         fast-path steps): their moments and step counts move along -- Adam must not restart"""
         for g, ps in rest:
@@ -457,97 +603,21 @@ class Adam(torch.optim.Optimizer):
                 st["step_dev"].zero_()
 
     # ------------------------------------------------------------------ checkpoints
-    def state_dict(self):
-        """torch's dict plus the flat Adam state of every fused model under "fused" (in the order the models appear in the
-        parameter groups): first / second moments and per-tensor step counts (capturable mode: the device counter)."""
-        sd = super().state_dict()
-        fused = []
-        for m, _ in self._fused_models():
-            st = self._fused.get(m)
-            if st is None:
-                continue
-            steps = st["steps"].copy()
-            if "step_dev" in st:
-                steps[:] = int(st["step_dev"].item())
-            fused.append(dict(m=st["m"].detach().clone(), v=st["v"].detach().clone(), steps=steps.tolist()))
-            if st["vmax"] is not None:       # (AMSGrad only: a state without it keeps the keys it always had)
-                fused[-1]["vmax"] = st["vmax"].detach().clone()
-        if self._pending_fused:          # loaded, not stepped yet: what was loaded is still the state
-            fused += [dict(f) for f in self._pending_fused]
-        sd["fused"] = fused
-        if self._fallback is not None:
-            sd["fallback"] = self._fallback.state_dict()
-        return sd
+    def _snapshot(self, m, st):
+        """a "fused" entry: first / second moments and per-tensor step counts (capturable mode: the device counter)"""
+        if st is None:
+            return None
+        steps = st["steps"].copy()
+        if "step_dev" in st:
+            steps[:] = int(st["step_dev"].item())
+        entry = dict(m=st["m"].detach().clone(), v=st["v"].detach().clone(), steps=steps.tolist())
+        if st["vmax"] is not None:       # (AMSGrad only: a state without it keeps the keys it always had)
+            entry["vmax"] = st["vmax"].detach().clone()
+        return entry
 
-    def load_state_dict(self, state_dict):
-        sd = dict(state_dict)
-        fused = sd.pop("fused", None)
-        fb = sd.pop("fallback", None)
-        super().load_state_dict(sd)
-        self._fused.clear()
-        self._pending_fused = [dict(f, steps=list(f["steps"])) for f in fused] if fused else None
-        self._pending_fallback = fb
-
-    # ------------------------------------------------------------------ Optimizer interface
-    def step(self, closure=None):
-        """(round 6) Not wrapped by torch's `profile_hook_step` (`step.hooked` below): that wrapper opens a record_function scope
-        around every step, ~10 us of host time against a 150 us device step the unchanged loop has to keep fed.  Step pre / post
-        hooks registered on this optimizer or globally are still honoured."""
-        hooks = self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(_GLOBAL_PRE) > 1 or _GLOBAL_POST
-        if hooks:
-            for h in list(_GLOBAL_PRE.values()) + list(self._optimizer_step_pre_hooks.values()):
-                if h is not _foreign_step_hook:
-                    h(self, (closure,) if closure is not None else (), {})
-        prev = torch.is_grad_enabled()
-        torch._C._set_grad_enabled(False)
-        try:
-            loss = self._step(closure)
-        finally:
-            torch._C._set_grad_enabled(prev)
-        if hooks:
-            for h in list(self._optimizer_step_post_hooks.values()) + list(_GLOBAL_POST.values()):
-                h(self, (closure,) if closure is not None else (), {})
-        return loss
-    step.hooked = True
-
-    def _step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        done, ndone = set(), 0
-        for m, gidx in self._fused_models():
-            if m._plist[0].is_cuda and self._fused_step(m, gidx):
-                done.add(id(m))
-                ndone += len(m._plist)
-        if ndone == sum(len(g["params"]) for g in self.param_groups):
-            return loss                               # (the reference's case: one model, nothing left)
-        rest = []
-        for group in self.param_groups:
-            left = [p for p in group["params"] if id(_owner(p)) not in done] if done else list(group["params"])
-            if left:
-                rest.append((group, left))
-        self._fallback_step(rest)
-        return loss
-
-    def zero_grad(self, set_to_none=True):
-        cleared, nh = set(), 0
-        for m, _ in self._fused_models():
-            if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
-                m._zero_flat_grads(set_to_none)
-                cleared.add(id(m))
-                nh += len(m._plist)
-        if nh == sum(len(g["params"]) for g in self.param_groups):
-            return
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None or (cleared and id(_owner(p)) in cleared):
-                    continue
-                if set_to_none:
-                    p.grad = None
-                else:
-                    p.grad.detach_()
-                    p.grad.zero_()
+    @staticmethod
+    def _loaded_entry(f):
+        return dict(f, steps=list(f["steps"]))
 
 
 class AdamW(Adam):
@@ -560,10 +630,7 @@ class AdamW(Adam):
                          capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
 
 
-_SGD_HYPER = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize")
-
-
-class SGD(torch.optim.Optimizer):
+class SGD(_FlatOptimizer):
     """torch.optim.SGD with momentum (same signature, validation and arithmetic) whose fused models are updated by ONE launch of
     `mfm_sgd_flat_spans_guarded` per step: the reference's other optimizer line (mfm_mosi.py:404, commented out under the Adam
     line in every driver).
@@ -587,6 +654,12 @@ class SGD(torch.optim.Optimizer):
     Which side holds a model's live buffers is tracked per model: a model that steps through the inner optimizer (from its
     first step on, or after flat steps) is "away", and its next flat step takes the inner optimizer's buffers back."""
 
+    _inner_cls = torch.optim.SGD
+    _hyper = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize")
+    _state_word = "momentum"
+    _capture_refusal = ("factorized_amd.optim.SGD.step() inside a stream capture: the SGD update is eager only "
+                        "(hipGraph capture of a training step: train.GraphedModuleStep with optim.Adam(capturable=True))")
+
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
                  foreach=None, differentiable=False, fused=None):
         # torch.optim.SGD's checks, in its order and with its messages
@@ -609,67 +682,30 @@ class SGD(torch.optim.Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=maximize, foreach=foreach, differentiable=False, fused=None)
         super().__init__(params, defaults)
-        import weakref
-        # module -> flat momentum state of a fused model (weak keys: a model that is gone takes its state with it)
-        self._fused = weakref.WeakKeyDictionary()
-        self._fallback = None       # inner torch.optim.SGD over everything that is not fused
-        self._fallback_ids = None
-        self._fm_key = None
-        self._fm_list = []
-        self._pending_fused = None  # fused states of a load_state_dict() waiting for their models' first step
-        self._pending_fallback = None
         # fused models whose live momentum buffers are in the inner optimizer (they stepped through it since their last flat step)
         self._away = weakref.WeakSet()
-        self._fused_models()        # marks the models this optimizer owns (their hand-overs stay on)
+        self._init_flat()
 
-    # ------------------------------------------------------------------ helpers
-    def _fused_models(self):
-        """[(model, group index of every tensor)] for the fused models whose parameters all lie in this optimizer's groups;
-        cached while the groups hold the same lists of the same lengths"""
-        key = tuple((id(g["params"]), len(g["params"]), id(g["params"][0]) if g["params"] else 0) for g in self.param_groups)
-        if key == self._fm_key and all(r() is not None for r, _ in self._fm_list):
-            return [(r(), gi) for r, gi in self._fm_list]
-        import weakref
-        gid = {}
-        for k, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                gid[id(p)] = k
-        seen, out = set(), []
-        for g in self.param_groups:
-            for p in g["params"]:
-                m = _owner(p)
-                if m is None or id(m) in seen:
-                    continue
-                seen.add(id(m))
-                if all(id(q) in gid for q in m._plist):
-                    out.append((weakref.ref(m), np.array([gid[id(q)] for q in m._plist], dtype=np.int64)))
-                    m._guarded = weakref.ref(self)
-        self._fm_key, self._fm_list = key, out
-        return [(r(), gi) for r, gi in out]
+    # ------------------------------------------------------------------ per-model state
+    @staticmethod
+    def _stale(st, eng):
+        return st["total"] != eng.layout.total or (st["buf"] is not None and st["buf"].device != eng.params.device)
 
-    def _state_for(self, m, eng):
-        st = self._fused.get(m)
-        n = len(eng.layout.slots)
-        if st is None or st["total"] != eng.layout.total or (st["buf"] is not None and st["buf"].device != eng.params.device):
-            order = np.argsort([o for o, _, _ in eng.layout.slots], kind="stable")
-            starts = [eng.layout.slots[i][0] for i in order] + [eng.layout.guard]
-            st = dict(total=eng.layout.total, buf=None, have=np.zeros(n, dtype=bool), pending=None, gseen=None,
-                      order=order, starts=starts, spans={})
-            if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
-                saved = self._pending_fused.pop(0)
-                if saved["total"] != eng.layout.total or len(saved["have"]) != n:
-                    raise _lib.MfmError(
-                        "factorized_amd.optim.SGD.load_state_dict: the saved fused state (%d elements, %d tensors) does not fit "
-                        "this model's flat layout (%d elements, %d tensors) -- a checkpoint of another model / library version; "
-                        "refusing to restart the momentum silently" % (saved["total"], len(saved["have"]), eng.layout.total, n))
-                st["have"][:] = np.asarray(saved["have"], dtype=bool)
-                if saved["buf"] is not None:
-                    st["buf"] = saved["buf"].to(eng.params.device, copy=True)
-                    for i in np.flatnonzero(~st["have"]):
-                        o, k, _ = eng.layout.slots[i]
-                        st["buf"][o:o + k].zero_()       # (no buffer: a zero slot, whatever the checkpoint held there)
-            self._fused[m] = st
-        return st
+    @staticmethod
+    def _new_state(eng):
+        """the flat momentum buffer (None before any momentum step), the per-tensor "buffer exists" flags, the first-step
+        bookkeeping of the class doc (pending, gseen) and the span tables of earlier steps"""
+        return dict(total=eng.layout.total, buf=None, have=np.zeros(len(eng.layout.slots), dtype=bool), pending=None, gseen=None,
+                    spans={})
+
+    def _restore(self, st, saved, eng):
+        self._require_fit(saved["total"], len(saved["have"]), eng)
+        st["have"][:] = np.asarray(saved["have"], dtype=bool)
+        if saved["buf"] is not None:
+            st["buf"] = saved["buf"].to(eng.params.device, copy=True)
+            for i in np.flatnonzero(~st["have"]):
+                o, k, _ = eng.layout.slots[i]
+                st["buf"][o:o + k].zero_()       # (no buffer: a zero slot, whatever the checkpoint held there)
 
     @staticmethod
     def _resolve_pending(st):
@@ -713,6 +749,9 @@ class SGD(torch.optim.Optimizer):
             else:
                 fb.state.pop(p, None)
 
+    # ------------------------------------------------------------------ the update
+    _FIELDS = ("lr", "weight_decay", "momentum", "dampening", "flags")
+
     def _spans_of(self, st, present, gidx):
         """ctypes span tables for this step (cached per pattern of present tensors, existing buffers and hyper-parameters)"""
         hyper = tuple((float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), float(g["dampening"]),
@@ -723,29 +762,17 @@ class SGD(torch.optim.Optimizer):
         hit = st["spans"].get(key)
         if hit is not None:
             return hit
-        starts, spans, first, first_damp = st["starts"], [], [], []
-        for k, i in enumerate(st["order"]):
-            if not present[i]:
-                continue
+        keys, first, first_damp = [None] * len(have), [], []
+        for i in np.flatnonzero(present):
             lr, wd, mom, damp, fl = hyper[gidx[i]]
             if mom != 0.0 and not have[i]:
                 fl |= _lib.MFM_SGD_FIRST
                 first.append(i)
                 if damp != 0.0:
                     first_damp.append(i)
-            b, e, h = starts[k], starts[k + 1], (lr, wd, mom, damp, fl)
-            if spans and spans[-1][1] == b and spans[-1][2] == h:
-                spans[-1] = (spans[-1][0], e, h)
-            else:
-                spans.append((b, e, h))
-        tables = []
-        for k in range(0, len(spans), _lib.MFM_SGD_MAX_SPANS):
-            part = spans[k:k + _lib.MFM_SGD_MAX_SPANS]
-            arr = (_lib.SgdSpan * len(part))()
-            for j, (b, e, (lr, wd, mom, damp, fl)) in enumerate(part):
-                arr[j].begin, arr[j].end, arr[j].flags = b, e, fl
-                arr[j].lr, arr[j].weight_decay, arr[j].momentum, arr[j].dampening = lr, wd, mom, damp
-            tables.append((arr, len(part)))
+            keys[i] = (lr, wd, mom, damp, fl)
+        spans = _merge_spans(st["order"], st["starts"], present, keys)
+        tables = _span_tables(spans, _lib.SgdSpan, _lib.MFM_SGD_MAX_SPANS, self._FIELDS)
         momentum = any(h[2] != 0.0 for _, _, h in spans)
         hit = (tables, np.array(first, dtype=np.int64), np.array(first_damp, dtype=np.int64), momentum)
         if len(st["spans"]) > 32:
@@ -755,18 +782,9 @@ class SGD(torch.optim.Optimizer):
 
     def _fused_step(self, m, gidx):
         eng = m.engine
-        import weakref
-        m._guarded = weakref.ref(self)          # (per step: the optimizer that steps the model answers for the guard)
-        gflat = getattr(m, "_grad_flat", None)
-        if gflat is None or not m._grad_views_attached():
-            return False                     # gradients are ordinary per-tensor tensors: the inner optimizer handles them
-        if not m._fast_last:
-            m._detach_grad_views()           # (Adam._fused_step: a parameter was frozen / got a hook after fast-path steps)
+        gflat = self._flat_grads(m, eng)
+        if gflat is None:
             return False
-        if eng.poll_status():
-            import warnings
-            eng.check_status(raise_on_error=False)
-            warnings.warn(eng.status_message(), RuntimeWarning, stacklevel=3)
         st = self._state_for(m, eng)
         if m in self._away:
             self._migrate_back(m, st, eng)
@@ -775,14 +793,10 @@ class SGD(torch.optim.Optimizer):
         tables, first, first_damp, momentum = self._spans_of(st, m._grad_present, gidx)
         if not tables:
             return True                      # no tensor has a gradient: torch's step does nothing either
-        L = _lib.lib()
-        stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index))
-        buf = C.c_void_p(self._buf(st, eng.params).data_ptr()) if momentum else C.c_void_p(None)
-        # guard word of the flat gradient buffer (Adam._fused_step): a NaN there leaves parameters and buffers alone
-        guard = C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard)
-        for arr, n in tables:
-            _lib.check(L.mfm_sgd_flat_spans_guarded(C.c_void_p(eng.params.data_ptr()), C.c_void_p(gflat.data_ptr()), buf, arr, n,
-                                                    1.0, guard, stream), "mfm_sgd_flat_spans_guarded")
+        stream, guard = _stream_and_guard(eng, gflat)
+        buf = _ptr(self._buf(st, eng.params)) if momentum else C.c_void_p(None)
+        _launch_tables(_lib.lib().mfm_sgd_flat_spans_guarded, "mfm_sgd_flat_spans_guarded", (_ptr(eng.params), _ptr(gflat), buf),
+                       tables, (1.0, guard, stream))
         if len(first):
             st["have"][first] = True
             if len(first_damp):
@@ -793,24 +807,14 @@ class SGD(torch.optim.Optimizer):
                 st["pending"] = first_damp
         return True
 
-    def _fallback_step(self, rest):
-        if not rest:
-            return
-        ids = tuple(id(p) for _, ps in rest for p in ps)
-        if self._fallback is None or self._fallback_ids != ids:
-            old = self._fallback
-            groups = [dict(params=ps, **{k: g[k] for k in _SGD_HYPER}) for g, ps in rest]
-            self._fallback = torch.optim.SGD(groups, foreach=self.defaults["foreach"])
-            self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
-            self._fallback_ids = ids
-            if old is not None:                     # buffers of tensors that stay with the inner optimizer stay too
-                idset = set(ids)
-                for p, s in old.state.items():
-                    if id(p) in idset:
-                        self._fallback.state[p] = s
-            if self._pending_fallback is not None:
-                self._fallback.load_state_dict(self._pending_fallback)
-                self._pending_fallback = None
+    def _inner_rebuilt(self, rest, old):
+        if old is not None:                     # buffers of tensors that stay with the inner optimizer stay too
+            idset = set(self._fallback_ids)
+            for p, s in old.state.items():
+                if id(p) in idset:
+                    self._fallback.state[p] = s
+
+    def _inner_stepping(self, ids):
         idset = set(ids)
         for m, _ in self._fused_models():
             if m in self._away or id(m._plist[0]) not in idset or not m._plist[0].is_cuda:
@@ -823,116 +827,36 @@ class SGD(torch.optim.Optimizer):
             if st is not None:
                 self._migrate_out(m, st)
             self._away.add(m)
-        for fg, (g, _) in zip(self._fallback.param_groups, rest):
-            for k in _SGD_HYPER:
-                fg[k] = g[k]                        # schedulers act on OUR groups
-        self._fallback.step()
 
     # ------------------------------------------------------------------ checkpoints
-    def state_dict(self):
-        """torch's dict plus, under "fused", the momentum state of every fused model (in the order the models appear in the
-        parameter groups): its flat buffer (None before any momentum step) and the per-tensor "buffer exists" flags; plus the
-        inner optimizer's state under "fallback"."""
-        sd = super().state_dict()
-        fused = []
-        for m, _ in self._fused_models():
-            st = self._fused.get(m)
-            away = m in self._away
-            if st is None and not away:
-                continue
-            if not away:
-                self._resolve_pending(st)
-                buf = st["buf"].detach().clone() if st["buf"] is not None else None
-                have = st["have"].tolist()
-            else:                            # stepping through the inner optimizer: its buffers are the live ones
-                eng = m.engine
-                buf, have = torch.zeros_like(eng.params), []
-                for i, p in enumerate(m._plist):
-                    b = self._fallback.state.get(p, {}).get("momentum_buffer")
-                    if b is not None:
-                        o, n, shp = eng.layout.slots[i]
-                        buf[o:o + n].view(shp).copy_(b)
-                    have.append(b is not None)
-            fused.append(dict(total=m.engine.layout.total, buf=buf, have=have))
-        if self._pending_fused:          # loaded, not stepped yet: what was loaded is still the state
-            fused += [dict(f) for f in self._pending_fused]
-        sd["fused"] = fused
-        if self._fallback is not None:
-            sd["fallback"] = self._fallback.state_dict()
-        return sd
+    def _snapshot(self, m, st):
+        """a "fused" entry: the model's flat momentum buffer (None before any momentum step) and the per-tensor "buffer exists"
+        flags"""
+        away = m in self._away
+        if st is None and not away:
+            return None
+        if not away:
+            self._resolve_pending(st)
+            buf = st["buf"].detach().clone() if st["buf"] is not None else None
+            have = st["have"].tolist()
+        else:                            # stepping through the inner optimizer: its buffers are the live ones
+            eng = m.engine
+            buf, have = torch.zeros_like(eng.params), []
+            for i, p in enumerate(m._plist):
+                b = self._fallback.state.get(p, {}).get("momentum_buffer")
+                if b is not None:
+                    o, n, shp = eng.layout.slots[i]
+                    buf[o:o + n].view(shp).copy_(b)
+                have.append(b is not None)
+        return dict(total=m.engine.layout.total, buf=buf, have=have)
+
+    @staticmethod
+    def _loaded_entry(f):
+        return dict(total=int(f["total"]), buf=f["buf"], have=list(f["have"]))
 
     def load_state_dict(self, state_dict):
-        sd = dict(state_dict)
-        fused = sd.pop("fused", None)
-        fb = sd.pop("fallback", None)
-        super().load_state_dict(sd)
-        self._fused.clear()
-        import weakref
+        super().load_state_dict(state_dict)
         self._away = weakref.WeakSet()      # (the loaded fused entries hold every model's live buffers)
-        self._pending_fused = [dict(total=int(f["total"]), buf=f["buf"], have=list(f["have"])) for f in fused] if fused else None
-        self._pending_fallback = fb
-        if self._fallback is not None and fb is not None:
-            self._fallback.load_state_dict(fb)
+        if self._fallback is not None and self._pending_fallback is not None:
+            self._fallback.load_state_dict(self._pending_fallback)
             self._pending_fallback = None
-
-    # ------------------------------------------------------------------ Optimizer interface
-    def step(self, closure=None):
-        """(Adam.step: not wrapped by torch's profile_hook_step; step hooks are still honoured)"""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise _lib.MfmError("factorized_amd.optim.SGD.step() inside a stream capture: the SGD update is eager only "
-                                "(hipGraph capture of a training step: train.GraphedModuleStep with optim.Adam(capturable=True))")
-        hooks = self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(_GLOBAL_PRE) > 1 or _GLOBAL_POST
-        if hooks:
-            for h in list(_GLOBAL_PRE.values()) + list(self._optimizer_step_pre_hooks.values()):
-                if h is not _foreign_step_hook:
-                    h(self, (closure,) if closure is not None else (), {})
-        prev = torch.is_grad_enabled()
-        torch._C._set_grad_enabled(False)
-        try:
-            loss = self._step(closure)
-        finally:
-            torch._C._set_grad_enabled(prev)
-        if hooks:
-            for h in list(self._optimizer_step_post_hooks.values()) + list(_GLOBAL_POST.values()):
-                h(self, (closure,) if closure is not None else (), {})
-        return loss
-    step.hooked = True
-
-    def _step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        done, ndone = set(), 0
-        for m, gidx in self._fused_models():
-            if m._plist[0].is_cuda and self._fused_step(m, gidx):
-                done.add(id(m))
-                ndone += len(m._plist)
-        if ndone == sum(len(g["params"]) for g in self.param_groups):
-            return loss                               # (the reference's case: one model, nothing left)
-        rest = []
-        for group in self.param_groups:
-            left = [p for p in group["params"] if id(_owner(p)) not in done] if done else list(group["params"])
-            if left:
-                rest.append((group, left))
-        self._fallback_step(rest)
-        return loss
-
-    def zero_grad(self, set_to_none=True):
-        cleared, nh = set(), 0
-        for m, _ in self._fused_models():
-            if getattr(m, "_grad_flat", None) is not None and m._grad_views_attached():
-                m._zero_flat_grads(set_to_none)
-                cleared.add(id(m))
-                nh += len(m._plist)
-        if nh == sum(len(g["params"]) for g in self.param_groups):
-            return
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None or (cleared and id(_owner(p)) in cleared):
-                    continue
-                if set_to_none:
-                    p.grad = None
-                else:
-                    p.grad.detach_()
-                    p.grad.zero_()
