@@ -38,6 +38,36 @@ def _require_cuda(t, what):
     _lib.lib()
 
 
+def _require_f32(what, dev, names, tensors):
+    """The kernels read parameters through raw pointers as dense fp32: a tensor of another dtype (a module after .double() /
+    .half() / .bfloat16()), on another device than the input, or not contiguous would be read as garbage or past its end.
+    Refused here, before any allocation or launch -- never converted silently (that would detach the gradient from the
+    parameter's dtype and hide the driver's mistake).  `None` entries (a Linear without bias) are skipped.  Works on CPU
+    tensors too: the CUDA requirement itself is `_require_cuda`'s."""
+    for name, t in zip(names, tensors):
+        if t is None:
+            continue
+        if t.dtype is not torch.float32 or t.device != dev or not t.is_contiguous():
+            raise _lib.MfmError("%s: %s is %s on %s with shape %s and strides %s; the HIP kernels take contiguous torch.float32 "
+                                "parameters on the input's device (%s) -- convert the module back with .float(), move it with "
+                                ".to(device), or make the tensor contiguous" % (what, name, t.dtype, t.device, tuple(t.shape),
+                                                                                tuple(t.stride()), dev))
+
+
+_LSTM_NAMES = ("lstm.weight_ih", "lstm.weight_hh", "lstm.bias_ih", "lstm.bias_hh", "fc1.weight", "fc1.bias")
+_CELL_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+def _consume(ctx, what):
+    """mfm_lstm_seq_bwd turns the saved gates into dA in place (through a raw pointer: torch's version counter does not see
+    it), so a graph through a recurrent op can be back-propagated once.  Raises on the second time; the caller sets
+    `ctx.consumed` once its BPTT launch is enqueued."""
+    if getattr(ctx, "consumed", False):
+        raise RuntimeError("%s backward: this graph was already back-propagated (BPTT overwrites the saved gates in place; "
+                           "a second backward()/autograd.grad() through the same forward is not supported -- run the forward "
+                           "again, or sum the losses and back-propagate once)" % what)
+
+
 def _hp(h):
     return (h + 15) // 16 * 16
 
@@ -83,6 +113,7 @@ class _EncoderSeqFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b):
+        _require_f32("encoderLSTM", x.device, _LSTM_NAMES, (w_ih, w_hh, b_ih, b_hh, fc_w, fc_b))
         T, B, d = x.shape
         h = w_hh.shape[1]
         Hp = _hp(h)
@@ -105,6 +136,7 @@ class _EncoderSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
+        _consume(ctx, "encoderLSTM")
         xr, w_ih, w_hh, fc_w, gates, hs, cs = ctx.saved_tensors
         T, B, d, h, Hp, ldx, need_dx, xshape = ctx.dims
         dev = d_out.device
@@ -122,6 +154,7 @@ class _EncoderSeqFn(torch.autograd.Function):
             E.make_gemm(d_out, ones, g_fcb, n_out, 1, B, a_sm=1, a_sk=n_out, b_sk=1, b_sn=1, ldc=1,
                         accumulate=1, split_k=0)])
         E.lstm_seq([E.make_seq(gates, hs, cs, w_hh, h, dh_ext=dh_last, ld_dh=h)], T, B, backward=True)
+        ctx.consumed = True
         descs = [E.make_gemm(gates, xr, g_wih, h, d, T * B, a_sm=1, a_sk=4 * Hp, b_sk=ldx, b_sn=1, ldc=d,
                              batch=4, a_sz=Hp, c_sz=h * d, accumulate=1, split_k=0),
                  E.make_gemm(gates, ones, g_bih, h, 1, T * B, a_sm=1, a_sk=4 * Hp, b_sk=1, b_sn=1, ldc=1,
@@ -142,6 +175,7 @@ class _EncoderSeqFn(torch.autograd.Function):
 class _DecoderSeqFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hT, t, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b):
+        _require_f32("decoderLSTM", hT.device, _LSTM_NAMES, (w_ih, w_hh, b_ih, b_hh, fc_w, fc_b))
         B, h = hT.shape
         T = int(t)
         Hp = _hp(h)
@@ -162,6 +196,7 @@ class _DecoderSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
+        _consume(ctx, "decoderLSTM")
         hT, w_ih, w_hh, b_ih, b_hh, fc_w, gates, hs, cs = ctx.saved_tensors
         T, B, d, h, Hp = ctx.dims
         dev = d_out.device
@@ -179,6 +214,7 @@ class _DecoderSeqFn(torch.autograd.Function):
         d_hT = torch.empty(B, h, device=dev)
         E.lstm_seq([E.make_seq(gates, hs, cs, w_hh, h, w_ih=w_ih, b_ih=b_ih, b_hh=b_hh, h_init=hT, is_dec=True,
                                dh_ext=dhs, ld_dh=Hp, d_h_init=d_hT)], T, B, backward=True)
+        ctx.consumed = True
         descs = [E.make_gemm(gates, hT, g_wih, h, h, B, a_sm=1, a_sk=4 * Hp, b_sk=h, b_sn=1, ldc=h,
                              batch=4, a_sz=Hp, c_sz=h * h, accumulate=1, split_k=0),
                  E.make_gemm(gates, ones, g_bih, h, 1, T * B, a_sm=1, a_sk=4 * Hp, b_sk=1, b_sn=1, ldc=1,
@@ -199,8 +235,11 @@ class _DecoderGroupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, n, t, *args):
+        ctx.set_materialize_grads(False)          # the gradient of an unused output arrives as None: zero-filled in backward
         T = int(t)
         dev = args[0].device
+        for i in range(n):
+            _require_f32("decoder_group[%d]" % i, dev, _LSTM_NAMES, args[7 * i + 1:7 * i + 7])
         seqs, heads, saved, dims, outs = [], [], [], [], []
         for i in range(n):
             hT, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b = args[7 * i:7 * i + 7]
@@ -225,6 +264,7 @@ class _DecoderGroupFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
+        _consume(ctx, "decoder_group")
         saved = ctx.saved_tensors
         T, dims = ctx.dims
         dev = saved[0].device
@@ -259,6 +299,7 @@ class _DecoderGroupFn(torch.autograd.Function):
         E.gemm_grouped(pre)
         for i in range(0, len(seqs), 4):
             E.lstm_seq(seqs[i:i + 4], T, dims[0][0], backward=True)
+        ctx.consumed = True
         E.gemm_grouped(post)
         del keep
         return (None, None) + tuple(grads)
@@ -281,6 +322,7 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
+        _require_f32("Linear", x.device, ("weight", "bias"), (w, b))
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous().float()
         M, K = x2.shape
@@ -344,6 +386,9 @@ class _MemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g1_att, g2_att, chat, w1m, w2m, w1b, b1b, w2b, b2b, p1, p2, train):
+        _require_f32("MFN memory recurrence", chat.device,
+                     ("gamma1_fc1.weight[:, mem]", "gamma2_fc1.weight[:, mem]", "gamma1_fc2.weight", "gamma1_fc2.bias",
+                      "gamma2_fc2.weight", "gamma2_fc2.bias"), (w1m, w2m, w1b, b1b, w2b, b2b))
         T, B, H1 = g1_att.shape
         H2, M = g2_att.shape[2], chat.shape[2]
         dev = chat.device
@@ -413,7 +458,10 @@ class _GroupLinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, n, *args):
+        ctx.set_materialize_grads(False)          # the gradient of an unused output arrives as None: zero-filled in backward
         xs, ws, bs = args[:n], args[n:2 * n], args[2 * n:3 * n]
+        for i in range(n):
+            _require_f32("linear_group[%d]" % i, xs[i].device, ("weight", "bias"), (ws[i], bs[i]))
         x2s, ys, descs = [], [], []
         for x, w, b in zip(xs, ws, bs):
             x2 = x.reshape(-1, x.shape[-1]).contiguous().float()
@@ -464,6 +512,7 @@ class HipLinear(nn.Linear):
 
     def forward(self, x):
         _require_cuda(x, "Linear.forward")
+        _require_f32("Linear", x.device, ("weight", "bias"), (self.weight, self.bias))
         return _LinearFn.apply(x, self.weight, self.bias)
 
 
@@ -477,6 +526,7 @@ class _SeqGroupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, kinds, *args):
+        ctx.set_materialize_grads(False)          # the gradient of an unused output arrives as None: zero-filled in backward
         specs, pos = [], 0
         for k in kinds:
             n = 7 if k == "enc" else 5
@@ -484,6 +534,11 @@ class _SeqGroupFn(torch.autograd.Function):
             pos += n
         T, B = args[0].shape[0], args[0].shape[1]
         dev = args[0].device
+        for i, sp in enumerate(specs):
+            if sp[0] == "enc":
+                _require_f32("seq_group encoder[%d]" % i, dev, _LSTM_NAMES, sp[2:8])
+            else:
+                _require_f32("seq_group state LSTM[%d]" % i, dev, _CELL_NAMES, sp[2:6])
         proj, seqs, heads, saved, dims, outs = [], [], [], [], [], []
         for sp in specs:
             k, x, w_ih, w_hh, b_ih, b_hh = sp[:6]
@@ -526,6 +581,7 @@ class _SeqGroupFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
+        _consume(ctx, "seq_group")
         saved = ctx.saved_tensors
         T, B, dims = ctx.dims
         dev = saved[0].device
@@ -583,6 +639,7 @@ class _SeqGroupFn(torch.autograd.Function):
             E.gemm_grouped(pre)
         for i in range(0, len(seqs), 4):
             E.lstm_seq(seqs[i:i + 4], T, B, backward=True)
+        ctx.consumed = True
         E.gemm_grouped(post)
         del keep
         return (None,) + tuple(grads)
