@@ -78,6 +78,14 @@ MFM_ADAMX_MAX_SPANS = 88
 MFM_ADAMX_MAXIMIZE, MFM_ADAMX_AMSGRAD, MFM_ADAMX_DECOUPLED = 1, 2, 4
 
 
+class ClipSpan(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64)]
+
+
+MFM_CLIP_MAX_SPANS = 112
+MFM_NORM_L2, MFM_NORM_INF, MFM_NORM_L1 = 0, 1, 2
+
+
 class LossWeights(C.Structure):
     _fields_ = [("disc", C.c_float), ("gen_l", C.c_float), ("gen_a", C.c_float), ("gen_v", C.c_float), ("reg", C.c_float),
                 ("write_disc_loss", C.c_int32)]
@@ -136,6 +144,10 @@ _SIGS = {
                                           C.c_int32, C.c_float, C.c_void_p]),
     "mfm_adam_ext_flat_spans_guarded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(AdamExtSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "mfm_clip_workspace_floats": (C.c_int64, []),
+    "mfm_clip_grad_norm_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mfm_clip_grad_value_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

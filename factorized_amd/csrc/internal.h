@@ -164,6 +164,12 @@ int sgd_spans_launch(float* p, const float* g, float* buf, const MfmSgdSpan* spa
 int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* vmax, const MfmAdamExtSpan* spans, int nspans,
                           float grad_scale, hipStream_t stream, const float* guard);
 
+// clip.hip -- gradient clipping over spans of a flat gradient buffer (include/mfm_hip.h, mfm_clip_grad_norm_flat_spans): the
+// norm clip is two launches (partials into ws, then total and scale); guard: anything but 0 leaves g alone, total_norm = NaN
+int clip_norm_launch(float* g, const MfmClipSpan* spans, int nspans, int norm_kind, float max_norm, float* ws, float* total_norm,
+                     const float* guard, hipStream_t stream);
+int clip_value_launch(float* g, const MfmClipSpan* spans, int nspans, float clip_value, const float* guard, hipStream_t stream);
+
 // mfn_att.hip -- row-wise glue of the MFN attention block (everything between its GEMMs)
 struct MfnCs { const float* cs[3]; float* dcx[3]; int h[3]; int T, B; };     // the three MFN LSTMs' cell states [T,B,Hp]
 int mfn_cstar_launch(const MfnCs& c, float* cstar, hipStream_t stream);

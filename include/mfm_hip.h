@@ -298,6 +298,32 @@ int mfm_adam_ext_flat_spans_guarded(float* p, const float* g, float* m, float* v
                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient clipping on one flat gradient buffer (torch.nn.utils.clip_grad_norm_ / clip_grad_value_ semantics;
+ * factorized_amd.nn_utils): g changed in place over up to MFM_CLIP_MAX_SPANS disjoint element ranges, given in ascending order;
+ * elements outside every span are neither read into a norm nor written (torch skips a parameter whose .grad is None, and
+ * the padding behind a tensor of the flat layout keeps its bits).  begin is a multiple of 4, end is ANY element index above
+ * it: a span is a tensor's exact extent.
+ *   norm:   total_norm = ||g over the spans|| of kind MFM_NORM_L2 / MFM_NORM_INF / MFM_NORM_L1 (the max propagates a NaN);
+ *           g *= min(max_norm / (total_norm + 1e-6), 1), always multiplied, a NaN coefficient stays NaN (as torch, in fp32).
+ *           Two launches on `stream`, no atomics: the same table gives the same bits.  `ws` holds
+ *           mfm_clip_workspace_floats() floats of scratch; total_norm is one device float.
+ *   value:  g = clamp(g, -clip_value, clip_value), a NaN stays NaN; one launch.
+ * max_norm and clip_value >= 0.  `guard`: optional device float; if it is anything but 0.0f, g is left untouched and
+ * total_norm is NaN (gradients that cannot be trusted are not rescaled and report no finite norm); NULL: unguarded. */
+#define MFM_CLIP_MAX_SPANS 112 /* >= 104: every tensor of MFM_KL as its own span */
+#define MFM_NORM_L2 0
+#define MFM_NORM_INF 1
+#define MFM_NORM_L1 2
+typedef struct MfmClipSpan {
+  int64_t begin, end; /* begin % 4 == 0, end > begin */
+} MfmClipSpan;
+int64_t mfm_clip_workspace_floats(void); /* host only: floats `ws` must hold */
+int mfm_clip_grad_norm_flat_spans(float* g, const MfmClipSpan* spans /*host*/, int32_t nspans, int32_t norm_kind, float max_norm,
+                                  float* ws, float* total_norm /*device, 1 float*/, const float* guard, void* stream);
+int mfm_clip_grad_value_flat_spans(float* g, const MfmClipSpan* spans /*host*/, int32_t nspans, float clip_value,
+                                   const float* guard, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
