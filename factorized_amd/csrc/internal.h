@@ -170,6 +170,11 @@ int clip_norm_launch(float* g, const MfmClipSpan* spans, int nspans, int norm_ki
                      const float* guard, hipStream_t stream);
 int clip_value_launch(float* g, const MfmClipSpan* spans, int nspans, float clip_value, const float* guard, hipStream_t stream);
 
+// avg.hip -- weight averaging of one flat parameter buffer into another (include/mfm_hip.h, mfm_avg_flat): the count n is read
+// from and advanced in device memory by the launch itself
+int avg_flat_launch(float* avg, const float* p, int64_t begin, int64_t end, int kind, float w, int64_t* n_averaged,
+                    int32_t* ticket, hipStream_t stream);
+
 // mfn_att.hip -- row-wise glue of the MFN attention block (everything between its GEMMs)
 struct MfnCs { const float* cs[3]; float* dcx[3]; int h[3]; int T, B; };     // the three MFN LSTMs' cell states [T,B,Hp]
 int mfn_cstar_launch(const MfnCs& c, float* cstar, hipStream_t stream);

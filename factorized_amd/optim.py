@@ -40,6 +40,7 @@ from . import _lib
 
 ReduceLROnPlateau = torch.optim.lr_scheduler.ReduceLROnPlateau      # convenience: `optim.lr_scheduler` users import torch's
 lr_scheduler = torch.optim.lr_scheduler
+from . import swa_utils  # noqa: E402,F401  (`optim.swa_utils.AveragedModel`: torch's on any module, one launch between two fused models)
 
 
 def _owner(p):

@@ -324,6 +324,23 @@ int mfm_clip_grad_value_flat_spans(float* g, const MfmClipSpan* spans /*host*/, 
                                    const float* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weight averaging of one flat parameter buffer into another of the same layout (torch.optim.swa_utils.AveragedModel
+ * semantics; factorized_amd.swa_utils): one launch over the element range [begin, end), nothing outside it is read or written
+ * in either buffer, p is never written.  The update count n is read from device memory (`n_averaged`: the int64 word of
+ * AveragedModel.n_averaged), never from the host:
+ *   n == 0:  avg = p, bit for bit (NaN payloads and infinities included), whatever the kind
+ *   n  > 0:  avg = lerp(avg, p, w) by torch's rule:  |w| < 0.5 ? avg + w * (p - avg) : p - (p - avg) * (1 - w)
+ *            MFM_AVG_SWA: w = 1.0f / (float)(n + 1) (the argument `w` is ignored);  MFM_AVG_EMA: w as passed, 1 - decay in [0, 1]
+ * and the launch stores n + 1 back itself (a captured launch advances the count on every replay): every workgroup reads n
+ * first and draws a ticket from `ticket` when it is done; the last one stores n + 1 and sets the ticket word back to 0.
+ * `ticket` is one device int32 that holds 0 between launches and is used by one launch at a time.  begin/end are multiples
+ * of 4, avg and p 16-byte aligned, n_averaged 8-byte aligned. */
+#define MFM_AVG_SWA 0
+#define MFM_AVG_EMA 1
+int mfm_avg_flat(float* avg, const float* p, int64_t begin, int64_t end, int32_t kind, float w, int64_t* n_averaged /*device*/,
+                 int32_t* ticket /*device, zero between launches*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
