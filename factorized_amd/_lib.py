@@ -151,6 +151,8 @@ _SIGS = {
     "mfm_clip_grad_value_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "mfm_avg_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "mfm_dataset_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -175,6 +175,11 @@ int clip_value_launch(float* g, const MfmClipSpan* spans, int nspans, float clip
 int avg_flat_launch(float* avg, const float* p, int64_t begin, int64_t end, int kind, float w, int64_t* n_averaged,
                     int32_t* ticket, hipStream_t stream);
 
+// dataset_gather.hip -- per-epoch reshuffle of a resident split: pool rows gathered through a device permutation into the
+// [nb, T, B, D] batch layout (include/mfm_hip.h, mfm_dataset_gather)
+int dataset_gather_launch(float* X, void* y, const float* X_pool, const void* y_pool, const int64_t* perm, int64_t N, int nb,
+                          int T, int B, int D, int64_t ybytes, hipStream_t stream);
+
 // mfn_att.hip -- row-wise glue of the MFN attention block (everything between its GEMMs)
 struct MfnCs { const float* cs[3]; float* dcx[3]; int h[3]; int T, B; };     // the three MFN LSTMs' cell states [T,B,Hp]
 int mfn_cstar_launch(const MfnCs& c, float* cstar, hipStream_t stream);

@@ -8,12 +8,13 @@ so to equal a single-process step at the global batch W*B each rank back-propaga
 `mean-terms + W * KLD` (reg_scale = W inside the plan) and the summed gradients are divided by W
 (grad_scale = 1/W inside the fused Adam).  tests/test_dp_gloo.py checks that algebra on CPU.
 """
+import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from . import synth
+from . import _lib, synth
 
 
 def dp_env():
@@ -31,25 +32,37 @@ def shard_batches(n_batches, rank, world):
 
 class DeviceDataset:
     """Synthetic MOSI-shape split kept resident in HBM as contiguous [nb, T, B, D] batches
-    (the reference slices a host array and copies H2D every step, mfm_mosi.py:428-429)."""
+    (the reference slices a host array and copies H2D every step, mfm_mosi.py:428-429).
 
-    def __init__(self, cfg, n_samples, T, batchsize, device, seed=11):
+    With `pool=True` all N samples stay resident too, sample-major (`X_pool [N, T, D]`, `y_pool [N, ...]`, the tail that fills
+    no batch included), and `reshuffle` regroups them into new batches on the device, one launch per epoch:
+
+        for epoch in range(epochs):
+            for x, y in data.reshuffle(seed=epoch).batches(rank, world):
+                step(x, y)
+
+    The batches start out in the order of the arrays either way; every reshuffle drops ANOTHER N mod B samples, so the
+    tail rotates into training."""
+
+    def __init__(self, cfg, n_samples, T, batchsize, device, seed=11, pool=False):
         loss = cfg.get("loss", "l1")
         classes = cfg["output_dim"] if loss == "ce" else 0
         X, y = synth.make_dataset(cfg["input_dims"], n_samples, T, seed=seed, output_dim=cfg["output_dim"],
                                   classes=classes)
+        X_all, y_all = X, y
         nb = n_samples // batchsize                       # floor: tail dropped (mfm_mosi.py:423)
         X = X[:, :nb * batchsize].reshape(T, nb, batchsize, -1).transpose(1, 0, 2, 3)
         y = y[:nb * batchsize].reshape((nb, batchsize) + y.shape[1:])
         self.X = torch.from_numpy(np.ascontiguousarray(X)).to(device)
         self.y = torch.from_numpy(np.ascontiguousarray(y)).to(device)
         self.nb = nb
+        self._set_pool(X_all, y_all, device, pool)
 
     @classmethod
-    def from_arrays(cls, X, y, batchsize, device):
+    def from_arrays(cls, X, y, batchsize, device, pool=False):
         """X [T, N, D] time-major float32 (what `data.assemble` / the reference's `swapaxes(0,1)` produce), y [N] or
         [N, k] -> the same HBM-resident `[nb, T, B, D]` batch layout; the tail that does not fill a batch is dropped
-        (mfm_mosi.py:423)."""
+        (mfm_mosi.py:423).  pool=True: all N samples stay resident as well, for `reshuffle`."""
         self = cls.__new__(cls)
         T, N = X.shape[0], X.shape[1]
         nb = N // batchsize
@@ -58,10 +71,82 @@ class DeviceDataset:
         self.X = torch.from_numpy(Xb).to(device)
         self.y = torch.from_numpy(yb).to(device)
         self.nb = nb
+        self._set_pool(X, np.asarray(y), device, pool)
         return self
+
+    def _set_pool(self, X, y, device, pool):
+        """X [T, N, D], y [N, ...] (host) -> the sample-major pool on the device, or none"""
+        self.X_pool = self.y_pool = self.perm = None
+        if pool:
+            # copies of its own: on the CPU from_numpy shares the caller's memory, and reshuffle writes the batches in place
+            self.X_pool = torch.from_numpy(np.array(X.transpose(1, 0, 2), order="C")).to(device)
+            self.y_pool = torch.from_numpy(np.array(y, order="C")).to(device)
+            if not self.X.is_cuda:
+                self.X, self.y = self.X.clone(), self.y.clone()
 
     def batch(self, i):
         return self.X[i], self.y[i]
+
+    def batches(self, rank=0, world=1):
+        """batch(i) over this rank's share of the batches (`shard_batches`): the loop of one epoch"""
+        for i in shard_batches(self.nb, rank, world):
+            yield self.batch(i)
+
+    def _permutation(self, seed, generator, perm):
+        """the epoch's order as an int64 tensor of N indices on the dataset's device"""
+        if (seed is not None) + (generator is not None) + (perm is not None) != 1:
+            raise ValueError("reshuffle: give exactly one of seed, generator and perm")
+        N, dev = self.X_pool.shape[0], self.X.device
+        if seed is not None:
+            # the reference's generator (np.random.permutation at the top of every train_* function): every rank that passes
+            # the same seed gets the same order, without communication
+            return torch.from_numpy(np.random.RandomState(seed).permutation(N).astype(np.int64)).to(dev)
+        if generator is not None:
+            return torch.randperm(N, generator=generator, device=dev)          # drawn on the device: no host round trip
+        p = torch.as_tensor(perm)
+        if p.dim() != 1 or p.numel() != N or p.is_floating_point() or p.is_complex() or p.dtype == torch.bool:
+            raise ValueError("reshuffle: perm must be %d integer indices in one dimension, got %s of shape %s"
+                             % (N, p.dtype, tuple(p.shape)))
+        p = p.to(device=dev, dtype=torch.int64)
+        if not torch.equal(torch.sort(p).values, torch.arange(N, device=dev)):          # (the one synchronisation)
+            raise ValueError("reshuffle: perm is not a permutation of range(%d) (an index repeats or is out of range)" % N)
+        return p
+
+    def reshuffle(self, seed=None, *, generator=None, perm=None):
+        """Regroup the resident samples into new batches: `X[b, t, r] = X_pool[p[b * B + r], t]`, `y[b, r] = y_pool[p[b * B + r]]`
+        for the permutation p of range(N) given by exactly one of
+
+            seed        int: `numpy.random.RandomState(seed).permutation(N)`, the reference's generator -- the same order on
+                        every rank that passes the same seed; N indices are uploaded
+            generator   a torch generator on the dataset's device: `torch.randperm` there, no host copy, no synchronisation
+            perm        N indices (array or tensor), checked once to be a permutation of range(N) (one synchronisation;
+                        ValueError otherwise)
+
+        The last N mod B entries of p are the samples this epoch leaves out.  On the GPU this is ONE launch of
+        `mfm_dataset_gather` on the current stream (CPU tensors: torch indexing).  `X` and `y` are rewritten IN PLACE from the
+        pool: views handed out earlier by `batch(i)` keep their storage and show the new samples once the launch has run.
+        `self.perm` keeps p.  Returns the dataset."""
+        if self.X_pool is None:
+            raise _lib.MfmError("DeviceDataset.reshuffle needs the sample pool on the device: build the dataset with pool=True")
+        p = self._permutation(seed, generator, perm)
+        self.perm = p
+        nb, T, B, D = self.X.shape
+        if not self.X.is_cuda:
+            idx = p[:nb * B]
+            self.X.copy_(self.X_pool[idx].view(nb, B, T, D).permute(0, 2, 1, 3))
+            self.y.copy_(self.y_pool[idx].view(self.y.shape))
+            return self
+        ybytes = self.y_pool[0].numel() * self.y_pool.element_size()
+        if self.X.dtype != torch.float32 or ybytes % 4:
+            raise _lib.MfmError("DeviceDataset.reshuffle on the GPU: X must be float32 and a label row a multiple of 4 bytes "
+                                "(X %s, %d bytes per label row)" % (self.X.dtype, ybytes))
+        dev = self.X.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mfm_dataset_gather(
+                C.c_void_p(self.X.data_ptr()), C.c_void_p(self.y.data_ptr()), C.c_void_p(self.X_pool.data_ptr()),
+                C.c_void_p(self.y_pool.data_ptr()), C.c_void_p(p.data_ptr()), self.X_pool.shape[0], nb, T, B, D, ybytes,
+                C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))), "mfm_dataset_gather")
+        return self
 
 
 def _mark_shared_device(engine):

@@ -341,6 +341,22 @@ int mfm_avg_flat(float* avg, const float* p, int64_t begin, int64_t end, int32_t
                  int32_t* ticket /*device, zero between launches*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Reshuffle of a device-resident split (factorized_amd.train.DeviceDataset.reshuffle): one launch gathers the samples of a
+ * sample-major pool through a device permutation into the batch layout the plans consume, for b < nb, t < T, r < B:
+ *   X[b, t, r, :] = X_pool[perm[b * B + r], t, :]         X [nb, T, B, D] fp32,  X_pool [N, T, D] fp32
+ *   y[b, r, :]    = y_pool[perm[b * B + r], :]            label rows of `ybytes` opaque bytes each (a multiple of 4:
+ *                                                         float [N], float [N, k], int64 [N], ...)
+ * `perm` is a DEVICE array of N int64 indices (what torch.randperm and torch indexing use); only its first nb * B entries
+ * are read, the rest are the samples this epoch leaves out.  A pure copy: every bit arrives unchanged, nothing outside
+ * the nb * T * B * D floats of X and the nb * B * ybytes bytes of y is written, the pool is never written.  An index outside
+ * [0, N) is skipped (its rows of X and y keep their bytes); a repeated index is copied twice: whether perm is a permutation
+ * is the caller's to check.  No constraint on D or B; rows move in 16-byte accesses when D % 4 == 0 and X and X_pool are
+ * 16-byte aligned, in dwords otherwise.  nb * B <= N, nb * T * B < 2^31, all buffers 4-byte aligned, perm 8-byte aligned,
+ * batches and pool disjoint.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int mfm_dataset_gather(float* X, void* y, const float* X_pool, const void* y_pool, const int64_t* perm /*device, N*/, int64_t N,
+                       int32_t nb, int32_t T, int32_t B, int32_t D, int64_t ybytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
