@@ -85,6 +85,9 @@ class ClipSpan(C.Structure):
 MFM_CLIP_MAX_SPANS = 112
 MFM_NORM_L2, MFM_NORM_INF, MFM_NORM_L1 = 0, 1, 2
 MFM_AVG_SWA, MFM_AVG_EMA = 0, 1
+MFM_KEEP_MIN, MFM_KEEP_MAX = 0, 1
+# MfmKeepBestState as int32 words: best_value (a float), calls, best_call, taken, ticket, 3 reserved
+MFM_KEEP_STATE_WORDS = 8
 
 
 class LossWeights(C.Structure):
@@ -151,6 +154,8 @@ _SIGS = {
     "mfm_clip_grad_value_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "mfm_avg_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "mfm_keep_best_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
+                                     C.c_void_p]),
     "mfm_dataset_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),

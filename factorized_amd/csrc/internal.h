@@ -175,6 +175,11 @@ int clip_value_launch(float* g, const MfmClipSpan* spans, int nspans, float clip
 int avg_flat_launch(float* avg, const float* p, int64_t begin, int64_t end, int kind, float w, int64_t* n_averaged,
                     int32_t* ticket, hipStream_t stream);
 
+// keep_best.hip -- conditional snapshot of one flat parameter buffer into another (include/mfm_hip.h, mfm_keep_best_flat): the
+// comparison with the best metric so far, the copy and the bookkeeping in device memory, by the launch itself
+int keep_best_flat_launch(float* best, const float* p, int64_t begin, int64_t end, int mode, const float* metric_dev,
+                          float metric, MfmKeepBestState* state, hipStream_t stream);
+
 // dataset_gather.hip -- per-epoch reshuffle of a resident split: pool rows gathered through a device permutation into the
 // [nb, T, B, D] batch layout (include/mfm_hip.h, mfm_dataset_gather)
 int dataset_gather_launch(float* X, void* y, const float* X_pool, const void* y_pool, const int64_t* perm, int64_t N, int nb,

@@ -341,6 +341,32 @@ int mfm_avg_flat(float* avg, const float* p, int64_t begin, int64_t end, int32_t
                  int32_t* ticket /*device, zero between launches*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Keep the best weights (factorized_amd.checkpoint.KeepBest; the reference's `if valid_loss <= best_valid: ... torch.save(model)`):
+ * one launch compares a metric with state->best_value and, if it is at least as good, copies the element range [begin, end)
+ * of the live flat parameter buffer `p` into the snapshot `best` of the same layout, bit for bit; nothing outside the range is
+ * read or written in either buffer, p is never written, and a launch that does not take moves no parameter byte at all.
+ *   MFM_KEEP_MIN: take = metric <= best_value      MFM_KEEP_MAX: take = metric >= best_value
+ * (a tie takes the newer weights; a NaN metric never takes; the comparison is in fp32).  The metric is the device float
+ * `metric_dev` points to or, when that is NULL, the argument `metric`.  The launch updates the state itself (a captured launch
+ * decides anew on every replay): taken -> best_value = metric, best_call = calls; always taken = 0 | 1 and calls += 1.  Every
+ * workgroup reads the state first and draws a ticket from state->ticket when it is done; the last one stores the new state and
+ * sets the ticket word back to 0.  The caller initialises the block (best_value = +inf / -inf or a bound such as the
+ * reference's 999999.0, calls = 0, best_call = -1, taken = 0, ticket = 0); one launch at a time may use it.  begin/end are
+ * multiples of 4, best and p 16-byte aligned, state 16-byte aligned, metric_dev 4-byte aligned. */
+#define MFM_KEEP_MIN 0
+#define MFM_KEEP_MAX 1
+typedef struct MfmKeepBestState {
+  float best_value;
+  int32_t calls;     /* launches so far */
+  int32_t best_call; /* 0-based index of the launch that last took a snapshot, -1: none yet */
+  int32_t taken;     /* 1: the latest launch took a snapshot */
+  int32_t ticket;    /* 0 between launches */
+  int32_t reserved_[3];
+} MfmKeepBestState;
+int mfm_keep_best_flat(float* best, const float* p, int64_t begin, int64_t end, int32_t mode, const float* metric_dev /*device or NULL*/,
+                       float metric, MfmKeepBestState* state /*device*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Reshuffle of a device-resident split (factorized_amd.train.DeviceDataset.reshuffle): one launch gathers the samples of a
  * sample-major pool through a device permutation into the batch layout the plans consume, for b < nb, t < T, r < B:
  *   X[b, t, r, :] = X_pool[perm[b * B + r], t, :]         X [nb, T, B, D] fp32,  X_pool [N, T, D] fp32
