@@ -88,6 +88,16 @@ MFM_AVG_SWA, MFM_AVG_EMA = 0, 1
 MFM_KEEP_MIN, MFM_KEEP_MAX = 0, 1
 # MfmKeepBestState as int32 words: best_value (a float), calls, best_call, taken, ticket, 3 reserved
 MFM_KEEP_STATE_WORDS = 8
+MFM_PLATEAU_MAX_GROUPS = 16
+MFM_PLATEAU_MIN, MFM_PLATEAU_MAX = 0, 1
+MFM_PLATEAU_REL, MFM_PLATEAU_ABS = 0, 1
+# MfmPlateauState as int32 words: best (a double: words 0-1), num_bad_epochs, cooldown_counter, last_epoch, reduced, reductions,
+# 1 reserved
+MFM_PLATEAU_STATE_WORDS = 8
+
+
+class PlateauGroups(C.Structure):
+    _fields_ = [("lr", C.c_void_p * MFM_PLATEAU_MAX_GROUPS), ("min_lr", C.c_double * MFM_PLATEAU_MAX_GROUPS)]
 
 
 class LossWeights(C.Structure):
@@ -156,6 +166,8 @@ _SIGS = {
                                C.c_void_p]),
     "mfm_keep_best_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
                                      C.c_void_p]),
+    "mfm_plateau_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(PlateauGroups), C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mfm_dataset_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),

@@ -180,6 +180,12 @@ int avg_flat_launch(float* avg, const float* p, int64_t begin, int64_t end, int 
 int keep_best_flat_launch(float* best, const float* p, int64_t begin, int64_t end, int mode, const float* metric_dev,
                           float metric, MfmKeepBestState* state, hipStream_t stream);
 
+// plateau.hip -- ReduceLROnPlateau.step on device lr words (include/mfm_hip.h, mfm_plateau_step): metric, plateau rule, state
+// and the learning rates of up to MFM_PLATEAU_MAX_GROUPS groups, by one lane of one launch
+int plateau_step_launch(MfmPlateauState* state, const float* metric_dev, double metric, const MfmPlateauGroups* groups,
+                        int n_groups, int mode, int threshold_mode, double factor, double threshold, double eps, int patience,
+                        int cooldown, int epoch, hipStream_t stream);
+
 // dataset_gather.hip -- per-epoch reshuffle of a resident split: pool rows gathered through a device permutation into the
 // [nb, T, B, D] batch layout (include/mfm_hip.h, mfm_dataset_gather)
 int dataset_gather_launch(float* X, void* y, const float* X_pool, const void* y_pool, const int64_t* perm, int64_t N, int nb,

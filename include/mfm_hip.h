@@ -367,6 +367,50 @@ int mfm_keep_best_flat(float* best, const float* p, int64_t begin, int64_t end, 
                        float metric, MfmKeepBestState* state /*device*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Reduce the learning rate on a plateau (factorized_amd.lr_scheduler.ReduceLROnPlateau; the reference's `scheduler.step(valid_loss)`
+ * with torch.optim.lr_scheduler.ReduceLROnPlateau at the end of every epoch): one launch of one wave, one working lane, reads
+ * a metric, advances *state and, when the rule says so, scales the fp32 learning-rate words of n_groups parameter groups in
+ * device memory.  The rule is torch 2.10's step / _is_better / _reduce_lr in fp64, statement for statement and without
+ * contraction, so state and lr bits equal torch's on the same inputs:
+ *   current = (double)metric;  last_epoch = epoch == -1 ? last_epoch + 1 : epoch
+ *   better:  MIN/REL current < best * (1 - threshold)   MIN/ABS current < best - threshold
+ *            MAX/REL current > best * (threshold + 1)   MAX/ABS current > best + threshold       (false for a NaN metric)
+ *   better ? (best = current, num_bad_epochs = 0) : num_bad_epochs += 1
+ *   cooldown_counter > 0 ?  cooldown_counter -= 1, num_bad_epochs = 0
+ *   num_bad_epochs > patience ?  for every group, in order:  old = (double)*lr;  new = max(old * factor, min_lr);
+ *                                                            if (old - new > eps) *lr = (float)new
+ *                                then cooldown_counter = cooldown, num_bad_epochs = 0
+ *   reduced = 1 if an lr word was stored, else 0;  reductions += reduced
+ * The metric is the device float `metric_dev` points to or, when that is NULL, the argument `metric` (a double: a host value
+ * keeps its precision).  Groups that share one lr word are reduced once per group, as by torch's loop; a launch that does not
+ * reduce stores no lr word.  The caller initialises the block (best = +inf for MIN, -inf for MAX, everything else 0); one launch
+ * at a time may use it.  state is 16-byte aligned, metric_dev and every lr pointer 4-byte aligned; 1 <= n_groups <=
+ * MFM_PLATEAU_MAX_GROUPS; factor < 1; patience, cooldown >= 0.  Stream-ordered, no host synchronisation, legal inside a stream
+ * capture (the scalar arguments and the table are then part of the graph; the decision is taken anew on every replay). */
+#define MFM_PLATEAU_MAX_GROUPS 16
+#define MFM_PLATEAU_MIN 0
+#define MFM_PLATEAU_MAX 1
+#define MFM_PLATEAU_REL 0
+#define MFM_PLATEAU_ABS 1
+typedef struct MfmPlateauState {
+  double best;
+  int32_t num_bad_epochs;
+  int32_t cooldown_counter;
+  int32_t last_epoch;
+  int32_t reduced;    /* 1: the latest launch changed at least one lr */
+  int32_t reductions; /* launches so far that did */
+  int32_t reserved_;
+} MfmPlateauState;
+typedef struct MfmPlateauGroups {
+  float* lr[MFM_PLATEAU_MAX_GROUPS]; /* device, one fp32 word per group */
+  double min_lr[MFM_PLATEAU_MAX_GROUPS];
+} MfmPlateauGroups;
+int mfm_plateau_step(MfmPlateauState* state /*device*/, const float* metric_dev /*device or NULL*/, double metric,
+                     const MfmPlateauGroups* groups /*host*/, int32_t n_groups, int32_t mode, int32_t threshold_mode, double factor,
+                     double threshold, double eps, int32_t patience, int32_t cooldown, int32_t epoch /*-1: last_epoch + 1*/,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Reshuffle of a device-resident split (factorized_amd.train.DeviceDataset.reshuffle): one launch gathers the samples of a
  * sample-major pool through a device permutation into the batch layout the plans consume, for b < nb, t < T, r < B:
  *   X[b, t, r, :] = X_pool[perm[b * B + r], t, :]         X [nb, T, B, D] fp32,  X_pool [N, T, D] fp32
