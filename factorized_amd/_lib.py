@@ -82,6 +82,13 @@ class ClipSpan(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64)]
 
 
+class DecFc1Item(C.Structure):
+    _fields_ = [("hs", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("x", C.c_void_p),
+                ("xhat", C.c_void_p), ("dxhat", C.c_void_p), ("dhs", C.c_void_p), ("loss", C.c_void_p),
+                ("ldx", C.c_int64), ("d", C.c_int32), ("h", C.c_int32), ("Hp", C.c_int32),
+                ("inv_count", C.c_float), ("grad_scale", C.c_float), ("pad_", C.c_int32)]
+
+
 MFM_CLIP_MAX_SPANS = 112
 MFM_NORM_L2, MFM_NORM_INF, MFM_NORM_L1 = 0, 1, 2
 MFM_AVG_SWA, MFM_AVG_EMA = 0, 1
@@ -162,6 +169,7 @@ _SIGS = {
     "mfm_clip_grad_norm_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "mfm_clip_grad_value_flat_spans": (C.c_int, [C.c_void_p, C.POINTER(ClipSpan), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "mfm_dec_fc1_f32": (C.c_int, [C.POINTER(DecFc1Item), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mfm_avg_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "mfm_keep_best_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,

@@ -16,19 +16,26 @@
 // Decomposition: one workgroup = 16 rows x one group of <= 8 output fragments (16 columns each) of one decoder.  Decoder l
 // (300 columns, 19 fragments) takes 3 column groups per row tile; their contributions to dH are partial sums over the
 // columns and are ADDED to dH with atomics -- the caller puts the dH block into the step's zero spans.  (A single column group
-// stores instead.)
+// stores instead: no atomics, the same bits every time.)
 //
-// 512 threads = 8 waves; MFMA 16x16x4 fp32 tiles.
+// 512 threads = 8 waves; MFMA 16x16x4 fp32 tiles.  Both products have the same shape:
 //   product 1: wave w owns output fragment w of the group; the reduction over hidden units walks 16-wide blocks: lane
 //              (bi, q) takes the four units 16 j + 4 q + {0..3} of its row of H (LDS, one 16-byte read) and of row
-//              n = bi of Wfc (one 16-byte buffer load) and feeds four MFMAs -- the order of the reduction index inside a
-//              block is free as long as both operands agree.
-//   product 2: the reduction over the group's columns is split into 8 contiguous ranges, one per wave, every wave
-//              accumulating all Hp/16 output fragments; the 8 partial tiles are summed through LDS in a fixed order
-//              (the sums over column GROUPS are atomics, so dH is reproducible to rounding order only when spread).
-//   Every global operand of both products (weights, targets, bias) is requested before the first MFMA: the workgroup is
-//   alone on its CU and a dependent load per reduction step would cost an L2 round trip each.
+//              n = bi of Wfc (one 16-byte buffer load) and feeds four MFMAs, one into each of four independent accumulators
+//              -- the order of the reduction index inside a block is free as long as both operands agree.
+//   product 2: wave w owns output fragment w of dH (16 hidden units) over the WHOLE column range of the group, so no two
+//              waves hold parts of one element and dH leaves straight from the accumulators.  Its weight operand is the
+//              transpose of product 1's: the group's slice of Wfc is read from memory ONCE -- every wave parks the weight
+//              registers of product 1 in LDS transposed (Wt[unit][column], behind the MFMAs' issue), and product 2 reads
+//              lane (bi, q)'s four columns 16 j + 4 q + {0..3} of unit row bi with one 16-byte LDS read, next to the same
+//              four columns of d x_hat.  (Before: a second, 4-byte strided fetch of Wfc -- 32 requests per lane in front of
+//              the targets and the bias in the in-order return queue --, the reduction over the columns split over the
+//              waves, and the eight partial tiles summed through LDS: write, barrier, add, barrier, sum.)
+//   One barrier separates the products (d x_hat, the parked weights and the waves' loss sums become visible together); the
+//   loss slot, x_hat and d x_hat leave behind product 2's issue.  Every global operand is requested before the first MFMA, in
+//   the order it is needed: H, weights, targets, bias.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "internal.h"
 #include "lstamp.h"
 
@@ -38,8 +45,8 @@ constexpr int FC1_THREADS = 512;
 constexpr int FC1_WAVES = 8;
 constexpr int FC1_ROWS = 16;
 constexpr int FC1_MAXF = 8;                  // Hp <= 128; <= 8 output fragments per column group
-constexpr int FC1_KS2W = 4;                  // reduction steps of product 2 per wave: 4 * 8 fragments / 8 waves
-constexpr int FC1_LD = 16 * FC1_MAXF + 4;    // LDS row stride: (LD / 4) odd and LD == 4 (mod 64): conflict-free reads
+constexpr int FC1_LD = 16 * FC1_MAXF + 4;    // LDS row stride: (LD / 4) odd and LD == 4 (mod 64): conflict-free 16-byte row reads,
+                                             // and 4 LD == 16 (mod 32): the transposed 4-byte writes of a half wave hit 32 banks
 constexpr int FC1_OOB = 0x7FFFFFF0;          // buffer offset beyond any resource: the load returns 0
 
 // bf16 plans: the same products with every operand (H, Wfc, dx_hat) rounded to bf16 first and fp32 accumulation -- what
@@ -49,8 +56,8 @@ __device__ __forceinline__ float rnd_bf16(float x, bool on) { return on ? (float
 __global__ __launch_bounds__(FC1_THREADS) void dec_fc1_kernel(const DecFc1Launch L) {
   __shared__ __attribute__((aligned(16))) float Ht[FC1_ROWS * FC1_LD];              // hidden rows
   __shared__ __attribute__((aligned(16))) float Dx[FC1_ROWS * FC1_LD];              // d x_hat of this column group
-  __shared__ __attribute__((aligned(16))) float Pt[(FC1_WAVES / 2) * FC1_ROWS * FC1_LD];  // partial dH tiles (two waves each)
   __shared__ float red[FC1_WAVES];
+  extern __shared__ __attribute__((aligned(16))) float Wt[];                        // training: [max Hp][FC1_LD], Wfc^T of the group
   LSTAMP(2, 0);
   // which decoder, row tile, column group
   int m = 0;
@@ -67,6 +74,7 @@ __global__ __launch_bounds__(FC1_THREADS) void dec_fc1_kernel(const DecFc1Launch
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bi = lane & 15, q = lane >> 4;
   const int J = Hp >> 4;                          // 16-wide reduction blocks of product 1 == output fragments of product 2
+  const bool bwd = L.with_bwd != 0;
 
   // ---- requests.  The 16 hidden rows (pad units of the saved states are exact zeros): one 16-byte piece per thread
   const int per_row = Hp >> 2;                    // 16 * per_row <= 512
@@ -76,25 +84,11 @@ __global__ __launch_bounds__(FC1_THREADS) void dec_fc1_kernel(const DecFc1Launch
   const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc((void*)I.w, 0, d * h * 4, 0x00020000);
   const int n = (f0 + wave) * 16 + bi;            // this lane's output column in product 1
   const bool cok = (int)(wave < nfw) & (int)(n < d);
-  f32x4 w1[FC1_MAXF];
+  f32x4 w1[FC1_MAXF];                             // (unconditional: blocks >= J and masked columns ask outside the resource)
 #pragma unroll
   for (int j = 0; j < FC1_MAXF; ++j) {
     const bool ok = (int)cok & (int)(j < J);
     w1[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wres, ok ? (n * h + 16 * j + 4 * q) * 4 : FC1_OOB, 0, 0));
-  }
-  const int KS = nfw * 4;                         // 4-wide reduction steps of product 2 over this group's columns
-  const int per = (KS + FC1_WAVES - 1) / FC1_WAVES;     // <= FC1_KS2W
-  const int ks0 = wave * per;
-  float w2[FC1_KS2W][FC1_MAXF];
-#pragma unroll
-  for (int i = 0; i < FC1_KS2W; ++i) {
-    const int k = f0 * 16 + 4 * (ks0 + i) + q;    // column of Wfc^T == row of Wfc
-#pragma unroll
-    for (int f = 0; f < FC1_MAXF; ++f) {
-      const int c = f * 16 + bi;
-      const bool ok = (int)(L.with_bwd != 0) & (int)(i < per) & (int)(ks0 + i < KS) & (int)(k < d) & (int)(c < h);
-      w2[i][f] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wres, ok ? (k * h + c) * 4 : FC1_OOB, 0, 0));
-    }
   }
   float xv[4];
 #pragma unroll
@@ -111,91 +105,111 @@ __global__ __launch_bounds__(FC1_THREADS) void dec_fc1_kernel(const DecFc1Launch
   if (hr < FC1_ROWS) *reinterpret_cast<f32x4*>(Ht + hr * FC1_LD + hk) = hreg;
   lds_barrier();
   LSTAMP(2, 1);
+  LSTAMP_V(2, 10, 5);                             // (behind the weights: 4 target loads + the bias; a tile with fewer than 4 valid
+                                                  //  rows per lane group issues fewer, and the stamp then comes early: full tiles only)
 
-  // ---- product 1 (branch-free: blocks >= J were requested as zeros and meet a clamped hidden block; units >= h of a
-  //      weight row belong to the next row -- finite values -- and meet zeros of the hidden tile)
-  f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (wave < nfw) {
+  // ---- product 1 (units >= h of a weight row belong to the next row -- finite values -- and meet zeros of the hidden tile).
+  //      Waves beyond the group's fragments have nothing to do until product 2: the columns they would own are never read.
+  f32x4 acc1[4];
 #pragma unroll
-    for (int j = 0; j < FC1_MAXF; ++j) {
-      const f32x4 hv = *reinterpret_cast<const f32x4*>(Ht + bi * FC1_LD + 16 * min(j, J - 1) + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc1 = mma16x16x4(hv[e], rnd_bf16(w1[j][e], rb), acc1);
-    }
-  }
-  // ---- squared-error epilogue
+  for (int e = 0; e < 4; ++e) acc1[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float xh[4] = {0.f, 0.f, 0.f, 0.f}, dxr[4] = {0.f, 0.f, 0.f, 0.f};
   float lsum = 0.0f;
   if (wave < nfw) {
 #pragma unroll
+    for (int j = 0; j < FC1_MAXF; ++j) {
+      if (j < J) {                                // (uniform)
+        const f32x4 hv = *reinterpret_cast<const f32x4*>(Ht + bi * FC1_LD + 16 * j + 4 * q);
+        f32x4 wv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) wv[e] = rnd_bf16(w1[j][e], rb);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc1[e] = mma16x16x4(hv[e], wv[e], acc1[e]);
+        if (bwd) {
+          // product 2's operand: Wt[unit][column of the group], pad units zero (they must come out of dH as exact zeros)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int u = 16 * j + 4 * q + e;
+            Wt[u * FC1_LD + wave * 16 + bi] = u < h ? wv[e] : 0.0f;
+          }
+        }
+      }
+    }
+    LSTAMP_W(2, 11);
+    // ---- squared-error epilogue
+    const f32x4 s1 = (acc1[0] + acc1[1]) + (acc1[2] + acc1[3]);
+#pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * q + r;
-      float dx = 0.0f;
+      xh[r] = s1[r] + bv;
+      dxr[r] = 0.0f;
       if (cok && row0 + row < L.rows) {
-        const float xh = acc1[r] + bv;
-        const float diff = xh - xv[r];
+        const float diff = xh[r] - xv[r];
         lsum = fmaf(diff, diff, lsum);
-        dx = I.grad_scale * diff;
-        const int64_t o = (int64_t)(row0 + row) * d + n;
-        if (I.xhat) I.xhat[o] = xh;
-        if (I.dxhat) I.dxhat[o] = dx;
+        dxr[r] = I.grad_scale * diff;
       }
-      Dx[row * FC1_LD + wave * 16 + bi] = rnd_bf16(dx, rb);
+      Dx[row * FC1_LD + wave * 16 + bi] = rnd_bf16(dxr[r], rb);
     }
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
   if (lane == 0) red[wave] = lsum;
+  LSTAMP(2, 12);
   lds_barrier();
-  if (tid == 0 && I.loss) {
+  LSTAMP(2, 2);
+
+  // ---- product 2: dH[16, fragment `wave`] (+)= dx_hat[16, group columns] Wfc[group columns, fragment `wave`]
+  f32x4 acc2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc2[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool w2on = (int)bwd & (int)(wave < J);
+  if (w2on) {
+    f32x4 av[FC1_MAXF], wv[FC1_MAXF];
+#pragma unroll
+    for (int j = 0; j < FC1_MAXF; ++j) {
+      if (j < nfw) {                              // (uniform)
+        av[j] = *reinterpret_cast<const f32x4*>(Dx + bi * FC1_LD + 16 * j + 4 * q);
+        wv[j] = *reinterpret_cast<const f32x4*>(Wt + (wave * 16 + bi) * FC1_LD + 16 * j + 4 * q);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < FC1_MAXF; ++j) {
+      if (j < nfw) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc2[e] = mma16x16x4(av[j][e], wv[j][e], acc2[e]);
+      }
+    }
+  }
+  // ---- behind product 2's issue: x_hat and d x_hat, the loss slot (the last wave: the one without a dH fragment unless Hp = 128)
+  if (cok) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + 4 * q + r;
+      if (row < L.rows) {
+        const int64_t o = (int64_t)row * d + n;
+        if (I.xhat) I.xhat[o] = xh[r];
+        if (I.dxhat) I.dxhat[o] = dxr[r];
+      }
+    }
+  }
+  if (tid == FC1_THREADS - 64 && I.loss) {
     float s = 0.0f;
 #pragma unroll
     for (int w = 0; w < FC1_WAVES; ++w) s += red[w];
     atomicAdd(I.loss, s * I.inv_count);
   }
-  LSTAMP(2, 2);
-  if (!L.with_bwd) return;
-
-  // ---- product 2: dH[16, Hp] (+)= dx_hat[16, group columns] Wfc[group columns, h]
-  {
-    f32x4 acc2[FC1_MAXF];
+  if (w2on) {
+    const f32x4 s2 = (acc2[0] + acc2[1]) + (acc2[2] + acc2[3]);      // pad units: exact zeros (zero rows of Wt)
+    float* o = I.dhs + (int64_t)(row0 + 4 * q) * Hp + wave * 16 + bi;
 #pragma unroll
-    for (int f = 0; f < FC1_MAXF; ++f) acc2[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // branch-free: masked weights are zeros, the dx_hat column index is clamped
-#pragma unroll
-    for (int i = 0; i < FC1_KS2W; ++i) {
-      const float a = Dx[bi * FC1_LD + 4 * min(ks0 + i, KS - 1) + q];
-#pragma unroll
-      for (int f = 0; f < FC1_MAXF; ++f) acc2[f] = mma16x16x4(a, rnd_bf16(w2[i][f], rb), acc2[f]);
-    }
-    // waves 4..7 park their tiles, waves 0..3 add theirs on top (same lane -> same element), then the 4 tiles are summed
-    float* P = Pt + (wave & 3) * FC1_ROWS * FC1_LD;
-    if (wave >= 4) {
-#pragma unroll
-      for (int f = 0; f < FC1_MAXF; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) P[(4 * q + r) * FC1_LD + f * 16 + bi] = acc2[f][r];
-    }
-    lds_barrier();
-    if (wave < 4) {
-#pragma unroll
-      for (int f = 0; f < FC1_MAXF; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) P[(4 * q + r) * FC1_LD + f * 16 + bi] += acc2[f][r];
+    for (int r = 0; r < 4; ++r) {
+      if (row0 + 4 * q + r < L.rows) {
+        if (I.col_groups == 1) o[r * Hp] = s2[r];
+        else atomicAdd(o + r * Hp, s2[r]);
+      }
     }
   }
-  lds_barrier();
-  if (hr < FC1_ROWS && row0 + hr < L.rows) {
-    f32x4 s = *reinterpret_cast<const f32x4*>(Pt + hr * FC1_LD + hk);
-#pragma unroll
-    for (int w = 1; w < FC1_WAVES / 2; ++w) s += *reinterpret_cast<const f32x4*>(Pt + (w * FC1_ROWS + hr) * FC1_LD + hk);
-    float* o = I.dhs + (int64_t)(row0 + hr) * Hp + hk;      // pad units: exact zeros (masked weights)
-    if (I.col_groups == 1) {
-      *reinterpret_cast<f32x4*>(o) = s;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) atomicAdd(o + e, s[e]);
-    }
-  }
+  LSTAMP(2, 13);
   LSTAMP_W(2, 15);
 }
 
@@ -222,10 +236,39 @@ int dec_fc1_launch(DecFc1Launch& L, bool dhs_zeroed, hipStream_t stream) {
     I.tile_begin = tiles;
     tiles += row_tiles * I.col_groups;
   }
+  // the transposed weight slice of product 2: [max Hp][FC1_LD] floats behind the static tiles (up to 66 KB at Hp = 128)
+  int max_hp = 0;
+  for (int i = 0; i < L.n_items; ++i) max_hp = std::max(max_hp, L.it[i].Hp);
+  const size_t smem = L.with_bwd ? (size_t)max_hp * FC1_LD * sizeof(float) : 0;
+  // (the attribute belongs to the device's copy of the kernel: once per device, from whichever thread comes first)
+  static std::atomic<unsigned long long> lds_attr_set{0};
+  int dev = 0;
+  MFM_HIP_CHECK(hipGetDevice(&dev));
+  const unsigned long long dev_bit = 1ull << (dev & 63);
+  if (!(lds_attr_set.load(std::memory_order_acquire) & dev_bit)) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void*)dec_fc1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * FC1_MAXF * FC1_LD * (int)sizeof(float)));
+    lds_attr_set.fetch_or(dev_bit, std::memory_order_release);
+  }
   LSTAMP_BIND();
-  MFM_LAUNCH_TIMED(dec_fc1_kernel, dim3(tiles), dim3(FC1_THREADS), 0, stream, L);
+  MFM_LAUNCH_TIMED(dec_fc1_kernel, dim3(tiles), dim3(FC1_THREADS), smem, stream, L);
   MFM_LAUNCH_CHECK("dec_fc1_kernel");
   return MFM_OK;
 }
 
 }  // namespace mfm
+
+extern "C" int mfm_dec_fc1_f32(const MfmDecFc1Item* items, int32_t count, int32_t rows, int32_t with_bwd, int32_t bf16_operands,
+                               int32_t dhs_zeroed, void* stream) {
+  MFM_REQUIRE(items && count >= 1 && count <= 3, "dec fc1: 1..3 items");
+  mfm::DecFc1Launch L;
+  memset(&L, 0, sizeof(L));
+  L.n_items = count; L.rows = rows; L.with_bwd = with_bwd ? 1 : 0; L.bf16 = bf16_operands ? 1 : 0;
+  for (int i = 0; i < count; ++i) {
+    mfm::DecFc1Item& I = L.it[i];
+    const MfmDecFc1Item& s = items[i];
+    I.hs = s.hs; I.w = s.w; I.bias = s.bias; I.x = s.x; I.ldx = s.ldx;
+    I.xhat = s.xhat; I.dxhat = s.dxhat; I.dhs = s.dhs; I.loss = s.loss;
+    I.d = s.d; I.h = s.h; I.Hp = s.Hp; I.inv_count = s.inv_count; I.grad_scale = s.grad_scale;
+  }
+  return mfm::dec_fc1_launch(L, dhs_zeroed != 0, (hipStream_t)stream);
+}

@@ -40,12 +40,20 @@ __device__ __forceinline__ void lstamp(int kid, int point, bool wait_loads = fal
       g_lstamp[((long)kid * LST_BLOCKS + blockIdx.x) * LST_POINTS + point] = wall_clock64();
   }
 }
+// "the first loads have arrived": waits until at most N of the wave's loads are outstanding (they return in order)
+template <int N>
+__device__ __forceinline__ void lstamp_v(int kid, int point) {
+  if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+  lstamp(kid, point);
+}
 }  // namespace mfm
 #define LSTAMP(kid, pt) ::mfm::lstamp(kid, pt)
+#define LSTAMP_V(kid, pt, n) ::mfm::lstamp_v<n>(kid, pt)
 #define LSTAMP_W(kid, pt) ::mfm::lstamp(kid, pt, true)
 #define LSTAMP_BIND() ::mfm::lstamp_bind()
 #else
 #define LSTAMP(kid, pt) ((void)0)
 #define LSTAMP_W(kid, pt) ((void)0)
+#define LSTAMP_V(kid, pt, n) ((void)0)
 #define LSTAMP_BIND() ((void)0)
 #endif

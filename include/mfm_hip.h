@@ -324,6 +324,27 @@ int mfm_clip_grad_value_flat_spans(float* g, const MfmClipSpan* spans /*host*/, 
                                    const float* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoder output layers, forward and backward to the hidden states, for up to 3 decoders in ONE launch (the launch the
+ * fp32 plans run between the decoder recurrence and its BPTT; csrc/dec_fc1.hip).  Per item, over `rows` rows:
+ *   x_hat = H Wfc^T + b;  diff = x_hat - x;  *loss += sum(diff^2) * inv_count;  dx_hat = grad_scale * diff;
+ *   with_bwd:  dH = dx_hat Wfc, units [h, Hp) of every row written as zeros
+ * H [rows, Hp] with units [h, Hp) zero, Hp a multiple of 16; Wfc [d, h]; x row stride ldx; xhat / dxhat [rows, d] optional.
+ * bf16_operands: H, Wfc and dx_hat are rounded to bf16 (RNE) on their way into the products (fp32 accumulation).
+ * d <= 128: dH is stored (same bits every time).  d > 128: the column groups ADD into dH, the caller clears it first and says
+ * so with dhs_zeroed.  Returns MFM_ERR_UNSUPPORTED (no error text, nothing launched) for Hp > 128, for d * h >= 2^28 and for
+ * d > 128 with with_bwd and without dhs_zeroed. */
+typedef struct MfmDecFc1Item {
+  const float* hs; const float* w; const float* bias; const float* x;
+  float* xhat; float* dxhat; float* dhs; float* loss;
+  int64_t ldx;
+  int32_t d, h, Hp;
+  float inv_count, grad_scale;
+  int32_t pad_;
+} MfmDecFc1Item;
+int mfm_dec_fc1_f32(const MfmDecFc1Item* items /*host*/, int32_t count, int32_t rows, int32_t with_bwd, int32_t bf16_operands,
+                    int32_t dhs_zeroed, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Weight averaging of one flat parameter buffer into another of the same layout (torch.optim.swa_utils.AveragedModel
  * semantics; factorized_amd.swa_utils): one launch over the element range [begin, end), nothing outside it is read or written
  * in either buffer, p is never written.  The update count n is read from device memory (`n_averaged`: the int64 word of

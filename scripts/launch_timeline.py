@@ -21,7 +21,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "scripts", "tmp", "lstamp", "libmfm_hip_lstamp.so")
+LIB = os.environ.get("MFM_LSTAMP_LIB") or os.path.join(ROOT, "scripts", "tmp", "lstamp", "libmfm_hip_lstamp.so")
 KNAMES = ["enc fwd (foldproj)", "dec fwd", "dec fc1 + MSE + dH", "dec BPTT", "enc BPTT (folddw)", "adam"]
 PT = {
     0: {0: "entry", 1: "weights in registers", 2: "top of the time loop (x-proj of t=0,1 arrived)", 5: "top of step 1", 6: "top of step T-1",
@@ -31,7 +31,10 @@ PT = {
         5: "top of step 2", 6: "top of step T-1", 7: "time loop done", 15: "exit"},
     2: {0: "entry", 3: "first fragment's weights + targets requested", 4: "H rows parked (in front of the barrier)", 1: "operands arrived, H tile in LDS",
         5: "first fragment's operands arrived", 6: "first fragment: products + epilogue done", 7: "all fragments done",
-        2: "product 1 + MSE done (loss reduced)", 8: "product 2: first weights arrived", 9: "product 2: first fragment multiplied", 15: "exit (dH added)"},
+        2: "product 1 + MSE done (loss reduced)", 8: "product 2: first weights arrived", 9: "product 2: first fragment multiplied", 15: "exit (dH added)",
+        # sub-stamps of the launch's chain (profiles/dec_fc1_phases.txt); 14 exists only in builds that sum partial tiles through LDS
+        10: "  product-1 weights arrived", 11: "  product 1 issued; targets + bias arrived", 12: "  product 1 + epilogue done, d x_hat written",
+        13: "  product 2 done", 14: "  partial dH tiles reduced"},
     3: {0: "entry", 1: "W^T in registers", 2: "top of the time loop (saved state of T-1 arrived)", 5: "top of step T-2", 6: "top of step 1",
         3: "top of step 0", 7: "done (d h_init written)", 15: "exit"},
     4: {0: "entry", 9: "latent bwd chain done", 8: "stores acknowledged, row stamped", 1: "W^T in registers",
@@ -62,7 +65,7 @@ PT[4][16] = "  latent bwd: tables + records in LDS"
 PT[4][17] = "  latent bwd: seeds done"
 SUB = ["A issued (stamps waited for if not prefetched)", "next block's stamps asked", "operands parked in LDS + barrier", "next operands requested",
        "product + epilogue done", "closing barrier"]
-ORDER = {0: [0, 1, 2, 5, 6, 7, 9, 8, 16, 17, 18, 26, 27, 28, 29, 30, 19, 20, 21, 22, 23, 24, 25, 15], 1: [0, 1, 2, 3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 15], 2: [0, 3, 4, 1, 5, 6, 7, 2, 8, 9, 15], 3: [0, 1, 2, 5, 6, 3, 8, 9, 10, 11, 7, 16, 17, 25, 24, 23, 22, 21, 20, 19, 18, 15],
+ORDER = {0: [0, 1, 2, 5, 6, 7, 9, 8, 16, 17, 18, 26, 27, 28, 29, 30, 19, 20, 21, 22, 23, 24, 25, 15], 1: [0, 1, 2, 3, 4, 5, 6, 7, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 15], 2: [0, 3, 4, 1, 10, 11, 5, 6, 7, 12, 2, 8, 9, 13, 14, 15], 3: [0, 1, 2, 5, 6, 3, 8, 9, 10, 11, 7, 16, 17, 25, 24, 23, 22, 21, 20, 19, 18, 15],
          4: [0, 16, 17, 25, 24, 23, 22, 21, 20, 19, 18, 9, 8, 1, 2, 5, 6, 3, 7, 15], 5: [0, 15]}
 
 CHILD_STEP = r"""
