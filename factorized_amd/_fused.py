@@ -141,6 +141,35 @@ class _FusedEngineMixin:
             self._adopt(dev)
         return self._engine
 
+    # ------------------------------------------------------------------ prediction only
+    def _predict(self, x, y):
+        """the engine's predict() on this module's parameters: always the deterministic eval computation (dropout off, the
+        zy mean), whatever `self.training` says -- which is left as found -- without autograd and without lazy outputs"""
+        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
+        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        if self._engine_variant == "mmd":
+            g = getattr(self, "mmd_gauss", None)
+            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        with torch.no_grad():
+            return eng.predict(x, y)
+
+    def predict(self, x):
+        """x [T, N, D] -> y_hat [N, output_dim], the reference's `predict(model, X)` (mfm_mosi.py:360-365) without the
+        generative half.  MFM_KL_EF: one recurrence and six row-wise layers (engine.predict); the buffer is reused by the next
+        call with the same shape.  MFM_KL / MFM: the fused eval forward."""
+        return self._predict(x, None)["y_hat"]
+
+    def evaluate(self, x, y, loss_fn=None):
+        """x, labels -> the loss as a 0-d tensor on the device (no host read), the reference's `evaluate(model, X, y)`
+        (mfm_mosi.py:349-357); accepted as is by KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  loss_fn=None: the
+        config's loss (nn.L1Loss(), or nn.CrossEntropyLoss() for loss="ce"), reduced inside the prediction launch; any other
+        `loss_fn` is applied with torch to the returned y_hat."""
+        if loss_fn is None:
+            return self._predict(x, y)["loss"]
+        with torch.no_grad():
+            return loss_fn(self._predict(x, None)["y_hat"], y)
+
     # ------------------------------------------------------------------ flat gradients
     def _flat_grads(self):
         eng = self.engine

@@ -14,6 +14,7 @@ MFM_KLEF_NPARAM = 78
 MFM_LOSS_SLOTS = 8
 MFM_MAX_SEQ = 6
 ABI_VERSION = 5
+MFM_ERR_UNSUPPORTED = -3
 
 
 class MfmError(RuntimeError):
@@ -178,6 +179,10 @@ _SIGS = {
                                    C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mfm_dataset_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
+    "mfm_predict_klef_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int64]),
+    "mfm_predict_klef": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

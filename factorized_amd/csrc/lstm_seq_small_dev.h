@@ -185,7 +185,10 @@ __device__ __forceinline__ void stage_gates2(const SeqDev& d, int mode, int g, f
 // kernels feed their matrix cores: same rounding points), fp32 accumulation, gate math, cell state and saved activations.
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // Returns where the row's LAST hidden state lies in LDS (one-row fp32 tiles: [HKB] floats, pad units exact zeros; else null).
-template <int KQ, int R, bool FLG = false, bool BF = false>
+// REC = false (predict.hip: inference, nothing comes back for a BPTT): no record of any step -- gates, c, h -- is dropped into
+// obuf or stored to HBM (d.hs / d.cs are not touched and may be null; d.gates is only read: the x-projections); h / c stay on
+// chip and the tile's last hidden states are returned for every R as [HX][R] floats (rows beyond B and pad units exact zeros).
+template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true>
 __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const int T, const int B, const int tile, float* lds,
                                                const unsigned* flg = nullptr, const unsigned epoch = 0, const int ncb = 0,
                                                const HoCtl ctl = HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u}) {
@@ -392,7 +395,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     float rprev[NOS];
 #pragma unroll
     for (int i = 0; i < NOS; ++i) rprev[i] = 0.0f;
-    if (MFM_SEQ_LATE_WRITEOUT && pend) {
+    if (REC && MFM_SEQ_LATE_WRITEOUT && pend) {
 #pragma unroll
       for (int i = 0; i < NOS; ++i) rprev[i] = obuf[(par ^ 1) * (6 * HKB * R) + ol[i]];
     }
@@ -452,7 +455,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
           for (int r = 0; r < R; ++r) acc[gl][r] = fmaf(w[gl][j], hv.v[r], acc[gl][r]);
       }
     }
-    if (MFM_SEQ_LATE_WRITEOUT && pend) {
+    if (REC && MFM_SEQ_LATE_WRITEOUT && pend) {
 #pragma unroll
       for (int i = 0; i < NOS; ++i) {
         if (ook[i]) *op[i] = rprev[i];
@@ -503,9 +506,11 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     asm volatile("s_memtime %0" : "=s"(st1), "+v"(hv), "+v"(c) :: "memory");
 #endif
     if (uact && rowner) {
-      float* ob = obuf + par * (6 * HKB * R) + my_o;
-      ob[0] = a0; ob[HKB * R] = a1;
-      ob[(4 - gp) * HKB * R] = gp ? hv : c;        // slot 4 (c) from gp 0, slot 5 (h) from gp 1
+      if constexpr (REC) {
+        float* ob = obuf + par * (6 * HKB * R) + my_o;
+        ob[0] = a0; ob[HKB * R] = a1;
+        ob[(4 - gp) * HKB * R] = gp ? hv : c;        // slot 4 (c) from gp 0, slot 5 (h) from gp 1
+      }
       if (gp == 0 && u < HX) {
         const float hn = (b < B) ? hv : 0.0f;
         if constexpr (BF) hb16[(cur ^ 1) * HX + u] = (__bf16)hn; else hbuf[(cur ^ 1) * (HX * R) + u * R + myrow] = hn;
@@ -527,7 +532,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
 #if MFM_SEQ_STAMP
     if (MFM_SEQ_STAMP != 6 && t >= 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st_sum += st1 - st0; }
 #endif
-    if (!MFM_SEQ_LATE_WRITEOUT) {
+    if (REC && !MFM_SEQ_LATE_WRITEOUT) {
 #pragma unroll
       for (int i = 0; i < NOS; ++i) {
         if (ook[i]) *op[i] = obuf[par * (6 * HKB * R) + ol[i]];
@@ -541,7 +546,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
   };
   // the record of the last step taken (still in obuf) -> HBM
   auto flush = [&](const int t_last) {
-    if (!pend) return;
+    if (!REC || !pend) return;
 #pragma unroll
     for (int i = 0; i < NOS; ++i) {
       if (ook[i]) *op[i] = obuf[(t_last & 1) * (6 * HKB * R) + ol[i]];
@@ -574,7 +579,8 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     p_cs[(int64_t)(T - 1) * sstep + (tid >> 6)] = (float)((double)st_sum / (double)nsteps);
   }
 #endif
-  if constexpr (R == 1 && !BF) return hbuf + cur * HX;
+  if constexpr (!REC && !BF) return hbuf + cur * (HX * R);
+  else if constexpr (R == 1 && !BF) return hbuf + cur * HX;
   else return nullptr;
 }
 

@@ -527,6 +527,68 @@ class MFMEngine:
         out["losses"] = p.losses
         return out
 
+    # ------------------------------------------------------------------ prediction only
+    PREDICT_MAX_ROWS = 1024      # default row cap of predict(): the x-projections of at most this many rows are alive at once
+
+    _PREDICT_TENSORS = ("ef_encoder.lstm.weight_ih", "ef_encoder.lstm.weight_hh", "ef_encoder.lstm.bias_ih",
+                        "ef_encoder.lstm.bias_hh", "ef_encoder.fc1.weight", "ef_encoder.fc1.bias",
+                        "last_to_zy_fc1.weight", "last_to_zy_fc1.bias", "zy_to_fy_fc1.weight", "zy_to_fy_fc1.bias",
+                        "zy_to_fy_fc2.weight", "zy_to_fy_fc2.bias", "fy_to_y_fc1.weight", "fy_to_y_fc1.bias",
+                        "fy_to_y_fc2.weight", "fy_to_y_fc2.bias")
+
+    def predict_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace predict() keeps for a [T, N, D] split (mfm_predict_klef_workspace_floats)"""
+        c = self.cfg
+        cap = self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
+        return int(_lib.lib().mfm_predict_klef_workspace_floats(int(T), int(N), c["zl_size"] + c["za_size"] + c["zv_size"], cap))
+
+    def predict(self, x, y=None, *, max_rows=None):
+        """x [T, N, D] (, labels) -> {"y_hat": [N, output_dim], "loss": 0-d device tensor or None}: the deterministic eval
+        computation of y_hat and, with labels, the mean L1 / cross-entropy loss, left on the device.
+
+        Variant "kl_ef": mfm_predict_klef -- the ef encoder's recurrence and the six layers behind it, nothing of the
+        generative half, no plan and no training workspace; the split is walked in chunks of at most `max_rows` rows
+        (default PREDICT_MAX_ROWS).  Workspace, y_hat and the loss word are kept per (T, N, max_rows) and REUSED: after the
+        first call for a shape nothing is allocated and nothing synchronises, and the returned tensors are overwritten by the
+        next call for the same shape (clone what must survive it).  Other variants, and sizes the entry refuses (h > 128):
+        the same dictionary from forward(train=False, want_xhat=False)."""
+        self._check_inputs(x, y)
+        T, N, D = x.shape
+        if T < 1 or N < 1:
+            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
+        c = self.cfg
+        od = c["output_dim"]
+        ce = c.get("loss", "l1") == "ce"
+        if y is not None and y.numel() != (N if ce else N * od):
+            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
+                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("max_rows must be at least 1, not %r" % (max_rows,))
+        if self.variant == "kl_ef" and not getattr(self, "_predict_refused", False):
+            cap = self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
+            cache = self.__dict__.setdefault("_predict_bufs", {})
+            st = cache.get((T, N, cap))
+            h = c["zl_size"] + c["za_size"] + c["zv_size"]
+            if st is None:
+                nws = int(_lib.lib().mfm_predict_klef_workspace_floats(T, N, h, cap))
+                offs = (C.c_int64 * 16)(*[self.layout.offsets[n] for n in self._PREDICT_TENSORS])
+                st = (torch.empty(nws, dtype=torch.float32, device=self.device),
+                      torch.empty(N, od, dtype=torch.float32, device=self.device),
+                      torch.zeros((), dtype=torch.float32, device=self.device), offs)
+            ws, y_hat, loss, offs = st
+            rc = _lib.lib().mfm_predict_klef(T, N, D, h, c["zy_size"], c["fy_size"], od, 1 if ce else 0, _ptr(self.params), offs,
+                                             _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat), _ptr(loss) if y is not None else None,
+                                             cap, _stream())
+            if rc == 0:
+                cache[(T, N, cap)] = st
+                return {"y_hat": y_hat, "loss": loss if y is not None else None}
+            if rc != _lib.MFM_ERR_UNSUPPORTED:
+                _lib.check(rc, "mfm_predict_klef")
+            self._predict_refused = True          # (sizes beyond the on-chip recurrence: a property of the configuration)
+        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
+        out = self.forward(x, y, train=False, want_xhat=False, handover=False)
+        return {"y_hat": out["y_hat"], "loss": out["losses"][0].clone() if y is not None else None}
+
     def forward_train(self, x, p, grads_to_zero=None):
         """Training-mode forward of the module path's lazy losses (mfm_plan_forward_train): no labels, no output tensors --
         x_hat / y_hat stay in the plan's workspace (`p.out_views`), the loss slots 1..4 are filled; `grads_to_zero`: a flat

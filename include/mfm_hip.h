@@ -448,6 +448,36 @@ int mfm_dataset_gather(float* X, void* y, const float* X_pool, const void* y_poo
                        int32_t nb, int32_t T, int32_t B, int32_t D, int64_t ybytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction-only path of MFM_KL_EF (csrc/predict.hip): `evaluate(model, X, y)` / `predict(model, X)` of the reference's
+ * drivers (mfm_mosi.py:445-477), which use y_hat alone.  In eval mode y_hat depends on ONE of the model's seven recurrences
+ * (mfm_model.py:637-657):
+ *   ef_last = ef_encoder(x); zy = last_to_zy_fc1(ef_last); fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy))));
+ *   y_hat = fy_to_y_fc2(relu(fy_to_y_fc1(fy)))
+ * so this entry runs the ef encoder's input projection (grouped fp32 GEMM) and ONE further launch per row chunk: the T-step
+ * recurrence with h / c on chip -- no hs / cs / gate record is stored -- and the six row-wise layers behind it in the same
+ * workgroup.  It needs no MfmPlan and no training workspace.  fp32.
+ *   sizes    x [T, N, D] time-major and contiguous; h = hidden size of the ef encoder (zl + za + zv); zy, fy, output_dim
+ *   params   base of the flat fp32 parameter buffer; `offsets` (host, 16 element offsets into it): ef_encoder.lstm
+ *            weight_ih, weight_hh, bias_ih, bias_hh, then weight and bias of ef_encoder.fc1, last_to_zy_fc1, zy_to_fy_fc1,
+ *            zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2 (torch layouts; the two LSTM weights 16-byte aligned)
+ *   y        NULL, or the labels: float [N, output_dim] (loss_kind 0, L1) / int64 [N] (loss_kind 1, cross entropy)
+ *   y_hat    out [N, output_dim]
+ *   loss_dev NULL, or one device float that receives the mean nn.L1Loss() / nn.CrossEntropyLoss() would give (needs y).
+ *            One partial per workgroup and a last-arriver ticket that adds the partials in a fixed order: no float atomics,
+ *            the value is bit-identical from run to run; the ticket word is cleared by the call itself and left at 0.
+ *   max_rows row cap: the split is walked in chunks of at most max_rows rows (0: one chunk) that share the workspace; the
+ *            loss is the mean over all N rows whatever the chunking
+ *   workspace mfm_predict_klef_workspace_floats(T, N, h, max_rows) floats, 16-byte aligned, contents arbitrary:
+ *            min(N, max_rows) * T * 4 * round_up(h, 16) for the x-projections + N loss partials + 4
+ * Nothing outside workspace, y_hat and *loss_dev is written.  Any N >= 1, T >= 1.  Sizes the on-chip recurrence does not cover
+ * (h > 128, or more LDS than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue nothing: run
+ * mfm_plan_forward(train = 0) instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_predict_klef_workspace_floats(int32_t T, int64_t N, int32_t h, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_klef(int32_t T, int64_t N, int32_t D, int32_t h, int32_t zy, int32_t fy, int32_t output_dim, int32_t loss_kind,
+                     const float* params, const int64_t* offsets /*host, 16*/, const float* x, const void* y /*or NULL*/,
+                     float* workspace, float* y_hat, float* loss_dev /*or NULL*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
