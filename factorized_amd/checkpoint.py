@@ -36,7 +36,7 @@ GPU whose parameters are the views of its engine's flat fp32 buffer, all trainab
     asks.  It is a view of live state: the next `update` overwrites it.
   * The snapshot buffer and the state block with its ticket word are allocated on first use, outside a capture; pickling and
     `copy.deepcopy` drop the ticket (a copy draws its own).  Model and engine are re-validated on every call with the pointer
-    checks of `_FusedEngineMixin._flat_ok`.
+    checks of `_FusedEngineMixin._flat_ok`; the metric argument and the state block are `_flat.metric_arg` / `_flat.pack_words`.
 
 `restore()` is one `copy_` of the range back into the live flat buffer.  After it the model is in the state
 `model.load_state_dict(<the same values>)` leaves it in.  What was checked for that: `nn.Module.load_state_dict` on a fused model
@@ -64,14 +64,15 @@ from collections import OrderedDict
 
 import torch
 
-from . import _lib
+from . import _flat, _lib
 from ._fused import _FusedEngineMixin
 
 __all__ = ["KeepBest"]
 
 _MODES = {"min": _lib.MFM_KEEP_MIN, "max": _lib.MFM_KEEP_MAX}
-# MfmKeepBestState as int32 words
+# MfmKeepBestState as int32 words; _STATE: the words the host form holds, in the order of (_value, _calls, _best_call, _taken)
 _W_VALUE, _W_CALLS, _W_BEST_CALL, _W_TAKEN, _W_TICKET = 0, 1, 2, 3, 4
+_STATE = ((_W_VALUE, "float32"), (_W_CALLS, "int32"), (_W_BEST_CALL, "int32"), (_W_TAKEN, "int32"))
 
 
 def _fp32(v):
@@ -100,7 +101,7 @@ class KeepBest:
         self._mfm_ticket = None          # its ticket word (a view)
         self._mfm_taken = None           # its taken word (a 0-d view: what update returns)
         self._mfm_flat = None            # snapshot buffer with the engine's layout
-        self._mfm_key = None             # (engine, layout, begin) the buffers were last validated against
+        self._mfm_key = None             # (engine, layout) the buffers were last validated against
 
     # ------------------------------------------------------------------ copies
     def __getstate__(self):
@@ -126,14 +127,10 @@ class KeepBest:
         key = self._mfm_key
         if key is None or key[0] is not eng or key[1] is not eng.layout:
             # (once per engine: a module with buffers has a state_dict the flat range does not cover)
-            if any(sub._buffers for sub in m.modules()):
+            if _flat.has_buffers(m):
                 return None
-            self._mfm_key = (eng, eng.layout, min(o for o, _, _ in eng.layout.slots))
+            self._mfm_key = (eng, eng.layout)
         return eng
-
-    @staticmethod
-    def _capturing():
-        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
     # ------------------------------------------------------------------ hand-over between the two forms of the state
     def _to_device(self, eng):
@@ -141,7 +138,7 @@ class KeepBest:
         dev = eng.params.device
         fresh = (self._mfm_state is None or self._mfm_state.device != dev or self._mfm_flat is None
                  or self._mfm_flat.device != dev or self._mfm_flat.numel() != eng.layout.total or self._mfm_ticket is None)
-        if (fresh or not self._on_device) and self._capturing():
+        if (fresh or not self._on_device) and _flat.capturing():
             raise _lib.MfmError("KeepBest.update: the snapshot buffer and the state block are set up on the first call on the "
                                 "flat path; make that call outside the stream capture")
         if self._on_device and not fresh:
@@ -157,19 +154,15 @@ class KeepBest:
                 raise _lib.MfmError("KeepBest: the snapshot's tensors do not match the model's parameters")
             torch._foreach_copy_([views[n] for n in names], [self._snap[n].to(dev) for n in names])
             self._snap = None
-        host = torch.zeros(_lib.MFM_KEEP_STATE_WORDS, dtype=torch.int32)
-        host[_W_VALUE:_W_VALUE + 1].view(torch.float32)[0] = self._value
-        host[_W_CALLS], host[_W_BEST_CALL], host[_W_TAKEN] = self._calls, self._best_call, self._taken
-        self._mfm_state = host.to(dev)
+        values = (self._value, self._calls, self._best_call, self._taken)
+        self._mfm_state = _flat.pack_words(_lib.MFM_KEEP_STATE_WORDS, [(w, kind, v) for (w, kind), v in zip(_STATE, values)]).to(dev)
         self._mfm_ticket = self._mfm_state[_W_TICKET:_W_TICKET + 1]
         self._mfm_taken = self._mfm_state[_W_TAKEN]
         self._on_device = True
 
     def _read_back(self):
         """the device state into the host fields (synchronises); the device form stays authoritative"""
-        host = self._mfm_state.cpu()
-        self._value = float(host[_W_VALUE:_W_VALUE + 1].view(torch.float32)[0])
-        self._calls, self._best_call, self._taken = int(host[_W_CALLS]), int(host[_W_BEST_CALL]), int(host[_W_TAKEN])
+        self._value, self._calls, self._best_call, self._taken = _flat.unpack_words(self._mfm_state.cpu(), _STATE)
 
     def _to_host(self):
         """state and snapshot into the torch-path form (synchronises; the first torch-path call after flat ones)"""
@@ -198,32 +191,12 @@ class KeepBest:
         if eng is None:
             return self._update_torch(metric)
         dev = eng.params.device
-        from . import lazy
-        ptr, scalar, keep = None, 0.0, None
-        if isinstance(metric, lazy.LossExpr):
-            keep = metric._value()
-            if keep.device != dev or keep.dtype != torch.float32:
-                keep = keep.to(device=dev, dtype=torch.float32)
-            ptr = keep.data_ptr()
-        elif isinstance(metric, torch.Tensor) and metric.is_cuda:
-            if metric.numel() != 1:
-                raise ValueError("KeepBest.update: the metric must have one element, not shape %s" % (tuple(metric.shape),))
-            keep = metric.detach()
-            if keep.device != dev or keep.dtype != torch.float32:
-                keep = keep.to(device=dev, dtype=torch.float32)
-            ptr = keep.data_ptr()
-        else:
-            if self._capturing():
-                raise _lib.MfmError("KeepBest.update: a host metric (python float or CPU tensor) inside a stream capture would "
-                                    "be baked into the graph -- every replay would compare the same number.  Pass the metric as "
-                                    "a 0-d fp32 tensor on the model's device")
-            scalar = _fp32(metric)
+        keep, host = _flat.metric_arg(metric, dev, "KeepBest.update", "the model's device")      # (keep: alive over the launch)
+        ptr, scalar = (keep.data_ptr(), 0.0) if keep is not None else (None, _fp32(host))
         self._to_device(eng)
-        begin = self._mfm_key[2]
-        _lib.check(_lib.lib().mfm_keep_best_flat(C.c_void_p(self._mfm_flat.data_ptr()), C.c_void_p(eng.params.data_ptr()), begin,
-                                                 eng.layout.guard, _MODES[self.mode], C.c_void_p(ptr), scalar,
-                                                 C.c_void_p(self._mfm_state.data_ptr()),
-                                                 C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))), "mfm_keep_best_flat")
+        _lib.check(_lib.lib().mfm_keep_best_flat(_flat.ptr(self._mfm_flat), _flat.ptr(eng.params), eng.layout.begin, eng.layout.guard,
+                                                 _MODES[self.mode], C.c_void_p(ptr), scalar, _flat.ptr(self._mfm_state),
+                                                 _flat.stream_ptr(dev)), "mfm_keep_best_flat")
         self.last_path = "flat"
         return self._mfm_taken
 
@@ -258,7 +231,7 @@ class KeepBest:
         eng = self._flat_engine()
         if (eng is not None and self._on_device and self._mfm_flat.device == eng.params.device
                 and self._mfm_flat.numel() == eng.layout.total):
-            begin, end = self._mfm_key[2], eng.layout.guard
+            begin, end = eng.layout.begin, eng.layout.guard
             with torch.no_grad():
                 eng.params[begin:end].copy_(self._mfm_flat[begin:end])
             return

@@ -207,6 +207,8 @@ class FlatLayout:
         self.offsets = OrderedDict((n, placed[n]) for n in self.shapes)
         # (offset, numel, shape) in state_dict order: per-tensor views of any buffer with this layout
         self.slots = [(placed[n], int(np.prod(self.shapes[n])), tuple(self.shapes[n])) for n in self.shapes]
+        # offset of the first tensor: [begin, guard) is the range the flat utilities (swa_utils, checkpoint) work on
+        self.begin = min(o for o, _, _ in self.slots)
         # one spare granule behind the last tensor: element `guard` of a GRADIENT buffer with this layout is the guard word of
         # the guarded Adam launches (include/mfm_hip.h): the fused plan stores a NaN there when an in-launch hand-over of the
         # step gave up, the optimizer then leaves the parameters alone; being part of the buffer it rides through the

@@ -61,14 +61,15 @@ from torch.optim import Optimizer
 from torch.optim.lr_scheduler import EPOCH_DEPRECATION_WARNING
 from torch.optim.lr_scheduler import ReduceLROnPlateau as _TorchReduceLROnPlateau
 
-from . import _lib
+from . import _flat, _lib
 
 __all__ = ["ReduceLROnPlateau"]
 
 _MODES = {"min": _lib.MFM_PLATEAU_MIN, "max": _lib.MFM_PLATEAU_MAX}
 _THRESHOLD_MODES = {"rel": _lib.MFM_PLATEAU_REL, "abs": _lib.MFM_PLATEAU_ABS}
-# MfmPlateauState as int32 words (best: the double in words 0-1)
-_W_BAD, _W_COOLDOWN, _W_EPOCH, _W_REDUCED, _W_REDUCTIONS = 2, 3, 4, 5, 6
+# MfmPlateauState as int32 words (best: the double in words 0-1); _STATE: the words of the host form, in the order of _read_back
+_W_BEST, _W_BAD, _W_COOLDOWN, _W_EPOCH, _W_REDUCED, _W_REDUCTIONS = 0, 2, 3, 4, 5, 6
+_STATE = ((_W_BEST, "float64"),) + tuple((w, "int32") for w in (_W_BAD, _W_COOLDOWN, _W_EPOCH, _W_REDUCED, _W_REDUCTIONS))
 _INT32_MAX = 2 ** 31 - 1
 
 
@@ -134,7 +135,7 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
         self._init_is_better(mode=mode, threshold=threshold, threshold_mode=threshold_mode)
         self._reset()
         lrs = self._device_lrs()
-        if lrs is not None and not self._capturing():
+        if lrs is not None and not _flat.capturing():
             self._to_device(lrs[0].device)          # (the state block is allocated here, not in the first step)
 
     # ------------------------------------------------------------------ copies
@@ -168,10 +169,6 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
             lrs.append(lr)
         return lrs
 
-    @staticmethod
-    def _capturing():
-        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
     def _lr_list(self):
         """torch's _param_groups_val_list(optimizer, "lr"): tensors as clones, so the list never aliases a live lr"""
         return [g["lr"].clone() if isinstance(g["lr"], torch.Tensor) else g["lr"] for g in self.optimizer.param_groups]
@@ -181,7 +178,7 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
         """the host state into the block beside the lr tensors (construction, or the first device step after host steps)"""
         if self._on_device and self._mfm_state.device == dev:
             return
-        if self._capturing():
+        if _flat.capturing():
             raise _lib.MfmError("ReduceLROnPlateau.step: the scheduler's state is on the host (it stepped on the host path, or "
                                 "was loaded or changed there) and is uploaded by the next step on the device path; make that "
                                 "step outside the stream capture")
@@ -192,10 +189,8 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
         if not all(isinstance(v, int) and -_INT32_MAX <= v < _INT32_MAX for v in ints):
             raise _lib.MfmError("ReduceLROnPlateau: num_bad_epochs, cooldown_counter and last_epoch must be int32 values for "
                                 "the device path, not %r" % (ints,))
-        host = torch.zeros(_lib.MFM_PLATEAU_STATE_WORDS, dtype=torch.int32)
-        host[0:2].view(torch.float64)[0] = float(self._h_best)
-        host[_W_BAD], host[_W_COOLDOWN], host[_W_EPOCH] = ints
-        host[_W_REDUCED], host[_W_REDUCTIONS] = self._h_reduced, self._h_reductions
+        values = (float(self._h_best),) + ints + (self._h_reduced, self._h_reductions)
+        host = _flat.pack_words(_lib.MFM_PLATEAU_STATE_WORDS, [(w, kind, v) for (w, kind), v in zip(_STATE, values)])
         if self._mfm_state is None or self._mfm_state.device != dev:
             self._mfm_state = host.to(dev)
             self._mfm_reduced = self._mfm_state[_W_REDUCED]
@@ -205,11 +200,8 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
 
     def _read_back(self):
         """the device state into the host fields (synchronises); the device form stays authoritative"""
-        host = self._mfm_state.cpu()
-        self._h_best = float(host[0:2].view(torch.float64)[0])
-        self._h_num_bad_epochs, self._h_cooldown_counter = int(host[_W_BAD]), int(host[_W_COOLDOWN])
-        self._h_last_epoch = int(host[_W_EPOCH])
-        self._h_reduced, self._h_reductions = int(host[_W_REDUCED]), int(host[_W_REDUCTIONS])
+        (self._h_best, self._h_num_bad_epochs, self._h_cooldown_counter, self._h_last_epoch, self._h_reduced,
+         self._h_reductions) = _flat.unpack_words(self._mfm_state.cpu(), _STATE)
 
     def _to_host(self):
         if self._on_device:
@@ -235,25 +227,9 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
         if lrs is None:
             return self._step_host(metrics, epoch)
         dev = lrs[0].device
-        from . import lazy
-        ptr, scalar, keep = None, 0.0, None
-        if isinstance(metrics, lazy.LossExpr):
-            keep = metrics._value()
-        elif isinstance(metrics, torch.Tensor) and metrics.is_cuda:
-            if metrics.numel() != 1:
-                raise ValueError("ReduceLROnPlateau.step: the metric must have one element, not shape %s"
-                                 % (tuple(metrics.shape),))
-            keep = metrics.detach()
-        else:
-            if self._capturing():
-                raise _lib.MfmError("ReduceLROnPlateau.step: a host metric (python float or CPU tensor) inside a stream capture "
-                                    "would be baked into the graph -- every replay would compare the same number.  Pass the "
-                                    "metric as a 0-d fp32 tensor on the learning rates' device")
-            scalar = float(metrics)
-        if keep is not None:
-            if keep.device != dev or keep.dtype != torch.float32:
-                keep = keep.to(device=dev, dtype=torch.float32)
-            ptr = keep.data_ptr()
+        # (keep: alive over the launch; a host metric keeps the double)
+        keep, host = _flat.metric_arg(metrics, dev, "ReduceLROnPlateau.step", "the learning rates' device")
+        ptr, scalar = (keep.data_ptr(), 0.0) if keep is not None else (None, host)
         if epoch is None:
             epoch = -1
         else:
@@ -274,7 +250,7 @@ class ReduceLROnPlateau(_TorchReduceLROnPlateau):
         _lib.check(_lib.lib().mfm_plateau_step(C.c_void_p(self._mfm_state.data_ptr()), C.c_void_p(ptr), scalar, C.byref(table), n,
                                                _MODES[self.mode], _THRESHOLD_MODES[self.threshold_mode], self.factor,
                                                self.threshold, self.eps, self.patience, self.cooldown, epoch,
-                                               C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))), "mfm_plateau_step")
+                                               _flat.stream_ptr(dev)), "mfm_plateau_step")
 
     def _step_host(self, metrics, epoch):
         """torch 2.10's step / _is_better / _reduce_lr, statement for statement (the rule csrc/plateau.hip restates)"""

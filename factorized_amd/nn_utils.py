@@ -23,14 +23,13 @@ caller's arguments: the gradient views are ordinary tensors, so that is always c
 Neither function touches the model's gradient bookkeeping or any optimizer state.  `error_if_nonfinite=True` reads the norm back
 (one synchronisation, as in torch) and raises torch's error; unlike torch the gradients have then already been multiplied by the
 non-finite coefficient."""
-import ctypes as C
 import math
 import weakref
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _flat, _lib
 from ._fused import _owner_of
 
 _KINDS = {2.0: _lib.MFM_NORM_L2, math.inf: _lib.MFM_NORM_INF, 1.0: _lib.MFM_NORM_L1}
@@ -43,11 +42,10 @@ _STATE = weakref.WeakKeyDictionary()
 def _state_of(m, eng):
     st = _STATE.get(m)
     if st is None or st["total"] != eng.layout.total or st["ws"].device != eng.params.device:
-        slots = eng.layout.slots
-        order = np.argsort([o for o, _, _ in slots], kind="stable")
+        order, extents = _flat.extents(eng.layout, padded=False)
         st = dict(total=eng.layout.total, ws=torch.empty(int(_lib.lib().mfm_clip_workspace_floats()), dtype=torch.float32,
                                                          device=eng.params.device),
-                  index={id(p): i for i, p in enumerate(m._plist)}, order=order.tolist(), tables={})
+                  index={id(p): i for i, p in enumerate(m._plist)}, order=order, extents=extents, tables={})
         _STATE[m] = st
     return st
 
@@ -95,33 +93,18 @@ def _table(m, eng, mask):
     key = sel.tobytes()
     hit = st["tables"].get(key)
     if hit is None:
-        slots, spans = eng.layout.slots, []
-        for i in st["order"]:
-            if not sel[i]:
-                continue
-            o, n, _ = slots[i]
-            if n == 0:
-                continue
-            if spans and spans[-1][1] == o:
-                spans[-1][1] = o + n
-            else:
-                spans.append([o, o + n])
+        spans = _flat.merge_spans(st["order"], st["extents"], sel)
         if len(spans) > _lib.MFM_CLIP_MAX_SPANS:
             hit = (None, -1)
         else:
             arr = (_lib.ClipSpan * max(len(spans), 1))()
-            for a, (b, e) in zip(arr, spans):
+            for a, (b, e, _) in zip(arr, spans):
                 a.begin, a.end = b, e
             hit = (arr, len(spans))
         if len(st["tables"]) > 32:
             st["tables"].clear()
         st["tables"][key] = hit
     return st, hit
-
-
-def _stream_and_guard(eng, gflat):
-    return (C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index)),
-            C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard))
 
 
 def _as_list(parameters):
@@ -140,10 +123,10 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
             return torch.tensor(0.0)                 # no listed tensor has a gradient (torch: every .grad is None)
         if arr is not None:
             total = torch.empty((), dtype=torch.float32, device=gflat.device)
-            stream, guard = _stream_and_guard(eng, gflat)
-            _lib.check(_lib.lib().mfm_clip_grad_norm_flat_spans(C.c_void_p(gflat.data_ptr()), arr, n, kind, float(max_norm),
-                                                                C.c_void_p(st["ws"].data_ptr()), C.c_void_p(total.data_ptr()),
-                                                                guard, stream), "mfm_clip_grad_norm_flat_spans")
+            stream, guard = _flat.stream_and_guard(eng, gflat)
+            _lib.check(_lib.lib().mfm_clip_grad_norm_flat_spans(_flat.ptr(gflat), arr, n, kind, float(max_norm),
+                                                                _flat.ptr(st["ws"]), _flat.ptr(total), guard, stream),
+                       "mfm_clip_grad_norm_flat_spans")
             if error_if_nonfinite and not math.isfinite(float(total)):
                 raise RuntimeError(
                     f"The total norm of order {float(norm_type)} for gradients from "
@@ -164,8 +147,8 @@ def clip_grad_value_(parameters, clip_value, foreach=None):
         if n == 0:
             return None
         if arr is not None:
-            stream, guard = _stream_and_guard(eng, gflat)
-            _lib.check(_lib.lib().mfm_clip_grad_value_flat_spans(C.c_void_p(gflat.data_ptr()), arr, n, float(clip_value), guard,
+            stream, guard = _flat.stream_and_guard(eng, gflat)
+            _lib.check(_lib.lib().mfm_clip_grad_value_flat_spans(_flat.ptr(gflat), arr, n, float(clip_value), guard,
                                                                  stream), "mfm_clip_grad_value_flat_spans")
             return None
     return torch.nn.utils.clip_grad_value_(params if params else parameters, clip_value, foreach)

@@ -36,7 +36,8 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib
+from . import _flat, _lib
+from ._flat import ptr as _ptr, stream_and_guard as _stream_and_guard      # (once per step: no attribute look-up)
 
 ReduceLROnPlateau = torch.optim.lr_scheduler.ReduceLROnPlateau      # convenience: `optim.lr_scheduler` users import torch's
 lr_scheduler = torch.optim.lr_scheduler
@@ -82,62 +83,6 @@ import importlib as _il
 _OPT_MOD = _il.import_module("torch.optim.optimizer")
 _OPT_MOD.register_optimizer_step_pre_hook(_foreign_step_hook)
 _GLOBAL_PRE, _GLOBAL_POST = _OPT_MOD._global_optimizer_pre_hooks, _OPT_MOD._global_optimizer_post_hooks
-
-
-# ---------------------------------------------------------------------- spans of a flat buffer
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream_and_guard(eng, gflat):
-    """the current stream, and the guard word of the flat gradient buffer: the plan's backward stores a NaN there when a
-    hand-over inside one of its launches gave up -- a guarded update then leaves parameters and optimizer state alone
-    (engine.check_status() reports it)"""
-    return (C.c_void_p(torch._C._cuda_getCurrentRawStream(eng.params.device.index)),
-            C.c_void_p(gflat.data_ptr() + 4 * eng.layout.guard))
-
-
-def _address_order(layout):
-    """the tensors of a flat layout in address order, and where each starts plus the end of the last (tensor starts are
-    64-float aligned: span bounds are multiples of 4)"""
-    order = np.argsort([o for o, _, _ in layout.slots], kind="stable")
-    return order, [layout.slots[i][0] for i in order] + [layout.guard]
-
-
-def _merge_spans(order, starts, present, keys):
-    """[(begin, end, key)]: walk the tensors in address order, skip tensor i unless present[i], merge adjacent ones whose
-    keys[i] agree"""
-    spans = []
-    for k, i in enumerate(order):
-        if not present[i]:
-            continue
-        b, e, h = starts[k], starts[k + 1], keys[i]
-        if spans and spans[-1][1] == b and spans[-1][2] == h:
-            spans[-1] = (spans[-1][0], e, h)
-        else:
-            spans.append((b, e, h))
-    return spans
-
-
-def _span_tables(spans, span_cls, max_spans, fields):
-    """[(ctypes array, length)]: the spans cut into chunks of at most max_spans (one launch each); a span's key is the tuple of
-    its `fields`"""
-    tables = []
-    for k in range(0, len(spans), max_spans):
-        part = spans[k:k + max_spans]
-        arr = (span_cls * len(part))()
-        for a, (b, e, key) in zip(arr, part):
-            a.begin, a.end = b, e
-            for name, val in zip(fields, key):
-                setattr(a, name, val)
-        tables.append((arr, len(part)))
-    return tables
-
-
-def _launch_tables(fn, name, head, tables, tail):
-    """one launch of the span entry point `fn(*head, spans, nspans, *tail)` per table"""
-    for arr, n in tables:
-        _lib.check(fn(*head, arr, n, *tail), name)
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -212,7 +157,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         st = self._fused.get(m)
         if st is None or self._stale(st, eng):
             st = self._new_state(eng)
-            st["order"], st["starts"] = _address_order(eng.layout)
+            st["order"], st["extents"] = _flat.extents(eng.layout, padded=True)
             if self._pending_fused:                     # state restored by load_state_dict(), in the order it was saved
                 self._restore(st, self._pending_fused.pop(0), eng)
             self._fused[m] = st
@@ -280,7 +225,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """Not wrapped by torch's `profile_hook_step` (`step.hooked` below): that wrapper opens a record_function scope around
         every step, ~10 us of host time against a 150 us device step the unchanged loop has to keep fed.  Step pre / post hooks
         registered on this optimizer or globally are still honoured."""
-        if self._capture_refusal and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        if self._capture_refusal and _flat.capturing():
             raise _lib.MfmError(self._capture_refusal)
         hooks = self._optimizer_step_pre_hooks or self._optimizer_step_post_hooks or len(_GLOBAL_PRE) > 1 or _GLOBAL_POST
         if hooks:
@@ -462,7 +407,7 @@ class Adam(_FlatOptimizer):
                 return st["step_dev"], lr                     # the caller's own device scalar (GraphedModuleStep.set_lr)
             lr = float(lr)
         if st["lr_host"] != lr:
-            if torch.cuda.is_current_stream_capturing():
+            if _flat.capturing():
                 raise _lib.MfmError("factorized_amd.optim.Adam(capturable=True): the learning rate changed inside a stream "
                                     "capture; pass lr as a float32 device tensor or change it between replays")
             st["lr_dev"].fill_(lr)
@@ -530,9 +475,10 @@ class Adam(_FlatOptimizer):
         # some tensors have no gradient (stage losses, unused layers): contiguous runs of present tensors with equal
         # step counts become spans
         steps[present] += 1
-        spans = _merge_spans(st["order"], st["starts"], present, [(s,) for s in steps.tolist()])
-        _launch_tables(L.mfm_adam_flat_spans_guarded, "mfm_adam_flat_spans_guarded", head,
-                       _span_tables(spans, _lib.AdamSpan, _lib.MFM_ADAM_MAX_SPANS, ("step",)), (lr, b1, b2, eps, 1.0, guard, stream))
+        spans = _flat.merge_spans(st["order"], st["extents"], present, [(s,) for s in steps.tolist()])
+        _flat.launch_tables(L.mfm_adam_flat_spans_guarded, "mfm_adam_flat_spans_guarded", head,
+                            _flat.span_tables(spans, _lib.AdamSpan, _lib.MFM_ADAM_MAX_SPANS, ("step",)),
+                            (lr, b1, b2, eps, 1.0, guard, stream))
         return True
 
     _EXT_FIELDS = ("lr", "beta1", "beta2", "eps", "weight_decay", "flags", "step")
@@ -549,10 +495,10 @@ class Adam(_FlatOptimizer):
             hyper.append((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), fl))
         # (layers no forward uses carry a zero gradient on the flat path; torch's .grad is None there: no decay, no step count)
         present, steps = m._grad_present & ~m._group_masks()["unreached"], st["steps"]
-        order, starts = st["order"], st["starts"]
+        order, extents = st["order"], st["extents"]
         if "runs" not in st or st["runs"][0] is not gidx:
             # the runs (begin, end, group) of adjacent tensors of one group
-            st["runs"] = (gidx, order, starts, _merge_spans(order, starts, np.ones(len(order), dtype=bool), gidx.tolist()))
+            st["runs"] = (gidx, order, extents, _flat.merge_spans(order, extents, np.ones(len(order), dtype=bool), gidx.tolist()))
         if present.all() and (steps == steps[0]).all():
             steps += 1
             s_ = int(steps[0])
@@ -560,15 +506,16 @@ class Adam(_FlatOptimizer):
         else:
             # no gradient: moments, vmax, step count and decoupled decay all stay (torch skips it)
             steps[present] += 1
-            spans = _merge_spans(order, starts, present, [hyper[gi] + (s,) for gi, s in zip(gidx.tolist(), steps.tolist())])
+            spans = _flat.merge_spans(order, extents, present, [hyper[gi] + (s,) for gi, s in zip(gidx.tolist(), steps.tolist())])
         if not spans:
             return True                  # no tensor has a gradient: torch's step does nothing either
         amsgrad = any(key[5] & _lib.MFM_ADAMX_AMSGRAD for _, _, key in spans)
         stream, guard = _stream_and_guard(eng, gflat)       # (a NaN guard leaves vmax alone too)
         vmax = _ptr(self._vmax(st)) if amsgrad else C.c_void_p(None)
-        _launch_tables(_lib.lib().mfm_adam_ext_flat_spans_guarded, "mfm_adam_ext_flat_spans_guarded",
-                       (_ptr(eng.params), _ptr(gflat), _ptr(st["m"]), _ptr(st["v"]), vmax),
-                       _span_tables(spans, _lib.AdamExtSpan, _lib.MFM_ADAMX_MAX_SPANS, self._EXT_FIELDS), (1.0, guard, stream))
+        _flat.launch_tables(_lib.lib().mfm_adam_ext_flat_spans_guarded, "mfm_adam_ext_flat_spans_guarded",
+                            (_ptr(eng.params), _ptr(gflat), _ptr(st["m"]), _ptr(st["v"]), vmax),
+                            _flat.span_tables(spans, _lib.AdamExtSpan, _lib.MFM_ADAMX_MAX_SPANS, self._EXT_FIELDS),
+                            (1.0, guard, stream))
         return True
 
     def _inner_rebuilt(self, rest, old):
@@ -772,8 +719,8 @@ class SGD(_FlatOptimizer):
                 if damp != 0.0:
                     first_damp.append(i)
             keys[i] = (lr, wd, mom, damp, fl)
-        spans = _merge_spans(st["order"], st["starts"], present, keys)
-        tables = _span_tables(spans, _lib.SgdSpan, _lib.MFM_SGD_MAX_SPANS, self._FIELDS)
+        spans = _flat.merge_spans(st["order"], st["extents"], present, keys)
+        tables = _flat.span_tables(spans, _lib.SgdSpan, _lib.MFM_SGD_MAX_SPANS, self._FIELDS)
         momentum = any(h[2] != 0.0 for _, _, h in spans)
         hit = (tables, np.array(first, dtype=np.int64), np.array(first_damp, dtype=np.int64), momentum)
         if len(st["spans"]) > 32:
@@ -796,8 +743,8 @@ class SGD(_FlatOptimizer):
             return True                      # no tensor has a gradient: torch's step does nothing either
         stream, guard = _stream_and_guard(eng, gflat)
         buf = _ptr(self._buf(st, eng.params)) if momentum else C.c_void_p(None)
-        _launch_tables(_lib.lib().mfm_sgd_flat_spans_guarded, "mfm_sgd_flat_spans_guarded", (_ptr(eng.params), _ptr(gflat), buf),
-                       tables, (1.0, guard, stream))
+        _flat.launch_tables(_lib.lib().mfm_sgd_flat_spans_guarded, "mfm_sgd_flat_spans_guarded",
+                            (_ptr(eng.params), _ptr(gflat), buf), tables, (1.0, guard, stream))
         if len(first):
             st["have"][first] = True
             if len(first_damp):

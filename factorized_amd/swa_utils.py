@@ -38,12 +38,10 @@ kept off `state_dict()`, dropped by pickling and `copy.deepcopy`, reallocated wh
 instances -- two instances may update on two streams.
 
 `SWALR` and `update_bn` are torch's objects (`SWALR` works on the flat optimizers: schedulers act on `param_groups`)."""
-import ctypes as C
-
 import torch
 from torch.optim import swa_utils as _T
 
-from . import _lib
+from . import _flat, _lib
 from ._fused import _FusedEngineMixin
 
 __all__ = list(_T.__all__)
@@ -80,10 +78,6 @@ def get_swa_avg_fn():
     return _named(_T.get_swa_avg_fn(), _lib.MFM_AVG_SWA, None)
 
 
-def _has_buffers(m):
-    return any(sub._buffers for sub in m.modules())
-
-
 class AveragedModel(_T.AveragedModel):
     """torch.optim.swa_utils.AveragedModel; between two fused models one launch over their flat buffers (see the module doc)"""
 
@@ -96,7 +90,7 @@ class AveragedModel(_T.AveragedModel):
             if p.is_cuda and self.n_averaged.device != p.device:
                 self.n_averaged = self.n_averaged.to(p.device)
         self._mfm_ticket = None
-        self._mfm_range = None          # (source layout, own layout, first offset) of the pair last checked for the flat path
+        self._mfm_range = None          # (source layout, own layout) of the pair last checked for the flat path
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -133,11 +127,11 @@ class AveragedModel(_T.AveragedModel):
         hit = self.__dict__.get("_mfm_range")
         if hit is None or hit[0] is not ls or hit[1] is not ld:
             # (once per pair of engines: walking the sub-modules for buffers costs as much host time as half a training step)
-            if ls.total != ld.total or ls.guard != ld.guard or ls.slots != ld.slots or _has_buffers(model) or _has_buffers(mine):
+            if (ls.total != ld.total or ls.guard != ld.guard or ls.slots != ld.slots or _flat.has_buffers(model)
+                    or _flat.has_buffers(mine)):
                 return None
-            hit = self._mfm_range = (ls, ld, min(o for o, _, _ in ld.slots))
-        begin = hit[2]
-        return dst, src, begin, rule[0], rule[1]
+            self._mfm_range = (ls, ld)
+        return dst, src, ld.begin, rule[0], rule[1]
 
     def update_parameters(self, model):
         hit = self._flat_args(model)
@@ -148,7 +142,5 @@ class AveragedModel(_T.AveragedModel):
         ticket = self.__dict__.get("_mfm_ticket")
         if ticket is None or ticket.device != dev:
             ticket = self._mfm_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(_lib.lib().mfm_avg_flat(C.c_void_p(dst.params.data_ptr()), C.c_void_p(src.params.data_ptr()), begin,
-                                           dst.layout.guard, kind, w, C.c_void_p(self.n_averaged.data_ptr()),
-                                           C.c_void_p(ticket.data_ptr()),
-                                           C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))), "mfm_avg_flat")
+        _lib.check(_lib.lib().mfm_avg_flat(_flat.ptr(dst.params), _flat.ptr(src.params), begin, dst.layout.guard, kind, w,
+                                           _flat.ptr(self.n_averaged), _flat.ptr(ticket), _flat.stream_ptr(dev)), "mfm_avg_flat")

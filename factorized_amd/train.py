@@ -8,13 +8,13 @@ so to equal a single-process step at the global batch W*B each rank back-propaga
 `mean-terms + W * KLD` (reg_scale = W inside the plan) and the summed gradients are divided by W
 (grad_scale = 1/W inside the fused Adam).  tests/test_dp_gloo.py checks that algebra on CPU.
 """
-import ctypes as C
+import gc
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _flat, _lib, synth
 
 
 def dp_env():
@@ -143,9 +143,8 @@ class DeviceDataset:
         dev = self.X.device
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().mfm_dataset_gather(
-                C.c_void_p(self.X.data_ptr()), C.c_void_p(self.y.data_ptr()), C.c_void_p(self.X_pool.data_ptr()),
-                C.c_void_p(self.y_pool.data_ptr()), C.c_void_p(p.data_ptr()), self.X_pool.shape[0], nb, T, B, D, ybytes,
-                C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))), "mfm_dataset_gather")
+                *(_flat.ptr(t) for t in (self.X, self.y, self.X_pool, self.y_pool, p)), self.X_pool.shape[0], nb, T, B, D, ybytes,
+                _flat.stream_ptr(dev)), "mfm_dataset_gather")
         return self
 
 
@@ -312,31 +311,32 @@ class GraphedModuleStep:
             self.opt = torch.optim.Adam(model.parameters(), lr=self.lr, capturable=True)
         disc_fn = torch.nn.CrossEntropyLoss() if ce else torch.nn.L1Loss()
         mse = torch.nn.MSELoss()
-        self._snap = self._snap_step = None
+        # `step` must not refer to `self`: through `self._step_fn` that is a reference cycle, and the cyclic collector would destroy
+        # the graph whenever it runs -- inside a later stream capture that ends the process (destroying a graph synchronises the device)
+        opt, x, y_static, snap = self.opt, self.x, self.y, []
 
         def step(apply=True):
             # (fused models: zero_grad() costs no launch -- the forward's first launch clears the flat gradient buffer)
-            self.opt.zero_grad(set_to_none=fused)
-            (xl, xa, xv, yh), reg, miss = model.forward(self.x)
-            x = self.x
+            opt.zero_grad(set_to_none=fused)
+            (xl, xa, xv, yh), reg, miss = model.forward(x)
             yhat = yh.squeeze(1) if (not ce and cfg["output_dim"] == 1) else yh
-            disc = disc_fn(yhat, self.y)
+            disc = disc_fn(yhat, y_static)
             gen = cfg["lda_xl"] * mse(xl, x[:, :, :d[0]]) + cfg["lda_xa"] * mse(xa, x[:, :, d[0]:d[0] + d[1]]) \
                 + cfg["lda_xv"] * mse(xv, x[:, :, d[0] + d[1]:])
             loss = disc + gen + cfg["lda_mmd"] * reg + miss
             loss.backward()
             if apply:
-                self.opt.step()
+                opt.step()
             from .lazy import LossExpr, SnapshotStep
             if isinstance(loss, LossExpr):
                 # symbolic losses: ONE copy node of the plan's 64-byte state block; the returned expressions read the copy
                 # (valid until the next replay, whatever else runs on the plan in between)
                 plan = model.engine.plan(T, B)
-                if self._snap is None:
-                    self._snap = torch.zeros_like(plan.state)
-                    self._snap_step = SnapshotStep(self._snap, self.x)
-                self._snap.copy_(plan.state)
-                return LossExpr(self._snap_step, loss._coef, loss._const), LossExpr(self._snap_step, disc._coef, disc._const)
+                if not snap:
+                    snap.append(torch.zeros_like(plan.state))
+                    snap.append(SnapshotStep(snap[0], x))
+                snap[0].copy_(plan.state)
+                return LossExpr(snap[1], loss._coef, loss._const), LossExpr(snap[1], disc._coef, disc._const)
             return loss.detach(), disc.detach()
 
         # the warm-up steps below run on the (zero) static batch: keep them from training the model
@@ -362,6 +362,7 @@ class GraphedModuleStep:
 
     def _capture(self):
         torch.cuda.synchronize(self.x.device)
+        gc.collect()          # (torch.cuda.graph no longer does: a dead cycle that owns a graph must not be finalised in the capture)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.disc = self._step_fn()

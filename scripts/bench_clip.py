@@ -10,21 +10,17 @@ factorized_amd.optim.SGD(lr=0.01, momentum=0.9), in three forms (the method of s
 """
 import argparse
 import gc
-import os
-import sys
-import time
 
 import torch
-import torch.nn as nn
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from factorized_amd import configs, nn_utils, synth  # noqa: E402
+from _bench_common import cfgs, config, loop, mosi_batch, need_gpu, timed_steps
+from factorized_amd import nn_utils  # noqa: E402
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
 import factorized_amd.optim as optim  # noqa: E402
 
 MAX_NORM = 20.0
-FORMS = {"none": None, "torch": lambda ps: torch.nn.utils.clip_grad_norm_(ps, MAX_NORM),
-         "flat": lambda ps: nn_utils.clip_grad_norm_(ps, MAX_NORM)}
+FORMS = {"none": None, "torch": lambda m: torch.nn.utils.clip_grad_norm_(m.parameters(), MAX_NORM),
+         "flat": lambda m: nn_utils.clip_grad_norm_(m.parameters(), MAX_NORM)}
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--only", choices=list(FORMS))
@@ -34,32 +30,8 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--no-item", action="store_true", help="leave out the loop's per-step disc_loss.item()")
 args = ap.parse_args()
 
-cfgs = configs.canonical_configs(dropout=True)
-config = cfgs[0]
-B, T = 32, 20
-xn, yn = synth.make_batch(config["input_dims"], B, T, seed=7)
-X, y = torch.from_numpy(xn).cuda(), torch.from_numpy(yn).cuda()
-d_l, d_a, d_v = config["input_dims"]
-
-
-def loop(model, optimizer, steps, clip, item):
-    criterion, gen_criterion = nn.L1Loss(), nn.MSELoss()
-    epoch_loss = 0.0
-    for _ in range(steps):
-        optimizer.zero_grad()
-        batch_X, batch_y = X, y
-        decoded, mmd_loss, missing_loss = model.forward(batch_X)
-        [x_l_hat, x_a_hat, x_v_hat, y_hat] = decoded
-        gen_loss = config["lda_xl"] * gen_criterion(x_l_hat, batch_X[:, :, :d_l]) + config["lda_xa"] * gen_criterion(x_a_hat, batch_X[:, :, d_l:d_l + d_a]) \
-            + config["lda_xv"] * gen_criterion(x_v_hat, batch_X[:, :, d_l + d_a:])
-        disc_loss = criterion(y_hat.squeeze(1), batch_y)
-        loss = disc_loss + gen_loss + config["lda_mmd"] * mmd_loss + missing_loss
-        loss.backward()
-        if clip is not None:
-            clip(model.parameters())
-        optimizer.step()
-        if item:
-            epoch_loss += disc_loss.item()
+need_gpu("bench_clip.py")
+mosi_batch()
 
 
 def run(form, item):
@@ -69,12 +41,7 @@ def run(form, item):
     optimizer = optim.SGD(model.parameters(), lr=config["lr"], momentum=config["momentum"])
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, args.warmup, FORMS[form], item)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, args.steps, FORMS[form], item)
-    torch.cuda.synchronize()
-    ms = 1e3 * (time.perf_counter() - t0) / args.steps
+    ms = timed_steps(lambda k: loop(model, optimizer, k, item, after_backward=FORMS[form]), args.steps, args.warmup)
     assert model._handover_ok() and model._grad_views_attached() and optimizer._fallback is None      # the flat path all along
     return ms
 

@@ -2,39 +2,14 @@
 stock torch.optim.Adam vs factorized_amd.optim.Adam, per-tensor autograd path vs flat gradients, torch.optim.SGD vs
 factorized_amd.optim.SGD (lr 0.01, momentum 0.9), torch.optim.AdamW vs factorized_amd.optim.AdamW (and AMSGrad, two parameter
 groups), and the fused engine call."""
-import os, sys, time
+import os, time
 import torch, torch.nn as nn
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from factorized_amd import configs, synth
+from _bench_common import B, T, cfgs, config, d_a, d_l, loop, mosi_batch, need_gpu, timed, timed_steps
 from factorized_amd.mfm_model import MFM_KL_EF
 import factorized_amd.optim as optim
 
-cfgs = configs.canonical_configs(dropout=True)
-config = cfgs[0]
-B, T = 32, 20
-xn, yn = synth.make_batch(config["input_dims"], B, T, seed=7)
-X, y = torch.from_numpy(xn).cuda(), torch.from_numpy(yn).cuda()
-d_l, d_a, d_v = config["input_dims"]
-
-
-def loop(model, optimizer, steps, item=True):
-    criterion, gen_criterion = nn.L1Loss(), nn.MSELoss()
-    epoch_loss = 0.0
-    for _ in range(steps):
-        optimizer.zero_grad()
-        batch_X, batch_y = X, y
-        decoded, mmd_loss, missing_loss = model.forward(batch_X)
-        [x_l_hat, x_a_hat, x_v_hat, y_hat] = decoded
-        gen_loss = config["lda_xl"] * gen_criterion(x_l_hat, batch_X[:, :, :d_l]) + config["lda_xa"] * gen_criterion(x_a_hat, batch_X[:, :, d_l:d_l + d_a]) \
-            + config["lda_xv"] * gen_criterion(x_v_hat, batch_X[:, :, d_l + d_a:])
-        disc_loss = criterion(y_hat.squeeze(1), batch_y)
-        loss = disc_loss + gen_loss + config["lda_mmd"] * mmd_loss + missing_loss
-        loss.backward()
-        optimizer.step()
-        if item:
-            epoch_loss += disc_loss.item()
-
-
+need_gpu("bench_dropin.py")
+X, y = mosi_batch()
 for name, opt_cls, fast, item in (("torch.optim.Adam, per-tensor autograd (round 2)", torch.optim.Adam, False, True),
                                   ("torch.optim.Adam, flat gradients", torch.optim.Adam, True, True),
                                   ("factorized_amd.optim.Adam, flat gradients", optim.Adam, True, True),
@@ -49,12 +24,7 @@ for name, opt_cls, fast, item in (("torch.optim.Adam, per-tensor autograd (round
     optimizer = opt_cls(model.parameters())
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, 30, item)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, 300, item)
-    torch.cuda.synchronize()
-    print("%-70s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
+    print("%-70s %.3f ms/step" % (name, timed_steps(lambda k: loop(model, optimizer, k, item), 300, 30)))
 # the reference's other optimizer line (mfm_mosi.py:404) at the canonical lr 0.01, momentum 0.9, flat gradients
 for name, opt_cls, item in (("torch.optim.SGD(lr=0.01, momentum=0.9), flat gradients", torch.optim.SGD, True),
                             ("factorized_amd.optim.SGD(lr=0.01, momentum=0.9), flat gradients", optim.SGD, True),
@@ -66,12 +36,7 @@ for name, opt_cls, item in (("torch.optim.SGD(lr=0.01, momentum=0.9), flat gradi
     optimizer = opt_cls(model.parameters(), lr=config["lr"], momentum=config["momentum"])
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, 30, item)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, 300, item)
-    torch.cuda.synchronize()
-    print("%-70s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
+    print("%-70s %.3f ms/step" % (name, timed_steps(lambda k: loop(model, optimizer, k, item), 300, 30)))
 # torch.optim.Adam's other options (span kernel mfm_adam_ext_flat_spans_guarded): AdamW with weight_decay 1e-2, AMSGrad, two
 # parameter groups; the plain Adam line repeated in between shows the spread of this run
 def two_groups(m):
@@ -95,21 +60,10 @@ for name, make, item in (("torch.optim.AdamW(weight_decay=1e-2), flat gradients"
     optimizer = make(model)
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, 30, item)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, 300, item)
-    torch.cuda.synchronize()
-    print("%-78s %.3f ms/step" % (name, 1e3 * (time.perf_counter() - t0) / 300))
+    print("%-78s %.3f ms/step" % (name, timed_steps(lambda k: loop(model, optimizer, k, item), 300, 30)))
 model = MFM_KL_EF(*cfgs).to("cuda")
-for _ in range(30):
-    model.engine.train_step(X, y)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(300):
-    model.engine.train_step(X, y)
-torch.cuda.synchronize()
-print("%-70s %.3f ms/step" % ("model.engine.train_step(X, y)  (one C call)", 1e3 * (time.perf_counter() - t0) / 300))
+print("%-70s %.3f ms/step" % ("model.engine.train_step(X, y)  (one C call)",
+                              timed(lambda: model.engine.train_step(X, y), 300, 30)))
 
 # eager, the other two classes of train_mfm (fused plan forward / backward since round 3 / 4)
 from factorized_amd import mfm_model as M2
@@ -118,12 +72,8 @@ for cls_name in ("MFM_KL", "MFM"):
     optimizer = optim.Adam(model.parameters())
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, 30, True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, 300, True)
-    torch.cuda.synchronize()
-    print("%-70s %.3f ms/step" % ("factorized_amd.optim.Adam, flat gradients, %s" % cls_name, 1e3 * (time.perf_counter() - t0) / 300))
+    print("%-70s %.3f ms/step" % ("factorized_amd.optim.Adam, flat gradients, %s" % cls_name,
+                                  timed_steps(lambda k: loop(model, optimizer, k, True), 300, 30)))
 
 # the same loop captured once into a hipGraph (train.GraphedModuleStep: fused plan with device-side epochs / dropout streams,
 # optim.Adam(capturable=True)) and replayed; per-step input copy into the static batch included
@@ -133,14 +83,8 @@ for cls_name in ("MFM_KL_EF", "MFM_KL", "MFM"):
     model = getattr(M, cls_name)(*cfgs).to("cuda")
     model.train()
     gs = train.GraphedModuleStep(model, config, B, T, lr=1e-3)
-    for _ in range(30):
-        gs.step(X, y)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(300):
-        gs.step(X, y)
-    torch.cuda.synchronize()
-    print("%-70s %.3f ms/step" % ("GraphedModuleStep(%s): the unchanged loop as one hipGraph replay" % cls_name, 1e3 * (time.perf_counter() - t0) / 300))
+    print("%-70s %.3f ms/step" % ("GraphedModuleStep(%s): the unchanged loop as one hipGraph replay" % cls_name,
+                                  timed(lambda: gs.step(X, y), 300, 30)))
     assert float(gs.loss) == float(gs.loss) and model.engine.check_status() == 0
 
 if os.environ.get("MFM_DROPIN_PROFILE"):

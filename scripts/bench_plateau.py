@@ -17,14 +17,10 @@ schedulers see a metric that never improves with a patience that never runs out:
 import argparse
 import os
 import subprocess
-import sys
-import time
 
 import torch
-import torch.nn as nn
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from factorized_amd import configs, synth  # noqa: E402
+from _bench_common import B, T, cfgs, loop, mosi_batch, need_gpu, report, say, timed, write_out
 from factorized_amd.lr_scheduler import ReduceLROnPlateau  # noqa: E402
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
 import factorized_amd.optim as optim  # noqa: E402
@@ -42,34 +38,8 @@ ap.add_argument("--commit", help="the commit the record is taken on (default: gi
 ap.add_argument("--out", help="write the record (every round, the medians, the ratios) to this file")
 args = ap.parse_args()
 
-if not torch.cuda.is_available():
-    sys.exit("bench_plateau.py needs the GPU: a time taken anywhere else says nothing")
-
-cfgs = configs.canonical_configs(dropout=True)
-config = cfgs[0]
-B, T = 32, 20
-xn, yn = synth.make_batch(config["input_dims"], B, T, seed=7)
-X, y = torch.from_numpy(xn).cuda(), torch.from_numpy(yn).cuda()
-d_l, d_a, d_v = config["input_dims"]
-
-
-def loop(model, optimizer, steps):
-    criterion, gen_criterion = nn.L1Loss(), nn.MSELoss()
-    epoch_loss = 0.0
-    for _ in range(steps):
-        optimizer.zero_grad()
-        batch_X, batch_y = X, y
-        decoded, mmd_loss, missing_loss = model.forward(batch_X)
-        [x_l_hat, x_a_hat, x_v_hat, y_hat] = decoded
-        gen_loss = config["lda_xl"] * gen_criterion(x_l_hat, batch_X[:, :, :d_l]) + config["lda_xa"] * gen_criterion(x_a_hat, batch_X[:, :, d_l:d_l + d_a]) \
-            + config["lda_xv"] * gen_criterion(x_v_hat, batch_X[:, :, d_l + d_a:])
-        disc_loss = criterion(y_hat.squeeze(1), batch_y)
-        loss = disc_loss + gen_loss + config["lda_mmd"] * mmd_loss + missing_loss
-        loss.backward()
-        optimizer.step()
-        epoch_loss += disc_loss.item()
-
-
+need_gpu("bench_plateau.py")
+mosi_batch()
 model = MFM_KL_EF(*cfgs).to("cuda")
 lr = torch.tensor([1e-3], device="cuda")
 optimizer = optim.Adam(model.parameters(), lr=lr, capturable=True)
@@ -84,30 +54,11 @@ ours.step(1.0)
 assert ours.last_path == "device"
 
 
-def timed(fn, n):
-    for _ in range(min(args.warmup, n)):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / n
-
-
 RUN = {
-    "torch": lambda: timed(lambda: theirs.step(valid_loss.item()), args.calls),
-    "device": lambda: timed(lambda: ours.step(valid_loss), args.calls),
-    "epoch": lambda: timed(lambda: loop(model, optimizer, STEPS_PER_EPOCH), args.epochs),
+    "torch": lambda: timed(lambda: theirs.step(valid_loss.item()), args.calls, args.warmup),
+    "device": lambda: timed(lambda: ours.step(valid_loss), args.calls, args.warmup),
+    "epoch": lambda: timed(lambda: loop(model, optimizer, STEPS_PER_EPOCH), args.epochs, args.warmup),
 }
-
-lines = []
-
-
-def say(text):
-    print(text, flush=True)
-    lines.append(text)
-
 
 forms = [args.only] if args.only else FORMS
 seen = {f: [] for f in forms}
@@ -119,10 +70,8 @@ for r in range(args.rounds):
 # every call was a bad epoch that reduced nothing, on the device path
 assert ours.last_path == "device" and ours.best == theirs.best == 1.0 and ours.reductions == 0 and float(lr) == float(torch.tensor(1e-3))
 assert ours.num_bad_epochs == ours.last_epoch - 1 and theirs.num_bad_epochs == theirs.last_epoch - 1
-med = {f: sorted(v)[len(v) // 2] for f, v in seen.items()}
-for f in forms:
-    say("%-7s median   %9.4f ms/%s   (spread of the rounds %.4f)" % (f, med[f], "epoch" if f == "epoch" else "call",
-                                                                    max(seen[f]) - min(seen[f])))
+med = report(seen, lambda f, m, spread: "%-7s median   %9.4f ms/%s   (spread of the rounds %.4f)"
+             % (f, m, "epoch" if f == "epoch" else "call", spread))
 if "epoch" in med:
     step = med["epoch"] / STEPS_PER_EPOCH
     say("step    = epoch / %d = %.4f ms" % (STEPS_PER_EPOCH, step))
@@ -137,8 +86,6 @@ if args.out:
                                              stderr=subprocess.DEVNULL).decode().strip()
         except (OSError, subprocess.CalledProcessError):
             commit = "unknown"
-    with open(args.out, "w") as f:
-        f.write("scripts/bench_plateau.py --calls %d --epochs %d --warmup %d --rounds %d: MFM_KL_EF, B=%d, T=%d, fp32, "
-                "optim.Adam(capturable=True, lr=device tensor); taken on commit %s\n"
-                % (args.calls, args.epochs, args.warmup, args.rounds, B, T, commit))
-        f.write("\n".join(lines) + "\n")
+    write_out(args.out, "scripts/bench_plateau.py --calls %d --epochs %d --warmup %d --rounds %d: MFM_KL_EF, B=%d, T=%d, fp32, "
+              "optim.Adam(capturable=True, lr=device tensor); taken on commit %s"
+              % (args.calls, args.epochs, args.warmup, args.rounds, B, T, commit))

@@ -17,15 +17,12 @@ Every time is a host clock around `--calls` calls that end in a device synchroni
 forms alternate within a round and the median over the rounds is reported with the spread (max - min of the rounds).
 """
 import argparse
-import os
-import sys
-import time
 
 import torch
 import torch.nn as nn
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from factorized_amd import _lib, configs, synth  # noqa: E402
+from _bench_common import batch, cfgs, loop, mosi_batch, need_gpu, say, timed, write_out
+from factorized_amd import _lib  # noqa: E402
 from factorized_amd.checkpoint import KeepBest  # noqa: E402
 from factorized_amd.lr_scheduler import ReduceLROnPlateau  # noqa: E402
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
@@ -43,59 +40,14 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--out", help="write the record to this file")
 args = ap.parse_args()
 
-if not torch.cuda.is_available():
-    sys.exit("bench_predict.py needs the GPU: a time taken anywhere else says nothing")
-
-cfgs = configs.canonical_configs(dropout=True)
-config = cfgs[0]
-d_l, d_a, d_v = config["input_dims"]
-lines = []
-
-
-def say(text):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def batch(N, T, seed):
-    xn, yn = synth.make_batch(config["input_dims"], N, T, seed=seed)
-    return torch.from_numpy(xn).cuda(), torch.from_numpy(yn).cuda()
-
-
-def loop(model, optimizer, X, y, steps):
-    criterion, gen_criterion = nn.L1Loss(), nn.MSELoss()
-    epoch_loss = 0.0
-    for _ in range(steps):
-        optimizer.zero_grad()
-        decoded, mmd_loss, missing_loss = model.forward(X)
-        [x_l_hat, x_a_hat, x_v_hat, y_hat] = decoded
-        gen_loss = config["lda_xl"] * gen_criterion(x_l_hat, X[:, :, :d_l]) + config["lda_xa"] * gen_criterion(x_a_hat, X[:, :, d_l:d_l + d_a]) \
-            + config["lda_xv"] * gen_criterion(x_v_hat, X[:, :, d_l + d_a:])
-        disc_loss = criterion(y_hat.squeeze(1), y)
-        loss = disc_loss + gen_loss + config["lda_mmd"] * mmd_loss + missing_loss
-        loss.backward()
-        optimizer.step()
-        epoch_loss += disc_loss.item()
-
-
-def timed(fn, n):
-    for _ in range(min(args.warmup, n)):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / n
-
-
+need_gpu("bench_predict.py")
+mosi_batch()                                             # (B=32, T=20: the training epoch beside the tails)
 model = MFM_KL_EF(*cfgs)
 lr = torch.tensor([1e-3], device="cuda")
 optimizer = optim.Adam(model.parameters(), lr=lr, capturable=True)
 model = model.to("cuda")
 model.train()
-Xt, yt = batch(32, 20, 7)
-loop(model, optimizer, Xt, yt, STEPS_PER_EPOCH)          # (on its engine, every code object loaded)
+loop(model, optimizer, STEPS_PER_EPOCH)                  # (on its engine, every code object loaded)
 eng = model.engine
 # patience beyond the run: the tail must not move the lr under the timed training epoch
 scheduler = ReduceLROnPlateau(optimizer, "min", patience=1 << 30)
@@ -139,7 +91,7 @@ for N, T in SHAPES:
     seen = {f: [] for f in FORMS}
     for r in range(args.rounds):
         for form in FORMS:
-            seen[form].append(timed(RUN[form], args.calls))
+            seen[form].append(timed(RUN[form], args.calls, args.warmup))
     say("N=%d T=%d   (valid loss %.6f both ways)" % (N, T, got))
     for f in FORMS:
         v = sorted(seen[f])
@@ -155,7 +107,7 @@ for N, T in SHAPES:
     eng.__dict__.get("_predict_bufs", {}).clear()
     torch.cuda.empty_cache()
 
-ep = sorted(timed(lambda: loop(model, optimizer, Xt, yt, STEPS_PER_EPOCH), args.epochs) for _ in range(args.rounds))
+ep = sorted(timed(lambda: loop(model, optimizer, STEPS_PER_EPOCH), args.epochs, args.warmup) for _ in range(args.rounds))
 say("epoch (40 steps, B=32, T=20) median %9.4f ms   (spread of the rounds %.4f)" % (ep[len(ep) // 2], ep[-1] - ep[0]))
 for N, T in SHAPES:
     base = med_all[(N, T, "ref_engine")]
@@ -163,8 +115,5 @@ for N, T in SHAPES:
         m = med_all[(N, T, f)]
         say("N=%d T=%d  %s / ref_engine = %.3f   (%.4f vs %.4f ms; spreads %.4f, %.4f)   = %.4f epochs"
             % (N, T, f, m[0] / base[0], m[0], base[0], m[1], base[1], m[0] / ep[len(ep) // 2]))
-if args.out:
-    with open(args.out, "w") as fh:
-        fh.write("scripts/bench_predict.py --calls %d --epochs %d --warmup %d --rounds %d: MFM_KL_EF, fp32, optim.Adam\n"
-                 % (args.calls, args.epochs, args.warmup, args.rounds))
-        fh.write("\n".join(lines) + "\n")
+write_out(args.out, "scripts/bench_predict.py --calls %d --epochs %d --warmup %d --rounds %d: MFM_KL_EF, fp32, optim.Adam"
+          % (args.calls, args.epochs, args.warmup, args.rounds))

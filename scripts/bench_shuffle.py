@@ -17,14 +17,13 @@ A form's time is a host clock around `reps` new orders that end in a device sync
 """
 import argparse
 import ctypes as C
-import os
+import itertools
 import sys
-import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_common import say, timed, write_out
 from factorized_amd import _lib, train  # noqa: E402
 
 SHAPES = {"mosi": (1284, 20, 32, 325), "mosei": (16265, 20, 32, 409)}
@@ -41,24 +40,6 @@ ap.add_argument("--out", help="write the record to this file")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_shuffle.py measures on the GPU: no ROCm device here")
-
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
-
-
-def timed(fn, reps, warmup):
-    for i in range(warmup):
-        fn(i)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(reps):
-        fn(warmup + i)
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps
 
 
 def events(fn, reps, warmup):
@@ -100,7 +81,7 @@ def bench(name):
     seen = {f: [] for f in which}
     for r in range(args.rounds):
         for f in which:
-            ms = timed(forms[f], reps[f], warm[f])
+            ms = timed(lambda i=itertools.count(): forms[f](next(i)), reps[f], warm[f])      # (order i of this window)
             seen[f].append(ms)
             say("  %-10s round %d  %10.4f ms per order   (%d orders)" % (f, r, ms, reps[f]))
     med = {f: sorted(v)[len(v) // 2] for f, v in seen.items()}
@@ -139,6 +120,4 @@ say("plain read on this part, recorded by scripts/micro/hbm_read_probe.hip: %s" 
 say()
 for name in ([args.shape] if args.shape else list(SHAPES)):
     bench(name)
-if args.out:
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+write_out(args.out)

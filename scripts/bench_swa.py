@@ -13,15 +13,11 @@ The time is a host clock around `--steps` steps that end in a device synchronise
 """
 import argparse
 import gc
-import os
-import sys
-import time
 
 import torch
-import torch.nn as nn
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from factorized_amd import configs, swa_utils, synth  # noqa: E402
+from _bench_common import B, T, cfgs, loop, mosi_batch, need_gpu, report, say, timed_steps, write_out
+from factorized_amd import swa_utils  # noqa: E402
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
 import factorized_amd.optim as optim  # noqa: E402
 
@@ -39,32 +35,8 @@ ap.add_argument("--no-item", action="store_true", help="leave out the loop's per
 ap.add_argument("--out", help="write the record (every round, the medians, what the averaging adds) to this file")
 args = ap.parse_args()
 
-cfgs = configs.canonical_configs(dropout=True)
-config = cfgs[0]
-B, T = 32, 20
-xn, yn = synth.make_batch(config["input_dims"], B, T, seed=7)
-X, y = torch.from_numpy(xn).cuda(), torch.from_numpy(yn).cuda()
-d_l, d_a, d_v = config["input_dims"]
-
-
-def loop(model, optimizer, steps, averaged, item):
-    criterion, gen_criterion = nn.L1Loss(), nn.MSELoss()
-    epoch_loss = 0.0
-    for _ in range(steps):
-        optimizer.zero_grad()
-        batch_X, batch_y = X, y
-        decoded, mmd_loss, missing_loss = model.forward(batch_X)
-        [x_l_hat, x_a_hat, x_v_hat, y_hat] = decoded
-        gen_loss = config["lda_xl"] * gen_criterion(x_l_hat, batch_X[:, :, :d_l]) + config["lda_xa"] * gen_criterion(x_a_hat, batch_X[:, :, d_l:d_l + d_a]) \
-            + config["lda_xv"] * gen_criterion(x_v_hat, batch_X[:, :, d_l + d_a:])
-        disc_loss = criterion(y_hat.squeeze(1), batch_y)
-        loss = disc_loss + gen_loss + config["lda_mmd"] * mmd_loss + missing_loss
-        loss.backward()
-        optimizer.step()
-        if averaged is not None:
-            averaged.update_parameters(model)
-        if item:
-            epoch_loss += disc_loss.item()
+need_gpu("bench_swa.py")
+mosi_batch()
 
 
 def run(form, item):
@@ -74,28 +46,16 @@ def run(form, item):
     optimizer = optim.Adam(model.parameters())
     model = model.to("cuda")
     model.train()
-    loop(model, optimizer, 1, None, item)                # (the source is on its engine before the copy is taken)
+    loop(model, optimizer, 1, item)                      # (the source is on its engine before the copy is taken)
     averaged = FORMS[form](model) if FORMS[form] else None
-    loop(model, optimizer, args.warmup, averaged, item)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop(model, optimizer, args.steps, averaged, item)
-    torch.cuda.synchronize()
-    ms = 1e3 * (time.perf_counter() - t0) / args.steps
+    update = averaged.update_parameters if averaged is not None else None
+    ms = timed_steps(lambda k: loop(model, optimizer, k, item, after_step=update), args.steps, args.warmup)
     assert model._handover_ok() and model._grad_views_attached() and optimizer._fallback is None      # the flat path all along
     if averaged is not None:
         assert int(averaged.n_averaged) == args.warmup + args.steps
         if form == "flat":
             assert averaged._mfm_ticket is not None and int(averaged._mfm_ticket) == 0                # ... of the averaging too
     return ms
-
-
-lines = []
-
-
-def say(text):
-    print(text, flush=True)
-    lines.append(text)
 
 
 items = (False,) if args.no_item else (True, False)
@@ -108,15 +68,10 @@ for item in items:
             ms = run(form, item)
             seen[form].append(ms)
             say("%-6s %-24s round %d  %.3f ms/step" % (form, what, r, ms))
-    med = {f: sorted(v)[len(v) // 2] for f, v in seen.items()}
-    for f in forms:
-        say("%-6s %-24s median   %.3f ms/step   (spread of the rounds %.3f)" % (f, what, med[f], max(seen[f]) - min(seen[f])))
+    med = report(seen, lambda f, m, spread: "%-6s %-24s median   %.3f ms/step   (spread of the rounds %.3f)" % (f, what, m, spread))
     if "none" in med:
         for f in forms:
             if f != "none":
                 say("%-6s %-24s adds     %+.3f ms/step to the loop without averaging" % (f, what, med[f] - med["none"]))
-if args.out:
-    with open(args.out, "w") as f:
-        f.write("scripts/bench_swa.py --steps %d --warmup %d --rounds %d: MFM_KL_EF, B=%d, T=%d, fp32, optim.Adam, EMA decay %g\n"
-                % (args.steps, args.warmup, args.rounds, B, T, DECAY))
-        f.write("\n".join(lines) + "\n")
+write_out(args.out, "scripts/bench_swa.py --steps %d --warmup %d --rounds %d: MFM_KL_EF, B=%d, T=%d, fp32, optim.Adam, EMA decay %g"
+          % (args.steps, args.warmup, args.rounds, B, T, DECAY))

@@ -8,6 +8,7 @@ relative bound on the eval-mode y_hat after restore() against a second model tha
 import copy
 import ctypes as C
 import io
+import re
 
 import numpy as np
 import pytest
@@ -372,6 +373,47 @@ def test_update_inside_a_capture_takes_device_metrics_only():
         twin.update(v)
         _check_against_twin(kb, twin, kb._mfm_taken, ("replay", k))
     assert (kb.calls, kb.epoch, kb.value) == (4, 2, 5.0)
+
+
+def _whole(text):
+    return "^" + re.escape(text) + "$"
+
+
+def test_metric_arg_of_the_flat_utilities():
+    """_flat.metric_arg, the metric resolution KeepBest.update and ReduceLROnPlateau.step share (no launch of the library)"""
+    _need_gpu()
+    from factorized_amd import _flat
+    dev = torch.device("cuda", torch.cuda.current_device())
+    who, where = "KeepBest.update", "the model's device"
+    # a 0-d fp32 tensor on the device goes in by its own pointer: no copy
+    own = torch.tensor(0.75, device=dev)
+    keep, host = _flat.metric_arg(own, dev, who, where)
+    assert host is None and keep.data_ptr() == own.data_ptr() and keep.dtype == torch.float32 and keep.dim() == 0
+    # a 1-element fp64 device tensor: fp32 on the device, rounded to nearest
+    wide = torch.tensor([1.0 + 2.0 ** -24 + 2.0 ** -40], dtype=torch.float64, device=dev)      # just above the midpoint: rounds up
+    keep, host = _flat.metric_arg(wide, dev, who, where)
+    assert host is None and keep.dtype == torch.float32 and keep.device == dev and keep.numel() == 1
+    assert float(keep) == 1.0 + 2.0 ** -23
+    # more than one element is refused with the caller's name in front
+    # (the whole text, by `match`: an ExceptionInfo kept in a local would tie this frame, and the graph below, into a cycle)
+    with pytest.raises(ValueError, match=_whole("KeepBest.update: the metric must have one element, not shape (2,)")):
+        _flat.metric_arg(torch.zeros(2, device=dev), dev, who, where)
+    # a host float inside a capture is refused; the capture ends cleanly and the graph replays
+    buf = torch.zeros(1, device=dev)
+    text = ("ReduceLROnPlateau.step: a host metric (python float or CPU tensor) inside a stream capture would be baked into the "
+            "graph -- every replay would compare the same number.  Pass the metric as a 0-d fp32 tensor on the learning rates' "
+            "device")
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):                       # (captures on a side stream of its own)
+        assert _flat.capturing()
+        buf.add_(1.0)
+        with pytest.raises(_lib.MfmError, match=_whole(text)):
+            _flat.metric_arg(3.0, dev, "ReduceLROnPlateau.step", "the learning rates' device")
+    assert not _flat.capturing()
+    graph.replay()
+    assert float(buf) == 1.0
+    assert _flat.metric_arg(3.0, dev, who, where) == (None, 3.0)
 
 
 def test_composed_and_frozen_models_take_the_torch_path_and_equal_the_twin():
