@@ -3,16 +3,18 @@
 //
 // Traffic per element of a span: p, m, v read and written, g read = 28 B; a span with MFM_ADAMX_AMSGRAD also reads and writes
 // vmax = 36 B.  A span without the flag neither reads nor writes vmax.
+#include "adam_dev.h"
 #include "span_tiles.h"
 
 namespace mfm {
 
-// One span in kernel form: the common head, the bias corrections of its step count (formed on the host in double precision, as
-// adam_launch does) and its hyper-parameters.
+// One span in kernel form: the common head, the coefficients of its hyper-parameters and step count (adam_coef, as adam_launch
+// forms them) and its weight decay.
 // `decay` is weight_decay for L2 decay (g += decay * p) and 1 - lr * weight_decay for decoupled decay (p *= decay).
 struct AdamxSpanDev {
   SpanHead h;
-  float step_size, bc2_sqrt, beta1, beta2, eps, decay;
+  AdamCoef c;
+  float decay;
 };
 // 88 x 40 bytes + 8 = 3528: well inside the 4 KiB a kernel argument block may hold
 struct AdamxSpansDev {
@@ -23,14 +25,14 @@ static_assert(sizeof(AdamxSpansDev) + 6 * sizeof(void*) + 8 <= 4096, "Adam span 
 
 constexpr int kAdamxDecay = 1 << 30;  // (device table only) the span has weight_decay != 0
 
-// Work is dealt in tiles as span_tiles.h describes.  The m / v / p lines keep adam_kernel's operation order: a span with no
-// option set computes what adam_kernel computes.
+// Work is dealt in tiles as span_tiles.h describes.  The update is adam_kernel's (adam_dev.h), the options its uniform
+// arguments: a span with no option set executes what adam_kernel executes.
 __global__ __launch_bounds__(kSpanTile) void adam_ext_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                                    float* __restrict__ m, float* __restrict__ v,
                                                                    float* __restrict__ vmax, const AdamxSpansDev S,
                                                                    float grad_scale, const float* __restrict__ guard) {
-  // guard word (mfm_adam_ext_flat_spans_guarded): anything but 0.0f leaves p, m, v and vmax as they are (adam_kernel)
-  if (guard && !(guard[0] == 0.0f)) return;
+  // guard word (mfm_adam_ext_flat_spans_guarded): raised, it leaves p, m, v and vmax as they are
+  if (guard_raised(guard)) return;
   int k = 0;
   for (int t = blockIdx.x; t < S.tiles; t += gridDim.x) {
     k = span_of_tile(S, t, k);
@@ -41,31 +43,14 @@ __global__ __launch_bounds__(kSpanTile) void adam_ext_spans_kernel(float* __rest
     const bool decay = (sp.h.flags & kAdamxDecay) != 0;
     const bool decoupled = (sp.h.flags & MFM_ADAMX_DECOUPLED) != 0;
     const float gs = (sp.h.flags & MFM_ADAMX_MAXIMIZE) ? -grad_scale : grad_scale;
-    const float beta1 = sp.beta1, beta2 = sp.beta2;
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
     f32x4 xv = {0.0f, 0.0f, 0.0f, 0.0f};
     if (amsgrad) xv = reinterpret_cast<const f32x4*>(vmax)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gg = gv[j] * gs;
-      if (decay) {
-        if (decoupled) pv[j] = pv[j] * sp.decay;      // param.mul_(1 - lr * weight_decay)
-        else gg = fmaf(sp.decay, pv[j], gg);          // grad.add(param, alpha=weight_decay)
-      }
-      mv[j] = mv[j] + (1.0f - beta1) * (gg - mv[j]);
-      vv[j] = vv[j] * beta2 + (1.0f - beta2) * gg * gg;
-      float s = vv[j];
-      if (amsgrad) {
-        // torch.maximum: a NaN on either side stays a NaN
-        xv[j] = (vv[j] > xv[j] || vv[j] != vv[j]) ? vv[j] : xv[j];
-        s = xv[j];
-      }
-      const float denom = sqrtf(s) / sp.bc2_sqrt + sp.eps;
-      pv[j] = pv[j] - sp.step_size * mv[j] / denom;
-    }
+    if (decay && decoupled) pv = pv * sp.decay;      // param.mul_(1 - lr * weight_decay)
+    adam_update4(pv, mv, vv, gv, sp.c, gs, decay && !decoupled, sp.decay, amsgrad, &xv);
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(v)[i] = vv;
@@ -96,14 +81,8 @@ int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* v
     MFM_REQUIRE((sp.flags & ~(MFM_ADAMX_MAXIMIZE | MFM_ADAMX_AMSGRAD | MFM_ADAMX_DECOUPLED)) == 0,
                 "adam ext spans[%d]: unknown flags 0x%x", k, (unsigned)sp.flags);
     MFM_REQUIRE(vmax || !(sp.flags & MFM_ADAMX_AMSGRAD), "adam ext spans[%d]: AMSGRAD needs a vmax buffer", k);
-    const double bc1 = 1.0 - pow((double)sp.beta1, (double)sp.step);
-    const double bc2 = 1.0 - pow((double)sp.beta2, (double)sp.step);
     d.h.flags = sp.flags | (sp.weight_decay != 0.0f ? kAdamxDecay : 0);
-    d.step_size = (float)((double)sp.lr / bc1);
-    d.bc2_sqrt = (float)sqrt(bc2);
-    d.beta1 = sp.beta1;
-    d.beta2 = sp.beta2;
-    d.eps = sp.eps;
+    d.c = adam_coef(sp.lr, sp.beta1, sp.beta2, sp.eps, sp.step);
     d.decay = (sp.flags & MFM_ADAMX_DECOUPLED) ? (float)(1.0 - (double)sp.lr * (double)sp.weight_decay) : sp.weight_decay;
   }
   int nb;

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kSpanTile) void clip_scale_kernel(float* __restrict
                                                                float* __restrict__ total_norm, const float* __restrict__ guard) {
   __shared__ float lds[kSpanTile / 64];
   // guard word (mfm_adam_flat_guarded): gradients that cannot be trusted are not rescaled and have no finite norm
-  if (guard && !(guard[0] == 0.0f)) {
+  if (guard_raised(guard)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) total_norm[0] = NAN;
     return;
   }
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kSpanTile) void clip_scale_kernel(float* __restrict
 // g = clamp(g, -c, c); a NaN stays a NaN (torch.clamp), so no fminf / fmaxf
 __global__ __launch_bounds__(kSpanTile) void clip_value_kernel(float* __restrict__ g, const ClipSpansDev S, float c,
                                                                const float* __restrict__ guard) {
-  if (guard && !(guard[0] == 0.0f)) return;
+  if (guard_raised(guard)) return;
   int k = 0;
   for (int t = blockIdx.x; t < S.tiles; t += gridDim.x) {
     k = span_of_tile(S, t, k);

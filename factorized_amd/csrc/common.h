@@ -74,6 +74,12 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // ---------------------------------------------------------------- device helpers
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// The guard word of the guarded entry points (include/mfm_hip.h, mfm_adam_flat_guarded): an optional device float, by
+// convention a spare element of the gradient buffer.  Anything but 0.0f -- the plan stores a NaN, hence no `!=` -- means the
+// gradients of this step cannot be trusted and the launch leaves its buffers as they are (uniform branch, one cached load per
+// thread).
+__device__ __forceinline__ bool guard_raised(const float* guard) { return guard && !(guard[0] == 0.0f); }
+
 // v_mfma_f32_16x16x4_f32: D = A[16x4] * B[4x16] + C, exact fp32 FMA chain (k ascending).
 // lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15];
 // result register r of lane l is D[row = (l>>4)*4 + r][col = l&15].

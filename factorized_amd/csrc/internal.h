@@ -148,9 +148,11 @@ struct MseItem {
   int64_t ldx, rows; int d; float inv_count, grad_scale; int block_begin;
 };
 int mse_group_launch(const MseItem* items, int count, hipStream_t stream);
+// (the update and its coefficients: adam_dev.h, shared with adam_ext.hip and p2p.hip)
 // guard: optional device float; the update is skipped unless it is exactly 0 (include/mfm_hip.h, mfm_adam_flat_guarded)
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float beta1,
                 float beta2, float eps, float grad_scale, hipStream_t stream, const float* guard = nullptr);
+// up to MFM_ADAM_MAX_SPANS disjoint spans in any order, one step count each (adam_spans_kernel)
 int adam_spans_launch(float* p, const float* g, float* m, float* v, const MfmAdamSpan* spans, int nspans, float lr,
                       float beta1, float beta2, float eps, float grad_scale, hipStream_t stream, const float* guard = nullptr);
 int fill_launch(float* p, int64_t n, float val, hipStream_t stream);
@@ -160,7 +162,8 @@ int sgd_spans_launch(float* p, const float* g, float* buf, const MfmSgdSpan* spa
                      hipStream_t stream, const float* guard);
 
 // adam_ext.hip -- Adam / AdamW / AMSGrad over spans of a flat buffer, hyper-parameters and step count per span
-// (include/mfm_hip.h, mfm_adam_ext_flat_spans); vmax may be NULL when no span has MFM_ADAMX_AMSGRAD; guard as for adam_launch
+// (include/mfm_hip.h, mfm_adam_ext_flat_spans), ascending; vmax may be NULL when no span has MFM_ADAMX_AMSGRAD; guard as for
+// adam_launch
 int adam_ext_spans_launch(float* p, const float* g, float* m, float* v, float* vmax, const MfmAdamExtSpan* spans, int nspans,
                           float grad_scale, hipStream_t stream, const float* guard);
 

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "adam_dev.h"
 #include "internal.h"
 
 namespace mfm {
@@ -132,22 +133,16 @@ __device__ __forceinline__ void publish(int* const* flags, int slot, int W, int 
 }
 
 // Optional fused optimizer: the rank that holds a reduced gradient in registers applies the flat Adam update
-// (same arithmetic as adam_kernel, elementwise.hip) instead of a separate launch reading it back.
+// (adam_update4 of adam_dev.h, what adam_kernel of elementwise.hip applies) instead of a separate launch reading it back.
 struct AdamArgs {
   float *p, *m, *v;
-  float beta1, beta2, eps, step_size, bc2_sqrt, grad_scale;
+  AdamCoef c;
+  float grad_scale;
 };
 
 __device__ __forceinline__ void adam4(const AdamArgs& a, int64_t idx, int64_t n, f32x4 g4) {
   f32x4 pv = load4_bounded(a.p, idx, n), mv = load4_bounded(a.m, idx, n), vv = load4_bounded(a.v, idx, n);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float gg = g4[j] * a.grad_scale;
-    mv[j] = mv[j] + (1.0f - a.beta1) * (gg - mv[j]);
-    vv[j] = vv[j] * a.beta2 + (1.0f - a.beta2) * gg * gg;
-    const float denom = sqrtf(vv[j]) / a.bc2_sqrt + a.eps;
-    pv[j] = pv[j] - a.step_size * mv[j] / denom;
-  }
+  adam_update4(pv, mv, vv, g4, a.c, a.grad_scale);
   store4_bounded(a.p, idx, n, pv);
   store4_bounded(a.m, idx, n, mv);
   store4_bounded(a.v, idx, n, vv);
@@ -286,14 +281,7 @@ __global__ __launch_bounds__(P2P_THREADS) void p2p_allreduce_flat_kernel(const P
   const bool skip = wait_flags(d.f1[me] + w, P2P_WGS, W, epoch, timeout, d.err, stat);
   auto adam_from = [&](int it, int64_t idx, f32x4 g4) {
     f32x4 p4 = pp[it], m4 = pm[it], v4 = pv[it];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gg = g4[j] * ad.grad_scale;
-      m4[j] = m4[j] + (1.0f - ad.beta1) * (gg - m4[j]);
-      v4[j] = v4[j] * ad.beta2 + (1.0f - ad.beta2) * gg * gg;
-      const float denom = sqrtf(v4[j]) / ad.bc2_sqrt + ad.eps;
-      p4[j] = p4[j] - ad.step_size * m4[j] / denom;
-    }
+    adam_update4(p4, m4, v4, g4, ad.c, ad.grad_scale);
     store4_bounded(ad.p, idx, n, p4); store4_bounded(ad.m, idx, n, m4); store4_bounded(ad.v, idx, n, v4);
   };
   // ---- reduce my slice's chunk in rank order, push 2: the result -> every rank's result row `me`
@@ -517,9 +505,7 @@ int mfm_p2p_allreduce_adam_guarded(void* handle, float* grads, float* p, float* 
     set_error("mfm_p2p_allreduce_adam: buffers must be 16-byte aligned");
     return MFM_ERR_ARG;
   }
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  AdamArgs ad{p, m, v, beta1, beta2, eps, (float)((double)lr / bc1), (float)sqrt(bc2), grad_scale};
+  AdamArgs ad{p, m, v, adam_coef(lr, beta1, beta2, eps, step), grad_scale};
   return p2p_launch(handle, grads, n, stream, &ad, "mfm_p2p_allreduce_adam", guard_index);
 }
 

@@ -20,8 +20,8 @@ static_assert(sizeof(SgdSpansDev) + 4 * sizeof(void*) + 8 <= 4096, "SGD span tab
 __global__ __launch_bounds__(kSpanTile) void sgd_spans_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ buf, const SgdSpansDev S, float grad_scale,
                                                               const float* __restrict__ guard) {
-  // guard word (mfm_sgd_flat_spans_guarded): anything but 0.0f leaves p and buf as they are (adam_kernel)
-  if (guard && !(guard[0] == 0.0f)) return;
+  // guard word (mfm_sgd_flat_spans_guarded): raised, it leaves p and buf as they are
+  if (guard_raised(guard)) return;
   int k = 0;
   for (int t = blockIdx.x; t < S.tiles; t += gridDim.x) {
     k = span_of_tile(S, t, k);

@@ -17,7 +17,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _flat, _lib
 
 ALIGN = 64  # floats
 
@@ -642,14 +642,9 @@ class MFMEngine:
             if has_grad[g] or (self.staged_adam == "legacy" and gs[g] > 0):
                 gs[g] += 1
                 active[g] = gs[g]
-        spans = [(b, e, active[g]) for g, b, e in self.layout.group_spans if g in active]
-        merged = []
-        for b, e, st in spans:                       # neighbours with the same step count become one span
-            if merged and merged[-1][1] == b and merged[-1][2] == st:
-                merged[-1] = (merged[-1][0], e, st)
-            else:
-                merged.append((b, e, st))
-        return merged
+        groups = self.layout.group_spans                 # neighbours with the same step count become one span
+        return _flat.merge_spans(range(len(groups)), [(b, e) for _, b, e in groups], [g in active for g, _, _ in groups],
+                                 [(active.get(g),) for g, _, _ in groups])
 
     def train_step(self, x, y, lr=1e-3, grad_scale=1.0, check=True, stage=0):
         """forward(train) + backward + Adam, one enqueue.  stage 0 = the joint loss of train_mfm
@@ -675,14 +670,12 @@ class MFMEngine:
             self.step_count = gs["shared"]
             if len(spans) > _lib.MFM_ADAM_MAX_SPANS:
                 raise _lib.MfmError("staged Adam: %d spans (max %d)" % (len(spans), _lib.MFM_ADAM_MAX_SPANS))
-            arr = (_lib.AdamSpan * len(spans))()
-            for i, (b, e_, st) in enumerate(spans):
-                arr[i].begin, arr[i].end, arr[i].step = b, e_, st
+            (arr, nspans), = _flat.span_tables(spans, _lib.AdamSpan, _lib.MFM_ADAM_MAX_SPANS, ("step",))
             p.fwd_serial += 1
             p.consumed = True
             _lib.check(_lib.lib().mfm_plan_train_step_staged(
                 p.handle, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), _ptr(x), _ptr(y),
-                C.c_uint64(self.seed), int(stage), arr, len(spans), lr, grad_scale, _ptr(p.workspace), _ptr(p.losses),
+                C.c_uint64(self.seed), int(stage), arr, nspans, lr, grad_scale, _ptr(p.workspace), _ptr(p.losses),
                 _stream()), "mfm_plan_train_step_staged")
             return p.losses
         self.step_count += 1

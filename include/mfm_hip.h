@@ -217,7 +217,9 @@ int mfm_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, int32
  * own 1-based step count; elements outside every span keep p, m and v untouched.  This is torch.optim.Adam's
  * treatment of parameters whose .grad is None (skipped; per-parameter step counters), which staged training
  * relies on: train_beta_vae (reference mfm_mosi.py:278-281, 346-358) trains gen+reg first -- the classifier gets no
- * gradient -- then disc+reg -- the decoders and the modality z->f MLPs get none.  begin/end are multiples of 4. */
+ * gradient -- then disc+reg -- the decoders and the modality z->f MLPs get none.  begin/end are multiples of 4.
+ * The spans may come in any order; spans that overlap are refused (MFM_ERR_ARG), as are more than MFM_ADAM_MAX_SPANS.  Every
+ * span computes the bits mfm_adam_flat computes. */
 /* Guarded forms (ABI 3): `guard` is an optional device pointer to ONE float -- by convention a spare element of the gradient
  * buffer itself, so that it travels through the data-parallel all-reduce with the gradients.  The kernels read it first and
  * leave p, m and v untouched unless it is exactly 0.0f.  The fused plan stores a NaN there when an in-launch hand-over of the

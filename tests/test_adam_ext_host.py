@@ -90,6 +90,40 @@ def test_adam_ext_launch_validates_on_the_host():
     assert b"ascending" in L.mfm_last_error()
 
 
+def test_adam_flat_spans_validates_on_the_host():
+    """mfm_adam_flat_spans takes its spans in any order: its refusals come before anything is enqueued (the pointers are never
+    used)"""
+    L = _lib.lib()
+    fake = C.c_void_p(1 << 20)
+
+    def call(spans, n=None, guarded=False):
+        arr = (_lib.AdamSpan * len(spans))()
+        for a, (b, e, st) in zip(arr, spans):
+            a.begin, a.end, a.step = b, e, st
+        args = [fake, fake, fake, fake, arr, len(spans) if n is None else n, 1e-3, 0.9, 0.999, 1e-8, 1.0]
+        if guarded:
+            return L.mfm_adam_flat_spans_guarded(*args, fake, None)
+        return L.mfm_adam_flat_spans(*args, None)
+
+    nine = [(64 * k, 64 * k + 64, 1) for k in range(_lib.MFM_ADAM_MAX_SPANS + 1)]
+    cases = [
+        ([(0, 128, 1), (64, 192, 1)], b"overlaps spans[0]"),
+        ([(64, 192, 2), (0, 128, 1)], b"overlaps spans[0]"),     # descending
+        ([(0, 64, 1), (256, 320, 1), (128, 260, 1)], b"spans[2]: [128,260) overlaps spans[1]"),
+        (nine, b"nspans=9"),
+        ([(2, 64, 1)], b"multiples of 4"),
+        ([(0, 62, 1)], b"multiples of 4"),
+        ([(0, 64, 1), (64, 130, 1)], b"multiples of 4"),
+        ([(0, 64, 0)], b"step 0"),
+        ([(0, 64, 1), (128, 192, 0)], b"step 0"),
+    ]
+    for spans, msg in cases:
+        for guarded in (False, True):
+            assert call(spans, guarded=guarded) != 0, spans
+            assert msg in L.mfm_last_error(), (spans, L.mfm_last_error())
+    assert call([(0, 64, 1)], n=0) != 0 and b"bad arguments" in L.mfm_last_error()
+
+
 CTOR_CASES = [
     dict(lr=-0.1),
     dict(eps=-1e-8),

@@ -33,7 +33,7 @@ def _flags(s):
             | (_lib.MFM_ADAMX_DECOUPLED if s["decoupled"] else 0))
 
 
-def _launch(p, g, m, v, vmax, spans, guard=None):
+def _launch(p, g, m, v, vmax, spans, guard=None, grad_scale=1.0):
     arr = (_lib.AdamExtSpan * len(spans))()
     for j, s in enumerate(spans):
         arr[j].begin, arr[j].end, arr[j].step, arr[j].flags = s["begin"], s["end"], s["step"], _flags(s)
@@ -42,10 +42,10 @@ def _launch(p, g, m, v, vmax, spans, guard=None):
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
     if guard is None:
-        _lib.check(L.mfm_adam_ext_flat_spans(ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), arr, len(spans), 1.0, stream),
+        _lib.check(L.mfm_adam_ext_flat_spans(ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), arr, len(spans), grad_scale, stream),
                    "mfm_adam_ext_flat_spans")
     else:
-        _lib.check(L.mfm_adam_ext_flat_spans_guarded(ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), arr, len(spans), 1.0, ptr(guard),
+        _lib.check(L.mfm_adam_ext_flat_spans_guarded(ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), arr, len(spans), grad_scale, ptr(guard),
                                                      stream), "mfm_adam_ext_flat_spans_guarded")
     torch.cuda.synchronize()
 
@@ -121,21 +121,97 @@ def test_kernel_matches_torch_adam_over_spans():
     _check_spans(spans, host, (p, m, v, x))
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _launch_plain_spans(p, g, m, v, spans, grad_scale=1.0, guard=None):
+    """mfm_adam_flat_spans[_guarded] over [(begin, end, step)], lr 0.01 and torch's default betas / eps"""
+    arr = (_lib.AdamSpan * len(spans))()
+    for a, (b, e, st) in zip(arr, spans):
+        a.begin, a.end, a.step = b, e, st
+    L = _lib.lib()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    head = (_ptr(p), _ptr(g), _ptr(m), _ptr(v), arr, len(spans), 0.01, 0.9, 0.999, 1e-8, grad_scale)
+    if guard is None:
+        _lib.check(L.mfm_adam_flat_spans(*head, stream), "mfm_adam_flat_spans")
+    else:
+        _lib.check(L.mfm_adam_flat_spans_guarded(*head, _ptr(guard), stream), "mfm_adam_flat_spans_guarded")
+    torch.cuda.synchronize()
+
+
 def test_span_without_options_matches_mfm_adam_flat():
+    """every Adam entry point computes the bits of mfm_adam_flat (five workgroups, a partial last tile), and mfm_adam_flat's
+    scalar tail (n % 4 elements) the bits of its float4 loop"""
     _need_gpu()
-    n = 4 * 1237
-    host = _data(n, 4)
+    n4 = 4 * 1237
+    n = n4 + 3
+    host = [t.clone() for t in _data(n, 4)[:4]]
+    for t in host:
+        t[n4:] = t[:3]                                           # the tail repeats elements 0..2
+    L = _lib.lib()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    none = dict(lr=0.01, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, maximize=False, amsgrad=False, decoupled=False)
+    guard = torch.zeros(1, device="cuda")
     for step in (1, 9):
-        p, g, m, v, _ = (t.cuda() for t in host)
-        _launch(p, g, m, v, None, [dict(begin=0, end=n, step=step, lr=0.01, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, maximize=False,
-                                        amsgrad=False, decoupled=False)])
-        q, _, qm, qv, _ = (t.cuda() for t in host)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(_lib.lib().mfm_adam_flat(ptr(q), ptr(g), ptr(qm), ptr(qv), n, step, 0.01, 0.9, 0.999, 1e-8, 1.0,
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mfm_adam_flat")
-        torch.cuda.synchronize()
-        for a, b in ((p, q), (m, qm), (v, qv)):
-            torch.testing.assert_close(a, b, rtol=1e-6, atol=1e-6)
+        for gs in (1.0, 1.0 / 3.0):
+            hyper = (0.01, 0.9, 0.999, 1e-8, gs)
+            p, g, m, v = (t.cuda() for t in host)
+            _lib.check(L.mfm_adam_flat(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, step, *hyper, stream), "mfm_adam_flat")
+            torch.cuda.synchronize()
+            for t in (p, m, v):
+                assert torch.equal(t[n4:], t[:3]), (step, gs)
+            want = (p[:n4].clone(), m[:n4].clone(), v[:n4].clone())
+            assert not torch.equal(want[0], host[0][:n4].cuda())
+            step_dev = torch.full((1,), step - 1, dtype=torch.int32, device="cuda")
+            lr_dev = torch.full((1,), 0.01, device="cuda")
+            entries = {
+                "guarded": lambda q, qg, qm, qv: _lib.check(L.mfm_adam_flat_guarded(
+                    _ptr(q), _ptr(qg), _ptr(qm), _ptr(qv), n4, step, *hyper, _ptr(guard), stream), "mfm_adam_flat_guarded"),
+                "dev": lambda q, qg, qm, qv: _lib.check(L.mfm_adam_flat_dev(
+                    _ptr(q), _ptr(qg), _ptr(qm), _ptr(qv), n4, _ptr(step_dev), _ptr(lr_dev), 0.9, 0.999, 1e-8, gs, None, stream),
+                    "mfm_adam_flat_dev"),
+                "one span": lambda q, qg, qm, qv: _launch_plain_spans(q, qg, qm, qv, [(0, n4, step)], gs),
+                "three spans": lambda q, qg, qm, qv: _launch_plain_spans(
+                    q, qg, qm, qv, [(1024, 1024 + 4 * 300, step), (0, 1024, step), (1024 + 4 * 300, n4, step)], gs),
+                "ext span": lambda q, qg, qm, qv: _launch(q, qg, qm, qv, None, [dict(none, begin=0, end=n4, step=step)],
+                                                          grad_scale=gs),
+            }
+            for name, run in entries.items():
+                q, qg, qm, qv = (t[:n4].cuda() for t in host)
+                run(q, qg, qm, qv)
+                torch.cuda.synchronize()
+                for a, b, what in zip((q, qm, qv), want, "pmv"):
+                    assert torch.equal(a, b), (name, what, step, gs, float((a - b).abs().max()))
+            assert int(step_dev.item()) == step
+
+
+def test_adam_flat_spans_descending_with_gaps():
+    """mfm_adam_flat_spans at its maximum of 8 spans, handed over in descending order, with gaps, a span shorter than a tile,
+    one of exactly a tile and mixed step counts: torch.optim.Adam inside, untouched outside; a raised guard writes nothing"""
+    _need_gpu()
+    spans, cur = [], 64
+    for k, (n, step) in enumerate(((4, 1), (1024, 2), (1200, 7), (2052, 1), (5000, 2), (36, 7), (3076, 1), (1028, 2))):
+        spans.append(dict(begin=cur, end=cur + n, step=step, lr=0.01, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, maximize=False,
+                          amsgrad=False, decoupled=False))
+        cur += n + 4 * (1 + 5 * k)                               # (a gap: elements nobody updates)
+    assert len(spans) == _lib.MFM_ADAM_MAX_SPANS
+    table = [(s["begin"], s["end"], s["step"]) for s in reversed(spans)]
+    host = _data(cur + 64, 5)
+    dev = [t.cuda() for t in host]
+    p, g, m, v, x = dev
+    guard = torch.empty(1, device="cuda")
+    for word in (float("nan"), 1.0):
+        guard.fill_(word)
+        _launch_plain_spans(p, g, m, v, table, guard=guard)
+        for t, t0 in zip(dev, host):
+            assert torch.equal(t.cpu(), t0)
+    _launch_plain_spans(p, g, m, v, table)
+    _check_spans(spans, host, (p, m, v, x))
+    p, g, m, v, x = (t.cuda() for t in host)
+    guard.zero_()
+    _launch_plain_spans(p, g, m, v, table, guard=guard)
+    _check_spans(spans, host, (p, m, v, x))
 
 
 def test_kernel_guard_and_launch_without_vmax():
