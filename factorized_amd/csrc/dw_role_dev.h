@@ -55,11 +55,6 @@ struct DwRole {
 constexpr int DWR_DEP_NONE = 0, DWR_DEP_LATENT = 5;     // 1..4: encoder e = dep - 1
 constexpr int DWR_FIRST = 1 << 24, DWR_LAST = 1 << 25, DWR_ACC1 = 1 << 26, DWR_STORE = 1 << 27;
 
-int seq_small_folddw_launch(SeqLaunch& L, const LatentDev& LD, DwRole& DR, const float* params, float* grads, hipStream_t stream);
-int seq_folddw_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, float* grads,
-                      DwRole& dr, hipStream_t stream, const float* const* wt_imgs = nullptr);
-bool seq_small_folddw_supported(int T, int B);
-
 __device__ __forceinline__ void dwr_stamp(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // wave-level wait for `n` stamps at f[0..n) (n <= 256)

@@ -319,37 +319,16 @@ __device__ __forceinline__ void seq_bwd_body(const SeqDev& d, const int T, const
   }
 }
 
-#define MFM_SEQ_CASES(BODY, KIND)                                                            \
-  switch (d.hk4) {                                                                           \
-    case 2: BODY<2, KIND>(d, L.T, L.B, tile, lds); break;                                                        \
-    case 4: BODY<4, KIND>(d, L.T, L.B, tile, lds); break;                                                        \
-    case 6: BODY<6, KIND>(d, L.T, L.B, tile, lds); break;                                                        \
-    case 8: BODY<8, KIND>(d, L.T, L.B, tile, lds); break;                                                        \
-    case 10: BODY<10, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 12: BODY<12, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 14: BODY<14, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 16: BODY<16, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 18: BODY<18, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 20: BODY<20, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 22: BODY<22, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 24: BODY<24, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 26: BODY<26, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 28: BODY<28, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 30: BODY<30, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    case 32: BODY<32, KIND>(d, L.T, L.B, tile, lds); break;                                                      \
-    default: break;                                                                          \
-  }
+#define MFM_SEQ_CASE(KK, BODY, KIND) case KK: BODY<KK, KIND>(d, L.T, L.B, tile, lds); break;
+#define MFM_SEQ_CASES(BODY, KIND) switch (d.hk4) { MFM_HK4_CASES(MFM_SEQ_CASE, BODY, KIND) default: break; }
 
 // One kernel per direction AND per kind (encoders / decoders): the encoder kernels then carry no weight-swap
 // code and keep all weights of the h = 120 instantiation in registers (0 spills; 165-750 before).
 template <bool BWD, int KIND>
 __global__ __launch_bounds__(512) void lstm_seq_kernel(const SeqLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int di = 0;
   const int bid = blockIdx.x;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
   if (BWD) { MFM_SEQ_CASES(seq_bwd_body, KIND) } else { MFM_SEQ_CASES(seq_fwd_body, KIND) }
@@ -377,35 +356,117 @@ bool bf16_seq_pays(int B) {
   return B >= (e ? atoi(e) : 128);
 }
 
-struct FoldArgs { const LatentDev* lat; const float* params; float* grads; ProjRole* pr; DwRole* dr; const float* const* wt_imgs;
-                  const WtImgItem* img_items; int n_img_items; bool* img_written; const float* const* wf_imgs; int dec_tail; };
+// What a recurrence launch carries besides the LSTMs themselves: the form by name, and the operands a form takes (null: not given)
+enum class SeqForm {
+  Plain,              // the recurrences alone
+  FwdImgWriters,      // forward, image-writer blocks behind the rows (img_items)
+  BwdImg,             // BPTT whose one-row workgroups read this step's transposed-weight images (wt_imgs)
+  FwdWf,              // forward whose one-row decoder workgroups read this step's forward images (wf_imgs)
+  Fold,               // encoders + their rows' latent chains (lat; forward: img_items, backward: wt_imgs)
+  FoldProj,           // forward Fold with projection role workgroups in front (pr)
+  FoldDw,             // backward Fold with weight-gradient role workgroups behind (dr, wt_imgs)
+  DecTail,            // decoders + the tail blocks of the latent forward chains (lat, wf_imgs)
+  DecBwdHead,         // decoder BPTTs + the head blocks of the latent backward chains (lat, wt_imgs)
+};
+struct SeqExtras {
+  SeqForm form = SeqForm::Plain;
+  const LatentDev* lat = nullptr; const float* params = nullptr; float* grads = nullptr;
+  ProjRole* pr = nullptr; DwRole* dr = nullptr;
+  const float* const* wt_imgs = nullptr;      // [count_in] transposed images (backward)
+  const float* const* wf_imgs = nullptr;      // [2 count_in] forward images of decoders: W_ih + W_hh, then W_ih alone
+  const WtImgItem* img_items = nullptr; int n_img_items = 0;      // images the writer blocks of a forward launch produce
+  bool* img_written = nullptr;                // out: whether they did
+};
+
+// Step 2 of seq_launch: the one place that says what a form needs, what happens when it does not get it, and which optional
+// operands reach the kernels.
+//   wide   some LSTM takes the step-by-step path        mfma   B is beyond the one-row / four-row VALU kernels (use_small_path)
+//   bf16   a bf16 entry point                           tuned  MFM_SEQ_KS / MFM_SEQ_ROWS is set
+//   moved  the launch's descriptors are not the call's, one to one: sorted widest first (count * B > CUs) or some split off
+//
+//   form            not taken when                      then               operands attached unless `moved`
+//   Plain           --                                                     --
+//   FwdImgWriters   wide | bf16 | mfma | tuned          Plain, no error    img_items (at most MFM_IMG_MAX)
+//   BwdImg          wide | bf16 | mfma | tuned          Plain, no error    wt_imgs
+//   FwdWf           wide | bf16 | mfma | tuned          Plain, no error    wf_imgs
+//   Fold            wide | bf16 | mfma                  MFM_ERR_UNSUPPORTED    forward: img_items; backward: wt_imgs
+//   FoldProj        wide | bf16 | mfma                  MFM_ERR_UNSUPPORTED    --
+//   FoldDw          wide | bf16 | mfma                  MFM_ERR_UNSUPPORTED    wt_imgs
+//   DecTail         wide | bf16 | mfma | tuned          MFM_ERR_UNSUPPORTED    wf_imgs
+//   DecBwdHead      wide | bf16 | mfma | tuned | moved  MFM_ERR_UNSUPPORTED    wt_imgs
+// (`tuned` is refused for the Fold forms by their launchers, lstm_seq_small.hip; wf_imgs reach decoders with h % 4 == 0 only.
+//  An image operand implies one-row tiles: not `moved` means count * B <= CUs, and one-row tiles run up to 6 CUs.)
+struct SeqRoute { SeqForm form; bool supported, attach; };
+static SeqRoute seq_route(SeqForm form, int count, int nwide, int B, bool bf16) {
+  const bool plain_only = nwide > 0 || bf16 || !use_small_path(B);
+  const bool moved = nwide > 0 || (long)count * B > (long)device_cus();
+  switch (form) {
+    case SeqForm::Plain: break;
+    case SeqForm::FwdImgWriters: case SeqForm::BwdImg: case SeqForm::FwdWf:
+      if (plain_only || seq_tuning_overrides()) break;
+      return {form, true, !moved};
+    case SeqForm::Fold: case SeqForm::FoldProj: case SeqForm::FoldDw:
+      return {form, !plain_only, !moved};
+    case SeqForm::DecTail:
+      return {form, !plain_only && !seq_tuning_overrides(), !moved};
+    case SeqForm::DecBwdHead:
+      return {form, !plain_only && !seq_tuning_overrides() && !moved, !moved};
+  }
+  return {SeqForm::Plain, true, false};
+}
+
+// Step 4 for the MFMA kernels: encoders and decoders run different kernels, a mixed call becomes two launches
+static int seq_mfma_launch(const SeqLaunch& L, bool bwd, hipStream_t stream) {
+  const int tiles = cdiv(L.B, 16);
+  int max_waves = 1;          // (block and LDS size: those of the widest LSTM of the call, for both launches)
+  size_t lds_bytes = 0;
+  for (int i = 0; i < L.count; ++i) {
+    max_waves = std::max(max_waves, L.d[i].Hp / 16);
+    const size_t HK = (size_t)L.d[i].hk4 * 4;
+    lds_bytes = std::max(lds_bytes, (bwd ? 2 * 4 * HK * 16 : 2 * HK * 16) * sizeof(float));
+  }
+  for (int kind = 0; kind < 2; ++kind) {
+    SeqLaunch K = L;
+    K.count = 0;
+    for (int i = 0; i < L.count; ++i) {
+      if ((L.d[i].is_dec != 0) != (kind == 1)) continue;
+      K.d[K.count] = L.d[i];
+      K.d[K.count].block_begin = tiles * K.count;
+      ++K.count;
+    }
+    if (K.count == 0) continue;
+    void (*const kern[2][2])(const SeqLaunch) = {{lstm_seq_kernel<false, 0>, lstm_seq_kernel<false, 1>}, {lstm_seq_kernel<true, 0>, lstm_seq_kernel<true, 1>}};
+    const int rc = seq_launch_kernel(kern[bwd][kind], bwd ? "lstm_seq_bwd_kernel" : "lstm_seq_fwd_kernel", dim3(tiles * K.count), dim3(64 * max_waves),
+                                     lds_bytes, stream, nullptr, K);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
 
 static int seq_launch(const MfmSeqDesc* descs_in, int count_in, int T, int B, bool bwd, hipStream_t stream, bool bf16 = false,
-                      const FoldArgs* fold = nullptr) {
+                      const SeqExtras& x = SeqExtras()) {
+  // 1. validation; LSTMs too wide for the weight-resident kernels take the step-by-step path (lstm_step.hip), the rest of the
+  //    group still shares one launch
   MFM_REQUIRE(descs_in && count_in >= 1 && count_in <= MFM_MAX_SEQ, "lstm_seq: count %d out of range", count_in);
   MFM_REQUIRE(T >= 1 && B >= 1, "lstm_seq: T=%d B=%d", T, B);
-  // LSTMs too wide for the weight-resident kernels take the step-by-step path (lstm_step.hip); the rest of
-  // the group still shares one launch
   MfmSeqDesc descs[MFM_MAX_SEQ], wide[MFM_MAX_SEQ];
   int count = 0, nwide = 0;
+  const bool force = opt_get("MFM_SEQ_STEPWISE") != nullptr;          // testing: every LSTM step by step
   for (int i = 0; i < count_in; ++i) {
     const MfmSeqDesc& s = descs_in[i];
     MFM_REQUIRE(s.h >= 1, "lstm_seq[%d]: h=%d", i, s.h);
     MFM_REQUIRE(s.gates && s.hs && s.cs && s.w_hh, "lstm_seq[%d]: null buffer", i);
     if (s.is_dec) MFM_REQUIRE(s.w_ih && s.b_ih && s.b_hh && s.h_init, "lstm_seq[%d]: decoder needs w_ih/b/h_init", i);
     if (bwd) MFM_REQUIRE(s.dh_ext, "lstm_seq_bwd[%d]: dh_ext is null", i);
-    const bool force = opt_get("MFM_SEQ_STEPWISE") != nullptr;          // testing: every LSTM step by step
     if (s.h > MFM_SEQ_MAX_RESIDENT_H || force) {
       MFM_REQUIRE(!s.store_bf16 && !s.h_last, "lstm_seq[%d]: h = %d takes the step-by-step fp32 path, which has no bf16-resident form", i, s.h);
       wide[nwide++] = s;
     } else descs[count++] = s;
   }
-  if (fold && fold->dec_tail) {
-    if (nwide || bf16 || !use_small_path(B) || opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS")) return MFM_ERR_UNSUPPORTED;
-  } else if (fold && !fold->lat && !fold->pr && !fold->dr) {      // (images only: a plain launch)
-    if (fold->img_written) *fold->img_written = false;
-    if (nwide || bf16 || !use_small_path(B) || opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS")) fold = nullptr;
-  } else if (fold && (nwide || bf16 || !use_small_path(B))) return MFM_ERR_UNSUPPORTED;
+  // 2. the form
+  if (x.img_written) *x.img_written = false;
+  const SeqRoute route = seq_route(x.form, count, nwide, B, bf16);
+  if (!route.supported) return MFM_ERR_UNSUPPORTED;
   if (nwide) {
     int rc = seq_stepwise(wide, nwide, T, B, bwd, stream);
     if (rc != MFM_OK) return rc;
@@ -415,17 +476,13 @@ static int seq_launch(const MfmSeqDesc* descs_in, int count_in, int T, int B, bo
   // round of workgroups (B >= 128 with four LSTMs) the widest LSTM must not start in the last round
   // (B=2048: encoder recurrences 154 -> 132 us forward, 163 -> 151 us backward).  While everything is
   // resident at once the caller's order is kept: widest-first measured 0.8 % slower per step at B=32.
-  bool sorted = false;
-  if ((long)count * B > (long)device_cus()) {
+  if ((long)count * B > (long)device_cus())
     std::stable_sort(descs, descs + count, [](const MfmSeqDesc& a, const MfmSeqDesc& b) { return a.h > b.h; });
-    sorted = true;
-  }
+  // 3. the launch descriptor (block layout: the launchers')
   SeqLaunch L;
   memset(&L, 0, sizeof(L));
   L.count = count; L.T = T; L.B = B;
-  const int tiles = cdiv(B, 16);
-  int total = 0, max_waves = 1;
-  size_t lds_bytes = 0;
+  L.bf16_dot = 1;
   for (int i = 0; i < count; ++i) {
     const MfmSeqDesc& s = descs[i];
     SeqDev& d = L.d[i];
@@ -438,127 +495,85 @@ static int seq_launch(const MfmSeqDesc* descs_in, int count_in, int T, int B, bo
     d.w_pack = bf16 ? s.w_pack : nullptr;
     d.h_last = bf16 ? s.h_last : nullptr;
     d.store_bf16 = s.store_bf16;
-    d.wt_img = (fold && fold->wt_imgs && bwd && !sorted && !nwide && count == count_in) ? fold->wt_imgs[i] : nullptr;
-    if (fold && fold->dec_tail == 2 && (sorted || count != count_in)) return MFM_ERR_UNSUPPORTED;
-    d.wf_img = (fold && fold->wf_imgs && !bwd && !sorted && !nwide && count == count_in && s.is_dec && (s.h & 3) == 0) ? fold->wf_imgs[i] : nullptr;
-    d.wf1_img = d.wf_img ? fold->wf_imgs[count_in + i] : nullptr;        // (second half of the list: W_ih alone)
     MFM_REQUIRE(bf16 || (!s.store_bf16 && !s.h_last), "lstm_seq[%d]: store_bf16 / h_last are taken by the bf16 entry points only", i);
     d.h = s.h; d.Hp = round_up(s.h, 16);
     d.hk4 = round_up(cdiv(s.h, 4), 2);
     d.is_dec = s.is_dec;
-    d.block_begin = total;
-    total += tiles;
-    if (d.Hp / 16 > max_waves) max_waves = d.Hp / 16;
-    const size_t HK = (size_t)d.hk4 * 4;
-    const size_t need = (bwd ? 2 * 4 * HK * 16 : 2 * HK * 16) * sizeof(float);
-    if (need > lds_bytes) lds_bytes = need;
+    if (route.attach && bwd && x.wt_imgs) d.wt_img = x.wt_imgs[i];
+    if (route.attach && !bwd && x.wf_imgs && s.is_dec && (s.h & 3) == 0) { d.wf_img = x.wf_imgs[i]; d.wf1_img = x.wf_imgs[count_in + i]; }
+    L.bf16_dot &= (s.bf16_dot != 0);
   }
-  L.bf16_dot = 1;
-  for (int i = 0; i < count; ++i) L.bf16_dot &= (descs[i].bf16_dot != 0);
-  if (fold && fold->img_written) *fold->img_written = false;
-  if (fold && fold->img_items && !bwd && !bf16 && !sorted && !nwide && fold->n_img_items <= MFM_IMG_MAX && use_small_path(B)) {
-    L.n_img = fold->n_img_items;
-    for (int i = 0; i < L.n_img; ++i) L.img[i] = fold->img_items[i];
+  if (route.attach && !bwd && x.img_items && x.n_img_items <= MFM_IMG_MAX) {
+    L.n_img = x.n_img_items;
+    for (int i = 0; i < L.n_img; ++i) L.img[i] = x.img_items[i];
   }
-  if (fold && fold->dec_tail == 2) return seq_small_decbwd_head_launch(L, *fold->lat, fold->params, fold->grads, stream);
-  if (fold && fold->dec_tail) return seq_small_dectail_launch(L, *fold->lat, fold->params, stream);
-  if (fold && !fold->lat && fold->img_items) {      // forward launch with image-writer blocks behind the rows
-    const int rc = seq_small_launch(L, false, stream);
-    if (rc == MFM_OK && fold->img_written) *fold->img_written = L.n_img > 0;
-    return rc;
+  // 4. the launchers
+  int rc = MFM_OK;
+  switch (route.form) {
+    case SeqForm::DecBwdHead: return seq_small_decbwd_head_launch(L, *x.lat, x.params, x.grads, stream);
+    case SeqForm::DecTail: return seq_small_dectail_launch(L, *x.lat, x.params, stream);
+    case SeqForm::FoldProj: return seq_small_foldproj_launch(L, *x.lat, *x.pr, x.params, stream);
+    case SeqForm::FoldDw: return seq_small_folddw_launch(L, *x.lat, *x.dr, x.params, x.grads, stream);
+    case SeqForm::Fold: rc = seq_small_fold_launch(L, bwd, *x.lat, x.params, x.grads, stream); break;
+    case SeqForm::FwdImgWriters: case SeqForm::BwdImg: case SeqForm::FwdWf: rc = seq_small_launch(L, bwd, stream); break;
+    case SeqForm::Plain:
+      if (bf16) return seq_bf16_launch(L, bwd, stream);      // bf16 MFMA operands: one kernel family for every batch size
+      return use_small_path(B) ? seq_small_launch(L, bwd, stream) : seq_mfma_launch(L, bwd, stream);
   }
-  if (fold && !fold->lat) {          // images only: the plain one-row launch (one-row tiles: checked by the caller's conditions)
-    if ((long)L.count * L.B >= 6L * device_cus()) for (int i = 0; i < L.count; ++i) { L.d[i].wt_img = nullptr; L.d[i].wf_img = nullptr; L.d[i].wf1_img = nullptr; }
-    return seq_small_launch(L, bwd, stream);
-  }
-  if (fold && fold->pr) return seq_small_foldproj_launch(L, *fold->lat, *fold->pr, fold->params, stream);
-  if (fold && fold->dr) return seq_small_folddw_launch(L, *fold->lat, *fold->dr, fold->params, fold->grads, stream);
-  if (fold) {
-    const int rc = seq_small_fold_launch(L, bwd, *fold->lat, fold->params, fold->grads, stream);
-    if (rc == MFM_OK && fold->img_written) *fold->img_written = !bwd && L.n_img > 0;
-    return rc;
-  }
-  if (bf16) return seq_bf16_launch(L, bwd, stream);      // bf16 MFMA operands: one kernel family for every batch size
-  if (use_small_path(B)) return seq_small_launch(L, bwd, stream);
-  // encoders and decoders run different kernels: a mixed call becomes two launches
-  for (int kind = 0; kind < 2; ++kind) {
-    SeqLaunch K = L;
-    K.count = 0;
-    int ktotal = 0;
-    for (int i = 0; i < L.count; ++i) {
-      if ((L.d[i].is_dec != 0) != (kind == 1)) continue;
-      K.d[K.count] = L.d[i];
-      K.d[K.count].block_begin = ktotal;
-      ktotal += tiles;
-      ++K.count;
-    }
-    if (K.count == 0) continue;
-    const dim3 grid(ktotal), block(64 * max_waves);
-    if (bwd) {
-      if (kind) MFM_LAUNCH_TIMED((lstm_seq_kernel<true, 1>), grid, block, lds_bytes, stream, K);
-      else MFM_LAUNCH_TIMED((lstm_seq_kernel<true, 0>), grid, block, lds_bytes, stream, K);
-    } else {
-      if (kind) MFM_LAUNCH_TIMED((lstm_seq_kernel<false, 1>), grid, block, lds_bytes, stream, K);
-      else MFM_LAUNCH_TIMED((lstm_seq_kernel<false, 0>), grid, block, lds_bytes, stream, K);
-    }
-    MFM_LAUNCH_CHECK(bwd ? "lstm_seq_bwd_kernel" : "lstm_seq_fwd_kernel");
-  }
-  return MFM_OK;
+  if (rc == MFM_OK && x.img_written) *x.img_written = L.n_img > 0;      // (the launchers clear n_img when no writer block ran)
+  return rc;
 }
 
-// encoder recurrences + their rows' latent chains in one launch (lstm_seq_small.hip); MFM_ERR_UNSUPPORTED: not applicable
+// The entry points of the plan (lstm_seq_dev.h): one form each
 int seq_fold_launch(const MfmSeqDesc* descs, int count, int T, int B, bool bwd, const LatentDev& lat, const float* params,
                     float* grads, hipStream_t stream, const float* const* wt_imgs, const WtImgItem* img_items, int n_img_items,
                     bool* img_written) {
-  FoldArgs f = {&lat, params, grads, nullptr, nullptr, wt_imgs, img_items, n_img_items, img_written, nullptr, 0};
-  return seq_launch(descs, count, T, B, bwd, stream, false, &f);
+  SeqExtras x;
+  x.form = SeqForm::Fold; x.lat = &lat; x.params = params; x.grads = grads;
+  x.wt_imgs = wt_imgs; x.img_items = img_items; x.n_img_items = n_img_items; x.img_written = img_written;
+  return seq_launch(descs, count, T, B, bwd, stream, false, x);
 }
-// the forward fold launch with projection role workgroups in front (proj_role_dev.h)
 int seq_foldproj_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, ProjRole& pr,
                         hipStream_t stream) {
-  FoldArgs f = {&lat, params, nullptr, &pr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
-  return seq_launch(descs, count, T, B, false, stream, false, &f);
+  SeqExtras x;
+  x.form = SeqForm::FoldProj; x.lat = &lat; x.params = params; x.pr = &pr;
+  return seq_launch(descs, count, T, B, false, stream, false, x);
 }
-
-}  // namespace mfm
-
-namespace mfm {
-// forward launch with a few blocks behind the recurrence rows that write this step's transposed-weight images (lstm_seq_dev.h);
-// *written: whether they did (one-row tiles and idle CUs left)
-int seq_fwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const WtImgItem* items, int n_items, bool* written,
-                       hipStream_t stream) {
-  FoldArgs f = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, items, n_items, written, nullptr, 0};
-  return seq_launch(descs, count, T, B, false, stream, false, &f);
-}
-// decoder recurrences + the tail blocks of the latent forward chains (lstm_seq_small_dectail_kernel)
-int seq_dec_tail_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, const LatentDev& lat,
-                        const float* params, hipStream_t stream) {
-  FoldArgs f = {&lat, params, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, wf_imgs, 1};
-  return seq_launch(descs, count, T, B, false, stream, false, &f);
-}
-// decoder BPTTs + the head blocks of the latent backward chains (lstm_seq_small_decbwd_head_kernel)
-int seq_dec_bwd_head_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, const LatentDev& lat,
-                            const float* params, float* grads, hipStream_t stream) {
-  FoldArgs f = {&lat, params, grads, nullptr, nullptr, wt_imgs, nullptr, 0, nullptr, nullptr, 2};
-  return seq_launch(descs, count, T, B, true, stream, false, &f);
-}
-// plain BPTT launch whose one-row workgroups take their transposed weights from this step's images (proj_role_dev.h)
-int seq_bwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, hipStream_t stream) {
-  FoldArgs f = {nullptr, nullptr, nullptr, nullptr, nullptr, wt_imgs, nullptr, 0, nullptr, nullptr, 0};
-  return seq_launch(descs, count, T, B, true, stream, false, &f);
-}
-// plain forward launch whose one-row decoder workgroups take W_ih + W_hh (steps >= 1) and W_ih (step 0) from this step's
-// forward images: wf_imgs[0 .. count) the sums, wf_imgs[count .. 2 count) W_ih
-int seq_fwd_wf_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, hipStream_t stream) {
-  FoldArgs f = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, wf_imgs, 0};
-  return seq_launch(descs, count, T, B, false, stream, false, &f);
-}
-// the backward fold launch with weight-gradient role workgroups behind the BPTT workgroups (dw_role_dev.h)
 int seq_folddw_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, float* grads,
                       DwRole& dr, hipStream_t stream, const float* const* wt_imgs) {
-  FoldArgs f = {&lat, params, grads, nullptr, &dr, wt_imgs, nullptr, 0, nullptr, nullptr, 0};
-  return seq_launch(descs, count, T, B, true, stream, false, &f);
+  SeqExtras x;
+  x.form = SeqForm::FoldDw; x.lat = &lat; x.params = params; x.grads = grads; x.dr = &dr; x.wt_imgs = wt_imgs;
+  return seq_launch(descs, count, T, B, true, stream, false, x);
 }
+int seq_fwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const WtImgItem* items, int n_items, bool* written,
+                       hipStream_t stream) {
+  SeqExtras x;
+  x.form = SeqForm::FwdImgWriters; x.img_items = items; x.n_img_items = n_items; x.img_written = written;
+  return seq_launch(descs, count, T, B, false, stream, false, x);
+}
+int seq_bwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, hipStream_t stream) {
+  SeqExtras x;
+  x.form = SeqForm::BwdImg; x.wt_imgs = wt_imgs;
+  return seq_launch(descs, count, T, B, true, stream, false, x);
+}
+int seq_fwd_wf_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, hipStream_t stream) {
+  SeqExtras x;
+  x.form = SeqForm::FwdWf; x.wf_imgs = wf_imgs;
+  return seq_launch(descs, count, T, B, false, stream, false, x);
+}
+int seq_dec_tail_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, const LatentDev& lat,
+                        const float* params, hipStream_t stream) {
+  SeqExtras x;
+  x.form = SeqForm::DecTail; x.lat = &lat; x.params = params; x.wf_imgs = wf_imgs;
+  return seq_launch(descs, count, T, B, false, stream, false, x);
+}
+int seq_dec_bwd_head_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, const LatentDev& lat,
+                            const float* params, float* grads, hipStream_t stream) {
+  SeqExtras x;
+  x.form = SeqForm::DecBwdHead; x.lat = &lat; x.params = params; x.grads = grads; x.wt_imgs = wt_imgs;
+  return seq_launch(descs, count, T, B, true, stream, false, x);
+}
+
 }  // namespace mfm
 
 extern "C" int mfm_lstm_seq_fwd(const MfmSeqDesc* descs, int count, int T, int B, void* stream) {

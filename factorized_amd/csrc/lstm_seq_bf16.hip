@@ -650,11 +650,8 @@ __device__ __forceinline__ void seqb_bwd_body(const SeqDev& d, const int T, cons
 template <bool BWD, int KIND, bool ST>
 __global__ __launch_bounds__(512) void lstm_seq_bf16_kernel(const SeqLaunch L) {
   extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
-  int di = 0;
   const int bid = blockIdx.x;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
   const int kb = (d.h + 31) >> 5;
@@ -750,25 +747,15 @@ int seq_bf16_launch(SeqLaunch& L, bool bwd, hipStream_t stream) {
     const bool st = K.d[0].store_bf16 != 0;
     for (int i = 1; i < K.count; ++i)
       MFM_REQUIRE((K.d[i].store_bf16 != 0) == st, "lstm_seq (bf16): the LSTMs of one launch must agree on store_bf16");
-#define MFM_SEQB_GO(BWD_, KIND_)                                                                                          \
-  do {                                                                                                                    \
-    static bool big_lds = false;                 /* (once per instantiation and process: not a stream operation) */       \
-    if (lds_bytes > 64 * 1024 && !big_lds) {                                                                              \
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_bf16_kernel<BWD_, KIND_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));  \
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_bf16_kernel<BWD_, KIND_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-      big_lds = true;                                                                                                     \
-    }                                                                                                                     \
-    MFM_REQUIRE(lds_bytes <= 160 * 1024, "lstm_seq (bf16): %zu bytes of LDS", lds_bytes);                                 \
-    if (st) MFM_LAUNCH_TIMED((lstm_seq_bf16_kernel<BWD_, KIND_, true>), grid, block, lds_bytes, stream, K);             \
-    else MFM_LAUNCH_TIMED((lstm_seq_bf16_kernel<BWD_, KIND_, false>), grid, block, lds_bytes, stream, K);               \
-  } while (0)
-    if (bwd) {
-      if (kind) MFM_SEQB_GO(true, 1); else MFM_SEQB_GO(true, 0);
-    } else {
-      if (kind) MFM_SEQB_GO(false, 1); else MFM_SEQB_GO(false, 0);
-    }
-#undef MFM_SEQB_GO
-    MFM_LAUNCH_CHECK(bwd ? "lstm_seq_bf16_bwd_kernel" : "lstm_seq_bf16_fwd_kernel");
+    MFM_REQUIRE(lds_bytes <= 160 * 1024, "lstm_seq (bf16): %zu bytes of LDS", lds_bytes);
+    // [bwd][kind][st]; the LDS attribute of a kernel is raised once per process: not a stream operation
+    void (*const kern[2][2][2])(const SeqLaunch) = {
+        {{lstm_seq_bf16_kernel<false, 0, false>, lstm_seq_bf16_kernel<false, 0, true>}, {lstm_seq_bf16_kernel<false, 1, false>, lstm_seq_bf16_kernel<false, 1, true>}},
+        {{lstm_seq_bf16_kernel<true, 0, false>, lstm_seq_bf16_kernel<true, 0, true>}, {lstm_seq_bf16_kernel<true, 1, false>, lstm_seq_bf16_kernel<true, 1, true>}}};
+    static bool big_lds[2][2][2];
+    const int rc = seq_launch_kernel(kern[bwd][kind][st], bwd ? "lstm_seq_bf16_bwd_kernel" : "lstm_seq_bf16_fwd_kernel", grid, block, lds_bytes, stream,
+                                     &big_lds[bwd][kind][st], K);
+    if (rc != MFM_OK) return rc;
   }
   return MFM_OK;
 }

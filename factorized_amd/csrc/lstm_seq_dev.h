@@ -106,16 +106,92 @@ __device__ __forceinline__ void wf_img_write(const WtImgItem* items, const int n
   }
 }
 
-int seq_small_launch(SeqLaunch& L, bool bwd, hipStream_t stream);
+// ---------------------------------------------------------------- kernel wrappers: what every sequence kernel opens with
+// declares `di`: the LSTM that block `bid` of the multi-LSTM launch L belongs to (its tile: bid - L.d[di].block_begin).  A macro:
+// as an inlined function the same loop comes out with other scalar registers, and these kernels are kept instruction for instruction
+#define MFM_SEQ_BLOCK_LSTM(L, bid, di)    \
+  int di = 0;                             \
+  _Pragma("unroll 1")                     \
+  for (int i = 1; i < (L).count; ++i)     \
+    if ((bid) >= (L).d[i].block_begin) di = i;
+// every SeqDev::hk4 the weight-resident kernels are instantiated for: X(hk4, ...) once per value
+#define MFM_HK4_CASES(X, ...)                                                                                         \
+  X(2, __VA_ARGS__) X(4, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__) X(10, __VA_ARGS__) X(12, __VA_ARGS__)      \
+  X(14, __VA_ARGS__) X(16, __VA_ARGS__) X(18, __VA_ARGS__) X(20, __VA_ARGS__) X(22, __VA_ARGS__) X(24, __VA_ARGS__)  \
+  X(26, __VA_ARGS__) X(28, __VA_ARGS__) X(30, __VA_ARGS__) X(32, __VA_ARGS__)
+// kernels instantiated for a size tuple <K0, K1, ...> (0: no such LSTM): the statement(s) given run for the LSTM `di` of this
+// block, with KQ its hk4 as a constant
+#define MFM_TUPLE_ONE(IDX, KK, ...) \
+  if (KK > 0 && di == IDX) { constexpr int KQ = KK > 0 ? KK : 2; __VA_ARGS__; }
+#define MFM_TUPLE3(...) MFM_TUPLE_ONE(0, K0, __VA_ARGS__) MFM_TUPLE_ONE(1, K1, __VA_ARGS__) MFM_TUPLE_ONE(2, K2, __VA_ARGS__)
+#define MFM_TUPLE4(...) MFM_TUPLE3(__VA_ARGS__) MFM_TUPLE_ONE(3, K3, __VA_ARGS__)
+#define MFM_TUPLE6(...) MFM_TUPLE4(__VA_ARGS__) MFM_TUPLE_ONE(4, K4, __VA_ARGS__) MFM_TUPLE_ONE(5, K5, __VA_ARGS__)
+
+// ---------------------------------------------------------------- host: launching
+// MFM_SEQ_KS / MFM_SEQ_ROWS are set: tuning overrides keep the plain launches
+static inline bool seq_tuning_overrides() { return opt_get("MFM_SEQ_KS") != nullptr || opt_get("MFM_SEQ_ROWS") != nullptr; }
+
+// One launch with `lds_bytes` of dynamic LDS: beyond the 64 KB a kernel may use unasked, its attribute is raised first -- to
+// lds_bytes on every such launch, or with `once` (one flag per kernel) to all 160 KB the first time only: the attribute call
+// is not a stream operation.  `name` is what an error is reported under; timed regions as MFM_LAUNCH_TIMED.
+template <typename... KArgs, typename... Args>
+static int seq_launch_kernel(void (*kernel)(KArgs...), const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream,
+                             bool* once, const Args&... args) {
+  if (lds_bytes > 64 * 1024 && !(once && *once)) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, once ? 160 * 1024 : (int)lds_bytes);
+    if (e != hipSuccess) { char what[96]; snprintf(what, sizeof(what), "hipFuncSetAttribute(%s)", name); return hip_fail(e, what); }
+    if (once) *once = true;
+  }
+  MFM_LAUNCH_TIMED(kernel, grid, block, lds_bytes, stream, args...);
+  MFM_LAUNCH_CHECK(name);
+  return MFM_OK;
+}
+
+// ---------------------------------------------------------------- host: the sequence launchers and what the plan asks them ahead of time
 struct LatentDev;
+struct ProjRole;
+struct DwRole;
+constexpr int MFM_SEQ_MAX_RESIDENT_H = 128;      // wider LSTMs take the step-by-step path
+// lstm_seq.hip -- the entry points of the plan: descriptors in, one launch form each (SeqForm); MFM_ERR_UNSUPPORTED: not a case
+// the form takes, nothing was launched
+// encoder recurrences + their rows' latent chains (forward: optional image-writer blocks; backward: optional transposed images)
+int seq_fold_launch(const MfmSeqDesc* descs, int count, int T, int B, bool bwd, const LatentDev& lat, const float* params,
+                    float* grads, hipStream_t stream, const float* const* wt_imgs = nullptr, const WtImgItem* img_items = nullptr,
+                    int n_img_items = 0, bool* img_written = nullptr);
+// the forward fold launch with projection role workgroups in front (proj_role_dev.h)
+int seq_foldproj_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, ProjRole& pr,
+                        hipStream_t stream);
+// the backward fold launch with weight-gradient role workgroups behind the BPTT workgroups (dw_role_dev.h)
+int seq_folddw_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, float* grads,
+                      DwRole& dr, hipStream_t stream, const float* const* wt_imgs = nullptr);
+// plain forward launch with a few blocks behind the rows that write this step's weight images; *written: whether they did
+int seq_fwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const WtImgItem* items, int n_items, bool* written,
+                       hipStream_t stream);
+// plain BPTT launch whose one-row workgroups take their transposed weights from this step's images
+int seq_bwd_img_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, hipStream_t stream);
+// plain forward launch whose one-row decoder workgroups take their weights from this step's forward images: wf_imgs[0 .. count)
+// W_ih + W_hh, wf_imgs[count .. 2 count) W_ih
+int seq_fwd_wf_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, hipStream_t stream);
+// decoder recurrences + the tail blocks of the latent forward chains
+int seq_dec_tail_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wf_imgs, const LatentDev& lat,
+                        const float* params, hipStream_t stream);
+// decoder BPTTs + the head blocks of the latent backward chains
+int seq_dec_bwd_head_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, const LatentDev& lat,
+                            const float* params, float* grads, hipStream_t stream);
+bool bf16_seq_pays(int B);     // batch size from which a bf16 plan runs its recurrences on the bf16 kernels
+// lstm_seq_small.hip -- fp32 VALU kernels, 1 / 4 rows per workgroup; L as filled by seq_launch, block layout by the launcher
+int seq_small_launch(SeqLaunch& L, bool bwd, hipStream_t stream);      // the plain launch (+ image-writer blocks when L.n_img)
+int seq_small_fold_launch(SeqLaunch& L, bool bwd, const LatentDev& LD, const float* params, float* grads, hipStream_t stream);
+bool seq_small_foldproj_supported(int T, int B, const int* h, const int* k, int n_enc);     // shapes the projection roles take, idle CUs
+int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, const float* params, hipStream_t stream);
+bool seq_small_folddw_supported(int T, int B);      // room for the weight-gradient role workgroups behind 4 B rows
+int seq_small_folddw_launch(SeqLaunch& L, const LatentDev& LD, DwRole& DR, const float* params, float* grads, hipStream_t stream);
+bool seq_small_dectail_supported(int T, int B, const int* dec_h, const LatentDev& LD);      // can the decoder launch carry tail / head blocks?
 int seq_small_dectail_launch(SeqLaunch& L, const LatentDev& LD, const float* params, hipStream_t stream);
 int seq_small_decbwd_head_launch(SeqLaunch& L, const LatentDev& LD, const float* params, float* grads, hipStream_t stream);
-int seq_small_fold_launch(SeqLaunch& L, bool bwd, const LatentDev& LD, const float* params, float* grads, hipStream_t stream);
 // lstm_seq_bf16.hip: bf16 MFMA operands, fp32 accumulate / cell state / saved activations
 int seq_bf16_launch(SeqLaunch& L, bool bwd, hipStream_t stream);
-bool bf16_seq_pays(int B);     // lstm_seq.hip: batch size from which a bf16 plan runs its recurrences on the bf16 kernels
 // lstm_step.hip: step-by-step path (recurrent GEMM + cell kernel per time step) for h > MFM_SEQ_MAX_RESIDENT_H
 int seq_stepwise(const MfmSeqDesc* descs, int count, int T, int B, bool bwd, hipStream_t stream);
-constexpr int MFM_SEQ_MAX_RESIDENT_H = 128;
 
 }  // namespace mfm

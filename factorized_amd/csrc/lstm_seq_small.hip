@@ -5,35 +5,14 @@
 
 namespace mfm {
 
-#define MFM_SMALL_CASES(BODY)                                                                \
-  switch (d.hk4) {                                                                           \
-    case 2: BODY<2, 4>(d, L.T, L.B, tile, lds); break;                                          \
-    case 4: BODY<4, 4>(d, L.T, L.B, tile, lds); break;                                          \
-    case 6: BODY<6, 4>(d, L.T, L.B, tile, lds); break;                                          \
-    case 8: BODY<8, 4>(d, L.T, L.B, tile, lds); break;                                          \
-    case 10: BODY<10, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 12: BODY<12, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 14: BODY<14, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 16: BODY<16, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 18: BODY<18, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 20: BODY<20, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 22: BODY<22, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 24: BODY<24, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 26: BODY<26, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 28: BODY<28, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 30: BODY<30, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    case 32: BODY<32, 4>(d, L.T, L.B, tile, lds); break;                                        \
-    default: break;                                                                          \
-  }
+#define MFM_SMALL_CASE(KK, BODY) case KK: BODY<KK, 4>(d, L.T, L.B, tile, lds); break;
+#define MFM_SMALL_CASES(BODY) switch (d.hk4) { MFM_HK4_CASES(MFM_SMALL_CASE, BODY) default: break; }
 
 template <bool BWD>
 __global__ __launch_bounds__(1024) void lstm_seq_small_kernel(const SeqLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int di = 0;
   const int bid = blockIdx.x;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
   if (BWD) {
@@ -52,54 +31,62 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_kernel(const SeqLaunch L)
 template <bool BWD, int R, int KS, int K0, int K1, int K2, int K3, int K4 = 0, int K5 = 0, bool BF = false>
 __global__ __launch_bounds__(KS == 16 ? 1024 : 512) void lstm_seq_small_kernel4(const SeqLaunch L) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int di = 0;
   const int bid = blockIdx.x;
   LSTAMP(BWD ? 3 : 1, 0);
   if constexpr (!BWD) {      // blocks behind the recurrence rows: this step's transposed-weight images (lstm_seq_dev.h)
     if (L.n_img > 0 && bid >= L.img_begin) { wt_img_write(L.img, L.n_img, bid - L.img_begin, L.n_img_blocks); LSTAMP(1, 15); return; }
   }
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
-#define MFM_ONE(IDX, KK)                                                         \
-  if (KK > 0 && di == IDX) {                                                     \
-    if (BWD) small_bwd_body<(KK > 0 ? KK : 2), R, KS>(d, L.T, L.B, tile, lds);   \
-    else small_fwd_body<(KK > 0 ? KK : 2), R, false, BF>(d, L.T, L.B, tile, lds);           \
-    LSTAMP(BWD ? 3 : 1, 15);                                                     \
-    return;                                                                      \
-  }
-  MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2) MFM_ONE(3, K3) MFM_ONE(4, K4) MFM_ONE(5, K5)
-#undef MFM_ONE
+  MFM_TUPLE6(if (BWD) small_bwd_body<KQ, R, KS>(d, L.T, L.B, tile, lds); else small_fwd_body<KQ, R, false, BF>(d, L.T, L.B, tile, lds);
+             LSTAMP(BWD ? 3 : 1, 15); return)
+}
+
+// ---------------------------------------------------------------- host helpers the launchers share
+static const int kEncHk4[4] = {8, 2, 20, 30};      // the canonical MFM_KL_EF encoders (h = 32 / 8 / 80 / 120) ...
+static const int kDecHk4[3] = {26, 6, 6};          // ... and decoders (h = 104 / 24 / 24)
+
+// L holds exactly the LSTMs of these hk4, in this order; kind 0: all encoders, 1: all decoders, -1: either
+static bool seq_is_tuple(const SeqLaunch& L, const int* hk4, int n, int kind) {
+  if (L.count != n) return false;
+  for (int i = 0; i < n; ++i)
+    if (L.d[i].hk4 != hk4[i] || (kind >= 0 && (L.d[i].is_dec != 0) != (kind == 1))) return false;
+  return true;
+}
+// the latent stack runs as four chain workgroups per row of the same batch: what a launch that carries chains needs
+static bool chain_rows_match(const LatentDev& LD, int B) { return LD.row_path && LD.nch == 4 && !LD.pre && LD.B == B; }
+// LDS of a chain workgroup: the stage tables + the row's record (backward: + its gradient record)
+static size_t chain_lds_bytes(const LatentDev& LD, bool bwd) {
+  return (size_t)(bwd ? latent_bwd_grd_floats(LD.rec_size) + LD.rec_size : latent_fwd_lds_floats(LD.rec_size)) * sizeof(float);
+}
+// `rows` blocks per LSTM from block `first` on; returns the first block behind them
+static int lay_out_blocks(SeqLaunch& L, int rows, int first = 0) {
+  int total = first;
+  for (int i = 0; i < L.count; ++i) { L.d[i].block_begin = total; total += rows; }
+  return total;
+}
+// forward, one-row tiles: blocks behind the `total` recurrence rows write this step's weight images (L.img) -- the idle CUs, at
+// most 64; no idle CU left: the writers still pay (they run in the launch's last round, ~2 us, against ~9 us of staging saved)
+static int add_img_writers(SeqLaunch& L, int total) {
+  const int idle = device_cus() - total;
+  L.img_begin = total; L.n_img_blocks = idle >= 8 ? std::min(idle, 64) : 32;
+  return total + L.n_img_blocks;
 }
 
 template <int R, int KS, int K0, int K1, int K2, int K3, int K4 = 0, int K5 = 0>
-static bool try_launch4(const SeqLaunch& L, bool bwd, int total, int threads, size_t lds_bytes, hipStream_t stream,
-                        hipError_t* err) {
+static bool try_launch4(const SeqLaunch& L, bool bwd, int total, int threads, size_t lds_bytes, hipStream_t stream, int* rc) {
   const int want[6] = {K0, K1, K2, K3, K4, K5};
   int n = 0;
   for (int i = 0; i < 6; ++i) if (want[i] > 0) n = i + 1;
-  if (L.count != n) return false;
-  for (int i = 0; i < n; ++i) if (L.d[i].hk4 != want[i]) return false;
-  *err = hipSuccess;
-  if (lds_bytes > 64 * 1024) {
-    *err = bwd ? hipFuncSetAttribute((const void*)lstm_seq_small_kernel4<true, R, KS, K0, K1, K2, K3, K4, K5>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)
-               : hipFuncSetAttribute((const void*)lstm_seq_small_kernel4<false, R, KS, K0, K1, K2, K3, K4, K5>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (*err != hipSuccess) return true;
-  }
-  if (bwd)
-    MFM_LAUNCH_TIMED((lstm_seq_small_kernel4<true, R, KS, K0, K1, K2, K3, K4, K5>), dim3(total), dim3(threads), lds_bytes, stream, L);
-  else
-    MFM_LAUNCH_TIMED((lstm_seq_small_kernel4<false, R, KS, K0, K1, K2, K3, K4, K5>), dim3(total), dim3(threads), lds_bytes, stream, L);
+  if (!seq_is_tuple(L, want, n, -1)) return false;
+  *rc = seq_launch_kernel(bwd ? lstm_seq_small_kernel4<true, R, KS, K0, K1, K2, K3, K4, K5> : lstm_seq_small_kernel4<false, R, KS, K0, K1, K2, K3, K4, K5>,
+                          bwd ? "lstm_seq_small_bwd_kernel4" : "lstm_seq_small_fwd_kernel4", dim3(total), dim3(threads), lds_bytes, stream, nullptr, L);
   return true;
 }
 
 template <int R>
-static bool try_all(const SeqLaunch& L, bool bwd, int total, int threads, size_t lds_bytes, hipStream_t stream,
-                    hipError_t* err) {
+static bool try_all(const SeqLaunch& L, bool bwd, int total, int threads, size_t lds_bytes, hipStream_t stream, int* err) {
   // (from 2 rounds of workgroups on, the launcher orders the LSTMs of a call widest first: lstm_seq.hip)
   return try_launch4<R, 16, 8, 2, 20, 30>(L, bwd, total, threads, lds_bytes, stream, err) ||     // MFM_KL_EF encoders
          try_launch4<R, 16, 30, 20, 8, 2>(L, bwd, total, threads, lds_bytes, stream, err) ||
@@ -120,7 +107,7 @@ static bool try_all(const SeqLaunch& L, bool bwd, int total, int threads, size_t
 }
 
 // backward, one-row tiles, 8 k-slices (4 * Hp threads): the pre-instantiated size tuples
-static bool try_all_fat(const SeqLaunch& L, int total, int threads, size_t lds_bytes, hipStream_t stream, hipError_t* err) {
+static bool try_all_fat(const SeqLaunch& L, int total, int threads, size_t lds_bytes, hipStream_t stream, int* err) {
   return try_launch4<1, 8, 8, 2, 20, 30>(L, true, total, threads, lds_bytes, stream, err) ||
          try_launch4<1, 8, 26, 6, 6, 0>(L, true, total, threads, lds_bytes, stream, err) ||
          try_launch4<1, 8, 30, 0, 0, 0>(L, true, total, threads, lds_bytes, stream, err) ||
@@ -140,27 +127,18 @@ template <bool BWD, int K0, int K1, int K2, int K3>
 __global__ __launch_bounds__(1024) void lstm_seq_small_fold_kernel(const SeqLaunch L, const LatentDev LD, const float* __restrict__ params,
                                                                    float* __restrict__ grads) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int di = 0;
   const int bid = blockIdx.x;
   if constexpr (!BWD) {      // blocks behind the recurrence rows: this step's transposed-weight images (lstm_seq_dev.h)
     if (L.n_img > 0 && bid >= L.img_begin) { wt_img_write(L.img, L.n_img, bid - L.img_begin, L.n_img_blocks); return; }
   }
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;          // == batch row (one-row tiles)
   if constexpr (BWD) {
     latent_bwd_row_body<false>(LD, params, grads, tile, di, lds);
     sync_stores();           // d h_T of this (row, encoder) is in memory (and the LDS is free) before the BPTT reads it
   }
-#define MFM_ONE(IDX, KK)                                                        \
-  if (KK > 0 && di == IDX) {                                                    \
-    if (BWD) small_bwd_body<(KK > 0 ? KK : 2), 1, 16>(d, L.T, L.B, tile, lds);  \
-    else small_fwd_body<(KK > 0 ? KK : 2), 1>(d, L.T, L.B, tile, lds);          \
-  }
-  MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2) MFM_ONE(3, K3)
-#undef MFM_ONE
+  MFM_TUPLE4(if (BWD) small_bwd_body<KQ, 1, 16>(d, L.T, L.B, tile, lds); else small_fwd_body<KQ, 1>(d, L.T, L.B, tile, lds))
   if constexpr (!BWD) {
     sync_stores();           // every store of the last time step has been acknowledged: h_T of this row is readable
     latent_fwd_row_body<false>(LD, params, tile, di, lds, true);
@@ -177,10 +155,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_foldproj_kernel(const Seq
   const unsigned epoch = ho_epoch(PR.epoch, PR.tick);
   LSTAMP(0, 0);
   if (bid < PR.n_role) { proj_role_body(L, PR, epoch, lds); LSTAMP(0, 15); return; }
-  int di = 0;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
   const unsigned* flg = PR.flags + (int64_t)di * L.T * PROJ_ROLE_FLAGS;
@@ -195,10 +170,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_foldproj_kernel(const Seq
     seq_lds = lds + latent_fwd_lds_floats(LD.rec_size);
   }
   const float* h_lds = nullptr;
-#define MFM_ONE(IDX, KK) \
-  if (KK > 0 && di == IDX) h_lds = small_fwd_body<(KK > 0 ? KK : 2), 1, true>(d, L.T, L.B, tile, seq_lds, flg, epoch, ncb, PR.ctl);
-  MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2) MFM_ONE(3, K3)
-#undef MFM_ONE
+  MFM_TUPLE4(h_lds = small_fwd_body<KQ, 1, true>(d, L.T, L.B, tile, seq_lds, flg, epoch, ncb, PR.ctl))
   // the loss slots are cleared by the producers of t = 0: all of them have passed before this row's chain adds to them
   // (the four flag sets are requested together: one round trip)
   if (threadIdx.x < 64) {
@@ -242,10 +214,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_folddw_kernel(const SeqLa
   // garbage) must not train: the guard word of the gradient buffer makes the optimizer skip (and travels through the all-reduce)
   if (bid == 0 && threadIdx.x == 0 && DR.ctl.status && DR.ctl.poison && *DR.ctl.status != 0u)
     __hip_atomic_store(DR.ctl.poison, __builtin_nanf(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int di = 0;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;          // == batch row (one-row tiles)
   unsigned* stamp = DR.flags + (int64_t)di * L.T * DWR_ROWS + tile;
@@ -257,20 +226,14 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_folddw_kernel(const SeqLa
     latent_bwd_row_body<false>(LD, params, grads, tile, di, lds, 1);        // (ends behind a barrier)
     LSTAMP(4, 9);
     const float* dh_lds = lds + latent_bwd_grd_floats(LD.rec_size) + LD.in_off[di];
-#define MFM_ONE(IDX, KK) \
-    if (KK > 0 && di == IDX) small_bwd_body_x<(KK > 0 ? KK : 2), 1, 16, true, LatentDev>(d, L.T, L.B, tile, lds, stamp, epoch, fault, LD, params, grads, di, dh_lds, lat_stamp);
-    MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2) MFM_ONE(3, K3)
-#undef MFM_ONE
+    MFM_TUPLE4(small_bwd_body_x<KQ, 1, 16, true, LatentDev>(d, L.T, L.B, tile, lds, stamp, epoch, fault, LD, params, grads, di, dh_lds, lat_stamp))
   } else {
     latent_bwd_row_body<false>(LD, params, grads, tile, di, lds);
     LSTAMP(4, 9);
     sync_stores();           // d h_T of this (row, encoder) is in memory (and the LDS is free) before the BPTT reads it
     LSTAMP(4, 8);
     if (threadIdx.x == 0) dwr_stamp(lat_stamp, epoch);
-#define MFM_ONE(IDX, KK) \
-    if (KK > 0 && di == IDX) small_bwd_body<(KK > 0 ? KK : 2), 1, 16, true>(d, L.T, L.B, tile, lds, stamp, epoch, fault);
-    MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2) MFM_ONE(3, K3)
-#undef MFM_ONE
+    MFM_TUPLE4(small_bwd_body<KQ, 1, 16, true>(d, L.T, L.B, tile, lds, stamp, epoch, fault))
   }
   LSTAMP_W(4, 15);
 }
@@ -291,16 +254,10 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_dectail_kernel(const SeqL
     LSTAMP(1, 15);
     return;
   }
-  int di = 0;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
-#define MFM_ONE(IDX, KK) \
-  if (KK > 0 && di == IDX) small_fwd_body<(KK > 0 ? KK : 2), 1>(d, L.T, L.B, tile, lds);
-  MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2)
-#undef MFM_ONE
+  MFM_TUPLE3(small_fwd_body<KQ, 1>(d, L.T, L.B, tile, lds))
   LSTAMP(1, 15);
 }
 
@@ -318,16 +275,10 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_decbwd_head_kernel(const 
     LSTAMP(3, 15);
     return;
   }
-  int di = 0;
-#pragma unroll 1
-  for (int i = 1; i < L.count; ++i)
-    if (bid >= L.d[i].block_begin) di = i;
+  MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
-#define MFM_ONE(IDX, KK) \
-  if (KK > 0 && di == IDX) small_bwd_body<(KK > 0 ? KK : 2), 1, 16>(d, L.T, L.B, tile, lds);
-  MFM_ONE(0, K0) MFM_ONE(1, K1) MFM_ONE(2, K2)
-#undef MFM_ONE
+  MFM_TUPLE3(small_bwd_body<KQ, 1, 16>(d, L.T, L.B, tile, lds))
   LSTAMP(3, 15);
 }
 
@@ -360,98 +311,64 @@ int seq_small_launch(SeqLaunch& L, bool bwd, hipStream_t stream) {
   // LSTMs per launch: +12 % per step at B=128/256 over 2- and 4-row tiles), 4-row tiles from there on
   // (B=512: 0.856 vs 0.948 ms); 2-row tiles never did (profiles/r01l_rows_per_workgroup.txt).  Only the
   // pre-instantiated size tuples have R < 4 variants.
-  const int cus = device_cus();
-  int R = ((long)L.count * L.B < 6L * cus) ? 1 : 4;
+  int R = ((long)L.count * L.B < 6L * device_cus()) ? 1 : 4;
   if (const char* e = opt_get("MFM_SEQ_ROWS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) R = v; }
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const int tiles = cdiv(L.B, R);
-    int total = 0;
-    for (int i = 0; i < L.count; ++i) { L.d[i].block_begin = total; total += tiles; }
+    int total = lay_out_blocks(L, cdiv(L.B, R));
     const size_t lds_bytes = small_lds_bytes(L, bwd, R);
-    hipError_t err = hipSuccess;
+    int rc = MFM_OK;
     bool done = false;
-    // forward, one-row tiles, idle CUs left: a few more blocks write this step's transposed-weight images
-    const int rows_total = total;
+    // forward, one-row tiles: a few more blocks write this step's transposed-weight images
     L.n_img_blocks = 0;
-    // (no idle CU left: the writers still pay -- they run in the launch's last round, ~2 us, against ~9 us of staging saved)
-    if (!bwd && R == 1 && L.n_img > 0) {
-      L.img_begin = total; L.n_img_blocks = cus - total >= 8 ? std::min(cus - total, 64) : 32; total += L.n_img_blocks;
-    }
+    if (!bwd && R == 1 && L.n_img > 0) total = add_img_writers(L, total);
     // backward, one-row tiles: MFM_SEQ_KS=8 selects 8 k-slices per unit pair (half the threads, twice the FMAs each).
     // Opt-in: measured equal (encoders 30.5 vs 29.8 us) or slower (decoders 37.9 vs 32.6 us, 24 spilled registers) at B=32
     // (profiles/r02_seq_ks8.txt) -- the step is a latency chain (LDS hand-over, barrier, reduction), not issue-bound enough
     // for fewer, fatter waves to pay
     bool fat = false;
     if (const char* e = opt_get("MFM_SEQ_KS")) fat = bwd && R == 1 && max_threads / 2 <= 512 && atoi(e) == 8;
-    if (fat) done = try_all_fat(L, total, max_threads / 2, lds_bytes, stream, &err);
+    if (fat) done = try_all_fat(L, total, max_threads / 2, lds_bytes, stream, &rc);
     // bf16 plans, forward, one-row tiles: the decoders' recurrent product on v_dot2c_f32_bf16 (opt-in, small_fwd_body<.., BF>)
-    if (!done && !bwd && R == 1 && L.bf16_dot && L.count == 3 && L.d[0].hk4 == 26 && L.d[1].hk4 == 6 && L.d[2].hk4 == 6) {
-      if (lds_bytes > 64 * 1024)
-        err = hipFuncSetAttribute((const void*)lstm_seq_small_kernel4<false, 1, 16, 26, 6, 6, 0, 0, 0, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      if (err == hipSuccess)
-        MFM_LAUNCH_TIMED((lstm_seq_small_kernel4<false, 1, 16, 26, 6, 6, 0, 0, 0, true>), dim3(total), dim3(max_threads), lds_bytes, stream, L);
+    if (!done && !bwd && R == 1 && L.bf16_dot && seq_is_tuple(L, kDecHk4, 3, -1)) {
+      rc = seq_launch_kernel(lstm_seq_small_kernel4<false, 1, 16, 26, 6, 6, 0, 0, 0, true>, "lstm_seq_small_fwd_kernel4", dim3(total), dim3(max_threads),
+                             lds_bytes, stream, nullptr, L);
       done = true;
     }
-    if (done) {}
-    else if (R == 1) done = try_all<1>(L, bwd, total, max_threads, lds_bytes, stream, &err);
-    else if (R == 2) done = try_all<2>(L, bwd, total, max_threads, lds_bytes, stream, &err);
-    else done = try_all<4>(L, bwd, total, max_threads, lds_bytes, stream, &err);
+    if (!done) done = R == 1 ? try_all<1>(L, bwd, total, max_threads, lds_bytes, stream, &rc)
+                    : R == 2 ? try_all<2>(L, bwd, total, max_threads, lds_bytes, stream, &rc)
+                             : try_all<4>(L, bwd, total, max_threads, lds_bytes, stream, &rc);
     if (done) {
-      if (err != hipSuccess) return hip_fail(err, "hipFuncSetAttribute(lstm_seq_small_kernel4)");
-      MFM_LAUNCH_CHECK(bwd ? "lstm_seq_small_bwd_kernel4" : "lstm_seq_small_fwd_kernel4");
-      if (L.n_img_blocks == 0) L.n_img = 0;        // (tells the caller that no images were written)
-      return MFM_OK;
+      if (rc == MFM_OK && L.n_img_blocks == 0) L.n_img = 0;        // (tells the caller that no images were written)
+      return rc;
     }
-    (void)rows_total;
     R = 4;    // no specialised kernel for this size tuple: generic 16-variant kernel, 4-row tiles
   }
   L.n_img = 0; L.n_img_blocks = 0;
-  const int tiles = cdiv(L.B, 4);
-  int total = 0;
-  for (int i = 0; i < L.count; ++i) { L.d[i].block_begin = total; total += tiles; }
-  const size_t lds_bytes = small_lds_bytes(L, bwd, 4);
-  if (lds_bytes > 64 * 1024) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_kernel<true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_kernel<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  }
-  if (bwd)
-    MFM_LAUNCH_TIMED(lstm_seq_small_kernel<true>, dim3(total), dim3(max_threads), lds_bytes, stream, L);
-  else
-    MFM_LAUNCH_TIMED(lstm_seq_small_kernel<false>, dim3(total), dim3(max_threads), lds_bytes, stream, L);
-  MFM_LAUNCH_CHECK(bwd ? "lstm_seq_small_bwd_kernel" : "lstm_seq_small_fwd_kernel");
-  return MFM_OK;
+  const int total = lay_out_blocks(L, cdiv(L.B, 4));
+  return seq_launch_kernel(bwd ? lstm_seq_small_kernel<true> : lstm_seq_small_kernel<false>, bwd ? "lstm_seq_small_bwd_kernel" : "lstm_seq_small_fwd_kernel",
+                           dim3(total), dim3(max_threads), small_lds_bytes(L, bwd, 4), stream, nullptr, L);
 }
 
-
-// MFM_OK: launched.  MFM_ERR_UNSUPPORTED: not a case the fold kernels take (the caller issues the separate launches).
+// The launchers below: MFM_OK: launched.  MFM_ERR_UNSUPPORTED: not a case the kernel takes (the caller issues the separate
+// launches); each is its predicate plus the block layout.
 // Whether the plan may use the role-workgroup launches at all is the plan's "handover" option (plan.hip): the in-launch
 // hand-overs count on this launch becoming resident workgroup by workgroup in block order; launches of two queues that
 // together exceed the CUs can block each other's producers until the waits give up (status word, poisoned gradient guard).
+static bool fold_enabled() { return !opt_disabled("MFM_LATENT_FOLD") && !seq_tuning_overrides(); }
+
 bool seq_small_folddw_supported(int T, int B) {
-  if (const char* e = opt_get("MFM_DW_FOLD")) { if (atoi(e) == 0) return false; }
-  if (opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS")) return false;
-  if (const char* e = opt_get("MFM_LATENT_FOLD")) { if (atoi(e) == 0) return false; }
+  if (opt_disabled("MFM_DW_FOLD") || !fold_enabled()) return false;
   return T >= 1 && B >= 1 && B <= DWR_ROWS && device_cus() - 4 * B >= 32;
 }
 
 int seq_small_folddw_launch(SeqLaunch& L, const LatentDev& LD, DwRole& DR, const float* params, float* grads, hipStream_t stream) {
-  const int want[4] = {8, 2, 20, 30};
-  if (L.count != 4 || !LD.row_path || LD.nch != 4 || LD.pre || LD.B != L.B) return MFM_ERR_UNSUPPORTED;
-  for (int i = 0; i < 4; ++i)
-    if (L.d[i].hk4 != want[i] || L.d[i].is_dec) return MFM_ERR_UNSUPPORTED;
-  if (!seq_small_folddw_supported(L.T, L.B)) return MFM_ERR_UNSUPPORTED;
+  if (!seq_is_tuple(L, kEncHk4, 4, 0) || !chain_rows_match(LD, L.B) || !seq_small_folddw_supported(L.T, L.B)) return MFM_ERR_UNSUPPORTED;
   LSTAMP_BIND();
   const int n_role = DR.n_role;          // the block table was laid out for this many role workgroups
   if (n_role < 1 || n_role > device_cus() - 4 * L.B) return MFM_ERR_UNSUPPORTED;
   DR.T = L.T; DR.B = L.B;
-  int total = 0;
-  for (int i = 0; i < 4; ++i) { L.d[i].block_begin = total; total += L.B; }
-  total += n_role;
+  const int total = lay_out_blocks(L, L.B) + n_role;
   size_t lds_bytes = small_lds_bytes(L, true, 1);
-  const size_t lat = ((size_t)MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4 + 2 * (size_t)LD.rec_size) * sizeof(float);
   const size_t role = (size_t)DWR_LDS_FLOATS * sizeof(float);      // one shared A image + four B images + the pipeline's answer word + the block records
   if (DR.n_iter * 4 > DWR_MAXREC) return MFM_ERR_UNSUPPORTED;
   // the chain's gradient record must survive into the BPTT's prologue: it has to lie behind everything the BPTT keeps in LDS, and
@@ -462,82 +379,57 @@ int seq_small_folddw_launch(SeqLaunch& L, const LatentDev& LD, DwRole& DR, const
     for (int i = 0; i < 4; ++i) imgs = imgs && L.d[i].wt_img != nullptr;
     if (imgs && lds_bytes <= (size_t)latent_bwd_grd_floats(LD.rec_size) * sizeof(float)) DR.lat_split = 1;
   }
-  lds_bytes = std::max(lds_bytes, std::max(lat, role));
+  lds_bytes = std::max(lds_bytes, std::max(chain_lds_bytes(LD, true), role));
   if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
-  MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_folddw_kernel<8, 2, 20, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  MFM_LAUNCH_TIMED((lstm_seq_small_folddw_kernel<8, 2, 20, 30>), dim3(total), dim3(1024), lds_bytes, stream, L, LD, DR, params, grads);
-  MFM_LAUNCH_CHECK("lstm_seq_small_folddw_kernel");
-  return MFM_OK;
+  return seq_launch_kernel(lstm_seq_small_folddw_kernel<8, 2, 20, 30>, "lstm_seq_small_folddw_kernel", dim3(total), dim3(1024), lds_bytes, stream, nullptr,
+                           L, LD, DR, params, grads);
 }
 
 // Can the decoder launch of this plan carry the tail blocks?  (asked by the encoder launch before it leaves the tails behind)
 bool seq_small_dectail_supported(int T, int B, const int* dec_h, const LatentDev& LD) {
-  if (const char* e = opt_get("MFM_LATENT_TAIL")) { if (atoi(e) == 0) return false; }
-  if (opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS") || opt_get("MFM_BF16_DOT")) return false;
-  const int want[3] = {26, 6, 6};
+  if (opt_disabled("MFM_LATENT_TAIL") || seq_tuning_overrides() || opt_get("MFM_BF16_DOT")) return false;
   for (int i = 0; i < 3; ++i)
-    if (round_up(cdiv(dec_h[i], 4), 2) != want[i]) return false;
-  if (!LD.row_path || LD.nch != 4 || LD.pre || LD.B != B || LD.tail_from < 1 || LD.tail_from >= LD.nstages) return false;
+    if (round_up(cdiv(dec_h[i], 4), 2) != kDecHk4[i]) return false;
+  if (!chain_rows_match(LD, B) || LD.tail_from < 1 || LD.tail_from >= LD.nstages) return false;
   return T >= 1 && 3 * B + 4 * B <= device_cus();
 }
-
-// MFM_OK: launched (decoder rows + tail blocks).  MFM_ERR_UNSUPPORTED: the caller runs the tails as a launch of their own.
-int seq_small_dectail_launch(SeqLaunch& L, const LatentDev& LD, const float* params, hipStream_t stream) {
-  LSTAMP_BIND();
-  const int want[3] = {26, 6, 6};
-  if (L.count != 3 || L.bf16_dot) return MFM_ERR_UNSUPPORTED;
-  int hh[3];
-  for (int i = 0; i < 3; ++i) {
-    if (L.d[i].hk4 != want[i] || !L.d[i].is_dec) return MFM_ERR_UNSUPPORTED;
-    hh[i] = L.d[i].h;
-  }
-  if (!seq_small_dectail_supported(L.T, L.B, hh, LD)) return MFM_ERR_UNSUPPORTED;
-  int total = 0, max_threads = 1024;          // (the chain's work items are tabulated for 1024 threads)
-  bool direct = true;
-  for (int i = 0; i < 3; ++i) { L.d[i].block_begin = total; total += L.B; direct = direct && (L.d[i].h & 3) == 0 && L.d[i].wf_img && L.d[i].wf1_img; }
-  const int tail_begin = total;
-  total += 4 * L.B;
-  L.n_img = 0; L.n_img_blocks = 0;
-  const size_t lat = (size_t)latent_fwd_lds_floats(LD.rec_size) * sizeof(float);
-  const size_t lds_bytes = std::max(lat, small_lds_bytes(L, false, 1, direct));
-  if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
-  MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_dectail_kernel<26, 6, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  MFM_LAUNCH_TIMED((lstm_seq_small_dectail_kernel<26, 6, 6>), dim3(total), dim3(max_threads), lds_bytes, stream, L, LD, params, tail_begin);
-  MFM_LAUNCH_CHECK("lstm_seq_small_dectail_kernel");
-  return MFM_OK;
+static bool dectail_takes(const SeqLaunch& L, const LatentDev& LD) {
+  if (!seq_is_tuple(L, kDecHk4, 3, 1)) return false;
+  const int hh[3] = {L.d[0].h, L.d[1].h, L.d[2].h};
+  return seq_small_dectail_supported(L.T, L.B, hh, LD);
 }
 
-// MFM_OK: launched (decoder BPTT rows + head blocks).  MFM_ERR_UNSUPPORTED: the caller runs the plain BPTT launch, the encoder
-// launch its whole chain.
+// decoder rows + tail blocks.  MFM_ERR_UNSUPPORTED: the caller runs the tails as a launch of their own.
+int seq_small_dectail_launch(SeqLaunch& L, const LatentDev& LD, const float* params, hipStream_t stream) {
+  LSTAMP_BIND();
+  if (L.bf16_dot || !dectail_takes(L, LD)) return MFM_ERR_UNSUPPORTED;
+  bool direct = true;
+  for (int i = 0; i < 3; ++i) direct = direct && (L.d[i].h & 3) == 0 && L.d[i].wf_img && L.d[i].wf1_img;
+  const int tail_begin = lay_out_blocks(L, L.B), total = tail_begin + 4 * L.B;
+  L.n_img = 0; L.n_img_blocks = 0;
+  const size_t lds_bytes = std::max(chain_lds_bytes(LD, false), small_lds_bytes(L, false, 1, direct));
+  if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
+  // (1024 threads: the chain's work items are tabulated for them)
+  return seq_launch_kernel(lstm_seq_small_dectail_kernel<26, 6, 6>, "lstm_seq_small_dectail_kernel", dim3(total), dim3(1024), lds_bytes, stream, nullptr,
+                           L, LD, params, tail_begin);
+}
+
+// decoder BPTT rows + head blocks.  MFM_ERR_UNSUPPORTED: the caller runs the plain BPTT launch, the encoder launch its whole chain.
 int seq_small_decbwd_head_launch(SeqLaunch& L, const LatentDev& LD, const float* params, float* grads, hipStream_t stream) {
   LSTAMP_BIND();
-  if (const char* e = opt_get("MFM_LATENT_BWD_HEAD")) { if (atoi(e) == 0) return MFM_ERR_UNSUPPORTED; }
-  const int want[3] = {26, 6, 6};
-  if (L.count != 3) return MFM_ERR_UNSUPPORTED;
-  int hh[3];
-  for (int i = 0; i < 3; ++i) {
-    if (L.d[i].hk4 != want[i] || !L.d[i].is_dec || !L.d[i].wt_img) return MFM_ERR_UNSUPPORTED;
-    hh[i] = L.d[i].h;
-  }
-  if (!seq_small_dectail_supported(L.T, L.B, hh, LD) || !LD.grd_out) return MFM_ERR_UNSUPPORTED;
-  int total = 0;
-  for (int i = 0; i < 3; ++i) { L.d[i].block_begin = total; total += L.B; }
-  const int head_begin = total;
-  total += 4 * L.B;
-  const size_t lat = ((size_t)MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4 + 2 * (size_t)LD.rec_size) * sizeof(float);
-  const size_t lds_bytes = std::max(lat, small_lds_bytes(L, true, 1));
+  if (opt_disabled("MFM_LATENT_BWD_HEAD") || !dectail_takes(L, LD) || !LD.grd_out) return MFM_ERR_UNSUPPORTED;
+  for (int i = 0; i < 3; ++i)
+    if (!L.d[i].wt_img) return MFM_ERR_UNSUPPORTED;
+  const int head_begin = lay_out_blocks(L, L.B), total = head_begin + 4 * L.B;
+  const size_t lds_bytes = std::max(chain_lds_bytes(LD, true), small_lds_bytes(L, true, 1));
   if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
-  MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_decbwd_head_kernel<26, 6, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  MFM_LAUNCH_TIMED((lstm_seq_small_decbwd_head_kernel<26, 6, 6>), dim3(total), dim3(1024), lds_bytes, stream, L, LD, params, grads, head_begin);
-  MFM_LAUNCH_CHECK("lstm_seq_small_decbwd_head_kernel");
-  return MFM_OK;
+  return seq_launch_kernel(lstm_seq_small_decbwd_head_kernel<26, 6, 6>, "lstm_seq_small_decbwd_head_kernel", dim3(total), dim3(1024), lds_bytes, stream,
+                           nullptr, L, LD, params, grads, head_begin);
 }
 
 // Projection role workgroups for a forward fold launch: shapes the role kernel takes and enough idle CUs
 bool seq_small_foldproj_supported(int T, int B, const int* h, const int* k, int n_enc) {
-  if (const char* e = opt_get("MFM_PROJ_FOLD")) { if (atoi(e) == 0) return false; }
-  if (opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS")) return false;
-  if (const char* e = opt_get("MFM_LATENT_FOLD")) { if (atoi(e) == 0) return false; }
+  if (opt_disabled("MFM_PROJ_FOLD") || !fold_enabled()) return false;
   if (n_enc != 4 || T < 1 || B < 1 || B > PROJ_ROLE_CB) return false;
   if (device_cus() - 4 * B < PROJ_ROLE_SLOTS) return false;
   int slots = 0, kmax = 0;
@@ -553,10 +445,7 @@ bool seq_small_foldproj_supported(int T, int B, const int* h, const int* k, int 
 }
 
 int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, const float* params, hipStream_t stream) {
-  const int want[4] = {8, 2, 20, 30};
-  if (L.count != 4 || !LD.row_path || LD.nch != 4 || LD.pre || LD.B != L.B) return MFM_ERR_UNSUPPORTED;
-  for (int i = 0; i < 4; ++i)
-    if (L.d[i].hk4 != want[i] || L.d[i].is_dec) return MFM_ERR_UNSUPPORTED;
+  if (!seq_is_tuple(L, kEncHk4, 4, 0) || !chain_rows_match(LD, L.B)) return MFM_ERR_UNSUPPORTED;
   int hh[4], kk[4];
   for (int i = 0; i < 4; ++i) { hh[i] = L.d[i].h; kk[i] = PR.e[i].k; }
   if (!seq_small_foldproj_supported(L.T, L.B, hh, kk, 4)) return MFM_ERR_UNSUPPORTED;
@@ -571,60 +460,36 @@ int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, c
     cb += PR.e[i].ncb;
   }
   PR.kstride = proj_role_kstride(kmax);
-  int total = n_role;
-  for (int i = 0; i < 4; ++i) { L.d[i].block_begin = total; total += L.B; }
-  size_t lds_bytes = small_lds_bytes(L, false, 1);
-  const size_t lat = ((size_t)MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4 + (size_t)LD.rec_size) * sizeof(float);
+  const int total = lay_out_blocks(L, L.B, n_role);
   const size_t role = ((size_t)2 * PROJ_ROLE_CB * PR.kstride + 16 * PROJ_ROLE_PW) * sizeof(float);
-  lds_bytes = std::max(lds_bytes, std::max(lat, role));
+  size_t lds_bytes = std::max(small_lds_bytes(L, false, 1), std::max(chain_lds_bytes(LD, false), role));
   // chain tables preloaded in front of the time loop: chain region + recurrence buffers side by side (lstm_seq_small_foldproj_kernel)
   PR.lat_pre = 0;
   if (!opt_disabled("MFM_LATENT_PRELOAD")) {
     bool direct = true;
     for (int i = 0; i < 4; ++i) direct = direct && (L.d[i].h & 3) == 0;
-    const size_t side = (size_t)latent_fwd_lds_floats(LD.rec_size) * sizeof(float) + small_lds_bytes(L, false, 1, true);
+    const size_t side = chain_lds_bytes(LD, false) + small_lds_bytes(L, false, 1, true);
     if (direct && side <= 160 * 1024) { PR.lat_pre = 1; lds_bytes = std::max(side, role); }
   }
   if (!PR.lat_pre) PR.lat_tail = 0;          // (the head / tail split is a form of the preloaded chain)
   if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
-  MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_foldproj_kernel<8, 2, 20, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  MFM_LAUNCH_TIMED((lstm_seq_small_foldproj_kernel<8, 2, 20, 30>), dim3(total), dim3(1024), lds_bytes, stream, L, LD, PR, params);
-  MFM_LAUNCH_CHECK("lstm_seq_small_foldproj_kernel");
-  return MFM_OK;
+  return seq_launch_kernel(lstm_seq_small_foldproj_kernel<8, 2, 20, 30>, "lstm_seq_small_foldproj_kernel", dim3(total), dim3(1024), lds_bytes, stream, nullptr,
+                           L, LD, PR, params);
 }
 
 int seq_small_fold_launch(SeqLaunch& L, bool bwd, const LatentDev& LD, const float* params, float* grads, hipStream_t stream) {
-  if (const char* e = opt_get("MFM_LATENT_FOLD")) { if (atoi(e) == 0) return MFM_ERR_UNSUPPORTED; }
-  if (opt_get("MFM_SEQ_KS") || opt_get("MFM_SEQ_ROWS")) return MFM_ERR_UNSUPPORTED;       // tuning overrides keep the plain launches
-  const int want[4] = {8, 2, 20, 30};
-  if (L.count != 4 || !LD.row_path || LD.nch != 4 || LD.pre || LD.B != L.B) return MFM_ERR_UNSUPPORTED;
-  for (int i = 0; i < 4; ++i)
-    if (L.d[i].hk4 != want[i] || L.d[i].is_dec) return MFM_ERR_UNSUPPORTED;
+  if (!fold_enabled() || !seq_is_tuple(L, kEncHk4, 4, 0) || !chain_rows_match(LD, L.B)) return MFM_ERR_UNSUPPORTED;
   if (!((long)L.count * L.B < 6L * device_cus())) return MFM_ERR_UNSUPPORTED;          // one-row tiles only
-  int max_threads = 64, total = 0;
-  for (int i = 0; i < 4; ++i) {
+  int max_threads = 1024;       // the chain's work items are tabulated for up to 1024 threads
+  for (int i = 0; i < 4; ++i)
     if (8 * L.d[i].Hp > max_threads) max_threads = 8 * L.d[i].Hp;
-    L.d[i].block_begin = total; total += L.B;
-  }
-  if (max_threads < 1024) max_threads = 1024;       // the chain's work items are tabulated for up to 1024 threads
+  int total = lay_out_blocks(L, L.B);
   L.n_img_blocks = 0;
-  if (!bwd && L.n_img > 0) {
-    L.img_begin = total; L.n_img_blocks = device_cus() - total >= 8 ? std::min(device_cus() - total, 64) : 32; total += L.n_img_blocks;
-  }
-  size_t lds_bytes = small_lds_bytes(L, bwd, 1);
-  const size_t lat = ((size_t)MFM_LAT_MAXSTAGES * MFM_LAT_ROW_THREADS * 4 + (bwd ? 2 : 1) * (size_t)LD.rec_size) * sizeof(float);
-  if (lat > lds_bytes) lds_bytes = lat;
+  if (!bwd && L.n_img > 0) total = add_img_writers(L, total);
+  const size_t lds_bytes = std::max(small_lds_bytes(L, bwd, 1), chain_lds_bytes(LD, bwd));
   if (lds_bytes > 160 * 1024) return MFM_ERR_UNSUPPORTED;
-  if (bwd) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_fold_kernel<true, 8, 2, 20, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    MFM_LAUNCH_TIMED((lstm_seq_small_fold_kernel<true, 8, 2, 20, 30>), dim3(total), dim3(max_threads), lds_bytes, stream, L, LD, params, grads);
-  } else {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void*)lstm_seq_small_fold_kernel<false, 8, 2, 20, 30>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    MFM_LAUNCH_TIMED((lstm_seq_small_fold_kernel<false, 8, 2, 20, 30>), dim3(total), dim3(max_threads), lds_bytes, stream, L, LD, params, grads);
-  }
-  MFM_LAUNCH_CHECK("lstm_seq_small_fold_kernel");
-  return MFM_OK;
+  return seq_launch_kernel(bwd ? lstm_seq_small_fold_kernel<true, 8, 2, 20, 30> : lstm_seq_small_fold_kernel<false, 8, 2, 20, 30>, "lstm_seq_small_fold_kernel",
+                           dim3(total), dim3(max_threads), lds_bytes, stream, nullptr, L, LD, params, grads);
 }
 
 }  // namespace mfm
-

@@ -161,21 +161,12 @@ static size_t predict_lds_bytes(int h, int R, int maxw) {
 
 template <int R>
 static int predict_launch_r(const PredictDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define PRED_CASE(KK)                                                                                                          \
-  case KK:                                                                                                                     \
-    if (lds_bytes > 64 * 1024)                                                                                                 \
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void*)predict_klef_kernel<KK, R>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds_bytes));                                                                      \
-    MFM_LAUNCH_TIMED((predict_klef_kernel<KK, R>), dim3(grid), dim3(threads), lds_bytes, stream, P);                           \
-    break;
-  switch (P.seq.hk4) {
-    PRED_CASE(2) PRED_CASE(4) PRED_CASE(6) PRED_CASE(8) PRED_CASE(10) PRED_CASE(12) PRED_CASE(14) PRED_CASE(16)
-    PRED_CASE(18) PRED_CASE(20) PRED_CASE(22) PRED_CASE(24) PRED_CASE(26) PRED_CASE(28) PRED_CASE(30) PRED_CASE(32)
-    default: set_error("predict klef: no kernel for h = %d", P.seq.h); return MFM_ERR_UNSUPPORTED;
-  }
+#define PRED_CASE(KK, ...) \
+  case KK: return seq_launch_kernel(predict_klef_kernel<KK, R>, "predict_klef_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
+  switch (P.seq.hk4) { MFM_HK4_CASES(PRED_CASE) }
 #undef PRED_CASE
-  MFM_LAUNCH_CHECK("predict_klef_kernel");
-  return MFM_OK;
+  set_error("predict klef: no kernel for h = %d", P.seq.h);
+  return MFM_ERR_UNSUPPORTED;
 }
 
 static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, int loss_kind, const float* params,

@@ -70,10 +70,6 @@ struct ProjRole {
 // LDS row stride of the operand images: k padded to 16, then to an odd number of 16-byte groups (the 16 rows of a fragment
 // read land on 64 distinct banks)
 static inline int proj_role_kstride(int k) { int s4 = ((k + 15) / 16 * 16) / 4; if ((s4 & 1) == 0) ++s4; return 4 * s4; }
-bool seq_small_foldproj_supported(int T, int B, const int* h, const int* k, int n_enc);
-int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, const float* params, hipStream_t stream);
-int seq_foldproj_launch(const MfmSeqDesc* descs, int count, int T, int B, const LatentDev& lat, const float* params, ProjRole& pr,
-                        hipStream_t stream);
 
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
