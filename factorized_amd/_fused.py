@@ -170,6 +170,90 @@ class _FusedEngineMixin:
         with torch.no_grad():
             return loss_fn(self._predict(x, None)["y_hat"], y)
 
+    # ------------------------------------------------------------------ the factorized latents and generation from them
+    def _split(self, x):
+        return x[:, :, :self.d_l], x[:, :, self.d_l:self.d_l + self.d_a], x[:, :, self.d_l + self.d_a:]
+
+    def _encode_composed(self, x):
+        """encode() as the composition of this module's own sub-modules (the granular HIP operations), in eval mode"""
+        from ._ops import linear_group, seq_group
+        x_l, x_a, x_v = self._split(x)
+        encs = [(x_l, self.encoder_l), (x_a, self.encoder_a), (x_v, self.encoder_v)]
+        was = self.training
+        self.eval()                   # (the MFN's attention / gamma dropouts go by the sub-modules' own mode)
+        try:
+            if self._engine_variant == "kl_ef":
+                (l_last, a_last, v_last, y_last), _ = seq_group(encs + [(x, self.ef_encoder)], [])
+            else:
+                mfn = self.mfn_encoder
+                (l_last, a_last, v_last), states = seq_group(encs, [(x_l, mfn.lstm_l), (x_a, mfn.lstm_a), (x_v, mfn.lstm_v)])
+                y_last = mfn.forward(x, states)
+        finally:
+            self.train(was)
+        if self._engine_variant == "mmd":
+            zy, = linear_group([(y_last, self.last_to_zy_fc1)])
+            return E.Factors(l_last, a_last, v_last, zy, None, None, None, None)
+        return E.Factors(*linear_group([
+            (l_last, self.last_to_zl_fc1), (a_last, self.last_to_za_fc1), (v_last, self.last_to_zv_fc1),
+            (y_last, self.last_to_zy_fc1), (l_last, self.last_to_logvarzl_fc1), (a_last, self.last_to_logvarza_fc1),
+            (v_last, self.last_to_logvarzv_fc1), (y_last, self.last_to_logvarzy_fc1)]))
+
+    def _decode_composed(self, zl, za, zv, zy, T):
+        """decode() as the composition of this module's own sub-modules; the dropout modules are left out (eval)"""
+        from ._ops import decoder_group, linear_group
+        relu = torch.relu
+        h1 = linear_group([(zy, self.zy_to_fy_fc1), (zl, self.zl_to_fl_fc1), (za, self.za_to_fa_fc1), (zv, self.zv_to_fv_fc1)])
+        fy, fl, fa, fv = [relu(v) for v in linear_group([(relu(h1[0]), self.zy_to_fy_fc2), (relu(h1[1]), self.zl_to_fl_fc2),
+                                                          (relu(h1[2]), self.za_to_fa_fc2), (relu(h1[3]), self.zv_to_fv_fc2)])]
+        xs = decoder_group([(torch.cat([fy, fl], dim=1), self.decoder_l), (torch.cat([fy, fa], dim=1), self.decoder_a),
+                            (torch.cat([fy, fv], dim=1), self.decoder_v)], T)
+        y1, = linear_group([(fy, self.fy_to_y_fc1)])
+        y_hat, = linear_group([(relu(y1), self.fy_to_y_fc2)])
+        return list(xs) + [y_hat]
+
+    def encode(self, x):
+        """x [T, N, D] -> Factors(zl, za, zv, zy, logvar_zl, logvar_za, logvar_zv, logvar_zy) (a namedtuple, engine.Factors) of
+        float32 device tensors [N, size]: the means and log-variances of the four latent factors (reference
+        mfm_model.py:627-639) -- always the deterministic eval computation (dropout off, no sampling), `self.training` left as
+        found, without autograd and without lazy outputs.  MFM_KL_EF: engine.encode (one projection launch and one launch for
+        the four recurrences and their heads); the returned tensors are REUSED: the next call with the same shape overwrites
+        them (clone what must survive it).  MFM_KL, and MFM_KL_EF at sizes the fused entry refuses: the composition of the
+        module's own operations.  MFM: likewise; it has no last_to_z* / logvar heads, so zl, za, zv are the encoders' outputs
+        and the four logvars are None."""
+        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
+        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        with torch.no_grad():
+            if self._engine_variant == "kl_ef" and not getattr(eng, "_encode_refused", False):
+                try:
+                    return eng.encode(x)
+                except _lib.MfmUnsupported:
+                    pass
+            eng._check_inputs(x, None)
+            if x.shape[0] < 1 or x.shape[1] < 1:
+                raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
+            return self._encode_composed(x)
+
+    def decode(self, zl, za, zv, zy, T):
+        """four factors [N, size], T -> [x_l_hat, x_a_hat, x_v_hat, y_hat] in the reference's `decoded` order, x_m_hat
+        [T, N, d_m] and y_hat [N, output_dim]: the generative half (reference mfm_model.py:644-657) -- always the deterministic
+        eval computation, `self.training` left as found, without autograd.  The factors are independent arguments: nothing
+        assumes that they came from the same sample or from encode().  All three classes run engine.decode (one launch for the
+        z -> f MLPs, the three decoders' recurrences and the classifier, one for the decoders' fc1); the returned tensors are
+        REUSED: the next call with the same shape overwrites them (clone what must survive it).  Sizes the fused entry refuses:
+        the composition of the module's own operations."""
+        eng = self.engine
+        zs = [z.contiguous().float() if torch.is_tensor(z) and z.is_cuda and not (z.dtype == torch.float32 and z.is_contiguous())
+              else z for z in (zl, za, zv, zy)]
+        with torch.no_grad():
+            if not getattr(eng, "_decode_refused", False):
+                try:
+                    return eng.decode(*zs, T)
+                except _lib.MfmUnsupported:
+                    pass
+            eng._check_factors(*zs, T)
+            return self._decode_composed(*zs, int(T))
+
     # ------------------------------------------------------------------ flat gradients
     def _flat_grads(self):
         eng = self.engine

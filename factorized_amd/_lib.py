@@ -21,6 +21,10 @@ class MfmError(RuntimeError):
     pass
 
 
+class MfmUnsupported(MfmError):
+    """an entry answered MFM_ERR_UNSUPPORTED (sizes its kernels do not cover) and enqueued nothing: the caller takes another path"""
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p), ("c2", C.c_void_p),
                 ("bias", C.c_void_p), ("bias2", C.c_void_p),
@@ -183,6 +187,13 @@ _SIGS = {
     "mfm_predict_klef": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p]),
+    "mfm_encode_klef_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "mfm_encode_klef": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int64,
+                                  C.c_void_p]),
+    "mfm_decode_factors_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "mfm_decode_factors": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,0 +1,431 @@
+// The factorized latents and generation from them (include/mfm_hip.h, mfm_encode_klef / mfm_decode_factors): the two halves of
+// the eval-mode forward (mfm_model.py:619-660) as calls of their own -- no plan, no training workspace, nothing a backward would
+// read leaves the chip.  The pattern of predict.hip: the recurrence with small_fwd_body<.., REC = false>, h / c on chip, the
+// row-wise layers (dense_rows_dev.h) in the same workgroup.
+//
+// mfm_encode_klef, per row chunk:
+//   1. the input projections of the four encoders (l, a, v on their column ranges of x, the ef encoder on all of x) as ONE
+//      grouped fp32 GEMM (one problem per encoder; a chunk that is not the whole split: one per encoder and time step);
+//   2. encode_klef_kernel: workgroup (encoder e, row tile) runs e's T-step recurrence and then, on the tile's last hidden
+//      states still in LDS, e's fc1, the mean head and the logvar head; it writes its rows of z_e / logvar_z_e.
+// mfm_decode_factors, per row chunk:
+//   1. decode_factors_kernel: workgroup (decoder m, row tile) computes fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy)))) and its
+//      own f_m for its rows into LDS -- the three decoders' workgroups recompute fy on the same code path from the same inputs,
+//      bit-identical -- and runs the decoder form of the recurrence on [fy | f_m] from LDS (step 0: W_ih on the embedding, then
+//      W_ih + W_hh on h); h_t alone is stored (small_fwd_body's HS mode); decoder l's workgroups also run the classifier on fy
+//      and write y_hat;
+//   2. the three decoders' fc1 over the stored h as one grouped fp32 GEMM straight into x_hat_m.
+// One launch for all encoders (decoders): the T-step chain is a latency chain and launches of one stream run one behind the
+// other, so four launches would cost the sum of the four chains where one costs the longest.  The price is that every
+// workgroup gets the block size and the LDS of the widest LSTM; at one-row tiles that is 11 KB and 16 waves, and two
+// workgroups still fit a CU.  The per-block switch is instantiated for the canonical size tuples only (the rule of
+// lstm_seq_small.hip: a switch over all sizes costs the register allocation of every body); any other size combination takes
+// one launch per LSTM of the same kernel.
+#include <algorithm>
+
+#include "lstm_seq_small_dev.h"
+#include "dense_rows_dev.h"
+
+namespace mfm {
+
+#define GEN_ENC 4
+#define GEN_DEC 3
+
+struct EncOne {
+  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
+  const float* w[3]; const float* b[3];        // fc1, the mean head, the logvar head
+  float* mu; float* lv;                        // this chunk's rows [n, zs]
+  int zs, block_begin;
+};
+struct EncodeDev { EncOne e[GEN_ENC]; int count, T, n, maxw; };
+
+struct DecOne {
+  SeqDev seq;                                  // w_ih, w_hh, b_ih, b_hh, h = fy + fm, Hp, hk4, is_dec; hs: this chunk's [T, n, Hp]
+  const float* w[2]; const float* b[2];        // z_m -> f_m: fc1, fc2
+  const float* zm;                             // this chunk's rows [n, zs]
+  int zs, fm, block_begin, writes_y;
+};
+struct DecodeDev {
+  DecOne d[GEN_DEC];
+  const float* wy[4]; const float* by[4];      // zy_to_fy fc1, fc2, fy_to_y fc1, fc2
+  const float* zy; float* y_hat;               // this chunk's rows [n, zys] / [n, od]
+  int count, T, n, zys, fy, od, maxw, seq_floats;
+};
+
+template <int R, int K0, int K1, int K2, int K3>
+__global__ __launch_bounds__(1024) void encode_klef_kernel(const EncodeDev P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, bid = blockIdx.x;
+  MFM_SEQ_BLOCK_OF(P, e, bid, di)
+  const EncOne& E = P.e[di];
+  const int tile = bid - E.block_begin, b0 = tile * R;
+  const float* hT = nullptr;
+  MFM_TUPLE4(hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds))
+  // the two h buffers stay where they are; fc1's output and the two heads' behind them ([maxw][R] each)
+  float* act0 = lds + 2 * E.seq.Hp * R;
+  float* act1 = act0 + P.maxw * R;
+  float* act2 = act1 + P.maxw * R;
+  const int h = E.seq.h, zs = E.zs;
+  dense_rows<R>(E.w[0], E.b[0], h, h, hT, act0, false);
+  dense_rows<R>(E.w[1], E.b[1], h, zs, act0, act1, false);
+  dense_rows<R>(E.w[2], E.b[2], h, zs, act0, act2, false);
+  for (int e = tid; e < zs * R; e += blockDim.x) {
+    const int r = e / zs, o = e - r * zs;
+    if (b0 + r < P.n) {
+      E.mu[(int64_t)(b0 + r) * zs + o] = act1[o * R + r];
+      E.lv[(int64_t)(b0 + r) * zs + o] = act2[o * R + r];
+    }
+  }
+}
+
+// rows [b0, b0 + R) of z [n, zs] -> LDS [zs][R]; rows beyond n: zeros
+template <int R>
+__device__ __forceinline__ void stage_rows(const float* __restrict__ z, const int zs, const int b0, const int n, float* out) {
+  for (int e = threadIdx.x; e < zs * R; e += blockDim.x) {
+    const int r = e / zs, k = e - r * zs;
+    out[k * R + r] = (b0 + r < n) ? z[(int64_t)(b0 + r) * zs + k] : 0.0f;
+  }
+  lds_barrier();
+}
+
+template <int R, int K0, int K1, int K2>
+__global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, bid = blockIdx.x;
+  MFM_SEQ_BLOCK_OF(P, d, bid, di)
+  const DecOne& D = P.d[di];
+  const int tile = bid - D.block_begin, b0 = tile * R;
+  const int h = D.seq.h, fy = P.fy;
+  // behind everything the recurrence uses: the embedding must survive its weight staging
+  float* zin = lds + P.seq_floats;             // [maxw][R] each
+  float* t0 = zin + P.maxw * R;
+  float* t1 = t0 + P.maxw * R;
+  float* cat = t1 + P.maxw * R;                // [fy | f_m] as [h][R]
+  float* emb = cat + P.maxw * R;               // the same as [R][h]: the recurrence's h_init
+  stage_rows<R>(P.zy, P.zys, b0, P.n, zin);
+  dense_rows<R>(P.wy[0], P.by[0], P.zys, fy, zin, t0, true);
+  dense_rows<R>(P.wy[1], P.by[1], fy, fy, t0, cat, true);
+  stage_rows<R>(D.zm, D.zs, b0, P.n, zin);
+  dense_rows<R>(D.w[0], D.b[0], D.zs, D.fm, zin, t0, true);
+  dense_rows<R>(D.w[1], D.b[1], D.fm, D.fm, t0, cat + fy * R, true);
+  if (D.writes_y) {
+    dense_rows<R>(P.wy[2], P.by[2], fy, fy, cat, t0, true);
+    dense_rows<R>(P.wy[3], P.by[3], fy, P.od, t0, t1, false);
+    const int od = P.od;
+    for (int e = tid; e < od * R; e += blockDim.x) {
+      const int r = e / od, o = e - r * od;
+      if (b0 + r < P.n) P.y_hat[(int64_t)(b0 + r) * od + o] = t1[o * R + r];
+    }
+  }
+  for (int e = tid; e < h * R; e += blockDim.x) {
+    const int k = e / R, r = e - k * R;
+    emb[r * h + k] = cat[e];
+  }
+  lds_barrier();
+  // the tile as a batch of its own: row r of the embedding in LDS is row r of the recurrence, and of this tile's part of hs
+  SeqDev d = D.seq;
+  d.h_init = emb; d.ld_init = h;
+  d.hs = D.seq.hs + (int64_t)b0 * D.seq.Hp;
+  const int rows = min(R, P.n - b0);
+  const int64_t hs_step = (int64_t)P.n * D.seq.Hp;
+  MFM_TUPLE3((small_fwd_body<KQ, R, false, false, false, true>(d, P.T, rows, 0, lds, nullptr, 0u, 0,
+                                                                HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u}, hs_step)))
+}
+
+// ---------------------------------------------------------------- host
+static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
+static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }
+
+// floats of LDS small_fwd_body<KQ, R> lays out for hidden size h (its two h buffers, then the weight staging panel / its record
+// and x-projection buffers, layout kept), a multiple of 4
+static size_t seq_lds_floats(int h, int R) {
+  const size_t HKB = (size_t)round_up(4 * round_up(cdiv(h, 4), 2), 16);
+  const size_t hh = (R == 1 && (h & 3) == 0) ? 0 : (size_t)h * h;
+  const size_t rec = (2 * 6 + 2 * 4) * HKB * R;
+  return (2 * HKB * R + std::max(2 * hh, rec) + 3) / 4 * 4;
+}
+
+static int gen_hk4(int h) { return round_up(cdiv(h, 4), 2); }
+
+static const int kGenEnc[GEN_ENC] = {8, 2, 20, 30};      // the canonical sizes: encoders h = 32 / 8 / 80 / 120 ...
+static const int kGenDec[GEN_DEC] = {26, 6, 6};          // ... decoders h = 104 / 24 / 24
+
+template <int R>
+static int encode_launch_one(const EncodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
+#define GEN_CASE(KK, ...) \
+  case KK: return seq_launch_kernel(encode_klef_kernel<R, KK, 0, 0, 0>, "encode_klef_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
+  switch (P.e[0].seq.hk4) { MFM_HK4_CASES(GEN_CASE) }
+#undef GEN_CASE
+  set_error("encode klef: no kernel for h = %d", P.e[0].seq.h);
+  return MFM_ERR_UNSUPPORTED;
+}
+
+template <int R>
+static int decode_launch_one(const DecodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
+#define GEN_CASE(KK, ...) \
+  case KK: return seq_launch_kernel(decode_factors_kernel<R, KK, 0, 0>, "decode_factors_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
+  switch (P.d[0].seq.hk4) { MFM_HK4_CASES(GEN_CASE) }
+#undef GEN_CASE
+  set_error("decode factors: no kernel for h = %d", P.d[0].seq.h);
+  return MFM_ERR_UNSUPPORTED;
+}
+
+// the launch(es) of one chunk of n rows: the canonical tuple in one launch, anything else one launch per encoder
+template <int R>
+static int encode_launch(EncodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
+  const int tiles = cdiv(P.n, R);
+  bool canon = true;
+  for (int i = 0; i < GEN_ENC; ++i) canon = canon && P.e[i].seq.hk4 == kGenEnc[i];
+  if (canon) {
+    for (int i = 0; i < GEN_ENC; ++i) P.e[i].block_begin = i * tiles;
+    P.count = GEN_ENC;
+    return seq_launch_kernel(encode_klef_kernel<R, 8, 2, 20, 30>, "encode_klef_kernel", dim3(GEN_ENC * tiles), dim3(threads), lds_bytes,
+                             stream, nullptr, P);
+  }
+  for (int i = 0; i < GEN_ENC; ++i) {
+    EncodeDev Q = P;
+    Q.e[0] = P.e[i]; Q.e[0].block_begin = 0; Q.count = 1;
+    const int rc = encode_launch_one<R>(Q, tiles, std::max(8 * Q.e[0].seq.Hp, 64), lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
+
+template <int R>
+static int decode_launch(DecodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
+  const int tiles = cdiv(P.n, R);
+  bool canon = true;
+  for (int i = 0; i < GEN_DEC; ++i) canon = canon && P.d[i].seq.hk4 == kGenDec[i];
+  if (canon) {
+    for (int i = 0; i < GEN_DEC; ++i) P.d[i].block_begin = i * tiles;
+    P.count = GEN_DEC;
+    return seq_launch_kernel(decode_factors_kernel<R, 26, 6, 6>, "decode_factors_kernel", dim3(GEN_DEC * tiles), dim3(threads), lds_bytes,
+                             stream, nullptr, P);
+  }
+  for (int i = 0; i < GEN_DEC; ++i) {
+    DecodeDev Q = P;
+    Q.d[0] = P.d[i]; Q.d[0].block_begin = 0; Q.count = 1;
+    const int rc = decode_launch_one<R>(Q, tiles, std::max(8 * Q.d[0].seq.Hp, 64), lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
+
+static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, int64_t zv, int64_t max_rows) {
+  return gen_rows(N, max_rows) * T * 4 * (hp_of(zl) + hp_of(za) + hp_of(zv) + hp_of(zl + za + zv));
+}
+static int64_t decode_ws_floats(int64_t T, int64_t N, int64_t fy, int64_t fl, int64_t fa, int64_t fv, int64_t max_rows) {
+  return gen_rows(N, max_rows) * T * (hp_of(fy + fl) + hp_of(fy + fa) + hp_of(fy + fv));
+}
+
+// one-row tiles below 6 workgroups per CU over the whole launch (the rule of the training recurrences), else four-row tiles
+static int gen_tile_rows(int lstms, int rows) { return ((long)lstms * rows < 6L * device_cus()) ? 1 : 4; }
+
+#define ENC_OFFS 40      // per encoder: lstm weight_ih, weight_hh, bias_ih, bias_hh, then weight and bias of fc1, mean head, logvar head
+
+static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int za, int zv, int zy, const float* params,
+                       const int64_t* offs, const float* x, float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
+  static const char* who = "encode klef";
+  MFM_REQUIRE(T >= 1 && N >= 1 && d_l >= 1 && d_a >= 1 && d_v >= 1 && zl >= 1 && za >= 1 && zv >= 1 && zy >= 1,
+              "%s: sizes must be positive (T %d, N %lld, dims %d %d %d, z %d %d %d %d)", who, T, (long long)N, d_l, d_a, d_v, zl, za, zv, zy);
+  MFM_REQUIRE(params && offs && x && ws && out, "%s: bad arguments (params, offsets, x, workspace and outputs must not be null)", who);
+  for (int i = 0; i < 8; ++i) MFM_REQUIRE(out[i], "%s: output %d is null", who, i);
+  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
+  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
+  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  for (int i = 0; i < ENC_OFFS; ++i)
+    MFM_REQUIRE(offs[i] >= 0 && (i % 10 >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
+                who, i, (long long)offs[i]);
+  const int D = d_l + d_a + d_v;
+  const int hh[GEN_ENC] = {zl, za, zv, zl + za + zv}, zs[GEN_ENC] = {zl, za, zv, zy};
+  const int dd[GEN_ENC] = {d_l, d_a, d_v, D}, col[GEN_ENC] = {0, d_l, d_l + d_a, 0};
+  const int rows = (int)gen_rows(N, max_rows);
+  const int R = gen_tile_rows(GEN_ENC, rows);
+  int maxw = 1, threads = 64;
+  size_t lds_floats = 0;
+  for (int i = 0; i < GEN_ENC; ++i) {
+    // what the on-chip recurrence does not cover is refused: the caller composes the granular operations instead
+    if (hh[i] > MFM_SEQ_MAX_RESIDENT_H) {
+      set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, hh[i], MFM_SEQ_MAX_RESIDENT_H);
+      return MFM_ERR_UNSUPPORTED;
+    }
+    maxw = std::max(maxw, std::max(hh[i], zs[i]));
+    threads = std::max(threads, 8 * round_up(hh[i], 16));
+  }
+  for (int i = 0; i < GEN_ENC; ++i)
+    lds_floats = std::max(lds_floats, std::max(seq_lds_floats(hh[i], R), (size_t)2 * round_up(hh[i], 16) * R + (size_t)3 * maxw * R));
+  const size_t lds_bytes = (lds_floats * sizeof(float) + 15) / 16 * 16;
+  if (lds_bytes > 160 * 1024) {
+    set_error("%s: %zu bytes of LDS per workgroup (widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, maxw, R);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  MFM_REQUIRE((int64_t)rows * T * D < ((int64_t)1 << 31) && (int64_t)rows * T * 4 * round_up(hh[3], 16) < ((int64_t)1 << 31),
+              "%s: a chunk of %d rows x %d steps is too large for one projection; pass a row cap", who, rows, T);
+
+  EncodeDev P;
+  memset(&P, 0, sizeof(P));
+  float* g0 = ws;
+  for (int i = 0; i < GEN_ENC; ++i) {
+    EncOne& E = P.e[i];
+    const int64_t* o = offs + 10 * i;
+    E.seq.gates = g0; g0 += (int64_t)rows * T * 4 * round_up(hh[i], 16);
+    E.seq.w_ih = params + o[0]; E.seq.w_hh = params + o[1]; E.seq.b_ih = params + o[2]; E.seq.b_hh = params + o[3];
+    E.seq.h = hh[i]; E.seq.Hp = round_up(hh[i], 16); E.seq.hk4 = gen_hk4(hh[i]); E.seq.is_dec = 0;
+    for (int l = 0; l < 3; ++l) { E.w[l] = params + o[4 + 2 * l]; E.b[l] = params + o[5 + 2 * l]; }
+    E.zs = zs[i];
+  }
+  P.T = T; P.maxw = maxw;
+
+  for (int64_t n0 = 0; n0 < N; n0 += rows) {
+    const int n = (int)std::min<int64_t>(rows, N - n0);
+    // gates_e[t][i][g][u] = x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
+    MfmGemmDesc g[MFM_GEMM_MAXP];
+    const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
+    const int nprob = GEN_ENC * (whole ? 1 : T);
+    for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
+      const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
+      memset(g, 0, sizeof(MfmGemmDesc) * cnt);
+      for (int i = 0; i < cnt; ++i) {
+        const int e = (p0 + i) % GEN_ENC, t = (p0 + i) / GEN_ENC;
+        const SeqDev& s = P.e[e].seq;
+        MfmGemmDesc& d = g[i];
+        d.a = x + ((int64_t)t * N + n0) * D + col[e]; d.a_sm = D; d.a_sk = 1; d.a_sz = 0;
+        d.b = s.w_ih; d.b_sz = (int64_t)s.h * dd[e]; d.b_sn = dd[e]; d.b_sk = 1;
+        d.c = s.gates + (int64_t)t * n * 4 * s.Hp; d.c_sz = s.Hp; d.ldc = 4 * (int64_t)s.Hp;
+        d.bias = s.b_ih; d.bias2 = s.b_hh; d.bias_sz = s.h;
+        d.m = whole ? T * n : n; d.n = s.Hp; d.n_valid = s.h; d.k = dd[e]; d.batch = 4; d.split_k = 1;
+        d.alpha = 1.0f;
+      }
+      const int rc = gemm_group_launch(g, cnt, stream);
+      if (rc != MFM_OK) return rc;
+    }
+    P.n = n;
+    for (int i = 0; i < GEN_ENC; ++i) {
+      P.e[i].mu = out[i] + n0 * zs[i];
+      P.e[i].lv = out[4 + i] + n0 * zs[i];
+    }
+    const int rc = (R == 1) ? encode_launch<1>(P, threads, lds_bytes, stream) : encode_launch<4>(P, threads, lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
+
+#define DEC_OFFS 38      // weight, bias of zy_to_fy fc1, fc2, zl_to_fl .., za_to_fa .., zv_to_fv ..; 3 x (lstm weight_ih, weight_hh,
+                         // bias_ih, bias_hh, fc1 weight, bias); weight, bias of fy_to_y fc1, fc2
+
+static int decode_factors(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* const* z,
+                          float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
+  static const char* who = "decode factors";
+  MFM_REQUIRE(sz && params && offs && z && ws && out, "%s: bad arguments (sizes, params, offsets, factors, workspace and outputs must not be null)", who);
+  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
+  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
+  for (int i = 0; i < 4; ++i) MFM_REQUIRE(z[i] && out[i], "%s: factor / output %d is null", who, i);
+  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)ws) & 15) == 0, "%s: params and workspace must be 16-byte aligned", who);
+  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
+  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  for (int i = 0; i < DEC_OFFS; ++i) {
+    const bool lstm_w = i >= 16 && i < 34 && (i - 16) % 6 < 2;
+    MFM_REQUIRE(offs[i] >= 0 && (!lstm_w || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
+                who, i, (long long)offs[i]);
+  }
+  const int zs[GEN_DEC] = {sz[0], sz[1], sz[2]}, zys = sz[3], fm[GEN_DEC] = {sz[4], sz[5], sz[6]}, fy = sz[7];
+  const int dm[GEN_DEC] = {sz[8], sz[9], sz[10]}, od = sz[11];
+  const int rows = (int)gen_rows(N, max_rows);
+  const int R = gen_tile_rows(GEN_DEC, rows);
+  int maxw = std::max(std::max(zys, fy), od), threads = 64;
+  size_t seq_floats = 0;
+  for (int i = 0; i < GEN_DEC; ++i) {
+    const int h = fy + fm[i];
+    if (h > MFM_SEQ_MAX_RESIDENT_H) {
+      set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, h, MFM_SEQ_MAX_RESIDENT_H);
+      return MFM_ERR_UNSUPPORTED;
+    }
+    maxw = std::max(maxw, std::max(h, zs[i]));
+    threads = std::max(threads, 8 * round_up(h, 16));
+    seq_floats = std::max(seq_floats, seq_lds_floats(h, R));
+  }
+  const size_t lds_bytes = ((seq_floats + (size_t)5 * maxw * R) * sizeof(float) + 15) / 16 * 16;
+  if (lds_bytes > 160 * 1024) {
+    set_error("%s: %zu bytes of LDS per workgroup (widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, maxw, R);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  MFM_REQUIRE((int64_t)rows * T * round_up(maxw, 16) < ((int64_t)1 << 31) && (int64_t)rows * T * std::max(dm[0], std::max(dm[1], dm[2])) < ((int64_t)1 << 31),
+              "%s: a chunk of %d rows x %d steps is too large for one product; pass a row cap", who, rows, T);
+
+  DecodeDev P;
+  memset(&P, 0, sizeof(P));
+  const float* fcw[GEN_DEC]; const float* fcb[GEN_DEC];
+  float* h0 = ws;
+  for (int i = 0; i < GEN_DEC; ++i) {
+    DecOne& Dd = P.d[i];
+    const int64_t* o = offs + 16 + 6 * i;
+    const int h = fy + fm[i];
+    Dd.seq.w_ih = params + o[0]; Dd.seq.w_hh = params + o[1]; Dd.seq.b_ih = params + o[2]; Dd.seq.b_hh = params + o[3];
+    fcw[i] = params + o[4]; fcb[i] = params + o[5];
+    Dd.seq.h = h; Dd.seq.Hp = round_up(h, 16); Dd.seq.hk4 = gen_hk4(h); Dd.seq.is_dec = 1;
+    Dd.seq.hs = h0; h0 += (int64_t)rows * T * Dd.seq.Hp;
+    for (int l = 0; l < 2; ++l) { Dd.w[l] = params + offs[4 + 4 * i + 2 * l]; Dd.b[l] = params + offs[5 + 4 * i + 2 * l]; }
+    Dd.zs = zs[i]; Dd.fm = fm[i]; Dd.writes_y = i == 0;
+  }
+  for (int l = 0; l < 2; ++l) {
+    P.wy[l] = params + offs[2 * l]; P.by[l] = params + offs[2 * l + 1];
+    P.wy[2 + l] = params + offs[34 + 2 * l]; P.by[2 + l] = params + offs[35 + 2 * l];
+  }
+  P.T = T; P.zys = zys; P.fy = fy; P.od = od; P.maxw = maxw; P.seq_floats = (int)seq_floats;
+
+  for (int64_t n0 = 0; n0 < N; n0 += rows) {
+    const int n = (int)std::min<int64_t>(rows, N - n0);
+    P.n = n;
+    for (int i = 0; i < GEN_DEC; ++i) P.d[i].zm = z[i] + n0 * zs[i];
+    P.zy = z[3] + n0 * zys;
+    P.y_hat = out[3] + n0 * od;
+    int rc = (R == 1) ? decode_launch<1>(P, threads, lds_bytes, stream) : decode_launch<4>(P, threads, lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+    // x_hat_m[t][n0 + i] = hs_m[t][i] . Wfc_m^T + b
+    MfmGemmDesc g[MFM_GEMM_MAXP];
+    const bool whole = n == N;
+    const int nprob = GEN_DEC * (whole ? 1 : T);
+    for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
+      const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
+      memset(g, 0, sizeof(MfmGemmDesc) * cnt);
+      for (int i = 0; i < cnt; ++i) {
+        const int m = (p0 + i) % GEN_DEC, t = (p0 + i) / GEN_DEC;
+        const SeqDev& s = P.d[m].seq;
+        MfmGemmDesc& d = g[i];
+        d.a = s.hs + (int64_t)t * n * s.Hp; d.a_sm = s.Hp; d.a_sk = 1;
+        d.b = fcw[m]; d.b_sn = s.h; d.b_sk = 1;
+        d.c = out[m] + ((int64_t)t * N + n0) * dm[m]; d.ldc = dm[m];
+        d.bias = fcb[m];
+        d.m = whole ? T * n : n; d.n = dm[m]; d.n_valid = dm[m]; d.k = s.h; d.batch = 1; d.split_k = 1;
+        d.alpha = 1.0f;
+      }
+      rc = gemm_group_launch(g, cnt, stream);
+      if (rc != MFM_OK) return rc;
+    }
+  }
+  return MFM_OK;
+}
+
+}  // namespace mfm
+
+extern "C" int64_t mfm_encode_klef_workspace_floats(int32_t T, int64_t N, int32_t zl, int32_t za, int32_t zv, int64_t max_rows) {
+  if (T < 1 || N < 1 || zl < 1 || za < 1 || zv < 1 || max_rows < 0) return 0;
+  return mfm::encode_ws_floats(T, N, zl, za, zv, max_rows);
+}
+
+extern "C" int mfm_encode_klef(int32_t T, int64_t N, int32_t d_l, int32_t d_a, int32_t d_v, int32_t zl, int32_t za, int32_t zv,
+                               int32_t zy, const float* params, const int64_t* offsets, const float* x, float* workspace,
+                               float* const* out, int64_t max_rows, void* stream) {
+  return mfm::encode_klef(T, N, d_l, d_a, d_v, zl, za, zv, zy, params, offsets, x, workspace, out, max_rows, (hipStream_t)stream);
+}
+
+extern "C" int64_t mfm_decode_factors_workspace_floats(int32_t T, int64_t N, int32_t fy, int32_t fl, int32_t fa, int32_t fv,
+                                                       int64_t max_rows) {
+  if (T < 1 || N < 1 || fy < 1 || fl < 1 || fa < 1 || fv < 1 || max_rows < 0) return 0;
+  return mfm::decode_ws_floats(T, N, fy, fl, fa, fv, max_rows);
+}
+
+extern "C" int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes, const float* params, const int64_t* offsets,
+                                  const float* const* z, float* workspace, float* const* out, int64_t max_rows, void* stream) {
+  return mfm::decode_factors(T, N, sizes, params, offsets, z, workspace, out, max_rows, (hipStream_t)stream);
+}

@@ -188,10 +188,15 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // REC = false (predict.hip: inference, nothing comes back for a BPTT): no record of any step -- gates, c, h -- is dropped into
 // obuf or stored to HBM (d.hs / d.cs are not touched and may be null; d.gates is only read: the x-projections); h / c stay on
 // chip and the tile's last hidden states are returned for every R as [HX][R] floats (rows beyond B and pad units exact zeros).
-template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true>
+// HS (with REC = false; generate.hip: the decoders of decode(), whose fc1 runs behind the launch): h_t alone leaves for HBM, read
+// back from the h buffer the step just filled by Hp * R / 64 full waves behind the step's barrier -- row b0 + r of step t at
+// d.hs[t * hs_step + (b0 + r) * Hp + unit], all Hp units (the pad units exact zeros: a GEMM over the rows masks its K tail by
+// multiplication and must not meet whatever the buffer held).
+template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true, bool HS = false>
 __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const int T, const int B, const int tile, float* lds,
                                                const unsigned* flg = nullptr, const unsigned epoch = 0, const int ncb = 0,
-                                               const HoCtl ctl = HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u}) {
+                                               const HoCtl ctl = HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u},
+                                               const int64_t hs_step = 0) {
   constexpr int HK = 4 * KQ;                    // padded hidden extent of the matvec
   constexpr int HKB = (HK + 15) / 16 * 16;      // == Hp
   constexpr int NTH = 8 * HKB;                  // threads this LSTM uses (blockDim may be larger)
@@ -214,6 +219,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
   constexpr int NWR = (R == 1) ? 4 * NM : KQ;     // weights per gate row and thread
   constexpr int HX = (R == 1) ? HKB : HK;          // extent of one h buffer
   static_assert(!BF || R == 1, "bf16 dot products: one-row tiles only");
+  static_assert(!HS || (!REC && !BF), "h-only record: fp32 inference bodies");
   float* hbuf = lds;                       // [2][HX][R]
   __bf16* hb16 = reinterpret_cast<__bf16*>(lds);   // BF: the same two buffers as bf16 (half the bytes)
   float* panel = lds + 2 * HKB * R;        // [2][h][h] weight staging (two gates at a time)
@@ -359,6 +365,16 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     op[i] = sl < 4 ? p_gates + ((int64_t)br * 4 + sl) * Hp + unit : (sl == 4 ? p_cs : p_hs) + (int64_t)br * Hp + unit;
     ostr[i] = sl < 4 ? gstep : sstep;
     ol[i] = (sl * HKB + unit) * R + r;
+  }
+  // HS: element tid -> (row r, unit), unit fastest
+  gfloat* hs_p = p_hs;
+  int hs_l = 0;
+  bool hs_ok = false;
+  if constexpr (HS) {
+    const int r = tid / HKB, unit = tid - r * HKB;
+    hs_ok = tid < HKB * R && b0 + r < B;
+    hs_p = p_hs + (int64_t)min(b0 + r, B - 1) * Hp + (hs_ok ? unit : 0);
+    hs_l = (hs_ok && unit < HX) ? unit * R + r : -1;          // (-1: a pad unit beyond the h buffer's extent)
   }
   const int ucl = min(u, HKB - 1);
   const int my_o = (2 * gp * HKB + ucl) * R + myrow;       // this lane's slots: 2gp, 2gp+1 and 4+gp
@@ -539,6 +555,10 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
         op[i] += ostr[i];
       }
       pend = false;
+    }
+    if constexpr (HS) {
+      if (hs_ok) *hs_p = hs_l >= 0 ? hbuf[(cur ^ 1) * (HX * R) + hs_l] : 0.0f;
+      hs_p += hs_step;
     }
 #pragma unroll
     for (int i = 0; i < NXL; ++i) xpf[i] = xn[i];

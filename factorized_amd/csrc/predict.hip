@@ -11,7 +11,7 @@
 //   2. predict_klef_kernel: a workgroup owns R batch rows (R chosen as seq_small_launch chooses it), runs the T-step
 //      recurrence with small_fwd_body<.., REC = false> -- h / c stay on chip, no hs / cs / gate record leaves for HBM -- and
 //      then, on the tile's last hidden states still in LDS, the encoder's fc1, the zy head, the fy MLP and the classifier
-//      (dense_rows below: a quad of lanes per output column, the weights straight from L2, activations in LDS).  It writes
+//      (dense_rows, dense_rows_dev.h: a quad of lanes per output column, the weights straight from L2, activations in LDS).  It writes
 //      y_hat and, with labels, its rows' part of the discriminative loss.
 // Loss: one partial per workgroup (plain sums in a fixed order), stored to the workspace; behind it lane 0 draws an arrival
 // ticket (agent-scope fetch_add, acquire-release -- the pattern of keep_best.hip).  The workgroup that draws the LAST ticket
@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "lstm_seq_small_dev.h"
+#include "dense_rows_dev.h"
 
 namespace mfm {
 
@@ -39,50 +40,6 @@ struct PredictDev {
   int wg_base, wg_total;                       // this launch's first slot in `partials`, workgroups of the whole call
   float inv;                                   // 1 / (N od) (L1) or 1 / N (CE) over the WHOLE call
 };
-
-// out[c][r] = act(bias[c] + sum_k W[c][k] in[k][r]) for the tile's R rows; in / out are LDS, [.][R].  A quad of lanes per
-// output column, lane q takes the 16-byte blocks k = 4 q + 16 j (K % 4 == 0 and an aligned row) or the elements k = q + 4 j.
-template <int R>
-__device__ __forceinline__ void dense_rows(const float* __restrict__ W, const float* __restrict__ bias, const int K, const int N,
-                                           const float* in, float* out, const bool relu) {
-  const int tid = threadIdx.x, nq = blockDim.x >> 2, q = tid & 3;
-  const bool vec = (K & 3) == 0 && (((uintptr_t)W) & 15) == 0;
-  for (int c = tid >> 2; c < N; c += nq) {
-    const float* wr = W + (int64_t)c * K;
-    float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-    if (vec) {
-      for (int k0 = 4 * q; k0 < K; k0 += 16) {
-        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + k0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const RowVec<R> xv = ld_rows<R>(in + (k0 + i) * R);
-#pragma unroll
-          for (int r = 0; r < R; ++r) acc[r] = fmaf(w4[i], xv.v[r], acc[r]);
-        }
-      }
-    } else {
-      for (int k = q; k < K; k += 4) {
-        const float wv = wr[k];
-        const RowVec<R> xv = ld_rows<R>(in + k * R);
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = fmaf(wv, xv.v[r], acc[r]);
-      }
-    }
-    const float bv = bias[c];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float v = acc[r];
-      v += dpp_f<DPP_QUAD_XOR1>(v);
-      v += dpp_f<DPP_QUAD_XOR2>(v);
-      v += bv;
-      if (relu) v = fmaxf(v, 0.0f);
-      if (q == 0) out[c * R + r] = v;
-    }
-  }
-  lds_barrier();
-}
 
 template <int KQ, int R>
 __global__ __launch_bounds__(1024) void predict_klef_kernel(const PredictDev P) {

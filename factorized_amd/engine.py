@@ -12,7 +12,7 @@ PyTorch is used for device memory, streams and torch.distributed only.
 """
 import ctypes as C
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -20,6 +20,9 @@ import torch
 from . import _flat, _lib
 
 ALIGN = 64  # floats
+
+# what encode() returns: the means and log-variances of the four latent factors, [N, size] each (logvars None for variant "mmd")
+Factors = namedtuple("Factors", ["zl", "za", "zv", "zy", "logvar_zl", "logvar_za", "logvar_zv", "logvar_zy"])
 
 
 def klef_param_shapes(cfg):
@@ -590,6 +593,143 @@ class MFMEngine:
         # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
         out = self.forward(x, y, train=False, want_xhat=False, handover=False)
         return {"y_hat": out["y_hat"], "loss": out["losses"][0].clone() if y is not None else None}
+
+    # ------------------------------------------------------------------ the factorized latents and generation from them
+    _ENCODE_TENSORS = tuple(
+        pre + suf
+        for enc, mu, lv in (("encoder_l", "last_to_zl_fc1", "last_to_logvarzl_fc1"),
+                            ("encoder_a", "last_to_za_fc1", "last_to_logvarza_fc1"),
+                            ("encoder_v", "last_to_zv_fc1", "last_to_logvarzv_fc1"),
+                            ("ef_encoder", "last_to_zy_fc1", "last_to_logvarzy_fc1"))
+        for pre, suf in ((enc, ".lstm.weight_ih"), (enc, ".lstm.weight_hh"), (enc, ".lstm.bias_ih"), (enc, ".lstm.bias_hh"),
+                         (enc, ".fc1.weight"), (enc, ".fc1.bias"), (mu, ".weight"), (mu, ".bias"), (lv, ".weight"), (lv, ".bias")))
+
+    _DECODE_TENSORS = tuple(
+        [mlp + fc + suf for mlp in ("zy_to_fy", "zl_to_fl", "za_to_fa", "zv_to_fv") for fc in ("_fc1", "_fc2")
+         for suf in (".weight", ".bias")]
+        + [dec + suf for dec in ("decoder_l", "decoder_a", "decoder_v")
+           for suf in (".lstm.weight_ih", ".lstm.weight_hh", ".lstm.bias_ih", ".lstm.bias_hh", ".fc1.weight", ".fc1.bias")]
+        + [fc + suf for fc in ("fy_to_y_fc1", "fy_to_y_fc2") for suf in (".weight", ".bias")])
+
+    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
+
+    def _row_cap(self, max_rows):
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("max_rows must be at least 1, not %r" % (max_rows,))
+        return self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
+
+    def encode_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace encode() keeps for a [T, N, D] split (mfm_encode_klef_workspace_floats)"""
+        c = self.cfg
+        return int(_lib.lib().mfm_encode_klef_workspace_floats(int(T), int(N), c["zl_size"], c["za_size"], c["zv_size"],
+                                                               self._row_cap(max_rows)))
+
+    def decode_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace decode() keeps for N rows and T steps (mfm_decode_factors_workspace_floats)"""
+        c = self.cfg
+        return int(_lib.lib().mfm_decode_factors_workspace_floats(int(T), int(N), c["fy_size"], c["fl_size"], c["fa_size"],
+                                                                  c["fv_size"], self._row_cap(max_rows)))
+
+    def encode(self, x, *, max_rows=None):
+        """x [T, N, D] -> Factors(zl, za, zv, zy, logvar_zl, logvar_za, logvar_zv, logvar_zy), float32 device tensors [N, size]:
+        the means and log-variances of the four latent factors (reference mfm_model.py:627-639), the deterministic eval
+        computation.  Variant "kl_ef" only (mfm_encode_klef: the four encoders' recurrences and their heads, no plan and no
+        training workspace; the split is walked in chunks of at most `max_rows` rows, default PREDICT_MAX_ROWS).  Workspace and
+        outputs are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated and nothing
+        synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what must survive
+        it).  Raises MfmUnsupported for another variant or for sizes the entry refuses: the model's encode() then composes the
+        granular operations.  A refusal for a hidden size above 128 is remembered (later calls raise at once); one for the LDS a
+        workgroup would need (very wide layers on four-row tiles: it depends on N and max_rows too) holds for that call alone."""
+        self._check_inputs(x, None)
+        T, N, D = x.shape
+        if T < 1 or N < 1:
+            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
+        cap = self._row_cap(max_rows)
+        if self.variant != "kl_ef":
+            raise _lib.MfmUnsupported("MFMEngine.encode: the fused encoder half exists for variant 'kl_ef' only, not %r" % self.variant)
+        if getattr(self, "_encode_refused", False):
+            raise _lib.MfmUnsupported("MFMEngine.encode: mfm_encode_klef refused this configuration")
+        c = self.cfg
+        cache = self.__dict__.setdefault("_encode_bufs", {})
+        st = cache.get((T, N, cap))
+        zsz = (c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"])
+        if st is None:
+            nws = int(_lib.lib().mfm_encode_klef_workspace_floats(T, N, zsz[0], zsz[1], zsz[2], cap))
+            offs = (C.c_int64 * 40)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS])
+            outs = tuple(torch.empty(N, s, dtype=torch.float32, device=self.device) for s in zsz + zsz)
+            st = (torch.empty(nws, dtype=torch.float32, device=self.device), outs, offs,
+                  (C.c_void_p * 8)(*[t.data_ptr() for t in outs]))
+        ws, outs, offs, optr = st
+        d_l, d_a, d_v = c["input_dims"]
+        rc = _lib.lib().mfm_encode_klef(T, N, d_l, d_a, d_v, zsz[0], zsz[1], zsz[2], zsz[3], _ptr(self.params), offs, _ptr(x),
+                                        _ptr(ws), optr, cap, _stream())
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            # a hidden size beyond the on-chip recurrence is a property of the configuration: remembered.  The LDS limit also
+            # depends on the tile rows, hence on N and max_rows: that refusal holds for this call alone
+            self._encode_refused = zsz[0] + zsz[1] + zsz[2] > self.MAX_RESIDENT_H
+            raise _lib.MfmUnsupported("MFMEngine.encode: %s" % _lib.lib().mfm_last_error().decode())
+        _lib.check(rc, "mfm_encode_klef")
+        cache[(T, N, cap)] = st
+        return Factors(*outs)
+
+    def _check_factors(self, zl, za, zv, zy, T):
+        c = self.cfg
+        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
+            raise _lib.MfmError("decode: T must be an integer >= 1, not %r" % (T,))
+        N = None
+        for name, z, size in (("zl", zl, c["zl_size"]), ("za", za, c["za_size"]), ("zv", zv, c["zv_size"]), ("zy", zy, c["zy_size"])):
+            if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous()):
+                raise _lib.MfmError("decode: %s must be a contiguous float32 CUDA tensor [N, %d]; got %s" % (
+                    name, size, "%s %s %s" % (tuple(z.shape), z.dtype, z.device) if torch.is_tensor(z) else type(z)))
+            if z.shape[1] != size:
+                raise _lib.MfmError("decode: %s has %d columns, the model's %s_size is %d" % (name, z.shape[1], name, size))
+            if self.device.index is not None and z.device != self.device:
+                raise _lib.MfmError("decode: %s lives on %s, the engine on %s" % (name, z.device, self.device))
+            if N is None:
+                N = z.shape[0]
+            if z.shape[0] != N or z.device != zl.device:
+                raise _lib.MfmError("decode: the four factors must have the same number of rows on one device; zl has %d on %s, "
+                                    "%s has %d on %s" % (N, zl.device, name, z.shape[0], z.device))
+        if N < 1:
+            raise _lib.MfmError("decode: no rows")
+        return int(N)
+
+    def decode(self, zl, za, zv, zy, T, *, max_rows=None):
+        """four factors [N, size] (independent arguments: any rows, from encode() or not), T -> [x_l_hat, x_a_hat, x_v_hat,
+        y_hat], x_m_hat [T, N, d_m], y_hat [N, output_dim]: the generative half (reference mfm_model.py:644-657), the
+        deterministic eval computation, for every variant (mfm_decode_factors: the z -> f MLPs, the three decoders' recurrences
+        from [fy | f_m], their fc1 and the classifier; no plan and no training workspace; chunks of at most `max_rows` rows).
+        Workspace and outputs are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated
+        and nothing synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what
+        must survive it).  Raises MfmUnsupported for sizes the entry refuses: the model's decode() then composes the granular
+        operations.  A refusal for a decoder with fy + f_m > 128 is remembered; one for the LDS limit holds for that call alone,
+        as in encode()."""
+        N = self._check_factors(zl, za, zv, zy, T)
+        T = int(T)
+        cap = self._row_cap(max_rows)
+        if getattr(self, "_decode_refused", False):
+            raise _lib.MfmUnsupported("MFMEngine.decode: mfm_decode_factors refused this configuration")
+        c = self.cfg
+        cache = self.__dict__.setdefault("_decode_bufs", {})
+        st = cache.get((T, N, cap))
+        if st is None:
+            nws = int(_lib.lib().mfm_decode_factors_workspace_floats(T, N, c["fy_size"], c["fl_size"], c["fa_size"], c["fv_size"], cap))
+            offs = (C.c_int64 * 38)(*[self.layout.offsets[n] for n in self._DECODE_TENSORS])
+            sizes = (C.c_int32 * 12)(c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], c["fl_size"], c["fa_size"],
+                                     c["fv_size"], c["fy_size"], *c["input_dims"], c["output_dim"])
+            outs = [torch.empty(T, N, d, dtype=torch.float32, device=self.device) for d in c["input_dims"]]
+            outs.append(torch.empty(N, c["output_dim"], dtype=torch.float32, device=self.device))
+            st = (torch.empty(nws, dtype=torch.float32, device=self.device), outs, offs, sizes,
+                  (C.c_void_p * 4)(*[t.data_ptr() for t in outs]))
+        ws, outs, offs, sizes, optr = st
+        zptr = (C.c_void_p * 4)(zl.data_ptr(), za.data_ptr(), zv.data_ptr(), zy.data_ptr())
+        rc = _lib.lib().mfm_decode_factors(T, N, sizes, _ptr(self.params), offs, zptr, _ptr(ws), optr, cap, _stream())
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            self._decode_refused = c["fy_size"] + max(c["fl_size"], c["fa_size"], c["fv_size"]) > self.MAX_RESIDENT_H      # (as in encode)
+            raise _lib.MfmUnsupported("MFMEngine.decode: %s" % _lib.lib().mfm_last_error().decode())
+        _lib.check(rc, "mfm_decode_factors")
+        cache[(T, N, cap)] = st
+        return list(outs)
 
     def forward_train(self, x, p, grads_to_zero=None):
         """Training-mode forward of the module path's lazy losses (mfm_plan_forward_train): no labels, no output tensors --

@@ -480,6 +480,56 @@ int mfm_predict_klef(int32_t T, int64_t N, int32_t D, int32_t h, int32_t zy, int
                      float* workspace, float* y_hat, float* loss_dev /*or NULL*/, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The factorized latents and generation from them (csrc/generate.hip): the two halves of the eval-mode forward
+ * (mfm_model.py:619-660) as calls of their own, in the pattern of mfm_predict_klef -- recurrences with h / c on chip, the
+ * row-wise layers in the same workgroup, no MfmPlan and no training workspace, nothing a backward would read is stored.  fp32;
+ * dropout is the identity and the means are used (no sampling).
+ *
+ * mfm_encode_klef: the encoder half of MFM_KL_EF (mfm_model.py:627-639),
+ *   z_m = last_to_z{m}_fc1(encoder_m(x_m)), logvar_z_m = last_to_logvarz{m}_fc1(encoder_m(x_m)) for m = l, a, v on the column
+ *   ranges [0, d_l), [d_l, d_l + d_a), [d_l + d_a, D) of x, and zy / logvar_zy likewise from ef_encoder(x).
+ * Per row chunk: the four input projections as one grouped fp32 GEMM, then ONE launch whose workgroups are (encoder, row
+ * tile): the T-step recurrence, then the encoder's fc1, the mean head and the logvar head on the tile's last hidden states.
+ *   sizes    x [T, N, D] time-major and contiguous, D = d_l + d_a + d_v; hidden sizes zl, za, zv and zl + za + zv; zy
+ *   params   base of the flat fp32 parameter buffer; `offsets` (host, 40 element offsets into it), per encoder in the order
+ *            encoder_l, encoder_a, encoder_v, ef_encoder: lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1 weight, bias, then
+ *            weight and bias of its mean head (last_to_zl / za / zv / zy _fc1) and of its logvar head (torch layouts; the LSTM
+ *            weights 16-byte aligned)
+ *   out      host array of 8 device pointers: zl [N, zl], za [N, za], zv [N, zv], zy [N, zy], then the four logvars alike
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_encode_klef_workspace_floats(T, N, zl, za, zv, max_rows) floats, 16-byte aligned, contents arbitrary:
+ *            min(N, max_rows) * T * 4 * (round_up(zl, 16) + round_up(za, 16) + round_up(zv, 16) + round_up(zl + za + zv, 16))
+ *
+ * mfm_decode_factors: the generative half, identical in MFM_KL_EF, MFM_KL and MFM (mfm_model.py:644-657),
+ *   fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy)))), f_m likewise from z_m; x_m_hat = decoder_m(cat([fy, f_m]), T);
+ *   y_hat = fy_to_y_fc2(relu(fy_to_y_fc1(fy)))
+ * The four factors are independent inputs with N rows each.  Per row chunk: ONE launch whose workgroups are (decoder, row
+ * tile) -- fy and f_m of the tile's rows into LDS (the three decoders' workgroups recompute fy on the same code path:
+ * bit-identical), the decoder recurrence from there (step 0: W_ih on the embedding, then W_ih + W_hh on h) storing h_t alone,
+ * decoder l's workgroups also the classifier and y_hat -- then the three decoders' fc1 as one grouped fp32 GEMM into x_m_hat.
+ *   sizes    host, 12: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim (decoder m has hidden size fy + f_m)
+ *   offsets  host, 38 element offsets: weight and bias of zy_to_fy_fc1, zy_to_fy_fc2, zl_to_fl_fc1, zl_to_fl_fc2, za_to_fa_fc1,
+ *            za_to_fa_fc2, zv_to_fv_fc1, zv_to_fv_fc2; per decoder (l, a, v) lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1
+ *            weight, bias; weight and bias of fy_to_y_fc1, fy_to_y_fc2 (the LSTM weights 16-byte aligned)
+ *   z        host array of 4 device pointers: zl [N, zl], za [N, za], zv [N, zv], zy [N, zy], contiguous
+ *   out      host array of 4 device pointers: x_l_hat [T, N, d_l], x_a_hat [T, N, d_a], x_v_hat [T, N, d_v], y_hat [N, output_dim]
+ *   workspace mfm_decode_factors_workspace_floats(T, N, fy, fl, fa, fv, max_rows) floats, 16-byte aligned, contents arbitrary:
+ *            min(N, max_rows) * T * (round_up(fy + fl, 16) + round_up(fy + fa, 16) + round_up(fy + fv, 16)) for the stored h
+ *
+ * Both: nothing outside the workspace and the outputs is written.  Any N >= 1, T >= 1.  Sizes the on-chip recurrence does not
+ * cover (a hidden size > 128, or more LDS than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue
+ * nothing: compose the granular entries instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_encode_klef_workspace_floats(int32_t T, int64_t N, int32_t zl, int32_t za, int32_t zv, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_encode_klef(int32_t T, int64_t N, int32_t d_l, int32_t d_a, int32_t d_v, int32_t zl, int32_t za, int32_t zv, int32_t zy,
+                    const float* params, const int64_t* offsets /*host, 40*/, const float* x, float* workspace,
+                    float* const* out /*host, 8*/, int64_t max_rows, void* stream);
+int64_t mfm_decode_factors_workspace_floats(int32_t T, int64_t N, int32_t fy, int32_t fl, int32_t fa, int32_t fv,
+                                            int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, const float* params, const int64_t* offsets /*host, 38*/,
+                       const float* const* z /*host, 4*/, float* workspace, float* const* out /*host, 4*/, int64_t max_rows,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
