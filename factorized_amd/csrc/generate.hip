@@ -21,10 +21,7 @@
 // workgroups still fit a CU.  The per-block switch is instantiated for the canonical size tuples only (the rule of
 // lstm_seq_small.hip: a switch over all sizes costs the register allocation of every body); any other size combination takes
 // one launch per LSTM of the same kernel.
-#include <algorithm>
-
-#include "lstm_seq_small_dev.h"
-#include "dense_rows_dev.h"
+#include "generate_dev.h"
 
 namespace mfm {
 
@@ -78,16 +75,6 @@ __global__ __launch_bounds__(1024) void encode_klef_kernel(const EncodeDev P) {
   }
 }
 
-// rows [b0, b0 + R) of z [n, zs] -> LDS [zs][R]; rows beyond n: zeros
-template <int R>
-__device__ __forceinline__ void stage_rows(const float* __restrict__ z, const int zs, const int b0, const int n, float* out) {
-  for (int e = threadIdx.x; e < zs * R; e += blockDim.x) {
-    const int r = e / zs, k = e - r * zs;
-    out[k * R + r] = (b0 + r < n) ? z[(int64_t)(b0 + r) * zs + k] : 0.0f;
-  }
-  lds_barrier();
-}
-
 template <int R, int K0, int K1, int K2>
 __global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -133,20 +120,6 @@ __global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P)
 }
 
 // ---------------------------------------------------------------- host
-static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
-static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }
-
-// floats of LDS small_fwd_body<KQ, R> lays out for hidden size h (its two h buffers, then the weight staging panel / its record
-// and x-projection buffers, layout kept), a multiple of 4
-static size_t seq_lds_floats(int h, int R) {
-  const size_t HKB = (size_t)round_up(4 * round_up(cdiv(h, 4), 2), 16);
-  const size_t hh = (R == 1 && (h & 3) == 0) ? 0 : (size_t)h * h;
-  const size_t rec = (2 * 6 + 2 * 4) * HKB * R;
-  return (2 * HKB * R + std::max(2 * hh, rec) + 3) / 4 * 4;
-}
-
-static int gen_hk4(int h) { return round_up(cdiv(h, 4), 2); }
-
 static const int kGenEnc[GEN_ENC] = {8, 2, 20, 30};      // the canonical sizes: encoders h = 32 / 8 / 80 / 120 ...
 static const int kGenDec[GEN_DEC] = {26, 6, 6};          // ... decoders h = 104 / 24 / 24
 
@@ -217,9 +190,6 @@ static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, in
 static int64_t decode_ws_floats(int64_t T, int64_t N, int64_t fy, int64_t fl, int64_t fa, int64_t fv, int64_t max_rows) {
   return gen_rows(N, max_rows) * T * (hp_of(fy + fl) + hp_of(fy + fa) + hp_of(fy + fv));
 }
-
-// one-row tiles below 6 workgroups per CU over the whole launch (the rule of the training recurrences), else four-row tiles
-static int gen_tile_rows(int lstms, int rows) { return ((long)lstms * rows < 6L * device_cus()) ? 1 : 4; }
 
 #define ENC_OFFS 40      // per encoder: lstm weight_ih, weight_hh, bias_ih, bias_hh, then weight and bias of fc1, mean head, logvar head
 

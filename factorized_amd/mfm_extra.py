@@ -10,10 +10,17 @@ tests/test_module_surface.py) and forward contracts.  They are re-wirings of the
 libmfm_hip.so -- `encoderLSTM`, `decoderLSTM`, `MFN`, `HipLinear`, `loss_MMD` -- so they are COMPOSED from those
 autograd ops here, with independent LSTMs / Linears sharing launches (`seq_group`, `decoder_group`, `linear_group`).
 There is no fused one-call plan for these classes ("pure re-wiring of existing ops").
+
+`MFM_missing.impute` is the exception: surrogate inference (a missing modality and the label from the other two) as one call
+of the library, `mfm_impute_missing` (csrc/impute.hip).
 """
+import collections
+import ctypes as C
+
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import mfm_model as M
 from .mfm_model import HipLinear, MFN, decoderLSTM, encoderLSTM, loss_MMD
 
@@ -173,9 +180,29 @@ class M_D(_Base):
         return [x_l, x_a, x_v, y_hat], 0.0, 0.0
 
 
+Imputed = collections.namedtuple("Imputed", ["x_hat", "y_hat"])
+
+
+def _lstm_fc(mod):
+    """the six tensors of an encoderLSTM / decoderLSTM in the order of the C ABI (plain dict look-ups: always the current ones)"""
+    lp, fp = mod._modules["lstm"]._parameters, mod._modules["fc1"]._parameters
+    return [lp["weight_ih"], lp["weight_hh"], lp["bias_ih"], lp["bias_hh"], fp["weight"], fp["bias"]]
+
+
+def _wb(lin):
+    return [lin._parameters["weight"], lin._parameters["bias"]]
+
+
 class MFM_missing(_Base):
     """reference mfm_model.py:766-898: MFM plus six surrogate encoders that predict a modality's (and z_y's) code
-    from the other two modalities; forward returns the four decodings (all present / no l / no a / no v)."""
+    from the other two modalities; forward returns the four decodings (all present / no l / no a / no v).
+    `impute(x, missing)`: the no-<missing> decoding's reconstruction of that modality and its label from the other two
+    modalities alone, as one call of the library."""
+
+    IMPUTE_MAX_ROWS = 1024       # default row cap of impute(): the x-projections of at most this many rows are alive at once
+    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
+    _CASES = ("l", "a", "v")
+    _PAIR = {"l": "av", "a": "lv", "v": "la"}       # the observed pair of each case
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(MFM_missing, self).__init__(config)
@@ -234,6 +261,145 @@ class MFM_missing(_Base):
         decoded_noa = decode(zl, za_noa, zv, zy_noa)
         decoded_nov = decode(zl, za, zv_nov, zy_nov)
         return decoded, decoded_nol, decoded_noa, decoded_nov, mmd_loss, missing_loss
+
+    # ------------------------------------------------------------------ surrogate inference
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_impute_bufs", None)          # (device workspaces and native pointer tables: rebuilt on the next call)
+        return state
+
+    def _impute_params(self, cases):
+        """the 74 tensors of mfm_impute_missing's parameter table (include/mfm_hip.h); None for the cases not asked for"""
+        mods = self._modules
+        out = []
+        for m in self._CASES:
+            if m not in cases:
+                out += [None] * 22
+                continue
+            pair = self._PAIR[m]
+            out += _lstm_fc(mods["encoder_%s_to_%s" % (pair, m)]) + _lstm_fc(mods["encoder_%s_to_y" % pair])
+            out += _wb(mods["z%s_to_f%s_fc1" % (m, m)]) + _wb(mods["z%s_to_f%s_fc2" % (m, m)]) + _lstm_fc(mods["decoder_" + m])
+        for name in ("zy_to_fy_fc1", "zy_to_fy_fc2", "fy_to_y_fc1", "fy_to_y_fc2"):
+            out += _wb(mods[name])
+        return out
+
+    def _impute_sizes(self):
+        """zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim, read off the parameters"""
+        shp = [tuple(self._modules[n]._parameters["weight"].shape) for n in ("zl_to_fl_fc1", "za_to_fa_fc1", "zv_to_fv_fc1", "zy_to_fy_fc1")]
+        return tuple(s[1] for s in shp) + tuple(s[0] for s in shp) + (self.d_l, self.d_a, self.d_v, self.fy_to_y_fc2.weight.shape[0])
+
+    def _impute_composed(self, x, missing):
+        """impute() for ONE case as the composition of this module's own sub-modules (the granular HIP operations); the dropout
+        modules are left out (eval)"""
+        relu = torch.relu
+        d_l, d_a = self.d_l, self.d_a
+        # a COPY of the observed pair, never a column slice of x: the projection GEMM masks the 16-byte fetches that pass a row's
+        # K range by multiplying with zero, and on a slice those fetches meet the missing modality's columns (csrc/impute.hip)
+        pair = {"l": lambda: x[:, :, d_l:].contiguous(), "v": lambda: x[:, :, :d_l + d_a].contiguous(),
+                "a": lambda: torch.cat([x[:, :, :d_l], x[:, :, d_l + d_a:]], dim=2)}[missing]()
+        name = self._PAIR[missing]
+        zm, zy = _encode([(pair, getattr(self, "encoder_%s_to_%s" % (name, missing))), (pair, getattr(self, "encoder_%s_to_y" % name))])
+        tag = "z%s_to_f%s" % (missing, missing)
+        h1 = M.linear_group([(zy, self.zy_to_fy_fc1), (zm, getattr(self, tag + "_fc1"))])
+        fy, fm = [relu(v) for v in M.linear_group([(relu(h1[0]), self.zy_to_fy_fc2), (relu(h1[1]), getattr(self, tag + "_fc2"))])]
+        x_hat, = M.decoder_group([(torch.cat([fy, fm], dim=1), getattr(self, "decoder_" + missing))], x.shape[0])
+        y1, = M.linear_group([(fy, self.fy_to_y_fc1)])
+        y_hat, = M.linear_group([(relu(y1), self.fy_to_y_fc2)])
+        return Imputed(x_hat, y_hat)
+
+    def _impute_fused(self, x, cases, params, cap):
+        """mfm_impute_missing on the module's own tensors; MfmUnsupported when the entry refuses the sizes"""
+        T, N, _ = x.shape
+        L = _lib.lib()
+        bits = sum(1 << self._CASES.index(m) for m in cases)
+        cache = self.__dict__.setdefault("_impute_bufs", {})
+        key = (T, N, bits, cap, x.device)
+        st = cache.get(key)
+        if st is False:
+            raise _lib.MfmUnsupported("MFM_missing.impute: mfm_impute_missing refused this shape")
+        if st is None:
+            sz = self._impute_sizes()
+            sizes = (C.c_int32 * 12)(*sz)
+            nws = int(L.mfm_impute_missing_workspace_floats(T, N, sizes, bits, cap))
+            outs, optr = {}, (C.c_void_p * 6)()
+            for i, m in enumerate(self._CASES):
+                if m in cases:
+                    outs[m] = Imputed(torch.empty(T, N, sz[8 + i], dtype=torch.float32, device=x.device),
+                                      torch.empty(N, sz[11], dtype=torch.float32, device=x.device))
+                    optr[2 * i], optr[2 * i + 1] = outs[m].x_hat.data_ptr(), outs[m].y_hat.data_ptr()
+            st = (torch.empty(max(nws, 4), dtype=torch.float32, device=x.device), outs, sizes, optr, (C.c_void_p * 74)())
+        ws, outs, sizes, optr, pptr = st
+        for i, p in enumerate(params):
+            pptr[i] = None if p is None else p.data_ptr()
+        rc = L.mfm_impute_missing(T, N, sizes, bits, pptr, C.c_void_p(x.data_ptr()), C.c_void_p(ws.data_ptr()), optr, cap,
+                                  C.c_void_p(torch._C._cuda_getCurrentRawStream(x.device.index)))
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            # a hidden size beyond the on-chip recurrence is a property of the model: remembered.  The LDS limit also depends on the
+            # tile rows, hence on N and max_rows: that refusal is remembered for this shape alone (no buffers are kept for it)
+            sz = self._impute_sizes()
+            self._impute_refused = max(max(sz[0:4]), sz[7] + max(sz[4:7])) > self.MAX_RESIDENT_H
+            if not self._impute_refused:
+                cache[key] = False
+            raise _lib.MfmUnsupported("MFM_missing.impute: %s" % L.mfm_last_error().decode())
+        _lib.check(rc, "mfm_impute_missing")
+        cache[key] = st
+        return outs
+
+    def impute(self, x, missing, *, max_rows=None):
+        """x [T, N, D] (columns d_l | d_a | d_v), missing in "l" / "a" / "v" -> Imputed(x_hat [T, N, d_missing], y_hat [N, output_dim]):
+        the missing modality and the label from the other two modalities -- decoded_no<missing>[index of missing] and
+        decoded_no<missing>[3] of forward() (reference mfm_model.py:860-885; evaluated in mfm_mosi.py:572-596, :1023-1062).  THE
+        COLUMNS OF THE MISSING MODALITY ARE NEVER READ: they may hold anything, NaN included.  missing="each": all three cases
+        from a complete x in shared launches, as {"l": Imputed, "a": Imputed, "v": Imputed}.
+
+        Always the deterministic eval computation (dropout off), `self.training` left as found, without autograd; T of x is the
+        decoding length.  One call of mfm_impute_missing (csrc/impute.hip): the two surrogate encoders of a case, its z -> f
+        MLPs, decoder and the classifier -- no MFN, no own-modality encoder, no other decoder; the split is walked in chunks of
+        at most `max_rows` rows (default IMPUTE_MAX_ROWS).  Workspace and outputs are kept on the module (outside state_dict())
+        per (T, N, missing, max_rows) and REUSED: after the first call for a shape nothing is allocated and nothing synchronises
+        (legal inside a stream capture), and the returned tensors are overwritten by the next call for the same shape -- clone
+        what must survive it.  "each" gives the bits of the three single calls as long as both run on the same tile rows: the
+        rule counts the workgroups of a launch, so "each" turns to four-row tiles at a third of the rows per chunk at which a
+        single call does (in between -- about CUs to 3 CUs rows per chunk -- the two agree to rounding, not bit for bit;
+        include/mfm_hip.h, mfm_impute_missing_tile_rows).  A device x that is not contiguous float32 is converted.  Sizes the
+        entry refuses (a hidden size above 128, LDS beyond a CU's) take `_impute_composed`, the composition of the module's own
+        operations, which reads a copy of the observed columns.  So does a model with a parameter that is not a contiguous
+        float32 tensor on x's device, and there the operations' own check raises MfmError naming the tensor (convert the module
+        back first).  A CPU model or input raises MfmError: there is no CPU fallback."""
+        if missing not in ("l", "a", "v", "each"):
+            raise ValueError("MFM_missing.impute: missing must be 'l', 'a', 'v' or 'each', not %r" % (missing,))
+        dev = self.fy_to_y_fc1.weight.device
+        if dev.type != "cuda":
+            raise _lib.MfmError("MFM_missing.impute: parameters are on %s; move the model to the GPU first (no CPU fallback)" % dev)
+        D = self.d_l + self.d_a + self.d_v
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise _lib.MfmError("MFM_missing.impute: x must be a CUDA tensor [T, N, %d]; got %s" % (
+                D, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        M._require_cuda(x, "MFM_missing.impute")
+        if x.device != dev:
+            raise _lib.MfmError("MFM_missing.impute: x lives on %s, the model on %s" % (x.device, dev))
+        if x.shape[2] != D:
+            raise _lib.MfmError("MFM_missing.impute: x has %d features per time step, the model's input_dims sum to %d" % (x.shape[2], D))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise _lib.MfmError("MFM_missing.impute: empty split %s" % (tuple(x.shape),))
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("MFM_missing.impute: max_rows must be at least 1, not %r" % (max_rows,))
+        cap = self.IMPUTE_MAX_ROWS if max_rows is None else int(max_rows)
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        cases = self._CASES if missing == "each" else (missing,)
+        with torch.no_grad():
+            if not getattr(self, "_impute_refused", False):
+                params = self._impute_params(cases)
+                if all(p is None or (p.dtype == torch.float32 and p.device == dev and p.is_contiguous()) for p in params):
+                    try:
+                        outs = self._impute_fused(x, cases, params, cap)
+                        return dict(outs) if missing == "each" else outs[missing]
+                    except _lib.MfmUnsupported:
+                        pass
+            if missing == "each":
+                return {m: self._impute_composed(x, m) for m in cases}
+            return self._impute_composed(x, missing)
 
 
 class seq2seq(_Base):

@@ -530,6 +530,48 @@ int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, 
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Surrogate inference of MFM_missing (csrc/impute.hip; reference mfm_model.py:766-885, evaluated in mfm_mosi.py:572-596 and
+ * :1023-1062): a missing modality m and the label from the other two modalities, in the pattern of the entries above -- fp32,
+ * dropout the identity, no MfmPlan, no training workspace.  For every case m asked for
+ *   z_m' = encoder_<pair>_to_<m>(pair), zy' = encoder_<pair>_to_y(pair), pair = cat of the two observed modalities' columns of x
+ *   fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy')))), f_m likewise from z_m' through z<m>_to_f<m>
+ *   x_hat_m = decoder_m(cat([fy, f_m]), T),  y_hat_m = fy_to_y_fc2(relu(fy_to_y_fc1(fy)))
+ * which are decoded_no<m>[index of m] and decoded_no<m>[3] of MFM_missing.forward.  THE COLUMNS OF m ARE NEVER READ (case l:
+ * [0, d_l), case a: [d_l, d_l + d_a), case v: [d_l + d_a, D)): they may hold anything.  Per row chunk: a copy launch gathers the
+ * observed pair of every case into the workspace as a zero-padded matrix of its own (the GEMM masks the 16-byte fetches that
+ * pass a row's K range by multiplication: on a column range of x they would meet the missing modality's columns, and a NaN
+ * there would survive the mask); the input projections of the cases' surrogate encoders as one grouped GEMM on those copies;
+ * ONE launch of (encoder, row tile) workgroups (recurrence + fc1 -> the z rows, into the workspace); ONE launch of (case, row
+ * tile) workgroups (the z -> f MLPs, the classifier, the decoder recurrence storing h_t); the decoders' fc1 as one grouped
+ * GEMM into x_hat_m.  No workgroup waits for another.
+ *   sizes    host, 12: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim; x [T, N, D] time-major and contiguous (4-byte aligned: any contiguous view)
+ *   cases    bit 0: l missing, bit 1: a, bit 2: v; one bit, or all three (7: the three cases share the launches)
+ *   params   host array of 74 DEVICE pointers to the module's own tensors (torch layouts, contiguous fp32; the LSTM weights
+ *            16-byte aligned, the rest 4), per case m = l, a, v at 22 * m: the encoder -> z_m (av_to_l / lv_to_a / la_to_v): lstm
+ *            weight_ih, weight_hh, bias_ih, bias_hh, fc1 weight, bias; the encoder -> zy (av_to_y / lv_to_y / la_to_y) alike;
+ *            z<m>_to_f<m> fc1 weight, bias, fc2 weight, bias; decoder_m lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1
+ *            weight, bias.  Then at 66: weight and bias of zy_to_fy_fc1, zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2.  The 22 of a case
+ *            not asked for are not read and may be null
+ *   out      host array of 6 device pointers: x_hat_l [T, N, d_l], y_hat_l [N, output_dim], x_hat_a, y_hat_a, x_hat_v, y_hat_v;
+ *            those of a case not asked for are not read
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_impute_missing_workspace_floats(T, N, sizes, cases, max_rows) floats, 16-byte aligned, contents arbitrary; with
+ *            rows = min(N, max_rows), per case: rows * T * 4 * (round_up(z_m, 16) + round_up(zy, 16)) for the x-projections,
+ *            round_up(rows * z_m, 4) + round_up(rows * zy, 4) for the z rows, rows * T * round_up(fy + f_m, 16) for the stored h,
+ *            and rows * T * (round_up(k_m, 4) + 4) for the gathered pair, k_m = D - d_m
+ * mfm_impute_missing_tile_rows: host only; rows per workgroup the two recurrence launches of such a call use (tile_rows[0] the
+ * encoders', [1] the decoders': 1 below six workgroups per CU over the launch, else 4).  Results are bit-identical from call to
+ * call and across row caps that keep the tile rows.
+ * Nothing outside the workspace and the outputs is written.  Any N >= 1 (< 2^24), T >= 1.  Sizes the on-chip recurrence does not
+ * cover (a hidden size > 128, or more LDS than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue
+ * nothing: compose the granular entries instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_impute_missing_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t cases,
+                                            int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_impute_missing_tile_rows(int64_t N, int32_t cases, int64_t max_rows, int32_t* tile_rows /*host, 2*/);
+int mfm_impute_missing(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t cases, const float* const* params /*host, 74*/,
+                       const float* x, float* workspace, float* const* out /*host, 6*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
