@@ -1,7 +1,7 @@
 // The factorized latents and generation from them (include/mfm_hip.h, mfm_encode_klef / mfm_decode_factors): the two halves of
 // the eval-mode forward (mfm_model.py:619-660) as calls of their own -- no plan, no training workspace, nothing a backward would
-// read leaves the chip.  The pattern of predict.hip: the recurrence with small_fwd_body<.., REC = false>, h / c on chip, the
-// row-wise layers (dense_rows_dev.h) in the same workgroup.
+// read leaves the chip.  The pattern of the inference launches (infer_dev.h): the recurrence with small_fwd_body<.., REC = false>,
+// h / c on chip, the row-wise layers (dense_rows_dev.h) in the same workgroup.
 //
 // mfm_encode_klef, per row chunk:
 //   1. the input projections of the four encoders (l, a, v on their column ranges of x, the ef encoder on all of x) as ONE
@@ -13,20 +13,20 @@
 //      own f_m for its rows into LDS -- the three decoders' workgroups recompute fy on the same code path from the same inputs,
 //      bit-identical -- and runs the decoder form of the recurrence on [fy | f_m] from LDS (step 0: W_ih on the embedding, then
 //      W_ih + W_hh on h); h_t alone is stored (small_fwd_body's HS mode); decoder l's workgroups also run the classifier on fy
-//      and write y_hat;
+//      and write y_hat.  Every decoder carries its own zy and y_hat pointer: mfm_impute_missing (impute.hip) launches the same
+//      kernel with a zy and a y_hat per case;
 //   2. the three decoders' fc1 over the stored h as one grouped fp32 GEMM straight into x_hat_m.
 // One launch for all encoders (decoders): the T-step chain is a latency chain and launches of one stream run one behind the
 // other, so four launches would cost the sum of the four chains where one costs the longest.  The price is that every
 // workgroup gets the block size and the LDS of the widest LSTM; at one-row tiles that is 11 KB and 16 waves, and two
-// workgroups still fit a CU.  The per-block switch is instantiated for the canonical size tuples only (the rule of
-// lstm_seq_small.hip: a switch over all sizes costs the register allocation of every body); any other size combination takes
-// one launch per LSTM of the same kernel.
-#include "generate_dev.h"
+// workgroups still fit a CU.  The per-block switch is instantiated for the canonical size tuples only; any other size
+// combination takes one launch per LSTM of the same kernel (the launch rules of infer_dev.h).
+#include "infer_dev.h"
 
 namespace mfm {
 
 #define GEN_ENC 4
-#define GEN_DEC 3
+#define GEN_DEC INFER_DEC
 
 struct EncOne {
   SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
@@ -34,27 +34,14 @@ struct EncOne {
   float* mu; float* lv;                        // this chunk's rows [n, zs]
   int zs, block_begin;
 };
-struct EncodeDev { EncOne e[GEN_ENC]; int count, T, n, maxw; };
-
-struct DecOne {
-  SeqDev seq;                                  // w_ih, w_hh, b_ih, b_hh, h = fy + fm, Hp, hk4, is_dec; hs: this chunk's [T, n, Hp]
-  const float* w[2]; const float* b[2];        // z_m -> f_m: fc1, fc2
-  const float* zm;                             // this chunk's rows [n, zs]
-  int zs, fm, block_begin, writes_y;
-};
-struct DecodeDev {
-  DecOne d[GEN_DEC];
-  const float* wy[4]; const float* by[4];      // zy_to_fy fc1, fc2, fy_to_y fc1, fc2
-  const float* zy; float* y_hat;               // this chunk's rows [n, zys] / [n, od]
-  int count, T, n, zys, fy, od, maxw, seq_floats;
-};
+struct EncodeDev { EncOne d[GEN_ENC]; int count, T, n, maxw; };
 
 template <int R, int K0, int K1, int K2, int K3>
 __global__ __launch_bounds__(1024) void encode_klef_kernel(const EncodeDev P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, bid = blockIdx.x;
-  MFM_SEQ_BLOCK_OF(P, e, bid, di)
-  const EncOne& E = P.e[di];
+  MFM_SEQ_BLOCK_LSTM(P, bid, di)
+  const EncOne& E = P.d[di];
   const int tile = bid - E.block_begin, b0 = tile * R;
   const float* hT = nullptr;
   MFM_TUPLE4(hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds))
@@ -66,20 +53,15 @@ __global__ __launch_bounds__(1024) void encode_klef_kernel(const EncodeDev P) {
   dense_rows<R>(E.w[0], E.b[0], h, h, hT, act0, false);
   dense_rows<R>(E.w[1], E.b[1], h, zs, act0, act1, false);
   dense_rows<R>(E.w[2], E.b[2], h, zs, act0, act2, false);
-  for (int e = tid; e < zs * R; e += blockDim.x) {
-    const int r = e / zs, o = e - r * zs;
-    if (b0 + r < P.n) {
-      E.mu[(int64_t)(b0 + r) * zs + o] = act1[o * R + r];
-      E.lv[(int64_t)(b0 + r) * zs + o] = act2[o * R + r];
-    }
-  }
+  store_rows<R>(act1, E.mu, zs, b0, P.n, tid);
+  store_rows<R>(act2, E.lv, zs, b0, P.n, tid);
 }
 
 template <int R, int K0, int K1, int K2>
 __global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, bid = blockIdx.x;
-  MFM_SEQ_BLOCK_OF(P, d, bid, di)
+  MFM_SEQ_BLOCK_LSTM(P, bid, di)
   const DecOne& D = P.d[di];
   const int tile = bid - D.block_begin, b0 = tile * R;
   const int h = D.seq.h, fy = P.fy;
@@ -89,20 +71,16 @@ __global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P)
   float* t1 = t0 + P.maxw * R;
   float* cat = t1 + P.maxw * R;                // [fy | f_m] as [h][R]
   float* emb = cat + P.maxw * R;               // the same as [R][h]: the recurrence's h_init
-  stage_rows<R>(P.zy, P.zys, b0, P.n, zin);
+  stage_rows<R>(D.zy, P.zys, b0, P.n, zin);
   dense_rows<R>(P.wy[0], P.by[0], P.zys, fy, zin, t0, true);
   dense_rows<R>(P.wy[1], P.by[1], fy, fy, t0, cat, true);
   stage_rows<R>(D.zm, D.zs, b0, P.n, zin);
   dense_rows<R>(D.w[0], D.b[0], D.zs, D.fm, zin, t0, true);
   dense_rows<R>(D.w[1], D.b[1], D.fm, D.fm, t0, cat + fy * R, true);
-  if (D.writes_y) {
+  if (D.y_hat) {
     dense_rows<R>(P.wy[2], P.by[2], fy, fy, cat, t0, true);
     dense_rows<R>(P.wy[3], P.by[3], fy, P.od, t0, t1, false);
-    const int od = P.od;
-    for (int e = tid; e < od * R; e += blockDim.x) {
-      const int r = e / od, o = e - r * od;
-      if (b0 + r < P.n) P.y_hat[(int64_t)(b0 + r) * od + o] = t1[o * R + r];
-    }
+    store_rows<R>(t1, D.y_hat, P.od, b0, P.n, tid);
   }
   for (int e = tid; e < h * R; e += blockDim.x) {
     const int k = e / R, r = e - k * R;
@@ -123,65 +101,25 @@ __global__ __launch_bounds__(1024) void decode_factors_kernel(const DecodeDev P)
 static const int kGenEnc[GEN_ENC] = {8, 2, 20, 30};      // the canonical sizes: encoders h = 32 / 8 / 80 / 120 ...
 static const int kGenDec[GEN_DEC] = {26, 6, 6};          // ... decoders h = 104 / 24 / 24
 
-template <int R>
-static int encode_launch_one(const EncodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define GEN_CASE(KK, ...) \
-  case KK: return seq_launch_kernel(encode_klef_kernel<R, KK, 0, 0, 0>, "encode_klef_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
-  switch (P.e[0].seq.hk4) { MFM_HK4_CASES(GEN_CASE) }
-#undef GEN_CASE
-  set_error("encode klef: no kernel for h = %d", P.e[0].seq.h);
-  return MFM_ERR_UNSUPPORTED;
-}
-
-template <int R>
-static int decode_launch_one(const DecodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define GEN_CASE(KK, ...) \
-  case KK: return seq_launch_kernel(decode_factors_kernel<R, KK, 0, 0>, "decode_factors_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
-  switch (P.d[0].seq.hk4) { MFM_HK4_CASES(GEN_CASE) }
-#undef GEN_CASE
-  set_error("decode factors: no kernel for h = %d", P.d[0].seq.h);
-  return MFM_ERR_UNSUPPORTED;
-}
-
-// the launch(es) of one chunk of n rows: the canonical tuple in one launch, anything else one launch per encoder
+// the launch(es) of one chunk of n rows (infer_launch_tuple_or_each)
 template <int R>
 static int encode_launch(EncodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
-  const int tiles = cdiv(P.n, R);
   bool canon = true;
-  for (int i = 0; i < GEN_ENC; ++i) canon = canon && P.e[i].seq.hk4 == kGenEnc[i];
-  if (canon) {
-    for (int i = 0; i < GEN_ENC; ++i) P.e[i].block_begin = i * tiles;
-    P.count = GEN_ENC;
-    return seq_launch_kernel(encode_klef_kernel<R, 8, 2, 20, 30>, "encode_klef_kernel", dim3(GEN_ENC * tiles), dim3(threads), lds_bytes,
-                             stream, nullptr, P);
-  }
-  for (int i = 0; i < GEN_ENC; ++i) {
-    EncodeDev Q = P;
-    Q.e[0] = P.e[i]; Q.e[0].block_begin = 0; Q.count = 1;
-    const int rc = encode_launch_one<R>(Q, tiles, std::max(8 * Q.e[0].seq.Hp, 64), lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
-  }
-  return MFM_OK;
+  for (int i = 0; i < GEN_ENC; ++i) canon = canon && P.d[i].seq.hk4 == kGenEnc[i];
+  return infer_launch_tuple_or_each<R>("encode klef", "encode_klef_kernel", P, canon ? encode_klef_kernel<R, 8, 2, 20, 30> : nullptr,
+                                       [](auto kk) { return encode_klef_kernel<R, decltype(kk)::value, 0, 0, 0>; }, threads, lds_bytes, stream);
 }
 
 template <int R>
-static int decode_launch(DecodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
-  const int tiles = cdiv(P.n, R);
-  bool canon = true;
-  for (int i = 0; i < GEN_DEC; ++i) canon = canon && P.d[i].seq.hk4 == kGenDec[i];
-  if (canon) {
-    for (int i = 0; i < GEN_DEC; ++i) P.d[i].block_begin = i * tiles;
-    P.count = GEN_DEC;
-    return seq_launch_kernel(decode_factors_kernel<R, 26, 6, 6>, "decode_factors_kernel", dim3(GEN_DEC * tiles), dim3(threads), lds_bytes,
-                             stream, nullptr, P);
-  }
-  for (int i = 0; i < GEN_DEC; ++i) {
-    DecodeDev Q = P;
-    Q.d[0] = P.d[i]; Q.d[0].block_begin = 0; Q.count = 1;
-    const int rc = decode_launch_one<R>(Q, tiles, std::max(8 * Q.d[0].seq.Hp, 64), lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
-  }
-  return MFM_OK;
+static int decode_launch(const char* who, DecodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
+  bool canon = P.count == GEN_DEC;       // (fewer: one case of mfm_impute_missing, one LSTM -- its launch is the per-size instantiation)
+  for (int i = 0; canon && i < GEN_DEC; ++i) canon = P.d[i].seq.hk4 == kGenDec[i];
+  return infer_launch_tuple_or_each<R>(who, "decode_factors_kernel", P, canon ? decode_factors_kernel<R, 26, 6, 6> : nullptr,
+                                       [](auto kk) { return decode_factors_kernel<R, decltype(kk)::value, 0, 0>; }, threads, lds_bytes, stream);
+}
+
+int decode_factors_launch(const char* who, DecodeDev& P, int R, int threads, size_t lds_bytes, hipStream_t stream) {
+  return (R == 1) ? decode_launch<1>(who, P, threads, lds_bytes, stream) : decode_launch<4>(who, P, threads, lds_bytes, stream);
 }
 
 static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, int64_t zv, int64_t max_rows) {
@@ -201,8 +139,8 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
   MFM_REQUIRE(params && offs && x && ws && out, "%s: bad arguments (params, offsets, x, workspace and outputs must not be null)", who);
   for (int i = 0; i < 8; ++i) MFM_REQUIRE(out[i], "%s: output %d is null", who, i);
   MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
-  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  int rc = infer_check_rows(who, N, max_rows);
+  if (rc != MFM_OK) return rc;
   for (int i = 0; i < ENC_OFFS; ++i)
     MFM_REQUIRE(offs[i] >= 0 && (i % 10 >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
                 who, i, (long long)offs[i]);
@@ -214,67 +152,44 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
   int maxw = 1, threads = 64;
   size_t lds_floats = 0;
   for (int i = 0; i < GEN_ENC; ++i) {
-    // what the on-chip recurrence does not cover is refused: the caller composes the granular operations instead
-    if (hh[i] > MFM_SEQ_MAX_RESIDENT_H) {
-      set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, hh[i], MFM_SEQ_MAX_RESIDENT_H);
-      return MFM_ERR_UNSUPPORTED;
-    }
+    if ((rc = infer_check_resident(who, hh[i])) != MFM_OK) return rc;
     maxw = std::max(maxw, std::max(hh[i], zs[i]));
     threads = std::max(threads, 8 * round_up(hh[i], 16));
   }
-  for (int i = 0; i < GEN_ENC; ++i)
-    lds_floats = std::max(lds_floats, std::max(seq_lds_floats(hh[i], R), (size_t)2 * round_up(hh[i], 16) * R + (size_t)3 * maxw * R));
-  const size_t lds_bytes = (lds_floats * sizeof(float) + 15) / 16 * 16;
-  if (lds_bytes > 160 * 1024) {
-    set_error("%s: %zu bytes of LDS per workgroup (widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, maxw, R);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  MFM_REQUIRE((int64_t)rows * T * D < ((int64_t)1 << 31) && (int64_t)rows * T * 4 * round_up(hh[3], 16) < ((int64_t)1 << 31),
-              "%s: a chunk of %d rows x %d steps is too large for one projection; pass a row cap", who, rows, T);
+  for (int i = 0; i < GEN_ENC; ++i) lds_floats = std::max(lds_floats, enc_lds_floats(hh[i], R, 3, maxw));
+  const size_t lds_bytes = lds_bytes_of(lds_floats);
+  if ((rc = infer_check_lds(who, lds_bytes, maxw, R)) != MFM_OK) return rc;
+  if ((rc = infer_check_chunk(who, rows, T, std::max(D, 4 * round_up(hh[3], 16)), "projection")) != MFM_OK) return rc;
 
   EncodeDev P;
   memset(&P, 0, sizeof(P));
   float* g0 = ws;
   for (int i = 0; i < GEN_ENC; ++i) {
-    EncOne& E = P.e[i];
+    EncOne& E = P.d[i];
     const int64_t* o = offs + 10 * i;
-    E.seq.gates = g0; g0 += (int64_t)rows * T * 4 * round_up(hh[i], 16);
-    E.seq.w_ih = params + o[0]; E.seq.w_hh = params + o[1]; E.seq.b_ih = params + o[2]; E.seq.b_hh = params + o[3];
-    E.seq.h = hh[i]; E.seq.Hp = round_up(hh[i], 16); E.seq.hk4 = gen_hk4(hh[i]); E.seq.is_dec = 0;
+    seq_fill(E.seq, params + o[0], params + o[1], params + o[2], params + o[3], hh[i], 0);
+    E.seq.gates = g0; g0 += (int64_t)rows * T * 4 * E.seq.Hp;
     for (int l = 0; l < 3; ++l) { E.w[l] = params + o[4 + 2 * l]; E.b[l] = params + o[5 + 2 * l]; }
     E.zs = zs[i];
   }
-  P.T = T; P.maxw = maxw;
+  P.count = GEN_ENC; P.T = T; P.maxw = maxw;
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
     // gates_e[t][i][g][u] = x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
-    MfmGemmDesc g[MFM_GEMM_MAXP];
     const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
-    const int nprob = GEN_ENC * (whole ? 1 : T);
-    for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
-      const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
-      memset(g, 0, sizeof(MfmGemmDesc) * cnt);
-      for (int i = 0; i < cnt; ++i) {
-        const int e = (p0 + i) % GEN_ENC, t = (p0 + i) / GEN_ENC;
-        const SeqDev& s = P.e[e].seq;
-        MfmGemmDesc& d = g[i];
-        d.a = x + ((int64_t)t * N + n0) * D + col[e]; d.a_sm = D; d.a_sk = 1; d.a_sz = 0;
-        d.b = s.w_ih; d.b_sz = (int64_t)s.h * dd[e]; d.b_sn = dd[e]; d.b_sk = 1;
-        d.c = s.gates + (int64_t)t * n * 4 * s.Hp; d.c_sz = s.Hp; d.ldc = 4 * (int64_t)s.Hp;
-        d.bias = s.b_ih; d.bias2 = s.b_hh; d.bias_sz = s.h;
-        d.m = whole ? T * n : n; d.n = s.Hp; d.n_valid = s.h; d.k = dd[e]; d.batch = 4; d.split_k = 1;
-        d.alpha = 1.0f;
-      }
-      const int rc = gemm_group_launch(g, cnt, stream);
-      if (rc != MFM_OK) return rc;
-    }
+    rc = gemm_group_each(GEN_ENC * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
+      const int e = p % GEN_ENC, t = p / GEN_ENC;
+      const SeqDev& s = P.d[e].seq;
+      xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + col[e], D, dd[e], whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
+    });
+    if (rc != MFM_OK) return rc;
     P.n = n;
     for (int i = 0; i < GEN_ENC; ++i) {
-      P.e[i].mu = out[i] + n0 * zs[i];
-      P.e[i].lv = out[4 + i] + n0 * zs[i];
+      P.d[i].mu = out[i] + n0 * zs[i];
+      P.d[i].lv = out[4 + i] + n0 * zs[i];
     }
-    const int rc = (R == 1) ? encode_launch<1>(P, threads, lds_bytes, stream) : encode_launch<4>(P, threads, lds_bytes, stream);
+    rc = (R == 1) ? encode_launch<1>(P, threads, lds_bytes, stream) : encode_launch<4>(P, threads, lds_bytes, stream);
     if (rc != MFM_OK) return rc;
   }
   return MFM_OK;
@@ -291,8 +206,8 @@ static int decode_factors(int T, int64_t N, const int32_t* sz, const float* para
   for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
   for (int i = 0; i < 4; ++i) MFM_REQUIRE(z[i] && out[i], "%s: factor / output %d is null", who, i);
   MFM_REQUIRE((((uintptr_t)params | (uintptr_t)ws) & 15) == 0, "%s: params and workspace must be 16-byte aligned", who);
-  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
-  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  int rc = infer_check_rows(who, N, max_rows);
+  if (rc != MFM_OK) return rc;
   for (int i = 0; i < DEC_OFFS; ++i) {
     const bool lstm_w = i >= 16 && i < 34 && (i - 16) % 6 < 2;
     MFM_REQUIRE(offs[i] >= 0 && (!lstm_w || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
@@ -306,21 +221,14 @@ static int decode_factors(int T, int64_t N, const int32_t* sz, const float* para
   size_t seq_floats = 0;
   for (int i = 0; i < GEN_DEC; ++i) {
     const int h = fy + fm[i];
-    if (h > MFM_SEQ_MAX_RESIDENT_H) {
-      set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, h, MFM_SEQ_MAX_RESIDENT_H);
-      return MFM_ERR_UNSUPPORTED;
-    }
+    if ((rc = infer_check_resident(who, h)) != MFM_OK) return rc;
     maxw = std::max(maxw, std::max(h, zs[i]));
     threads = std::max(threads, 8 * round_up(h, 16));
     seq_floats = std::max(seq_floats, seq_lds_floats(h, R));
   }
-  const size_t lds_bytes = ((seq_floats + (size_t)5 * maxw * R) * sizeof(float) + 15) / 16 * 16;
-  if (lds_bytes > 160 * 1024) {
-    set_error("%s: %zu bytes of LDS per workgroup (widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, maxw, R);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  MFM_REQUIRE((int64_t)rows * T * round_up(maxw, 16) < ((int64_t)1 << 31) && (int64_t)rows * T * std::max(dm[0], std::max(dm[1], dm[2])) < ((int64_t)1 << 31),
-              "%s: a chunk of %d rows x %d steps is too large for one product; pass a row cap", who, rows, T);
+  const size_t lds_bytes = lds_bytes_of(seq_floats + (size_t)5 * maxw * R);
+  if ((rc = infer_check_lds(who, lds_bytes, maxw, R)) != MFM_OK) return rc;
+  if ((rc = infer_check_chunk(who, rows, T, std::max(round_up(maxw, 16), std::max(dm[0], std::max(dm[1], dm[2]))), "product")) != MFM_OK) return rc;
 
   DecodeDev P;
   memset(&P, 0, sizeof(P));
@@ -329,49 +237,34 @@ static int decode_factors(int T, int64_t N, const int32_t* sz, const float* para
   for (int i = 0; i < GEN_DEC; ++i) {
     DecOne& Dd = P.d[i];
     const int64_t* o = offs + 16 + 6 * i;
-    const int h = fy + fm[i];
-    Dd.seq.w_ih = params + o[0]; Dd.seq.w_hh = params + o[1]; Dd.seq.b_ih = params + o[2]; Dd.seq.b_hh = params + o[3];
+    seq_fill(Dd.seq, params + o[0], params + o[1], params + o[2], params + o[3], fy + fm[i], 1);
     fcw[i] = params + o[4]; fcb[i] = params + o[5];
-    Dd.seq.h = h; Dd.seq.Hp = round_up(h, 16); Dd.seq.hk4 = gen_hk4(h); Dd.seq.is_dec = 1;
     Dd.seq.hs = h0; h0 += (int64_t)rows * T * Dd.seq.Hp;
     for (int l = 0; l < 2; ++l) { Dd.w[l] = params + offs[4 + 4 * i + 2 * l]; Dd.b[l] = params + offs[5 + 4 * i + 2 * l]; }
-    Dd.zs = zs[i]; Dd.fm = fm[i]; Dd.writes_y = i == 0;
+    Dd.zs = zs[i]; Dd.fm = fm[i];
   }
   for (int l = 0; l < 2; ++l) {
     P.wy[l] = params + offs[2 * l]; P.by[l] = params + offs[2 * l + 1];
     P.wy[2 + l] = params + offs[34 + 2 * l]; P.by[2 + l] = params + offs[35 + 2 * l];
   }
-  P.T = T; P.zys = zys; P.fy = fy; P.od = od; P.maxw = maxw; P.seq_floats = (int)seq_floats;
+  P.count = GEN_DEC; P.T = T; P.zys = zys; P.fy = fy; P.od = od; P.maxw = maxw; P.seq_floats = (int)seq_floats;
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
     P.n = n;
-    for (int i = 0; i < GEN_DEC; ++i) P.d[i].zm = z[i] + n0 * zs[i];
-    P.zy = z[3] + n0 * zys;
-    P.y_hat = out[3] + n0 * od;
-    int rc = (R == 1) ? decode_launch<1>(P, threads, lds_bytes, stream) : decode_launch<4>(P, threads, lds_bytes, stream);
+    // the three decoders share the one zy; decoder l's workgroups write y_hat
+    for (int i = 0; i < GEN_DEC; ++i) { P.d[i].zm = z[i] + n0 * zs[i]; P.d[i].zy = z[3] + n0 * zys; }
+    P.d[0].y_hat = out[3] + n0 * od;
+    rc = decode_factors_launch(who, P, R, threads, lds_bytes, stream);
     if (rc != MFM_OK) return rc;
     // x_hat_m[t][n0 + i] = hs_m[t][i] . Wfc_m^T + b
-    MfmGemmDesc g[MFM_GEMM_MAXP];
     const bool whole = n == N;
-    const int nprob = GEN_DEC * (whole ? 1 : T);
-    for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
-      const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
-      memset(g, 0, sizeof(MfmGemmDesc) * cnt);
-      for (int i = 0; i < cnt; ++i) {
-        const int m = (p0 + i) % GEN_DEC, t = (p0 + i) / GEN_DEC;
-        const SeqDev& s = P.d[m].seq;
-        MfmGemmDesc& d = g[i];
-        d.a = s.hs + (int64_t)t * n * s.Hp; d.a_sm = s.Hp; d.a_sk = 1;
-        d.b = fcw[m]; d.b_sn = s.h; d.b_sk = 1;
-        d.c = out[m] + ((int64_t)t * N + n0) * dm[m]; d.ldc = dm[m];
-        d.bias = fcb[m];
-        d.m = whole ? T * n : n; d.n = dm[m]; d.n_valid = dm[m]; d.k = s.h; d.batch = 1; d.split_k = 1;
-        d.alpha = 1.0f;
-      }
-      rc = gemm_group_launch(g, cnt, stream);
-      if (rc != MFM_OK) return rc;
-    }
+    rc = gemm_group_each(GEN_DEC * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
+      const int m = p % GEN_DEC, t = p / GEN_DEC;
+      const SeqDev& s = P.d[m].seq;
+      dec_fc1_desc(d, s, s.hs + (int64_t)t * n * s.Hp, fcw[m], fcb[m], out[m] + ((int64_t)t * N + n0) * dm[m], dm[m], whole ? T * n : n);
+    });
+    if (rc != MFM_OK) return rc;
   }
   return MFM_OK;
 }

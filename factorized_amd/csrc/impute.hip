@@ -1,8 +1,9 @@
 // Surrogate inference of MFM_missing (include/mfm_hip.h, mfm_impute_missing): a missing modality m and the label from the other
 // two modalities -- decoded_no<m>[index of m] and decoded_no<m>[3] of the class's forward (mfm_model.py:766-885) in eval mode --
 // on what they depend on alone: the two surrogate encoders that read the observed pair (-> z_m', -> zy'), zy_to_fy, z{m}_to_f{m},
-// decoder_m and fy_to_y.  No MFN, no own-modality encoder, no other decoder.  The pattern of generate.hip: the recurrence with
-// small_fwd_body<.., REC = false>, h / c on chip, the row-wise layers (dense_rows_dev.h) in the workgroup that holds the rows.
+// decoder_m and fy_to_y.  No MFN, no own-modality encoder, no other decoder.  The pattern of the inference launches
+// (infer_dev.h): the recurrence with small_fwd_body<.., REC = false>, h / c on chip, the row-wise layers (dense_rows_dev.h) in the
+// workgroup that holds the rows.
 //
 // Per row chunk and for the cases asked for (one of l / a / v, or all three):
 //   0. impute_gather_kernel copies the observed pair of every case -- (a, v), (l, v), (l, a): the columns of x without those of
@@ -14,18 +15,18 @@
 //      of a case share theirs);
 //   2. impute_encode_kernel: workgroup (encoder e, row tile) runs e's T-step recurrence and then e's fc1 on the tile's last hidden
 //      states still in LDS; it writes its rows of z (plain encoderLSTMs: no mean / logvar heads);
-//   3. impute_decode_kernel: workgroup (case m, row tile) computes fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy'_m)))) and f_m
-//      likewise from z_m' into LDS, the classifier on fy -> y_hat_m, and runs the decoder form of the recurrence on [fy | f_m]
-//      storing h_t alone.  Every case has its OWN zy' and its own y_hat (decode_factors_kernel shares one zy: another struct);
+//   3. decode_factors_kernel (generate.hip): workgroup (case m, row tile) computes fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy'_m))))
+//      and f_m likewise from z_m' into LDS, the classifier on fy -> y_hat_m, and runs the decoder form of the recurrence on
+//      [fy | f_m] storing h_t alone.  Every case has its OWN zy' and its own y_hat;
 //   4. the decoders' fc1 over the stored h as one grouped fp32 GEMM straight into x_hat_m.
 // The z rows travel through HBM between launches 2 and 3 (stream order: no flag, no workgroup waits for another).  Launches 2
-// and 3 follow the rule at the top of generate.hip: the per-block switch is instantiated for the canonical size tuples only (one
-// per case, one for all three cases), any other combination takes one launch per LSTM of the same kernel.
-#include "generate_dev.h"
+// and 3 follow the launch rules of infer_dev.h: the per-block switch is instantiated for the canonical size tuples only (the
+// encoders: one per case, one for all three cases), any other combination takes one launch per LSTM of the same kernel.
+#include "infer_dev.h"
 
 namespace mfm {
 
-#define IMP_CASES 3
+#define IMP_CASES INFER_DEC
 #define IMP_ENC (2 * IMP_CASES)
 #define IMP_CASE_PTRS 22     // per case: 6 of the encoder -> z_m, 6 of the encoder -> zy, 4 of z{m}_to_f{m}, 6 of decoder_m
 #define IMP_NPARAM (IMP_CASES * IMP_CASE_PTRS + 8)
@@ -36,20 +37,7 @@ struct ImpEnc {
   float* z;                                    // this chunk's rows [n, h]
   int block_begin;
 };
-struct ImpEncodeDev { ImpEnc e[IMP_ENC]; int count, T, n, maxw; };
-
-struct ImpDec {
-  SeqDev seq;                                  // w_ih, w_hh, b_ih, b_hh, h = fy + fm, Hp, hk4, is_dec; hs: this chunk's [T, n, Hp]
-  const float* w[2]; const float* b[2];        // z_m -> f_m: fc1, fc2
-  const float* zm; const float* zy;            // this chunk's rows [n, zs] / [n, zys]: this case's own pair
-  float* y_hat;                                // this chunk's rows [n, od]
-  int zs, fm, block_begin;
-};
-struct ImpDecodeDev {
-  ImpDec d[IMP_CASES];
-  const float* wy[4]; const float* by[4];      // zy_to_fy fc1, fc2, fy_to_y fc1, fc2
-  int count, T, n, zys, fy, od, maxw, seq_floats;
-};
+struct ImpEncodeDev { ImpEnc d[IMP_ENC]; int count, T, n, maxw; };
 
 // out_c [T * n, ld_c] <- rows [n0, n0 + n) of x [T, N, D], columns s0 .. s0 + len0 - 1 then s1 .. up to k_c in all; [k_c, ld_c): zeros
 struct ImpGather {
@@ -75,8 +63,8 @@ template <int R, int K0, int K1, int K2, int K3, int K4, int K5>
 __global__ __launch_bounds__(1024) void impute_encode_kernel(const ImpEncodeDev P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, bid = blockIdx.x;
-  MFM_SEQ_BLOCK_OF(P, e, bid, di)
-  const ImpEnc& E = P.e[di];
+  MFM_SEQ_BLOCK_LSTM(P, bid, di)
+  const ImpEnc& E = P.d[di];
   const int tile = bid - E.block_begin, b0 = tile * R;
   const float* hT = nullptr;
   MFM_TUPLE6(hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds))
@@ -84,51 +72,7 @@ __global__ __launch_bounds__(1024) void impute_encode_kernel(const ImpEncodeDev 
   float* act0 = lds + 2 * E.seq.Hp * R;
   const int h = E.seq.h;
   dense_rows<R>(E.w, E.b, h, h, hT, act0, false);
-  for (int e = tid; e < h * R; e += blockDim.x) {
-    const int r = e / h, o = e - r * h;
-    if (b0 + r < P.n) E.z[(int64_t)(b0 + r) * h + o] = act0[o * R + r];
-  }
-}
-
-template <int R, int K0, int K1, int K2>
-__global__ __launch_bounds__(1024) void impute_decode_kernel(const ImpDecodeDev P) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, bid = blockIdx.x;
-  MFM_SEQ_BLOCK_OF(P, d, bid, di)
-  const ImpDec& D = P.d[di];
-  const int tile = bid - D.block_begin, b0 = tile * R;
-  const int h = D.seq.h, fy = P.fy, od = P.od;
-  // behind everything the recurrence uses: the embedding must survive its weight staging
-  float* zin = lds + P.seq_floats;             // [maxw][R] each
-  float* t0 = zin + P.maxw * R;
-  float* t1 = t0 + P.maxw * R;
-  float* cat = t1 + P.maxw * R;                // [fy | f_m] as [h][R]
-  float* emb = cat + P.maxw * R;               // the same as [R][h]: the recurrence's h_init
-  stage_rows<R>(D.zy, P.zys, b0, P.n, zin);
-  dense_rows<R>(P.wy[0], P.by[0], P.zys, fy, zin, t0, true);
-  dense_rows<R>(P.wy[1], P.by[1], fy, fy, t0, cat, true);
-  stage_rows<R>(D.zm, D.zs, b0, P.n, zin);
-  dense_rows<R>(D.w[0], D.b[0], D.zs, D.fm, zin, t0, true);
-  dense_rows<R>(D.w[1], D.b[1], D.fm, D.fm, t0, cat + fy * R, true);
-  dense_rows<R>(P.wy[2], P.by[2], fy, fy, cat, t0, true);
-  dense_rows<R>(P.wy[3], P.by[3], fy, od, t0, t1, false);
-  for (int e = tid; e < od * R; e += blockDim.x) {
-    const int r = e / od, o = e - r * od;
-    if (b0 + r < P.n) D.y_hat[(int64_t)(b0 + r) * od + o] = t1[o * R + r];
-  }
-  for (int e = tid; e < h * R; e += blockDim.x) {
-    const int k = e / R, r = e - k * R;
-    emb[r * h + k] = cat[e];
-  }
-  lds_barrier();
-  // the tile as a batch of its own: row r of the embedding in LDS is row r of the recurrence, and of this tile's part of hs
-  SeqDev d = D.seq;
-  d.h_init = emb; d.ld_init = h;
-  d.hs = D.seq.hs + (int64_t)b0 * D.seq.Hp;
-  const int rows = min(R, P.n - b0);
-  const int64_t hs_step = (int64_t)P.n * D.seq.Hp;
-  MFM_TUPLE3((small_fwd_body<KQ, R, false, false, false, true>(d, P.T, rows, 0, lds, nullptr, 0u, 0,
-                                                                HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u}, hs_step)))
+  store_rows<R>(act0, E.z, h, b0, P.n, tid);
 }
 
 // ---------------------------------------------------------------- host
@@ -170,85 +114,22 @@ static int64_t imp_ws_floats(int64_t T, int64_t N, const ImpSizes& S, int64_t ma
   return f;
 }
 
-static const int kImpEnc[IMP_ENC] = {8, 8, 2, 8, 20, 8};     // the canonical sizes: encoders -> z_m h = 32 / 8 / 80, -> zy h = 32 ...
-static const int kImpDec[IMP_CASES] = {26, 6, 6};            // ... decoders h = 104 / 24 / 24
+static const int kImpEnc[IMP_ENC] = {8, 8, 2, 8, 20, 8};     // the canonical sizes: encoders -> z_m h = 32 / 8 / 80, -> zy h = 32
 
-template <int R>
-static int imp_encode_launch_one(const ImpEncodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define IMP_CASE(KK, ...) \
-  case KK: return seq_launch_kernel(impute_encode_kernel<R, KK, 0, 0, 0, 0, 0>, "impute_encode_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
-  switch (P.e[0].seq.hk4) { MFM_HK4_CASES(IMP_CASE) }
-#undef IMP_CASE
-  set_error("impute missing: no kernel for h = %d", P.e[0].seq.h);
-  return MFM_ERR_UNSUPPORTED;
-}
-
-template <int R>
-static int imp_decode_launch_one(const ImpDecodeDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define IMP_CASE(KK, ...) \
-  case KK: return seq_launch_kernel(impute_decode_kernel<R, KK, 0, 0>, "impute_decode_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
-  switch (P.d[0].seq.hk4) { MFM_HK4_CASES(IMP_CASE) }
-#undef IMP_CASE
-  set_error("impute missing: no kernel for h = %d", P.d[0].seq.h);
-  return MFM_ERR_UNSUPPORTED;
-}
-
-// the launch(es) of one chunk of n rows; P.e holds the encoders of the cases asked for, two per case; m0: the case when it is one
+// the launch(es) of one chunk of n rows (infer_launch_tuple_or_each); P.d holds the encoders of the cases asked for, two per
+// case; m0: the case when it is one
 template <int R>
 static int imp_encode_launch(ImpEncodeDev& P, int m0, int threads, size_t lds_bytes, hipStream_t stream) {
-  const int tiles = cdiv(P.n, R), ne = P.count;
+  const int ne = P.count;
   bool canon = true;
-  for (int i = 0; i < ne; ++i) canon = canon && P.e[i].seq.hk4 == kImpEnc[ne == IMP_ENC ? i : 2 * m0 + i];
-  if (canon) {
-    for (int i = 0; i < ne; ++i) P.e[i].block_begin = i * tiles;
-    const dim3 grid(ne * tiles), block(threads);
-    static const char* name = "impute_encode_kernel";
-    if (ne == IMP_ENC) return seq_launch_kernel(impute_encode_kernel<R, 8, 8, 2, 8, 20, 8>, name, grid, block, lds_bytes, stream, nullptr, P);
-    if (m0 == 0) return seq_launch_kernel(impute_encode_kernel<R, 8, 8, 0, 0, 0, 0>, name, grid, block, lds_bytes, stream, nullptr, P);
-    if (m0 == 1) return seq_launch_kernel(impute_encode_kernel<R, 2, 8, 0, 0, 0, 0>, name, grid, block, lds_bytes, stream, nullptr, P);
-    return seq_launch_kernel(impute_encode_kernel<R, 20, 8, 0, 0, 0, 0>, name, grid, block, lds_bytes, stream, nullptr, P);
-  }
-  for (int i = 0; i < ne; ++i) {
-    ImpEncodeDev Q = P;
-    Q.e[0] = P.e[i]; Q.e[0].block_begin = 0; Q.count = 1;
-    const int rc = imp_encode_launch_one<R>(Q, tiles, std::max(8 * Q.e[0].seq.Hp, 64), lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
-  }
-  return MFM_OK;
-}
-
-template <int R>
-static int imp_decode_launch(ImpDecodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
-  const int tiles = cdiv(P.n, R), nd = P.count;
-  bool canon = nd == IMP_CASES;
-  for (int i = 0; canon && i < nd; ++i) canon = P.d[i].seq.hk4 == kImpDec[i];
-  if (canon) {
-    for (int i = 0; i < nd; ++i) P.d[i].block_begin = i * tiles;
-    return seq_launch_kernel(impute_decode_kernel<R, 26, 6, 6>, "impute_decode_kernel", dim3(nd * tiles), dim3(threads), lds_bytes,
-                             stream, nullptr, P);
-  }
-  // (one case is one LSTM: its launch is the per-size instantiation)
-  for (int i = 0; i < nd; ++i) {
-    ImpDecodeDev Q = P;
-    Q.d[0] = P.d[i]; Q.d[0].block_begin = 0; Q.count = 1;
-    const int rc = imp_decode_launch_one<R>(Q, tiles, std::max(8 * Q.d[0].seq.Hp, 64), lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
-  }
-  return MFM_OK;
-}
-
-// grouped GEMM over `nprob` problems, MFM_GEMM_MAXP at a time; fill(p, desc) describes problem p
-template <class F>
-static int imp_gemm(int nprob, hipStream_t stream, F fill) {
-  MfmGemmDesc g[MFM_GEMM_MAXP];
-  for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
-    const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
-    memset(g, 0, sizeof(MfmGemmDesc) * cnt);
-    for (int i = 0; i < cnt; ++i) fill(p0 + i, g[i]);
-    const int rc = gemm_group_launch(g, cnt, stream);
-    if (rc != MFM_OK) return rc;
-  }
-  return MFM_OK;
+  for (int i = 0; i < ne; ++i) canon = canon && P.d[i].seq.hk4 == kImpEnc[ne == IMP_ENC ? i : 2 * m0 + i];
+  void (*kernel)(const ImpEncodeDev) = nullptr;
+  if (canon && ne == IMP_ENC) kernel = impute_encode_kernel<R, 8, 8, 2, 8, 20, 8>;
+  else if (canon && m0 == 0) kernel = impute_encode_kernel<R, 8, 8, 0, 0, 0, 0>;
+  else if (canon && m0 == 1) kernel = impute_encode_kernel<R, 2, 8, 0, 0, 0, 0>;
+  else if (canon) kernel = impute_encode_kernel<R, 20, 8, 0, 0, 0, 0>;
+  return infer_launch_tuple_or_each<R>("impute missing", "impute_encode_kernel", P, kernel,
+                                       [](auto kk) { return impute_encode_kernel<R, decltype(kk)::value, 0, 0, 0, 0, 0>; }, threads, lds_bytes, stream);
 }
 
 static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const float* const* prm, const float* x, float* ws,
@@ -258,8 +139,8 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
   MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
   for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
   MFM_REQUIRE(cases == 1 || cases == 2 || cases == 4 || cases == 7, "%s: cases = %d (bit 0 l, bit 1 a, bit 2 v: one of them, or all three)", who, cases);
-  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
-  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  int rc = infer_check_rows(who, N, max_rows);
+  if (rc != MFM_OK) return rc;
   // (x is read by the gather alone, element by element; the GEMMs and the recurrences read the workspace 16 bytes at a time)
   MFM_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)ws & 15) == 0, "%s: x must be 4-byte aligned, the workspace 16-byte aligned", who);
   ImpSizes S;
@@ -279,17 +160,13 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
 
   const int rows = (int)gen_rows(N, max_rows);
   const int Re = gen_tile_rows(2 * S.nc, rows), Rd = gen_tile_rows(S.nc, rows);
-  // what the on-chip recurrence does not cover is refused: the caller composes the granular operations instead
   int enc_maxw = 1, enc_threads = 64, dec_maxw = std::max(std::max(S.zy, S.fy), S.od), dec_threads = 64, maxd = 1, maxhp = 16;
   size_t enc_floats = 0, dec_seq = 0;
   for (int c = 0; c < S.nc; ++c) {
     const int m = S.cs[c];
     const int hs[3] = {S.z[m], S.zy, S.fy + S.fm[m]};
     for (int i = 0; i < 3; ++i)
-      if (hs[i] > MFM_SEQ_MAX_RESIDENT_H) {
-        set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, hs[i], MFM_SEQ_MAX_RESIDENT_H);
-        return MFM_ERR_UNSUPPORTED;
-      }
+      if ((rc = infer_check_resident(who, hs[i])) != MFM_OK) return rc;
     enc_maxw = std::max(enc_maxw, std::max(hs[0], hs[1]));
     enc_threads = std::max(enc_threads, 8 * round_up(std::max(hs[0], hs[1]), 16));
     dec_maxw = std::max(dec_maxw, std::max(hs[2], std::max(S.z[m], S.fm[m])));
@@ -299,22 +176,13 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
     maxhp = std::max(maxhp, round_up(std::max(std::max(hs[0], hs[1]), hs[2]), 16));
   }
   for (int c = 0; c < S.nc; ++c)
-    for (int i = 0; i < 2; ++i) {
-      const int h = i ? S.zy : S.z[S.cs[c]];
-      enc_floats = std::max(enc_floats, std::max(seq_lds_floats(h, Re), (size_t)2 * round_up(h, 16) * Re + (size_t)enc_maxw * Re));
-    }
-  const size_t enc_lds = (enc_floats * sizeof(float) + 15) / 16 * 16;
-  const size_t dec_lds = ((dec_seq + (size_t)5 * dec_maxw * Rd) * sizeof(float) + 15) / 16 * 16;
-  if (enc_lds > 160 * 1024 || dec_lds > 160 * 1024) {
-    set_error("%s: %zu bytes of LDS per workgroup (widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who,
-              std::max(enc_lds, dec_lds), std::max(enc_maxw, dec_maxw), enc_lds > dec_lds ? Re : Rd);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  MFM_REQUIRE((int64_t)rows * T * std::max(S.D, maxd) < ((int64_t)1 << 31) && (int64_t)rows * T * 4 * maxhp < ((int64_t)1 << 31),
-              "%s: a chunk of %d rows x %d steps is too large for one product; pass a row cap", who, rows, T);
+    for (int i = 0; i < 2; ++i) enc_floats = std::max(enc_floats, enc_lds_floats(i ? S.zy : S.z[S.cs[c]], Re, 1, enc_maxw));
+  const size_t enc_lds = lds_bytes_of(enc_floats), dec_lds = lds_bytes_of(dec_seq + (size_t)5 * dec_maxw * Rd);
+  if ((rc = infer_check_lds(who, std::max(enc_lds, dec_lds), std::max(enc_maxw, dec_maxw), enc_lds > dec_lds ? Re : Rd)) != MFM_OK) return rc;
+  if ((rc = infer_check_chunk(who, rows, T, std::max(std::max(S.D, maxd), 4 * maxhp), "product")) != MFM_OK) return rc;
 
   ImpEncodeDev PE;
-  ImpDecodeDev PD;
+  DecodeDev PD;
   memset(&PE, 0, sizeof(PE));
   memset(&PD, 0, sizeof(PD));
   const float* fcw[IMP_CASES]; const float* fcb[IMP_CASES];
@@ -327,19 +195,15 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
     const int m = S.cs[c];
     const float* const* p = prm + m * IMP_CASE_PTRS;
     for (int i = 0; i < 2; ++i) {
-      ImpEnc& E = PE.e[2 * c + i];
-      const int h = i ? S.zy : S.z[m];
-      E.seq.gates = w0; w0 += (int64_t)rows * T * 4 * round_up(h, 16);
-      E.seq.w_ih = p[6 * i]; E.seq.w_hh = p[6 * i + 1]; E.seq.b_ih = p[6 * i + 2]; E.seq.b_hh = p[6 * i + 3];
-      E.seq.h = h; E.seq.Hp = round_up(h, 16); E.seq.hk4 = gen_hk4(h); E.seq.is_dec = 0;
+      ImpEnc& E = PE.d[2 * c + i];
+      seq_fill(E.seq, p[6 * i], p[6 * i + 1], p[6 * i + 2], p[6 * i + 3], i ? S.zy : S.z[m], 0);
+      E.seq.gates = w0; w0 += (int64_t)rows * T * 4 * E.seq.Hp;
       E.w = p[6 * i + 4]; E.b = p[6 * i + 5];
     }
     for (int i = 0; i < 2; ++i) { zbuf[c][i] = w0; w0 += up4((int64_t)rows * (i ? S.zy : S.z[m])); }
-    ImpDec& Dd = PD.d[c];
-    const int h = S.fy + S.fm[m];
-    Dd.seq.w_ih = p[16]; Dd.seq.w_hh = p[17]; Dd.seq.b_ih = p[18]; Dd.seq.b_hh = p[19];
+    DecOne& Dd = PD.d[c];
+    seq_fill(Dd.seq, p[16], p[17], p[18], p[19], S.fy + S.fm[m], 1);
     fcw[c] = p[20]; fcb[c] = p[21];
-    Dd.seq.h = h; Dd.seq.Hp = round_up(h, 16); Dd.seq.hk4 = gen_hk4(h); Dd.seq.is_dec = 1;
     Dd.seq.hs = w0; w0 += (int64_t)rows * T * Dd.seq.Hp;
     for (int l = 0; l < 2; ++l) { Dd.w[l] = p[12 + 2 * l]; Dd.b[l] = p[13 + 2 * l]; }
     Dd.zs = S.z[m]; Dd.fm = S.fm[m];
@@ -360,40 +224,29 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
     MFM_LAUNCH_CHECK("impute_gather_kernel");
     // gates_e[t][i][g][u] = pair_e[t][i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros.  The gathered pair of a
     // chunk is one [T * n, ld] matrix whatever the chunk
-    const int ne = PE.count;
-    int rc = imp_gemm(ne, stream, [&](int e, MfmGemmDesc& d) {
-      const int c = e / 2, k = G.k[c];
-      const SeqDev& s = PE.e[e].seq;
-      d.a = G.out[c]; d.a_sm = G.ld[c]; d.a_sk = 1; d.a_sz = 0;
-      d.b = s.w_ih; d.b_sz = (int64_t)s.h * k; d.b_sn = k; d.b_sk = 1;
-      d.c = s.gates; d.c_sz = s.Hp; d.ldc = 4 * (int64_t)s.Hp;
-      d.bias = s.b_ih; d.bias2 = s.b_hh; d.bias_sz = s.h;
-      d.m = T * n; d.n = s.Hp; d.n_valid = s.h; d.k = k; d.batch = 4; d.split_k = 1;
-      d.alpha = 1.0f;
+    rc = gemm_group_each(PE.count, stream, [&](int e, MfmGemmDesc& d) {
+      const int c = e / 2;
+      xproj_desc(d, PE.d[e].seq, G.out[c], G.ld[c], G.k[c], T * n, PE.d[e].seq.gates);
     });
     if (rc != MFM_OK) return rc;
     PE.n = PD.n = n;
     for (int c = 0; c < S.nc; ++c) {
       const int m = S.cs[c];
-      PE.e[2 * c].z = zbuf[c][0]; PE.e[2 * c + 1].z = zbuf[c][1];
+      PE.d[2 * c].z = zbuf[c][0]; PE.d[2 * c + 1].z = zbuf[c][1];
       PD.d[c].zm = zbuf[c][0]; PD.d[c].zy = zbuf[c][1];
       PD.d[c].y_hat = out[2 * m + 1] + n0 * S.od;
     }
     rc = (Re == 1) ? imp_encode_launch<1>(PE, S.cs[0], enc_threads, enc_lds, stream) : imp_encode_launch<4>(PE, S.cs[0], enc_threads, enc_lds, stream);
     if (rc != MFM_OK) return rc;
-    rc = (Rd == 1) ? imp_decode_launch<1>(PD, dec_threads, dec_lds, stream) : imp_decode_launch<4>(PD, dec_threads, dec_lds, stream);
+    rc = decode_factors_launch(who, PD, Rd, dec_threads, dec_lds, stream);
     if (rc != MFM_OK) return rc;
     // x_hat_m[t][n0 + i] = hs_m[t][i] . Wfc_m^T + b: one problem per case -- the whole split as one matrix, a chunk as T batched
     // products (the stored h of a chunk is [T][n, Hp], its rows of x_hat_m lie N rows apart per step)
-    rc = imp_gemm(PD.count, stream, [&](int c, MfmGemmDesc& d) {
+    rc = gemm_group_each(PD.count, stream, [&](int c, MfmGemmDesc& d) {
       const int m = S.cs[c];
       const SeqDev& s = PD.d[c].seq;
-      d.a = s.hs; d.a_sm = s.Hp; d.a_sk = 1; d.a_sz = (int64_t)n * s.Hp;
-      d.b = fcw[c]; d.b_sn = s.h; d.b_sk = 1; d.b_sz = 0;
-      d.c = out[2 * m] + n0 * S.dm[m]; d.ldc = S.dm[m]; d.c_sz = N * S.dm[m];
-      d.bias = fcb[c]; d.bias_sz = 0;
-      d.m = whole ? T * n : n; d.n = S.dm[m]; d.n_valid = S.dm[m]; d.k = s.h; d.batch = whole ? 1 : T; d.split_k = 1;
-      d.alpha = 1.0f;
+      dec_fc1_desc(d, s, s.hs, fcw[c], fcb[c], out[2 * m] + n0 * S.dm[m], S.dm[m], whole ? T * n : n, whole ? 1 : T, (int64_t)n * s.Hp,
+                   N * S.dm[m]);
     });
     if (rc != MFM_OK) return rc;
   }

@@ -1,0 +1,179 @@
+// What the inference launches built on small_fwd_body<.., REC = false> share (predict.hip, generate.hip, impute.hip).  Device: a
+// tile's rows into LDS and back out.  Host: the sizing rules (chunk rows, tile rows, the LDS the recurrence lays out), the
+// refusals and argument checks, the SeqDev of an LSTM, the grouped GEMMs around the recurrence, and the two launch rules.
+//
+// The launch rules: a kernel that runs several LSTMs in one launch picks its body per block with a switch, and that switch is
+// instantiated for the canonical size tuples only (the rule of lstm_seq_small.hip: a switch over all sizes costs the register
+// allocation of every body).  Any other size combination takes one launch per LSTM of the same kernel, instantiated for that
+// LSTM's size alone (infer_launch_tuple_or_each, infer_launch_hk4).
+#pragma once
+#include <algorithm>
+#include <type_traits>
+
+#include "lstm_seq_small_dev.h"
+#include "dense_rows_dev.h"
+
+namespace mfm {
+
+// rows [b0, b0 + R) of z [n, zs] -> LDS [zs][R]; rows beyond n: zeros
+template <int R>
+__device__ __forceinline__ void stage_rows(const float* __restrict__ z, const int zs, const int b0, const int n, float* out) {
+  for (int e = threadIdx.x; e < zs * R; e += blockDim.x) {
+    const int r = e / zs, k = e - r * zs;
+    out[k * R + r] = (b0 + r < n) ? z[(int64_t)(b0 + r) * zs + k] : 0.0f;
+  }
+  lds_barrier();
+}
+
+// the way back: LDS [w][R] -> rows [b0, b0 + R) of dst [n, w]; rows beyond n are not written.  tid: threadIdx.x as the kernel
+// read it at its top -- a second read here, behind the per-block switch, cost six encoder instantiations 16 bytes of scratch
+template <int R>
+__device__ __forceinline__ void store_rows(const float* act, float* dst, const int w, const int b0, const int n, const int tid) {
+  for (int e = tid; e < w * R; e += blockDim.x) {
+    const int r = e / w, o = e - r * w;
+    if (b0 + r < n) dst[(int64_t)(b0 + r) * w + o] = act[o * R + r];
+  }
+}
+
+// ---------------------------------------------------------------- the decoders' launch (generate.hip; impute.hip launches it too)
+#define INFER_DEC 3
+struct DecOne {
+  SeqDev seq;                                  // w_ih, w_hh, b_ih, b_hh, h = fy + fm, Hp, hk4, is_dec; hs: this chunk's [T, n, Hp]
+  const float* w[2]; const float* b[2];        // z_m -> f_m: fc1, fc2
+  const float* zm; const float* zy;            // this chunk's rows [n, zs] / [n, zys]
+  float* y_hat;                                // this chunk's rows [n, od]; null: this decoder's workgroups skip the classifier
+  int zs, fm, block_begin;
+};
+struct DecodeDev {
+  DecOne d[INFER_DEC];
+  const float* wy[4]; const float* by[4];      // zy_to_fy fc1, fc2, fy_to_y fc1, fc2
+  int count, T, n, zys, fy, od, maxw, seq_floats;
+};
+// decode_factors_kernel on one chunk of P.n rows in tiles of R (1 or 4) rows; P.d[0 .. P.count) filled but for block_begin.  The
+// kernel's instantiations stay in generate.hip alone
+int decode_factors_launch(const char* who, DecodeDev& P, int R, int threads, size_t lds_bytes, hipStream_t stream);
+
+// ---------------------------------------------------------------- host: sizes
+static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
+static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }
+
+// floats of LDS small_fwd_body<KQ, R> lays out for hidden size h (its two h buffers, then the weight staging panel / its record
+// and x-projection buffers, layout kept), a multiple of 4
+static size_t seq_lds_floats(int h, int R) {
+  const size_t HKB = (size_t)round_up(4 * round_up(cdiv(h, 4), 2), 16);
+  const size_t hh = (R == 1 && (h & 3) == 0) ? 0 : (size_t)h * h;
+  const size_t rec = (2 * 6 + 2 * 4) * HKB * R;
+  return (2 * HKB * R + std::max(2 * hh, rec) + 3) / 4 * 4;
+}
+// the same for an encoder workgroup that keeps the two h buffers and puts `nact` activations [maxw][R] of its heads behind them
+static size_t enc_lds_floats(int h, int R, int nact, int maxw) {
+  return std::max(seq_lds_floats(h, R), (size_t)2 * round_up(h, 16) * R + (size_t)nact * maxw * R);
+}
+static size_t lds_bytes_of(size_t floats) { return (floats * sizeof(float) + 15) / 16 * 16; }
+
+static int gen_hk4(int h) { return round_up(cdiv(h, 4), 2); }
+
+// one-row tiles below 6 workgroups per CU over the whole launch (the rule of the training recurrences), else four-row tiles
+static int gen_tile_rows(int lstms, int rows) { return ((long)lstms * rows < 6L * device_cus()) ? 1 : 4; }
+
+static void seq_fill(SeqDev& s, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int h, int is_dec) {
+  s.w_ih = w_ih; s.w_hh = w_hh; s.b_ih = b_ih; s.b_hh = b_hh;
+  s.h = h; s.Hp = round_up(h, 16); s.hk4 = gen_hk4(h); s.is_dec = is_dec;
+}
+
+// ---------------------------------------------------------------- host: checks (MFM_OK, or the error set and its code)
+static int infer_check_rows(const char* who, int64_t N, int64_t max_rows) {
+  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
+  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  return MFM_OK;
+}
+// what the on-chip recurrence does not cover is refused: the caller composes the granular operations (the training forward) instead
+static int infer_check_resident(const char* who, int h) {
+  if (h <= MFM_SEQ_MAX_RESIDENT_H) return MFM_OK;
+  set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, h, MFM_SEQ_MAX_RESIDENT_H);
+  return MFM_ERR_UNSUPPORTED;
+}
+// h: named in front of the widest layer when not 0
+static int infer_check_lds(const char* who, size_t lds_bytes, int maxw, int R, int h = 0) {
+  if (lds_bytes <= 160 * 1024) return MFM_OK;
+  char hs[24] = "";
+  if (h) snprintf(hs, sizeof(hs), "h = %d, ", h);
+  set_error("%s: %zu bytes of LDS per workgroup (%swidest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, hs, maxw, R);
+  return MFM_ERR_UNSUPPORTED;
+}
+// the GEMMs index a chunk's operands with 32 bits; width: the widest row among them; what: "projection" / "product"
+static int infer_check_chunk(const char* who, int rows, int T, int64_t width, const char* what) {
+  MFM_REQUIRE((int64_t)rows * T * width < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large for one %s; pass a row cap",
+              who, rows, T, what);
+  return MFM_OK;
+}
+
+// ---------------------------------------------------------------- host: the grouped GEMMs
+// grouped GEMM over `nprob` problems, MFM_GEMM_MAXP at a time; fill(p, desc) describes problem p on a zeroed descriptor
+template <class F>
+static int gemm_group_each(int nprob, hipStream_t stream, F fill) {
+  MfmGemmDesc g[MFM_GEMM_MAXP];
+  for (int p0 = 0; p0 < nprob; p0 += MFM_GEMM_MAXP) {
+    const int cnt = std::min(MFM_GEMM_MAXP, nprob - p0);
+    memset(g, 0, sizeof(MfmGemmDesc) * cnt);
+    for (int i = 0; i < cnt; ++i) fill(p0 + i, g[i]);
+    const int rc = gemm_group_launch(g, cnt, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
+
+// the x-projection of LSTM s: gates [m, 4, Hp] = a [m, k] (rows lda apart) . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
+static void xproj_desc(MfmGemmDesc& d, const SeqDev& s, const float* a, int64_t lda, int k, int m, float* gates) {
+  d.a = a; d.a_sm = lda; d.a_sk = 1; d.a_sz = 0;
+  d.b = s.w_ih; d.b_sz = (int64_t)s.h * k; d.b_sn = k; d.b_sk = 1;
+  d.c = gates; d.c_sz = s.Hp; d.ldc = 4 * (int64_t)s.Hp;
+  d.bias = s.b_ih; d.bias2 = s.b_hh; d.bias_sz = s.h;
+  d.m = m; d.n = s.Hp; d.n_valid = s.h; d.k = k; d.batch = 4; d.split_k = 1;
+  d.alpha = 1.0f;
+}
+
+// fc1 of decoder s over its stored h: c [m, dm] = hs [m, Hp] . w^T + b, `batch` times a_sz / c_sz apart
+static void dec_fc1_desc(MfmGemmDesc& d, const SeqDev& s, const float* hs, const float* w, const float* b, float* c, int dm, int m,
+                         int batch = 1, int64_t a_sz = 0, int64_t c_sz = 0) {
+  d.a = hs; d.a_sm = s.Hp; d.a_sk = 1; d.a_sz = a_sz;
+  d.b = w; d.b_sn = s.h; d.b_sk = 1;
+  d.c = c; d.ldc = dm; d.c_sz = c_sz;
+  d.bias = b;
+  d.m = m; d.n = dm; d.n_valid = dm; d.k = s.h; d.batch = batch; d.split_k = 1;
+  d.alpha = 1.0f;
+}
+
+// ---------------------------------------------------------------- host: the two launch rules
+// the kernel instantiated for s.hk4 alone: pick(std::integral_constant<int, hk4>) names it
+template <class Dev, class Pick>
+static int infer_launch_hk4(const char* who, const char* name, const SeqDev& s, Pick pick, const Dev& P, int grid, int threads,
+                            size_t lds_bytes, hipStream_t stream) {
+#define MFM_INFER_CASE(KK, ...) \
+  case KK: return seq_launch_kernel(pick(std::integral_constant<int, KK>()), name, dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
+  switch (s.hk4) { MFM_HK4_CASES(MFM_INFER_CASE) }
+#undef MFM_INFER_CASE
+  set_error("%s: no kernel for h = %d", who, s.h);
+  return MFM_ERR_UNSUPPORTED;
+}
+
+// the launch(es) of one chunk of P.n rows in tiles of R: the LSTMs P.d[0 .. P.count) in one launch of `canon`, the kernel of
+// their canonical size tuple -- or, canon null (other sizes), one launch per LSTM of the kernel pick names for its size
+template <int R, class Dev, class Pick>
+static int infer_launch_tuple_or_each(const char* who, const char* name, Dev& P, void (*canon)(const Dev), Pick pick, int threads,
+                                      size_t lds_bytes, hipStream_t stream) {
+  const int tiles = cdiv(P.n, R);
+  if (canon) {
+    for (int i = 0; i < P.count; ++i) P.d[i].block_begin = i * tiles;
+    return seq_launch_kernel(canon, name, dim3(P.count * tiles), dim3(threads), lds_bytes, stream, nullptr, P);
+  }
+  for (int i = 0; i < P.count; ++i) {
+    Dev Q = P;
+    Q.d[0] = P.d[i]; Q.d[0].block_begin = 0; Q.count = 1;
+    const int rc = infer_launch_hk4(who, name, Q.d[0].seq, pick, Q, tiles, std::max(8 * Q.d[0].seq.Hp, 64), lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
+
+}  // namespace mfm

@@ -109,13 +109,12 @@ __device__ __forceinline__ void wf_img_write(const WtImgItem* items, const int n
 // ---------------------------------------------------------------- kernel wrappers: what every sequence kernel opens with
 // declares `di`: the LSTM that block `bid` of the multi-LSTM launch L belongs to (its tile: bid - L.d[di].block_begin).  A macro:
 // as an inlined function the same loop comes out with other scalar registers, and these kernels are kept instruction for instruction
-// (MFM_SEQ_BLOCK_OF: the same for a launch descriptor whose per-LSTM array has another name, generate.hip)
-#define MFM_SEQ_BLOCK_OF(L, arr, bid, di) \
-  int di = 0;                             \
-  _Pragma("unroll 1")                     \
-  for (int i = 1; i < (L).count; ++i)     \
-    if ((bid) >= (L).arr[i].block_begin) di = i;
-#define MFM_SEQ_BLOCK_LSTM(L, bid, di) MFM_SEQ_BLOCK_OF(L, d, bid, di)
+// (any launch descriptor with `count` and a per-LSTM array `d` whose elements carry block_begin: SeqLaunch, those of infer_dev.h)
+#define MFM_SEQ_BLOCK_LSTM(L, bid, di) \
+  int di = 0;                          \
+  _Pragma("unroll 1")                  \
+  for (int i = 1; i < (L).count; ++i)  \
+    if ((bid) >= (L).d[i].block_begin) di = i;
 // every SeqDev::hk4 the weight-resident kernels are instantiated for: X(hk4, ...) once per value
 #define MFM_HK4_CASES(X, ...)                                                                                         \
   X(2, __VA_ARGS__) X(4, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__) X(10, __VA_ARGS__) X(12, __VA_ARGS__)      \

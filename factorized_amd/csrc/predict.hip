@@ -21,10 +21,7 @@
 // bit-identical from run to run.  Nobody waits or spins.
 // Any N >= 1, T >= 1: the grid is ceil(n / R) per chunk; rows beyond the chunk are neither read (clamped re-reads of the last
 // row inside the body) nor written.
-#include <algorithm>
-
-#include "lstm_seq_small_dev.h"
-#include "dense_rows_dev.h"
+#include "infer_dev.h"
 
 namespace mfm {
 
@@ -60,10 +57,7 @@ __global__ __launch_bounds__(1024) void predict_klef_kernel(const PredictDev P) 
   }
   // in == act1: y_hat of the tile as [od][R]
   const int od = P.od;
-  for (int e = tid; e < od * R; e += blockDim.x) {
-    const int r = e / od, o = e - r * od;
-    if (b0 + r < P.n) P.y_hat[(int64_t)(b0 + r) * od + o] = in[o * R + r];
-  }
+  store_rows<R>(in, P.y_hat, od, b0, P.n, tid);
   if (!P.y || !P.loss || tid >= 64) return;       // (the first wave alone goes on)
   float part = 0.0f;
   if (P.loss_kind == 0) {
@@ -99,31 +93,15 @@ __global__ __launch_bounds__(1024) void predict_klef_kernel(const PredictDev P) 
   }
 }
 
-static int64_t predict_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
-
 // floats: the x-projections of one row chunk, one loss partial per row (a one-row tile each at most), the ticket word (+ pad)
 static int64_t predict_ws_floats(int64_t T, int64_t N, int64_t h, int64_t max_rows) {
-  const int64_t Hp = (h + 15) / 16 * 16;
-  return predict_rows(N, max_rows) * T * 4 * Hp + N + 4;
-}
-
-static size_t predict_lds_bytes(int h, int R, int maxw) {
-  const size_t HKB = (size_t)round_up(4 * round_up(cdiv(h, 4), 2), 16);
-  const size_t hh = (R == 1 && (h & 3) == 0) ? 0 : (size_t)h * h;       // the weight staging panel of small_fwd_body
-  const size_t rec = (2 * 6 + 2 * 4) * HKB * R;                          // its record / x-projection buffers (layout kept)
-  const size_t heads = 2 * (size_t)maxw * R;
-  const size_t need = 2 * HKB * R + std::max(std::max(2 * hh, rec), heads);
-  return (need * sizeof(float) + 15) / 16 * 16;
+  return gen_rows(N, max_rows) * T * 4 * hp_of(h) + N + 4;
 }
 
 template <int R>
 static int predict_launch_r(const PredictDev& P, int grid, int threads, size_t lds_bytes, hipStream_t stream) {
-#define PRED_CASE(KK, ...) \
-  case KK: return seq_launch_kernel(predict_klef_kernel<KK, R>, "predict_klef_kernel", dim3(grid), dim3(threads), lds_bytes, stream, nullptr, P);
-  switch (P.seq.hk4) { MFM_HK4_CASES(PRED_CASE) }
-#undef PRED_CASE
-  set_error("predict klef: no kernel for h = %d", P.seq.h);
-  return MFM_ERR_UNSUPPORTED;
+  return infer_launch_hk4("predict klef", "predict_klef_kernel", P.seq, [](auto kk) { return predict_klef_kernel<decltype(kk)::value, R>; },
+                          P, grid, threads, lds_bytes, stream);
 }
 
 static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, int loss_kind, const float* params,
@@ -135,27 +113,18 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
   MFM_REQUIRE(loss_kind == 0 || loss_kind == 1, "%s: unknown loss kind %d (0 = L1, 1 = cross entropy)", who, loss_kind);
   MFM_REQUIRE(params && offs && x && ws && y_hat, "%s: bad arguments (params, offsets, x, workspace and y_hat must not be null)", who);
   MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
-  MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);
+  int rc = infer_check_rows(who, N, max_rows);
+  if (rc != MFM_OK) return rc;
   for (int i = 0; i < 4 + 2 * PRED_LAYERS; ++i)
     MFM_REQUIRE(offs[i] >= 0 && (i >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)", who, i, (long long)offs[i]);
   const int maxw = std::max(std::max(h, zy), std::max(fy, od));
-  const int rows = (int)predict_rows(N, max_rows);
-  const int R = ((long)rows < 6L * device_cus()) ? 1 : 4;
-  // what the on-chip recurrence does not cover is refused: the caller runs the training forward instead
-  if (h > MFM_SEQ_MAX_RESIDENT_H) {
-    set_error("%s: hidden size h = %d is beyond the register-resident recurrence (at most %d)", who, h, MFM_SEQ_MAX_RESIDENT_H);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  const size_t lds_bytes = predict_lds_bytes(h, R, maxw);
-  if (lds_bytes > 160 * 1024) {
-    set_error("%s: %zu bytes of LDS per workgroup (h = %d, widest layer %d, %d rows per workgroup) exceed the 160 KB of a CU", who, lds_bytes, h, maxw, R);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  MFM_REQUIRE((int64_t)rows * T * D < ((int64_t)1 << 31) && (int64_t)rows * T * 4 * round_up(h, 16) < ((int64_t)1 << 31),
-              "%s: a chunk of %d rows x %d steps is too large for one projection; pass a row cap", who, rows, T);
+  const int rows = (int)gen_rows(N, max_rows);
+  const int R = gen_tile_rows(1, rows), Hp = round_up(h, 16);
+  const size_t lds_bytes = lds_bytes_of(enc_lds_floats(h, R, 2, maxw));      // (the heads ping-pong between two activations)
+  if ((rc = infer_check_resident(who, h)) != MFM_OK) return rc;
+  if ((rc = infer_check_lds(who, lds_bytes, maxw, R, h)) != MFM_OK) return rc;
+  if ((rc = infer_check_chunk(who, rows, T, std::max(D, 4 * Hp), "projection")) != MFM_OK) return rc;
 
-  const int Hp = round_up(h, 16);
   float* gates = ws;
   float* partials = ws + (int64_t)rows * T * 4 * Hp;
   int* ticket = reinterpret_cast<int*>(partials + N);
@@ -167,9 +136,8 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
 
   PredictDev P;
   memset(&P, 0, sizeof(P));
-  P.seq.gates = gates; P.seq.w_hh = params + offs[1]; P.seq.w_ih = params + offs[0];
-  P.seq.b_ih = params + offs[2]; P.seq.b_hh = params + offs[3];
-  P.seq.h = h; P.seq.Hp = Hp; P.seq.hk4 = round_up(cdiv(h, 4), 2); P.seq.is_dec = 0;
+  P.seq.gates = gates;
+  seq_fill(P.seq, params + offs[0], params + offs[1], params + offs[2], params + offs[3], h, 0);
   const int K[PRED_LAYERS] = {h, h, zy, fy, fy, fy}, Nn[PRED_LAYERS] = {h, zy, fy, fy, fy, od};
   const int relu[PRED_LAYERS] = {0, 0, 1, 1, 1, 0};
   for (int l = 0; l < PRED_LAYERS; ++l) {
@@ -186,25 +154,11 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
     // gates[t][i][g][u] = x[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
-    MfmGemmDesc g[MFM_GEMM_MAXP];
     const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
-    const int nprob = whole ? 1 : T;
-    for (int t0 = 0; t0 < nprob; t0 += MFM_GEMM_MAXP) {
-      const int cnt = std::min(MFM_GEMM_MAXP, nprob - t0);
-      memset(g, 0, sizeof(MfmGemmDesc) * cnt);
-      for (int i = 0; i < cnt; ++i) {
-        const int t = t0 + i;
-        MfmGemmDesc& d = g[i];
-        d.a = x + ((int64_t)t * N + n0) * D; d.a_sm = D; d.a_sk = 1; d.a_sz = 0;
-        d.b = P.seq.w_ih; d.b_sz = (int64_t)h * D; d.b_sn = D; d.b_sk = 1;
-        d.c = gates + (int64_t)t * n * 4 * Hp; d.c_sz = Hp; d.ldc = 4 * (int64_t)Hp;
-        d.bias = P.seq.b_ih; d.bias2 = P.seq.b_hh; d.bias_sz = h;
-        d.m = whole ? T * n : n; d.n = Hp; d.n_valid = h; d.k = D; d.batch = 4; d.split_k = 1;
-        d.alpha = 1.0f;
-      }
-      const int rc = gemm_group_launch(g, cnt, stream);
-      if (rc != MFM_OK) return rc;
-    }
+    rc = gemm_group_each(whole ? 1 : T, stream, [&](int t, MfmGemmDesc& d) {
+      xproj_desc(d, P.seq, x + ((int64_t)t * N + n0) * D, D, D, whole ? T * n : n, gates + (int64_t)t * n * 4 * Hp);
+    });
+    if (rc != MFM_OK) return rc;
     P.n = n;
     P.y = !with_loss ? nullptr
                      : (loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od)
@@ -212,8 +166,7 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
     P.y_hat = y_hat + n0 * od;
     P.wg_base = wg_base;
     const int grid = cdiv(n, R);
-    const int rc = (R == 1) ? predict_launch_r<1>(P, grid, threads, lds_bytes, stream)
-                            : predict_launch_r<4>(P, grid, threads, lds_bytes, stream);
+    rc = (R == 1) ? predict_launch_r<1>(P, grid, threads, lds_bytes, stream) : predict_launch_r<4>(P, grid, threads, lds_bytes, stream);
     if (rc != MFM_OK) return rc;
     wg_base += grid;
   }
