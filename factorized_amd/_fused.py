@@ -170,6 +170,24 @@ class _FusedEngineMixin:
         with torch.no_grad():
             return loss_fn(self._predict(x, None)["y_hat"], y)
 
+    def objective(self, x, y):
+        """x [T, N, D], labels -> Objective(loss, disc, gen_l, gen_a, gen_v, reg) (a namedtuple, engine.Objective) of 0-d float32
+        device tensors, all views of one [6] tensor: the whole validation objective of the reference's drivers
+        (mfm_mosi.py:319-324, :724-726, :826-845), loss = disc + lda_xl gen_l + lda_xa gen_a + lda_xv gen_v + lda_mmd reg with the
+        config's lambdas (default 1) -- always the deterministic eval computation (dropout off, z = the mean heads),
+        `self.training` left as found, without autograd, lazy outputs or a host read; `.loss` is accepted as is by
+        KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  MFM_KL_EF: engine.objective (no plan, x_hat never written);
+        the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must survive it).
+        MFM_KL / MFM, and sizes the fused entry refuses: the fused eval forward's loss slots."""
+        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
+        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        if self._engine_variant == "mmd":
+            g = getattr(self, "mmd_gauss", None)
+            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        with torch.no_grad():
+            return eng.objective(x, y)
+
     # ------------------------------------------------------------------ the factorized latents and generation from them
     def _split(self, x):
         return x[:, :, :self.d_l], x[:, :, self.d_l:self.d_l + self.d_a], x[:, :, self.d_l + self.d_a:]

@@ -25,16 +25,8 @@
 
 namespace mfm {
 
-#define GEN_ENC 4
+#define GEN_ENC INFER_ENC
 #define GEN_DEC INFER_DEC
-
-struct EncOne {
-  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
-  const float* w[3]; const float* b[3];        // fc1, the mean head, the logvar head
-  float* mu; float* lv;                        // this chunk's rows [n, zs]
-  int zs, block_begin;
-};
-struct EncodeDev { EncOne d[GEN_ENC]; int count, T, n, maxw; };
 
 template <int R, int K0, int K1, int K2, int K3>
 __global__ __launch_bounds__(1024) void encode_klef_kernel(const EncodeDev P) {
@@ -122,23 +114,10 @@ int decode_factors_launch(const char* who, DecodeDev& P, int R, int threads, siz
   return (R == 1) ? decode_launch<1>(who, P, threads, lds_bytes, stream) : decode_launch<4>(who, P, threads, lds_bytes, stream);
 }
 
-static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, int64_t zv, int64_t max_rows) {
-  return gen_rows(N, max_rows) * T * 4 * (hp_of(zl) + hp_of(za) + hp_of(zv) + hp_of(zl + za + zv));
-}
-static int64_t decode_ws_floats(int64_t T, int64_t N, int64_t fy, int64_t fl, int64_t fa, int64_t fv, int64_t max_rows) {
-  return gen_rows(N, max_rows) * T * (hp_of(fy + fl) + hp_of(fy + fa) + hp_of(fy + fv));
-}
-
 #define ENC_OFFS 40      // per encoder: lstm weight_ih, weight_hh, bias_ih, bias_hh, then weight and bias of fc1, mean head, logvar head
 
-static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int za, int zv, int zy, const float* params,
-                       const int64_t* offs, const float* x, float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
-  static const char* who = "encode klef";
-  MFM_REQUIRE(T >= 1 && N >= 1 && d_l >= 1 && d_a >= 1 && d_v >= 1 && zl >= 1 && za >= 1 && zv >= 1 && zy >= 1,
-              "%s: sizes must be positive (T %d, N %lld, dims %d %d %d, z %d %d %d %d)", who, T, (long long)N, d_l, d_a, d_v, zl, za, zv, zy);
-  MFM_REQUIRE(params && offs && x && ws && out, "%s: bad arguments (params, offsets, x, workspace and outputs must not be null)", who);
-  for (int i = 0; i < 8; ++i) MFM_REQUIRE(out[i], "%s: output %d is null", who, i);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
+int encode_klef_prepare(const char* who, int T, int64_t N, int d_l, int d_a, int d_v, int zl, int za, int zv, int zy, const float* params,
+                        const int64_t* offs, float* ws, int64_t max_rows, EncLaunch& L) {
   int rc = infer_check_rows(who, N, max_rows);
   if (rc != MFM_OK) return rc;
   for (int i = 0; i < ENC_OFFS; ++i)
@@ -161,8 +140,8 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
   if ((rc = infer_check_lds(who, lds_bytes, maxw, R)) != MFM_OK) return rc;
   if ((rc = infer_check_chunk(who, rows, T, std::max(D, 4 * round_up(hh[3], 16)), "projection")) != MFM_OK) return rc;
 
-  EncodeDev P;
-  memset(&P, 0, sizeof(P));
+  EncodeDev& P = L.P;
+  memset(&L, 0, sizeof(L));
   float* g0 = ws;
   for (int i = 0; i < GEN_ENC; ++i) {
     EncOne& E = P.d[i];
@@ -171,26 +150,45 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
     E.seq.gates = g0; g0 += (int64_t)rows * T * 4 * E.seq.Hp;
     for (int l = 0; l < 3; ++l) { E.w[l] = params + o[4 + 2 * l]; E.b[l] = params + o[5 + 2 * l]; }
     E.zs = zs[i];
+    L.dd[i] = dd[i]; L.col[i] = col[i];
   }
   P.count = GEN_ENC; P.T = T; P.maxw = maxw;
+  L.R = R; L.threads = threads; L.rows = rows; L.D = D; L.lds_bytes = lds_bytes;
+  return MFM_OK;
+}
 
-  for (int64_t n0 = 0; n0 < N; n0 += rows) {
-    const int n = (int)std::min<int64_t>(rows, N - n0);
-    // gates_e[t][i][g][u] = x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
-    const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
-    rc = gemm_group_each(GEN_ENC * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
-      const int e = p % GEN_ENC, t = p / GEN_ENC;
-      const SeqDev& s = P.d[e].seq;
-      xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + col[e], D, dd[e], whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
-    });
-    if (rc != MFM_OK) return rc;
-    P.n = n;
-    for (int i = 0; i < GEN_ENC; ++i) {
-      P.d[i].mu = out[i] + n0 * zs[i];
-      P.d[i].lv = out[4 + i] + n0 * zs[i];
-    }
-    rc = (R == 1) ? encode_launch<1>(P, threads, lds_bytes, stream) : encode_launch<4>(P, threads, lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
+int encode_klef_chunk(EncLaunch& L, const float* x, int64_t N, int64_t n0, int n, float* const* out, hipStream_t stream) {
+  EncodeDev& P = L.P;
+  const int T = P.T, D = L.D;
+  // gates_e[t][i][g][u] = x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
+  const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
+  int rc = gemm_group_each(GEN_ENC * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
+    const int e = p % GEN_ENC, t = p / GEN_ENC;
+    const SeqDev& s = P.d[e].seq;
+    xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + L.col[e], D, L.dd[e], whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
+  });
+  if (rc != MFM_OK) return rc;
+  P.n = n;
+  for (int i = 0; i < GEN_ENC; ++i) { P.d[i].mu = out[i]; P.d[i].lv = out[4 + i]; }
+  return (L.R == 1) ? encode_launch<1>(P, L.threads, L.lds_bytes, stream) : encode_launch<4>(P, L.threads, L.lds_bytes, stream);
+}
+
+static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int za, int zv, int zy, const float* params,
+                       const int64_t* offs, const float* x, float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
+  static const char* who = "encode klef";
+  MFM_REQUIRE(T >= 1 && N >= 1 && d_l >= 1 && d_a >= 1 && d_v >= 1 && zl >= 1 && za >= 1 && zv >= 1 && zy >= 1,
+              "%s: sizes must be positive (T %d, N %lld, dims %d %d %d, z %d %d %d %d)", who, T, (long long)N, d_l, d_a, d_v, zl, za, zv, zy);
+  MFM_REQUIRE(params && offs && x && ws && out, "%s: bad arguments (params, offsets, x, workspace and outputs must not be null)", who);
+  for (int i = 0; i < 8; ++i) MFM_REQUIRE(out[i], "%s: output %d is null", who, i);
+  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
+  EncLaunch L;
+  int rc = encode_klef_prepare(who, T, N, d_l, d_a, d_v, zl, za, zv, zy, params, offs, ws, max_rows, L);
+  if (rc != MFM_OK) return rc;
+  for (int64_t n0 = 0; n0 < N; n0 += L.rows) {
+    const int n = (int)std::min<int64_t>(L.rows, N - n0);
+    float* o[2 * GEN_ENC];
+    for (int i = 0; i < GEN_ENC; ++i) { o[i] = out[i] + n0 * L.P.d[i].zs; o[4 + i] = out[4 + i] + n0 * L.P.d[i].zs; }
+    if ((rc = encode_klef_chunk(L, x, N, n0, n, o, stream)) != MFM_OK) return rc;
   }
   return MFM_OK;
 }
@@ -198,14 +196,8 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
 #define DEC_OFFS 38      // weight, bias of zy_to_fy fc1, fc2, zl_to_fl .., za_to_fa .., zv_to_fv ..; 3 x (lstm weight_ih, weight_hh,
                          // bias_ih, bias_hh, fc1 weight, bias); weight, bias of fy_to_y fc1, fc2
 
-static int decode_factors(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* const* z,
-                          float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
-  static const char* who = "decode factors";
-  MFM_REQUIRE(sz && params && offs && z && ws && out, "%s: bad arguments (sizes, params, offsets, factors, workspace and outputs must not be null)", who);
-  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
-  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
-  for (int i = 0; i < 4; ++i) MFM_REQUIRE(z[i] && out[i], "%s: factor / output %d is null", who, i);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)ws) & 15) == 0, "%s: params and workspace must be 16-byte aligned", who);
+int decode_factors_prepare(const char* who, int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, float* ws,
+                           int64_t max_rows, DecLaunch& L) {
   int rc = infer_check_rows(who, N, max_rows);
   if (rc != MFM_OK) return rc;
   for (int i = 0; i < DEC_OFFS; ++i) {
@@ -230,39 +222,59 @@ static int decode_factors(int T, int64_t N, const int32_t* sz, const float* para
   if ((rc = infer_check_lds(who, lds_bytes, maxw, R)) != MFM_OK) return rc;
   if ((rc = infer_check_chunk(who, rows, T, std::max(round_up(maxw, 16), std::max(dm[0], std::max(dm[1], dm[2]))), "product")) != MFM_OK) return rc;
 
-  DecodeDev P;
-  memset(&P, 0, sizeof(P));
-  const float* fcw[GEN_DEC]; const float* fcb[GEN_DEC];
+  DecodeDev& P = L.P;
+  memset(&L, 0, sizeof(L));
   float* h0 = ws;
   for (int i = 0; i < GEN_DEC; ++i) {
     DecOne& Dd = P.d[i];
     const int64_t* o = offs + 16 + 6 * i;
     seq_fill(Dd.seq, params + o[0], params + o[1], params + o[2], params + o[3], fy + fm[i], 1);
-    fcw[i] = params + o[4]; fcb[i] = params + o[5];
+    L.fcw[i] = params + o[4]; L.fcb[i] = params + o[5];
     Dd.seq.hs = h0; h0 += (int64_t)rows * T * Dd.seq.Hp;
     for (int l = 0; l < 2; ++l) { Dd.w[l] = params + offs[4 + 4 * i + 2 * l]; Dd.b[l] = params + offs[5 + 4 * i + 2 * l]; }
     Dd.zs = zs[i]; Dd.fm = fm[i];
+    L.dm[i] = dm[i];
   }
   for (int l = 0; l < 2; ++l) {
     P.wy[l] = params + offs[2 * l]; P.by[l] = params + offs[2 * l + 1];
     P.wy[2 + l] = params + offs[34 + 2 * l]; P.by[2 + l] = params + offs[35 + 2 * l];
   }
   P.count = GEN_DEC; P.T = T; P.zys = zys; P.fy = fy; P.od = od; P.maxw = maxw; P.seq_floats = (int)seq_floats;
+  L.R = R; L.threads = threads; L.rows = rows; L.lds_bytes = lds_bytes;
+  return MFM_OK;
+}
 
-  for (int64_t n0 = 0; n0 < N; n0 += rows) {
-    const int n = (int)std::min<int64_t>(rows, N - n0);
-    P.n = n;
-    // the three decoders share the one zy; decoder l's workgroups write y_hat
-    for (int i = 0; i < GEN_DEC; ++i) { P.d[i].zm = z[i] + n0 * zs[i]; P.d[i].zy = z[3] + n0 * zys; }
-    P.d[0].y_hat = out[3] + n0 * od;
-    rc = decode_factors_launch(who, P, R, threads, lds_bytes, stream);
-    if (rc != MFM_OK) return rc;
+int decode_factors_chunk(const char* who, DecLaunch& L, const float* const* z, float* y_hat, int n, hipStream_t stream) {
+  DecodeDev& P = L.P;
+  P.n = n;
+  // the three decoders share the one zy; decoder l's workgroups write y_hat
+  for (int i = 0; i < GEN_DEC; ++i) { P.d[i].zm = z[i]; P.d[i].zy = z[3]; }
+  P.d[0].y_hat = y_hat;
+  return decode_factors_launch(who, P, L.R, L.threads, L.lds_bytes, stream);
+}
+
+static int decode_factors(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* const* z,
+                          float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
+  static const char* who = "decode factors";
+  MFM_REQUIRE(sz && params && offs && z && ws && out, "%s: bad arguments (sizes, params, offsets, factors, workspace and outputs must not be null)", who);
+  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
+  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
+  for (int i = 0; i < 4; ++i) MFM_REQUIRE(z[i] && out[i], "%s: factor / output %d is null", who, i);
+  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)ws) & 15) == 0, "%s: params and workspace must be 16-byte aligned", who);
+  DecLaunch L;
+  int rc = decode_factors_prepare(who, T, N, sz, params, offs, ws, max_rows, L);
+  if (rc != MFM_OK) return rc;
+  const DecodeDev& P = L.P;
+  for (int64_t n0 = 0; n0 < N; n0 += L.rows) {
+    const int n = (int)std::min<int64_t>(L.rows, N - n0);
+    const float* zc[4] = {z[0] + n0 * sz[0], z[1] + n0 * sz[1], z[2] + n0 * sz[2], z[3] + n0 * sz[3]};
+    if ((rc = decode_factors_chunk(who, L, zc, out[3] + n0 * sz[11], n, stream)) != MFM_OK) return rc;
     // x_hat_m[t][n0 + i] = hs_m[t][i] . Wfc_m^T + b
     const bool whole = n == N;
     rc = gemm_group_each(GEN_DEC * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
       const int m = p % GEN_DEC, t = p / GEN_DEC;
       const SeqDev& s = P.d[m].seq;
-      dec_fc1_desc(d, s, s.hs + (int64_t)t * n * s.Hp, fcw[m], fcb[m], out[m] + ((int64_t)t * N + n0) * dm[m], dm[m], whole ? T * n : n);
+      dec_fc1_desc(d, s, s.hs + (int64_t)t * n * s.Hp, L.fcw[m], L.fcb[m], out[m] + ((int64_t)t * N + n0) * L.dm[m], L.dm[m], whole ? T * n : n);
     });
     if (rc != MFM_OK) return rc;
   }

@@ -1,5 +1,5 @@
-// What the inference launches built on small_fwd_body<.., REC = false> share (predict.hip, generate.hip, impute.hip).  Device: a
-// tile's rows into LDS and back out.  Host: the sizing rules (chunk rows, tile rows, the LDS the recurrence lays out), the
+// What the inference launches built on small_fwd_body<.., REC = false> share (predict.hip, generate.hip, impute.hip,
+// objective.hip).  Device: a tile's rows into LDS and back out.  Host: the sizing rules (chunk rows, tile rows, the LDS the recurrence lays out), the
 // refusals and argument checks, the SeqDev of an LSTM, the grouped GEMMs around the recurrence, and the two launch rules.
 //
 // The launch rules: a kernel that runs several LSTMs in one launch picks its body per block with a switch, and that switch is
@@ -53,9 +53,39 @@ struct DecodeDev {
 // kernel's instantiations stay in generate.hip alone
 int decode_factors_launch(const char* who, DecodeDev& P, int R, int threads, size_t lds_bytes, hipStream_t stream);
 
+// ---------------------------------------------------------------- the encoders' launch (generate.hip)
+#define INFER_ENC 4
+struct EncOne {
+  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
+  const float* w[3]; const float* b[3];        // fc1, the mean head, the logvar head
+  float* mu; float* lv;                        // this chunk's rows [n, zs]
+  int zs, block_begin;
+};
+struct EncodeDev { EncOne d[INFER_ENC]; int count, T, n, maxw; };
+
+// ---------------------------------------------------------------- the two halves chunk by chunk (generate.hip; objective.hip walks them too)
+// prepare: the checks behind the caller's own argument checks (row cap, offsets, the refusals), then everything of the launches
+// that does not depend on the chunk; workspace: *_ws_floats below.  chunk: the launches of one chunk of n <= rows rows
+struct EncLaunch { EncodeDev P; int R, threads, rows, D, dd[INFER_ENC], col[INFER_ENC]; size_t lds_bytes; };
+struct DecLaunch { DecodeDev P; int R, threads, rows, dm[INFER_DEC]; size_t lds_bytes; const float* fcw[INFER_DEC]; const float* fcb[INFER_DEC]; };
+int encode_klef_prepare(const char* who, int T, int64_t N, int d_l, int d_a, int d_v, int zl, int za, int zv, int zy, const float* params,
+                        const int64_t* offs, float* ws, int64_t max_rows, EncLaunch& L);
+// x: the whole split [T, N, D], the chunk its rows [n0, n0 + n); out: the chunk's first rows of the four means, then the four logvars
+int encode_klef_chunk(EncLaunch& L, const float* x, int64_t N, int64_t n0, int n, float* const* out, hipStream_t stream);
+int decode_factors_prepare(const char* who, int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, float* ws,
+                           int64_t max_rows, DecLaunch& L);
+// z: the chunk's first rows of zl, za, zv, zy; y_hat: the chunk's.  The recurrence launch alone: h_t is left in P.d[m].seq.hs [T, n, Hp]
+int decode_factors_chunk(const char* who, DecLaunch& L, const float* const* z, float* y_hat, int n, hipStream_t stream);
+
 // ---------------------------------------------------------------- host: sizes
 static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
 static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }
+static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, int64_t zv, int64_t max_rows) {
+  return gen_rows(N, max_rows) * T * 4 * (hp_of(zl) + hp_of(za) + hp_of(zv) + hp_of(zl + za + zv));
+}
+static int64_t decode_ws_floats(int64_t T, int64_t N, int64_t fy, int64_t fl, int64_t fa, int64_t fv, int64_t max_rows) {
+  return gen_rows(N, max_rows) * T * (hp_of(fy + fl) + hp_of(fy + fa) + hp_of(fy + fv));
+}
 
 // floats of LDS small_fwd_body<KQ, R> lays out for hidden size h (its two h buffers, then the weight staging panel / its record
 // and x-projection buffers, layout kept), a multiple of 4

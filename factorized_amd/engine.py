@@ -24,6 +24,9 @@ ALIGN = 64  # floats
 # what encode() returns: the means and log-variances of the four latent factors, [N, size] each (logvars None for variant "mmd")
 Factors = namedtuple("Factors", ["zl", "za", "zv", "zy", "logvar_zl", "logvar_za", "logvar_zv", "logvar_zy"])
 
+# what objective() returns: the validation objective and its five terms, 0-d float32 device tensors (views of one [6] tensor)
+Objective = namedtuple("Objective", ["loss", "disc", "gen_l", "gen_a", "gen_v", "reg"])
+
 
 def klef_param_shapes(cfg):
     """Ordered name -> shape of MFM_KL_EF's 78 parameters (reference mfm_model.py:579-617)."""
@@ -730,6 +733,71 @@ class MFMEngine:
         _lib.check(rc, "mfm_decode_factors")
         cache[(T, N, cap)] = st
         return list(outs)
+
+    # ------------------------------------------------------------------ the full validation objective
+    def _objective_sizes(self):
+        c = self.cfg
+        return (C.c_int32 * 13)(c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], c["fl_size"], c["fa_size"], c["fv_size"],
+                                c["fy_size"], *c["input_dims"], c["output_dim"], 1 if c.get("loss", "l1") == "ce" else 0)
+
+    def objective_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace objective() keeps for a [T, N, D] split (mfm_objective_klef_workspace_floats)"""
+        return int(_lib.lib().mfm_objective_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
+
+    def objective(self, x, y, *, max_rows=None):
+        """x [T, N, D], labels -> Objective(loss, disc, gen_l, gen_a, gen_v, reg), 0-d float32 device tensors (views of one [6]
+        tensor): what the reference's drivers validate and report (mfm_mosi.py:319-324, :724-726, :826-845) -- disc the mean L1 /
+        cross entropy as evaluate() defines it, gen_m = F.mse_loss(x_m_hat, x_m), reg the sum of the four loss_KLD(mu, logvar),
+        loss = disc + lda_xl gen_l + lda_xa gen_a + lda_xv gen_v + lda_mmd reg -- from the deterministic eval computation, left
+        on the device.
+
+        Variant "kl_ef": mfm_objective_klef -- the launches of encode(), the recurrence launch of decode(), then the decoders'
+        fc1 fused with the squared error (x_hat is never written) and one small finishing launch; no plan and no training
+        workspace; the split is walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS).  Workspace and the [6]
+        result are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated and nothing
+        synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what must survive
+        it).  Other variants, and sizes the entry refuses: the same namedtuple from forward(train=False, handover=False), the
+        total formed on the device.  A refusal for a hidden size above 128 is remembered; one for the LDS limit holds for that
+        call alone, as in encode()."""
+        self._check_inputs(x, y)
+        if y is None:
+            raise _lib.MfmError("objective needs the labels")
+        T, N, D = x.shape
+        if T < 1 or N < 1:
+            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
+        c = self.cfg
+        od = c["output_dim"]
+        ce = c.get("loss", "l1") == "ce"
+        if y.numel() != (N if ce else N * od):
+            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
+                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
+        cap = self._row_cap(max_rows)
+        if self.variant == "kl_ef" and not getattr(self, "_objective_refused", False):
+            cache = self.__dict__.setdefault("_objective_bufs", {})
+            st = cache.get((T, N, cap))
+            if st is None:
+                sizes = self._objective_sizes()
+                nws = int(_lib.lib().mfm_objective_klef_workspace_floats(T, N, sizes, cap))
+                offs = (C.c_int64 * 78)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS + self._DECODE_TENSORS])
+                lda = (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"])
+                out = torch.zeros(6, dtype=torch.float32, device=self.device)
+                st = (torch.empty(nws, dtype=torch.float32, device=self.device), out, Objective(*out.unbind(0)), sizes, offs, lda)
+            ws, out, res, sizes, offs, lda = st
+            rc = _lib.lib().mfm_objective_klef(T, N, sizes, lda, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(out),
+                                               cap, _stream())
+            if rc == 0:
+                cache[(T, N, cap)] = st
+                return res
+            if rc != _lib.MFM_ERR_UNSUPPORTED:
+                _lib.check(rc, "mfm_objective_klef")
+            hs = [c["zl_size"] + c["za_size"] + c["zv_size"]] + [c["fy_size"] + c[k] for k in ("fl_size", "fa_size", "fv_size")]
+            self._objective_refused = max(hs) > self.MAX_RESIDENT_H          # (as in encode)
+        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
+        l = self.forward(x, y, train=False, handover=False)["losses"]
+        out = torch.empty(6, dtype=torch.float32, device=self.device)
+        out[1:6] = l[0:5]
+        out[0] = l[0] + c["lda_xl"] * l[1] + c["lda_xa"] * l[2] + c["lda_xv"] * l[3] + c["lda_mmd"] * l[4]
+        return Objective(*out.unbind(0))
 
     def forward_train(self, x, p, grads_to_zero=None):
         """Training-mode forward of the module path's lazy losses (mfm_plan_forward_train): no labels, no output tensors --

@@ -530,6 +530,42 @@ int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, 
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The full validation objective of MFM_KL_EF (csrc/objective.hip; reference mfm_mosi.py:319-324, :724-726, :826-845): the six
+ * numbers every driver reports for a validation split, from the deterministic eval forward, in the pattern of the entries
+ * above -- fp32, dropout the identity, z = the mean heads, no MfmPlan, no training workspace, and no x_hat in memory.
+ *   out[1] disc   mean L1 (loss_kind 0) / cross entropy (1) of y_hat, as mfm_predict_klef defines it
+ *   out[2..4] gen_l, gen_a, gen_v   mean over T * N * d_m of (x_m_hat - x_m)^2
+ *   out[5] reg    sum over the four factors of -0.5 * sum(1 + logvar - mu^2 - exp(logvar))
+ *   out[0] loss   disc + lambdas[0] * gen_l + lambdas[1] * gen_a + lambdas[2] * gen_v + lambdas[3] * reg
+ * Per row chunk: the launches of mfm_encode_klef (means and log-variances into the workspace), the recurrence launch of
+ * mfm_decode_factors on the means (h_t of the three decoders and y_hat into the workspace), ONE launch of (decoder, 64-row
+ * tile, 64-column tile) workgroups that form x_hat = h W_fc1^T + b in registers, subtract the matching slice of x and leave one
+ * squared-error partial each, and one single-workgroup launch that adds the chunk's partials, KLD terms and label-loss terms
+ * in a fixed order into fp64 accumulators of the workspace; behind the last chunk it divides by the counts of the WHOLE split
+ * and writes `out`.  No float atomics: the six values are bit-identical from run to run for a given (T, N, max_rows).
+ *   sizes    host, 13: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim (as mfm_decode_factors), loss_kind
+ *   lambdas  host, 4: lda_xl, lda_xa, lda_xv, lda_mmd
+ *   offsets  host, 78 element offsets into the flat fp32 parameter buffer `params`: the 40 of mfm_encode_klef, then the 38 of
+ *            mfm_decode_factors
+ *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 16-byte aligned
+ *   y        the labels: float [N, output_dim] (loss_kind 0) / int64 [N] (loss_kind 1)
+ *   out      6 device floats (4-byte aligned)
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace; every mean is over the whole
+ *            split whatever the chunking
+ *   workspace mfm_objective_klef_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary; with
+ *            rows = min(N, max_rows): the larger of the two entries' workspaces above (the stored h takes the place of the
+ *            x-projections), the chunk's eight factors and y_hat, one partial per workgroup of the squared-error launch, and
+ *            the accumulators -- it does not grow with N beyond the row cap
+ * Nothing outside the workspace and `out` is written.  T < 1, N < 1, a null pointer or max_rows < 0 return MFM_ERR_ARG before
+ * anything touches the GPU.  Any N >= 1 (< 2^24), T >= 1.  Sizes the on-chip recurrence does not cover (a hidden size > 128, or more LDS
+ * than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue nothing: run mfm_plan_forward(train = 0)
+ * instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_objective_klef_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_objective_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, const float* lambdas /*host, 4*/, const float* params,
+                       const int64_t* offsets /*host, 78*/, const float* x, const void* y, float* workspace, float* out /*6*/,
+                       int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Surrogate inference of MFM_missing (csrc/impute.hip; reference mfm_model.py:766-885, evaluated in mfm_mosi.py:572-596 and
  * :1023-1062): a missing modality m and the label from the other two modalities, in the pattern of the entries above -- fp32,
  * dropout the identity, no MfmPlan, no training workspace.  For every case m asked for
