@@ -158,8 +158,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_foldproj_kernel(const Seq
   MFM_SEQ_BLOCK_LSTM(L, bid, di)
   const SeqDev& d = L.d[di];
   const int tile = bid - d.block_begin;
-  const unsigned* flg = PR.flags + (int64_t)di * L.T * PROJ_ROLE_FLAGS;
-  const int ncb = PR.e[di].ncb;
+  const unsigned long long* pw = PR.words + PR.e[di].w_off;          // this encoder's columns of the projection words
   // PR.lat_pre (every encoder loads its weights straight into registers: no LDS weight panel): the chain's tables go to LDS NOW,
   // while the row waits for its first projections anyway; the recurrence's buffers lie behind the chain's region, and the chain
   // takes h_T from the recurrence's LDS buffer instead of reading it back from memory behind a store wait
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(1024) void lstm_seq_small_foldproj_kernel(const Seq
     seq_lds = lds + latent_fwd_lds_floats(LD.rec_size);
   }
   const float* h_lds = nullptr;
-  MFM_TUPLE4(h_lds = small_fwd_body<KQ, 1, true>(d, L.T, L.B, tile, seq_lds, flg, epoch, ncb, PR.ctl))
+  MFM_TUPLE4(h_lds = small_fwd_body<KQ, 1, true>(d, L.T, L.B, tile, seq_lds, pw, epoch, PR.w_ld, PR.ctl))
   // the loss slots are cleared by the producers of t = 0: all of them have passed before this row's chain adds to them
   // (the four flag sets are requested together: one round trip)
   if (threadIdx.x < 64) {
@@ -453,11 +452,14 @@ int seq_small_foldproj_launch(SeqLaunch& L, const LatentDev& LD, ProjRole& PR, c
   int n_role = (device_cus() - 4 * L.B) / PROJ_ROLE_SLOTS * PROJ_ROLE_SLOTS;
   if (const char* e = opt_get("MFM_PROJ_FOLD_ROLES")) { const int v = atoi(e) / PROJ_ROLE_SLOTS * PROJ_ROLE_SLOTS; if (v >= PROJ_ROLE_SLOTS) n_role = v; }
   PR.n_role = n_role; PR.groups = n_role / PROJ_ROLE_SLOTS;
+  if (!PR.words || ((uintptr_t)PR.words & 7) != 0) return MFM_ERR_UNSUPPORTED;      // (64-bit atomics: naturally aligned words)
   int kmax = 0, cb = 0;
+  PR.w_ld = 0;
   for (int i = 0; i < 4; ++i) {
     kmax = std::max(kmax, PR.e[i].k);
     PR.e[i].cb_begin = cb; PR.e[i].ncb = 4 * L.d[i].Hp / PROJ_ROLE_CB;
     cb += PR.e[i].ncb;
+    PR.e[i].w_off = PR.w_ld; PR.w_ld += 4 * L.d[i].Hp;       // a row of words: the encoders' 4 Hp gate columns side by side
   }
   PR.kstride = proj_role_kstride(kmax);
   const int total = lay_out_blocks(L, L.B, n_role);

@@ -178,8 +178,9 @@ __device__ __forceinline__ void stage_gates2(const SeqDev& d, int mode, int g, f
 // Instead the owners drop (i, f, g, o, c, h) into an LDS record and 6*Hp*R/64 waves write it out after
 // the step's barrier; the encoders' x-projections are fetched two steps ahead by 4*Hp*R/64 waves.
 // FLG (encoders of the fold launch with projection role workgroups, proj_role_dev.h): the x-projections of a time step
-// are produced inside this launch; the fetching waves check the step's block flags (requested one step earlier) before they
-// request its values, and read them with agent-scope loads.
+// are produced inside this launch and arrive as 64-bit words {value, epoch} (`pw`: the encoder's first column of words[0][0],
+// `pw_ld`: words per batch row); the fetching waves request them two steps ahead like any other projection and look at the
+// epoch halves where they park the values in LDS -- a slice with a word of another launch is loaded again (proj_words_wait).
 // BF (one-row tiles, bf16 plans below the batch size of the bf16 MFMA kernels; round 4): the recurrent product on
 // v_dot2c_f32_bf16 -- W packed as bf16 pairs in half the registers, h_{t-1} exchanged through LDS as bf16 (what the bf16 MFMA
 // kernels feed their matrix cores: same rounding points), fp32 accumulation, gate math, cell state and saved activations.
@@ -194,7 +195,7 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // multiplication and must not meet whatever the buffer held).
 template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true, bool HS = false>
 __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const int T, const int B, const int tile, float* lds,
-                                               const unsigned* flg = nullptr, const unsigned epoch = 0, const int ncb = 0,
+                                               const unsigned long long* pw = nullptr, const unsigned epoch = 0, const int pw_ld = 0,
                                                const HoCtl ctl = HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u},
                                                const int64_t hs_step = 0) {
   constexpr int HK = 4 * KQ;                    // padded hidden extent of the matvec
@@ -220,6 +221,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
   constexpr int HX = (R == 1) ? HKB : HK;          // extent of one h buffer
   static_assert(!BF || R == 1, "bf16 dot products: one-row tiles only");
   static_assert(!HS || (!REC && !BF), "h-only record: fp32 inference bodies");
+  static_assert(!FLG || R == 1, "projection words: one-row tiles only (one word per fetching lane)");
   float* hbuf = lds;                       // [2][HX][R]
   __bf16* hb16 = reinterpret_cast<__bf16*>(lds);   // BF: the same two buffers as bf16 (half the bytes)
   float* panel = lds + 2 * HKB * R;        // [2][h][h] weight staging (two gates at a time)
@@ -326,24 +328,39 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     xl[i] = (g * HKB + unit) * R + r;
     xpf[i] = 0.0f;
   }
-  // FLG: only the waves that fetch projections look at flags (wave-uniform)
+  // FLG: the same elements as words (step stride wstep); xpw: the words of the coming step, checked where they are parked;
+  // only the waves that fetch projections load and check words (wave-uniform)
   const bool fetch_wave = FLG && !dec && (tid & ~63) < 4 * HKB * R && (tid & ~63) < NTH;
-  unsigned fv = 0;
+  const int64_t wstep = (int64_t)B * pw_ld;
+  const gu64* xw[NXL];
+  unsigned long long xpw[NXL];
+#pragma unroll
+  for (int i = 0; i < NXL; ++i) {
+    xw[i] = nullptr; xpw[i] = 0ull;
+    if constexpr (FLG) {
+      const int ec = xok[i] ? tid + i * NTH : 0;
+      const int sr = ec / HKB, unit = ec % HKB, r = sr % R, g = sr / R;
+      xw[i] = (const gu64*)pw + (int64_t)min(b0 + r, B - 1) * pw_ld + g * Hp + unit;
+    }
+  }
   if (!dec) {
     if constexpr (FLG) {
       if (fetch_wave) {
-        const int t1 = (T > 1) ? 1 : 0;
-        proj_flags_wait(flg, proj_flags_load(flg, ncb), epoch, ncb, ctl);
-        proj_flags_wait(flg + t1 * PROJ_ROLE_FLAGS, proj_flags_load(flg + t1 * PROJ_ROLE_FLAGS, ncb), epoch, ncb, ctl);
-        fv = proj_flags_load(flg + min(2, T - 1) * PROJ_ROLE_FLAGS, ncb);
-      }
-    }
+        unsigned long long w0[NXL];
 #pragma unroll
-    for (int i = 0; i < NXL; ++i) {
-      float v0;
-      if constexpr (FLG) { v0 = ld_agent((const float*)xp[i]); xpf[i] = ld_agent((const float*)xp[i] + ((T > 1) ? gstep : 0)); }
-      else { v0 = xp[i][0]; xpf[i] = xp[i][(T > 1) ? gstep : 0]; }
-      if (xok[i]) xbuf[xl[i]] = v0;
+        for (int i = 0; i < NXL; ++i) { w0[i] = ld_word(xw[i]); xpw[i] = ld_word(xw[i] + ((T > 1) ? wstep : 0)); }
+        proj_words_wait(xw, 0, w0, xok, epoch, ctl);
+#pragma unroll
+        for (int i = 0; i < NXL; ++i)
+          if (xok[i]) xbuf[xl[i]] = word_value(w0[i]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NXL; ++i) {
+        const float v0 = xp[i][0];
+        xpf[i] = xp[i][(T > 1) ? gstep : 0];
+        if (xok[i]) xbuf[xl[i]] = v0;
+      }
     }
   }
   // output elements: e -> (slot s in i,f,g,o,c,h ; row r ; unit)
@@ -483,16 +500,17 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     float xn[NXL];
 #pragma unroll
     for (int i = 0; i < NXL; ++i) xn[i] = 0.0f;
+    unsigned long long xnw[NXL];
+#pragma unroll
+    for (int i = 0; i < NXL; ++i) xnw[i] = 0ull;
     if (!dec) {
-      const int64_t off = (int64_t)min(t + 2, T - 1) * gstep;
       if constexpr (FLG) {
         if (fetch_wave) {
-          proj_flags_wait(flg + min(t + 2, T - 1) * PROJ_ROLE_FLAGS, fv, epoch, ncb, ctl);
 #pragma unroll
-          for (int i = 0; i < NXL; ++i) xn[i] = ld_agent((const float*)xp[i] + off);
-          fv = proj_flags_load(flg + min(t + 3, T - 1) * PROJ_ROLE_FLAGS, ncb);
+          for (int i = 0; i < NXL; ++i) xnw[i] = ld_word(xw[i] + (int64_t)min(t + 2, T - 1) * wstep);
         }
       } else {
+        const int64_t off = (int64_t)min(t + 2, T - 1) * gstep;
 #pragma unroll
         for (int i = 0; i < NXL; ++i) xn[i] = xp[i][off];
       }
@@ -533,6 +551,12 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
       }
     }
     if (!dec) {
+      if constexpr (FLG) {
+        // the words of step t + 1, requested one step ago: of this launch, or loaded again until they are
+        if (fetch_wave) proj_words_wait(xw, (int64_t)min(t + 1, T - 1) * wstep, xpw, xok, epoch, ctl);
+#pragma unroll
+        for (int i = 0; i < NXL; ++i) xpf[i] = word_value(xpw[i]);
+      }
 #pragma unroll
       for (int i = 0; i < NXL; ++i)
         if (xok[i]) xbuf[(par ^ 1) * (4 * HKB * R) + xl[i]] = xpf[i];
@@ -561,7 +585,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
       hs_p += hs_step;
     }
 #pragma unroll
-    for (int i = 0; i < NXL; ++i) xpf[i] = xn[i];
+    for (int i = 0; i < NXL; ++i) { xpf[i] = xn[i]; xpw[i] = xnw[i]; }
     cur ^= 1;
   };
   // the record of the last step taken (still in obuf) -> HBM

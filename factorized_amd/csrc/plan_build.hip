@@ -455,6 +455,13 @@ int build(MfmPlan* P) {
 
   P->lat_ops_off = carve(cur, (int64_t)(sizeof(P->lat_ops) / (sizeof(float))));
   P->pf_flags = (V == 0) ? carve(cur, (int64_t)4 * P->T * PROJ_ROLE_FLAGS) : -1;
+  // the projections of the role form travel as 64-bit words (two floats each; carve keeps 256-byte granules).  A region of its
+  // own: the recurrence writes its activation record into the gates buffers while later projections are still in flight
+  if (V == 0 && P->n_enc == 4 && c.B <= PROJ_ROLE_CB) {
+    int64_t cols = 0;
+    for (int e = 0; e < 4; ++e) cols += 4 * (int64_t)P->enc[e].Hp;
+    P->pf_words = carve(cur, 2 * (int64_t)P->T * c.B * cols);
+  }
   if ((long)(P->n_enc > 3 ? P->n_enc : 3) * c.B < 6L * device_cus() && !P->seq_bf16) {        // (one-row BPTT tiles)
     for (int i = 0; i < P->n_enc + 3; ++i) {
       const int hh = i < P->n_enc ? P->enc[i].h : P->dec[i - P->n_enc].h;

@@ -147,7 +147,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
   // by role workgroups of the encoder launch itself (proj_role_dev.h), which also clear the zero spans
   bool proj_in_fold = false;
   const bool capturing = stream_capturing(s);
-  if (V == 0 && !seq_bf16 && !st16 && P->n_enc == 4 && P->fold_state >= 0 && P->projfold_state >= 0 && P->pf_flags >= 0 &&
+  if (V == 0 && !seq_bf16 && !st16 && P->n_enc == 4 && P->fold_state >= 0 && P->projfold_state >= 0 && P->pf_flags >= 0 && P->pf_words >= 0 &&
       P->opt_handover && TB * P->D < ((int64_t)1 << 28)) {
     int hh[4], kk[4];
     for (int e = 0; e < 4; ++e) { hh[e] = P->enc[e].h; kk[e] = P->enc_d[e]; }
@@ -270,6 +270,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
     memset(&PR, 0, sizeof(PR));
     PR.x = x; PR.ldx = P->D; PR.x_rows = (int)TB;
     PR.flags = reinterpret_cast<unsigned*>(W + P->pf_flags); PR.epoch = epoch_base(P->calls); PR.tick = P->tick_ptr(W);
+    PR.words = reinterpret_cast<unsigned long long*>(W + P->pf_words);
     // a consumer that gives up: status bit 0, NaN into the regulariser slot (what the module path returns as `kld`)
     PR.ctl = P->ho_ctl(W, losses + 4, 1u);
     PR.fault = (P->opt_fault == 1) ? 1 : 0;

@@ -92,6 +92,7 @@ struct MfmPlan {
   int fold_state = 0;               // encoder + latent fold launches (lstm_seq_small.hip): 0 untried, 1 in use, -1 not applicable
   int projfold_state = 0;           // projection role workgroups in the forward fold launch (proj_role_dev.h): 0 / 1 / -1 alike
   int64_t pf_flags = -1;            // their flag words [4][T][16] (u32)
+  int64_t pf_words = -1;            // the projections they hand over: 64-bit words {value, epoch} [T][B][sum of 4 Hp] (B <= 32 only)
   int64_t wt_img[mfm::MFM_WT_MAX] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};     // transposed-weight images: encoders in plan order, then the 3 decoders (lstm_seq_dev.h)
   unsigned long long wt_call = ~0ull;       // value of `calls` whose forward wrote them
   int64_t wf_img[6] = {-1, -1, -1, -1, -1, -1};     // forward-order images of the decoders' W_ih + W_hh, then of W_ih (lstm_seq_dev.h, wf_img_write)

@@ -7,13 +7,21 @@
 //   * role workgroup r (blockIdx < n_role, dispatched first) owns one 32-column block of one encoder's 4 Hp gate columns
 //     for good -- its W_ih rows stay in LDS -- and walks the time steps t = r / 32, + n_role / 32, ...: the B x k slice of
 //     x_t by 16-byte loads (the next step's slice is requested before the current product starts), 16 waves = 4
-//     16x16 fragments x 4 k-parts on v_mfma_f32_16x16x4_f32, partial tiles joined through LDS, bias added, stored with
-//     agent-scope stores; when every store of the tile is acknowledged, flags[e][t][block] <- epoch;
-//   * the recurrence workgroup of (encoder e, row b) polls the flags of (e, t + 2) one step before it fetches that
-//     step's projections (lstm_seq_small.hip, small_fwd_body<.., FLG = true>).
+//     16x16 fragments x 4 k-parts on v_mfma_f32_16x16x4_f32, partial tiles joined through LDS, bias added, and every
+//     element leaves as ONE 64-bit word {value, epoch} (words[t][b][encoder's columns], one relaxed agent-scope 64-bit
+//     atomic store each): the value announces itself, nothing waits for an acknowledgement and no flag follows;
+//   * the recurrence workgroup of (encoder e, row b) loads the words of step t + 2 during step t and looks at their epoch
+//     halves when it parks them in LDS one step later; a word that does not carry this launch's epoch has not arrived and
+//     the wave re-loads its slice (lstm_seq_small_dev.h, small_fwd_body<.., FLG = true>).  A 64-bit atomic is single-copy
+//     atomic: the value half of a word whose epoch half matches came from the same store, so no ordering between
+//     different addresses is relied on (the two-message form this replaces -- data, acknowledgement wait, flag; flag, then
+//     data -- paid ~2.5 us in front of the first flag and two dependent round trips behind it: DESIGN.md section 4);
+//   * t = 0 tiles ALSO raise flags[e][0][block] <- epoch once every store of the tile -- and, in front of it, of the loss
+//     slots' clearing -- is acknowledged: the rows' latent chains wait for all of them before they add into the slots.
 // No deadlock: producers never wait, and every XCD dispatches its workgroups in block order, so whatever a consumer
-// waits for is resident or finished.  Flags are epoch stamps (the plan's call counter; the workspace starts zeroed):
-// nothing to reset, nothing accumulates.  The launch's zero spans (gradient buffer, dH) ride on the role workgroups too.
+// waits for is resident or finished.  Words and flags carry epoch stamps (a function of the plan's call counter, never 0 and
+// never reused on a plan; the workspace starts zeroed): what an earlier launch left reads as "not yet", nothing to reset,
+// nothing accumulates.  The launch's zero spans (gradient buffer, dH) ride on the role workgroups too.
 #pragma once
 #include "internal.h"
 #include "lstm_seq_dev.h"
@@ -27,7 +35,7 @@ constexpr int PROJ_ROLE_MAXG = 4;         // 16-byte groups per thread and opera
 constexpr int PROJ_ROLE_FLAGS = 16;       // flag words per (encoder, time step)
 constexpr int PROJ_ROLE_PW = 4 * 96 + 4;  // floats per wave in the partial-tile buffer ([reg][96] + skew)
 
-struct ProjRoleEnc { const float* w; const float* b_ih; const float* b_hh; int k_off, k, cb_begin, ncb; };
+struct ProjRoleEnc { const float* w; const float* b_ih; const float* b_hh; int k_off, k, cb_begin, ncb, w_off; };   // w_off: first column of the encoder in a row of words
 constexpr int PROJ_ROLE_WT = 7;
 // What a consumer does when its producer does not show up (shared by the projection and weight-gradient hand-overs): after
 // `timeout` ticks of the 100 MHz wall clock it gives up, ORs `bit` into the plan's sticky STATUS word (the host reads it at its
@@ -53,10 +61,11 @@ __device__ __forceinline__ unsigned ho_epoch(unsigned base, const unsigned* tick
 struct ProjRole {
   const float* x; int ldx; int x_rows;    // x[T * B, ldx]
   int n_role, groups, kstride;            // groups = n_role / 32
-  unsigned* flags; unsigned epoch;        // flags[(e * T + t) * 16 + block]; epoch: host part (ho_epoch)
+  unsigned* flags; unsigned epoch;        // flags[(e * T + t) * 16 + block] (t = 0 only); epoch: host part (ho_epoch)
+  unsigned long long* words; int w_ld;    // the projections: words[(t * B + b) * w_ld + e[.].w_off + gate column] = {value, epoch}; w_ld = sum of 4 Hp
   const unsigned* tick;                   // device part of the epoch (low word of the plan's replay counter)
   HoCtl ctl;                              // consumer side: time-out, status word, poison
-  int fault;                              // fault injection (tests): role workgroup 0 does not raise its first flag
+  int fault;                              // fault injection (tests): role workgroup 0 withholds its first tile (words and flag)
   int lat_pre;                            // the rows' latent chains preload their tables in front of the time loop (lstm_seq_small.hip)
   int lat_tail;                           // ... and stop behind the z -> f MLPs: tail blocks of the decoder launch finish them
   float* loss_ptr; int loss_n;            // loss slots: cleared with agent-scope stores before any flag of t = 0 is raised
@@ -72,10 +81,37 @@ struct ProjRole {
 static inline int proj_role_kstride(int k) { int s4 = ((k + 15) / 16 * 16) / 4; if ((s4 & 1) == 0) ++s4; return 4 * s4; }
 
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned ld_agent_u(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// consumer side: true when every block flag of one (encoder, time step) carries this launch's epoch (wave-uniform)
+// A projection as it travels: value bits in the low half, the launch's epoch in the high half, one 64-bit access each way
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+__device__ __forceinline__ void st_word(gu64* p, float v, unsigned epoch) {
+  __hip_atomic_store(p, ((unsigned long long)epoch << 32) | __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long ld_word(const gu64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float word_value(unsigned long long w) { return __builtin_bit_cast(float, (unsigned)w); }
+// consumer side: one wave's slice of words (w[i] loaded from p[i] + off; `act`: the lanes that carry one) -- wave-uniform: while
+// any of them is not of this launch the whole slice is loaded again; gives up after ctl.timeout like proj_flags_wait below
+template <int N>
+__device__ __forceinline__ void proj_words_wait(const gu64* const (&p)[N], const int64_t off, unsigned long long (&w)[N], const bool (&act)[N],
+                                                const unsigned epoch, const HoCtl& ctl) {
+  auto stale = [&]() {
+    bool s = false;
+#pragma unroll
+    for (int i = 0; i < N; ++i) s = s || (act[i] && (unsigned)(w[i] >> 32) != epoch);
+    return __builtin_amdgcn_ballot_w64(s) != 0ull;
+  };
+  if (!stale()) return;
+  const long long t0 = wall_clock64();
+  do {
+    __builtin_amdgcn_s_sleep(2);
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = ld_word(p[i] + off);
+    if (wall_clock64() - t0 >= ctl.timeout) { ho_give_up(ctl); return; }
+  } while (stale());
+}
+
+// the t = 0 flags (the rows' latent chains wait for them): true when every block flag of one (encoder, time step) carries this launch's epoch (wave-uniform)
 __device__ __forceinline__ bool proj_flags_ready(unsigned v, unsigned epoch, int ncb) {
   const int lane = threadIdx.x & 63;
   return __builtin_amdgcn_ballot_w64(lane < ncb && v != epoch) == 0ull;
@@ -184,8 +220,7 @@ __device__ __forceinline__ void proj_role_body(const SeqLaunch& L, const ProjRol
     const int NG16 = G >> 2;
     // partial (row, col) of fragment (fr, fc) lives in lane (col & 15) + 16 ((row & 15) >> 2), register row & 3
     const int pw0 = (((orow >> 4) * 2 + (ocol >> 4)) * 4) * PROJ_ROLE_PW + (orow & 3) * 96 + (ocol & 15) + 16 * ((orow & 15) >> 2);
-    float* const out = d.gates;
-    const int64_t orow_stride = 4 * (int64_t)Hp;
+    gu64* const out = (gu64*)PR.words + E.w_off + col0 + ocol;
     for (int t = grp; t < T; t += PR.groups) {
       const int tn = t + PR.groups;
       if (tn < T) load_x(tn, rx);
@@ -201,14 +236,17 @@ __device__ __forceinline__ void proj_role_body(const SeqLaunch& L, const ProjRol
 #pragma unroll
       for (int c = 0; c < 4; ++c) Ps[wave * PROJ_ROLE_PW + c * 96 + lane] = acc[c];
       __syncthreads();
-      if (orow < B) {
+      const bool withheld = PR.fault && r == 0 && t == grp;  // (uniform) fault injection: this tile is never published
+      if (orow < B && !withheld) {
         const float v = Ps[pw0] + Ps[pw0 + PROJ_ROLE_PW] + Ps[pw0 + 2 * PROJ_ROLE_PW] + Ps[pw0 + 3 * PROJ_ROLE_PW];
-        st_agent(out + ((int64_t)t * B + orow) * orow_stride + col0 + ocol, cvalid ? v + bias : 0.0f);
+        st_word(out + ((int64_t)t * B + orow) * PR.w_ld, cvalid ? v + bias : 0.0f, epoch);
       }
       if (tn < T) park(Xs, rx);                              // (every wave is past its product: the barrier above)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every store of this thread has been acknowledged
-      __syncthreads();
-      if (tid == 0 && !(PR.fault && r == 0 && t == grp))
+      // t = 0 (uniform): the flag the latent chains wait for -- every store of this thread, the loss slots' clearing among them,
+      // has been acknowledged
+      if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();                                       // (the next product reads the slice parked above)
+      if (t == 0 && tid == 0 && !withheld)
         __hip_atomic_store(PR.flags + ((int64_t)e * T + t) * PROJ_ROLE_FLAGS + cbl, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       LSTAMP(0, 16 + (t - grp) / PR.groups);
     }

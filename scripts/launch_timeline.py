@@ -196,7 +196,7 @@ def main():
             if (k == 0 and name.startswith("projection")):
                 pts = [0, 1] + list(range(16, 32)) + [12, 13, 15]
                 labels = {0: "entry", 1: "W_ih block + x_t slice in LDS", 12: "items done", 13: "W^T images written", 15: "exit (zero spans cleared)"}
-                labels.update({16 + i: "flag of item %d raised" % i for i in range(16)})
+                labels.update({16 + i: "item %d: words stored (t = 0: flag raised)" % i for i in range(16)})
             elif (k == 4 and name.startswith("weight")):
                 pts = [0] + list(range(16, 32)) + [15] + list(range(7, 13)) + list(range(1, 7))
                 labels = {0: "entry", 15: "exit"}
