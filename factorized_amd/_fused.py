@@ -188,6 +188,26 @@ class _FusedEngineMixin:
         with torch.no_grad():
             return eng.objective(x, y)
 
+    def predict_zeros(self, x, y=None):
+        """x [T, N, D] (, labels) -> Zeros(y_hat, gen, disc) (a namedtuple, engine.Zeros) of float32 device tensors: the test
+        protocol of the reference's train_mfm_test_zeros (mfm_mosi.py:572-596), the model's robustness to a modality missing at
+        test time.  The split goes through the model with modality l, a, v zeroed in turn; y_hat [3, N, output_dim] holds the
+        predictions of the three cases in that order (the reference's y_hat_nol, y_hat_noa, y_hat_nov), gen [3] the
+        F.mse_loss of the zeroed modality's reconstruction against the real one (what the reference prints, unweighted), disc
+        [3] the mean L1 / cross entropy per case as evaluate() defines it, None without labels.  Always the deterministic eval
+        computation (dropout off, z = the mean heads), `self.training` left as found, without autograd, lazy outputs or a host
+        read.  MFM_KL_EF: engine.predict_zeros (no plan, no zeroed copies, x_hat never written); buffers are kept per (T, N,
+        max_rows) and the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must
+        survive it).  MFM_KL / MFM, and sizes the fused entry refuses: three fused eval forwards on zeroed copies."""
+        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
+        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        if self._engine_variant == "mmd":
+            g = getattr(self, "mmd_gauss", None)
+            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        with torch.no_grad():
+            return eng.predict_zeros(x, y)
+
     # ------------------------------------------------------------------ the factorized latents and generation from them
     def _split(self, x):
         return x[:, :, :self.d_l], x[:, :, self.d_l:self.d_l + self.d_a], x[:, :, self.d_l + self.d_a:]

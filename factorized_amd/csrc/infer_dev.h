@@ -1,5 +1,5 @@
 // What the inference launches built on small_fwd_body<.., REC = false> share (predict.hip, generate.hip, impute.hip,
-// objective.hip).  Device: a tile's rows into LDS and back out.  Host: the sizing rules (chunk rows, tile rows, the LDS the recurrence lays out), the
+// objective.hip, zeros.hip).  Device: a tile's rows into LDS and back out.  Host: the sizing rules (chunk rows, tile rows, the LDS the recurrence lays out), the
 // refusals and argument checks, the SeqDev of an LSTM, the grouped GEMMs around the recurrence, and the two launch rules.
 //
 // The launch rules: a kernel that runs several LSTMs in one launch picks its body per block with a switch, and that switch is
@@ -52,6 +52,64 @@ struct DecodeDev {
 // decode_factors_kernel on one chunk of P.n rows in tiles of R (1 or 4) rows; P.d[0 .. P.count) filled but for block_begin.  The
 // kernel's instantiations stay in generate.hip alone
 int decode_factors_launch(const char* who, DecodeDev& P, int R, int threads, size_t lds_bytes, hipStream_t stream);
+
+// ---------------------------------------------------------------- the decoders' fc1 fused with the squared error (objective.hip; zeros.hip launches it too)
+#define OBJ_BM 64          // rows of h per workgroup: 4 waves x 16
+#define OBJ_BN 64          // columns of x_hat per workgroup: up to 4 fragments of 16 per wave
+#define OBJ_THREADS 256
+struct Fc1SqItem {
+  const float* hs; const float* w; const float* bias;      // H [M, Hp] (the chunk's [T, n, Hp]), W_fc1 [d, h], b [d]
+  const float* x;                                          // x[0][n0][first column of m]: chunk row (t, i) at ((int64)t N + i) D
+  float* partials;                                         // one slot per workgroup of this item
+  int d, h, Hp, col_tiles, tile_begin;
+};
+struct Fc1SqDev { Fc1SqItem it[INFER_DEC]; int64_t N; int M, n, D; };
+// fc1_sqerr_kernel on one chunk: `tiles` workgroups in all (the items' tile_begin and partials set by the caller), hmax the
+// widest h among the items.  The kernel stays in objective.hip alone
+int fc1_sqerr_launch(const Fc1SqDev& F, int tiles, int hmax, hipStream_t stream);
+// workgroups (= partial slots) of fc1_sqerr_kernel over a chunk of n rows; dm: the three decoders' output widths
+static int64_t fc1_sqerr_tiles(int64_t T, int64_t n, const int32_t* dm) {
+  int64_t t = 0;
+  for (int m = 0; m < INFER_DEC; ++m) t += ((T * n + OBJ_BM - 1) / OBJ_BM) * ((dm[m] + OBJ_BN - 1) / OBJ_BN);
+  return t;
+}
+
+// sum over a workgroup of OBJ_THREADS in a fixed order; every thread returns it
+__device__ __forceinline__ double finish_sum(double v, double* red, const int tid) {
+  red[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = OBJ_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// this thread's part of a chunk's label loss: |y_hat - y| over [n, od] (loss_kind 0), or logsumexp - picked per row as in
+// predict.hip (1); thread-strided over a workgroup of OBJ_THREADS
+__device__ __forceinline__ double label_loss_part(const float* y_hat, const void* y, const int n, const int od, const int loss_kind,
+                                                  const int tid) {
+  double disc = 0.0;
+  if (loss_kind == 0) {
+    const float* yt = reinterpret_cast<const float*>(y);
+    for (int i = tid; i < n * od; i += OBJ_THREADS) disc += (double)fabsf(y_hat[i] - yt[i]);
+  } else {
+    const int64_t* lab = reinterpret_cast<const int64_t*>(y);
+    for (int r = tid; r < n; r += OBJ_THREADS) {
+      const float* yr = y_hat + (int64_t)r * od;
+      float mx = yr[0];
+      for (int o = 1; o < od; ++o) mx = fmaxf(mx, yr[o]);
+      float se = 0.0f;
+      for (int o = 0; o < od; ++o) se += expf(yr[o] - mx);
+      const int lc = (int)min(max(lab[r], (int64_t)0), (int64_t)(od - 1));      // (a label outside [0, od) must not index outside y_hat)
+      disc += (double)((logf(se) + mx) - yr[lc]);
+    }
+  }
+  return disc;
+}
 
 // ---------------------------------------------------------------- the encoders' launch (generate.hip)
 #define INFER_ENC 4

@@ -24,19 +24,8 @@
 
 namespace mfm {
 
-#define OBJ_BM 64          // rows of h per workgroup: 4 waves x 16
-#define OBJ_BN 64          // columns of x_hat per workgroup: up to 4 fragments of 16 per wave
-#define OBJ_THREADS 256
 #define OBJ_ACC 5          // squared errors l, a, v; KLD sum; label-loss sum
 static_assert(OBJ_BM == OBJ_BN && OBJ_BM * 4 == OBJ_THREADS, "one staging loop fills both LDS tiles; a wave owns 16 rows");
-
-struct Fc1SqItem {
-  const float* hs; const float* w; const float* bias;      // H [M, Hp] (the chunk's [T, n, Hp]), W_fc1 [d, h], b [d]
-  const float* x;                                          // x[0][n0][first column of m]: chunk row (t, i) at ((int64)t N + i) D
-  float* partials;                                         // one slot per workgroup of this item
-  int d, h, Hp, col_tiles, tile_begin;
-};
-struct Fc1SqDev { Fc1SqItem it[INFER_DEC]; int64_t N; int M, n, D; };
 
 __global__ __launch_bounds__(OBJ_THREADS) void fc1_sqerr_kernel(const Fc1SqDev P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -107,20 +96,6 @@ struct ObjFinishDev {
   int n, od, loss_kind, first, last;
 };
 
-// sum over the workgroup in a fixed order; every thread returns it
-__device__ __forceinline__ double finish_sum(double v, double* red, const int tid) {
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = OBJ_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const ObjFinishDev P) {
   __shared__ double red[OBJ_THREADS];
   const int tid = threadIdx.x;
@@ -139,23 +114,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const Obj
       kld += (double)(1.0f + lv - mu * mu - expf(lv));
     }
   sums[3] = finish_sum(kld, red, tid);
-  double disc = 0.0;
-  const int od = P.od;
-  if (P.loss_kind == 0) {
-    const float* yt = reinterpret_cast<const float*>(P.y);
-    for (int i = tid; i < P.n * od; i += OBJ_THREADS) disc += (double)fabsf(P.y_hat[i] - yt[i]);
-  } else {
-    const int64_t* lab = reinterpret_cast<const int64_t*>(P.y);
-    for (int r = tid; r < P.n; r += OBJ_THREADS) {
-      const float* yr = P.y_hat + (int64_t)r * od;
-      float mx = yr[0];
-      for (int o = 1; o < od; ++o) mx = fmaxf(mx, yr[o]);
-      float se = 0.0f;
-      for (int o = 0; o < od; ++o) se += expf(yr[o] - mx);
-      const int lc = (int)min(max(lab[r], (int64_t)0), (int64_t)(od - 1));      // (a label outside [0, od) must not index outside y_hat)
-      disc += (double)((logf(se) + mx) - yr[lc]);
-    }
-  }
+  const double disc = label_loss_part(P.y_hat, P.y, P.n, P.od, P.loss_kind, tid);
   sums[4] = finish_sum(disc, red, tid);
   if (tid != 0) return;
 #pragma unroll
@@ -172,16 +131,15 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const Obj
 }
 
 // ---------------------------------------------------------------- host
+int fc1_sqerr_launch(const Fc1SqDev& F, int tiles, int hmax, hipStream_t stream) {
+  const size_t lds_bytes = (size_t)(OBJ_BM + OBJ_BN) * (round_up(hmax, 4) + 2) * sizeof(float);
+  return seq_launch_kernel(fc1_sqerr_kernel, "fc1_sqerr_kernel", dim3(tiles), dim3(OBJ_THREADS), lds_bytes, stream, nullptr, F);
+}
+
 #define OBJ_SIZES 13       // the 12 of mfm_decode_factors, then loss_kind
 #define OBJ_OFFS 78        // the 40 of mfm_encode_klef, then the 38 of mfm_decode_factors
 
 static int64_t r4(int64_t v) { return (v + 3) / 4 * 4; }
-// workgroups (= partial slots) of fc1_sqerr_kernel over a chunk of n rows
-static int64_t fc1_sqerr_tiles(int64_t T, int64_t n, const int32_t* sz) {
-  int64_t t = 0;
-  for (int m = 0; m < INFER_DEC; ++m) t += ((T * n + OBJ_BM - 1) / OBJ_BM) * ((sz[8 + m] + OBJ_BN - 1) / OBJ_BN);
-  return t;
-}
 // the workspace, in this order (every part a multiple of 4 floats): the chunk's x-projections and, behind the encoders, the
 // decoders' h in the same place; its eight factors; its y_hat; its squared-error partials; the OBJ_ACC fp64 accumulators
 struct ObjLayout { int64_t seq, z, y_hat, part, total; };
@@ -192,7 +150,7 @@ static ObjLayout objective_layout(int64_t T, int64_t N, const int32_t* sz, int64
   o.z = o.seq;
   o.y_hat = o.z + 2 * (r4(rows * sz[0]) + r4(rows * sz[1]) + r4(rows * sz[2]) + r4(rows * sz[3]));
   o.part = o.y_hat + r4(rows * sz[11]);
-  o.total = o.part + r4(fc1_sqerr_tiles(T, rows, sz)) + r4(2 * OBJ_ACC);
+  o.total = o.part + r4(fc1_sqerr_tiles(T, rows, sz + 8)) + r4(2 * OBJ_ACC);
   return o;
 }
 
@@ -215,10 +173,9 @@ static int objective_klef(int T, int64_t N, const int32_t* sz, const float* lamb
   if (rc != MFM_OK) return rc;
   if ((rc = decode_factors_prepare(who, T, N, sz, params, offs + 40, ws, max_rows, Dl)) != MFM_OK) return rc;
   const int rows = E.rows;
-  MFM_REQUIRE(fc1_sqerr_tiles(T, rows, sz) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, rows, T);
+  MFM_REQUIRE(fc1_sqerr_tiles(T, rows, sz + 8) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, rows, T);
   int hmax = 1;
   for (int m = 0; m < INFER_DEC; ++m) hmax = std::max(hmax, Dl.P.d[m].seq.h);
-  const size_t lds_bytes = (size_t)(OBJ_BM + OBJ_BN) * (round_up(hmax, 4) + 2) * sizeof(float);
 
   const ObjLayout lay = objective_layout(T, N, sz, max_rows);
   float* zbuf[2 * INFER_ENC];
@@ -264,8 +221,7 @@ static int objective_klef(int T, int64_t N, const int32_t* sz, const float* lamb
       Q.part[m] = I.partials; Q.npart[m] = row_tiles * I.col_tiles;
       tiles += Q.npart[m];
     }
-    if ((rc = seq_launch_kernel(fc1_sqerr_kernel, "fc1_sqerr_kernel", dim3(tiles), dim3(OBJ_THREADS), lds_bytes, stream, nullptr, F)) != MFM_OK)
-      return rc;
+    if ((rc = fc1_sqerr_launch(F, tiles, hmax, stream)) != MFM_OK) return rc;
     for (int i = 0; i < INFER_ENC; ++i) Q.nz[i] = n * zs[i];
     Q.y = loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od) : (const void*)(reinterpret_cast<const int64_t*>(y) + n0);
     Q.n = n; Q.first = n0 == 0; Q.last = n0 + n == N;

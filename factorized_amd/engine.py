@@ -27,6 +27,10 @@ Factors = namedtuple("Factors", ["zl", "za", "zv", "zy", "logvar_zl", "logvar_za
 # what objective() returns: the validation objective and its five terms, 0-d float32 device tensors (views of one [6] tensor)
 Objective = namedtuple("Objective", ["loss", "disc", "gen_l", "gen_a", "gen_v", "reg"])
 
+# what predict_zeros() returns, the cases in the reference's order (no l, no a, no v): y_hat [3, N, output_dim], gen [3] (the
+# zeroed modality's reconstruction against the real one), disc [3] or None without labels -- float32 device tensors
+Zeros = namedtuple("Zeros", ["y_hat", "gen", "disc"])
+
 
 def klef_param_shapes(cfg):
     """Ordered name -> shape of MFM_KL_EF's 78 parameters (reference mfm_model.py:579-617)."""
@@ -798,6 +802,74 @@ class MFMEngine:
         out[1:6] = l[0:5]
         out[0] = l[0] + c["lda_xl"] * l[1] + c["lda_xa"] * l[2] + c["lda_xv"] * l[3] + c["lda_mmd"] * l[4]
         return Objective(*out.unbind(0))
+
+    # ------------------------------------------------------------------ the zeroed-modality test protocol
+    def predict_zeros_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace predict_zeros() keeps for a [T, N, D] split (mfm_predict_zeros_klef_workspace_floats)"""
+        return int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
+
+    def predict_zeros(self, x, y=None, *, max_rows=None):
+        """x [T, N, D] (, labels) -> Zeros(y_hat [3, N, output_dim], gen [3], disc [3] or None), float32 device tensors: the test
+        protocol of the reference's train_mfm_test_zeros (mfm_mosi.py:572-596) -- the split through the deterministic eval forward
+        with modality l, a, v zeroed in turn (the cases in that order); gen[c] = F.mse_loss(x_c_hat of case c, the REAL x_c),
+        unweighted, disc[c] the mean L1 / cross entropy of y_hat[c] as evaluate() defines it (None without labels).  Every mean is
+        over the whole split.
+
+        Variant "kl_ef": mfm_predict_zeros_klef -- no zeroed copy of x, the ef encoder's projection computed once for the three
+        cases, the zeroed encoder one row of work, one decoder per case with its fc1 fused into the squared error (x_hat is
+        never written); no plan and no training workspace; the split is walked in chunks of at most `max_rows` rows (default
+        PREDICT_MAX_ROWS).  Workspace and the three result tensors are kept per (T, N, max_rows) and REUSED: after the first
+        call for a shape nothing is allocated and nothing synchronises, and the returned tensors are overwritten by the next
+        call for the same shape (clone what must survive it).  Other variants, and sizes the entry refuses: the same namedtuple
+        from three forward(train=False, handover=False) calls on zeroed copies, the means formed on the device.  A refusal for a
+        hidden size above 128 is remembered; one for the LDS limit holds for that call alone, as in encode()."""
+        self._check_inputs(x, y)
+        T, N, D = x.shape
+        if T < 1 or N < 1:
+            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
+        c = self.cfg
+        od = c["output_dim"]
+        ce = c.get("loss", "l1") == "ce"
+        if y is not None and y.numel() != (N if ce else N * od):
+            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
+                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
+        cap = self._row_cap(max_rows)
+        if self.variant == "kl_ef" and not getattr(self, "_zeros_refused", False):
+            cache = self.__dict__.setdefault("_zeros_bufs", {})
+            st = cache.get((T, N, cap))
+            if st is None:
+                sizes = self._objective_sizes()
+                nws = int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(T, N, sizes, cap))
+                offs = (C.c_int64 * 78)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS + self._DECODE_TENSORS])
+                st = (torch.empty(nws, dtype=torch.float32, device=self.device),
+                      torch.empty(3, N, od, dtype=torch.float32, device=self.device),
+                      torch.zeros(3, dtype=torch.float32, device=self.device),
+                      torch.zeros(3, dtype=torch.float32, device=self.device), sizes, offs)
+            ws, y_hat, gen, disc, sizes, offs = st
+            rc = _lib.lib().mfm_predict_zeros_klef(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat),
+                                                   _ptr(gen), _ptr(disc) if y is not None else None, cap, _stream())
+            if rc == 0:
+                cache[(T, N, cap)] = st
+                return Zeros(y_hat, gen, disc if y is not None else None)
+            if rc != _lib.MFM_ERR_UNSUPPORTED:
+                _lib.check(rc, "mfm_predict_zeros_klef")
+            hs = [c["zl_size"] + c["za_size"] + c["zv_size"]] + [c["fy_size"] + c[k] for k in ("fl_size", "fa_size", "fv_size")]
+            self._zeros_refused = max(hs) > self.MAX_RESIDENT_H          # (as in encode)
+        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
+        y_hat = torch.empty(3, N, od, dtype=torch.float32, device=self.device)
+        gen = torch.empty(3, dtype=torch.float32, device=self.device)
+        disc = torch.empty(3, dtype=torch.float32, device=self.device) if y is not None else None
+        d_l, d_a, d_v = c["input_dims"]
+        for i, (a, b, key) in enumerate(((0, d_l, "x_l_hat"), (d_l, d_l + d_a, "x_a_hat"), (d_l + d_a, D, "x_v_hat"))):
+            xz = x.clone()
+            xz[:, :, a:b] = 0
+            out = self.forward(xz, y, train=False, handover=False)
+            y_hat[i].copy_(out["y_hat"])
+            # (the forward's own loss slot is the error against the zeroed columns: the protocol asks for the real ones)
+            gen[i] = (out[key] - x[:, :, a:b]).square().mean()
+            if y is not None:
+                disc[i] = out["losses"][0]
+        return Zeros(y_hat, gen, disc)
 
     def forward_train(self, x, p, grads_to_zero=None):
         """Training-mode forward of the module path's lazy losses (mfm_plan_forward_train): no labels, no output tensors --

@@ -566,6 +566,47 @@ int mfm_objective_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, 
                        int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The zeroed-modality test protocol of MFM_KL_EF (csrc/zeros.hip; reference mfm_mosi.py:572-596, `predict` of
+ * train_mfm_test_zeros): the split through the deterministic eval forward three times, each time with one modality's columns
+ * taken as zero -- case 0: no l ([0, d_l)), 1: no a ([d_l, d_l + d_a)), 2: no v ([d_l + d_a, D)) -- in the pattern of the entries
+ * above: fp32, dropout the identity, z = the mean heads, no MfmPlan, no training workspace, no zeroed copy of x and no x_hat in
+ * memory.
+ *   y_hat[c]  [N, output_dim]: y_hat of case c
+ *   gen[c]    mean over T * N * d_c of (x_c_hat of case c - the REAL x_c)^2: F.mse_loss as the reference prints it, unweighted
+ *   disc[c]   mean L1 (loss_kind 0) / cross entropy (1) of y_hat[c], as mfm_predict_klef defines it
+ * Only what these depend on runs (mfm_model.py:619-660): the ef encoder on the three zeroed inputs, encoder_c on zeros -- the
+ * same row z_c^0 for every sample --, decoder_c of case c, the classifier.  The encoders of the present modalities reach none of
+ * the results and do not run.  Per row chunk: ONE grouped fp32 GEMM of the ef encoder's input projection split by modality
+ * (P_m = x_m W_ih[:, columns of m]^T: every column of x meets W_ih once for the three cases); one pass that forms the gates of
+ * case c as the sum of the P_m, m != c, plus b_ih + b_hh; ONE launch of (ef encoder, case, row tile) workgroups (recurrence, fc1,
+ * last_to_zy_fc1 -> zy_c) which in the first chunk carries three more one-row workgroups for the z_c^0; the recurrence launch of
+ * mfm_decode_factors with decoder c on (z_c^0, zy_c), every decoder's workgroups also the classifier -> y_hat[c]; the fused fc1 /
+ * squared-error launch of mfm_objective_klef against the real x; one single-workgroup launch that adds the chunk's partials and
+ * label-loss terms in a fixed order into fp64 accumulators and, behind the last chunk, divides by the counts of the WHOLE split.
+ * No float atomics: the results are bit-identical from run to run for a given (T, N, max_rows).
+ *   sizes    host, 13: as mfm_objective_klef
+ *   offsets  host, 78 element offsets into the flat fp32 parameter buffer `params`: as mfm_objective_klef (the logvar heads'
+ *            are not read)
+ *   x        [T, N, D] time-major and contiguous, 16-byte aligned; it is read only, all of it
+ *   y        NULL, or the labels: float [N, output_dim] (loss_kind 0) / int64 [N] (loss_kind 1)
+ *   y_hat    out, [3, N, output_dim]; gen: out, 3 device floats; disc: out, 3 device floats -- NULL exactly when y is
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace; every mean is over the whole
+ *            split whatever the chunking
+ *   workspace mfm_predict_zeros_klef_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary; with
+ *            rows = min(N, max_rows): the larger of 6 * rows * T * 4 * round_up(zl + za + zv, 16) (three partial projections,
+ *            three gate sets) and the workspace of mfm_decode_factors (the stored h takes their place), the constant gates and
+ *            rows of the zeroed encoders, zy of the three cases, one partial per workgroup of the squared-error launch, and the
+ *            accumulators -- it does not grow with N beyond the row cap
+ * Nothing outside the workspace, y_hat, gen and disc is written.  T < 1, N < 1, a null pointer or max_rows < 0 return MFM_ERR_ARG
+ * before anything touches the GPU.  Any N >= 1 (< 2^24), T >= 1.  Sizes the on-chip recurrence does not cover (a hidden size > 128,
+ * or more LDS than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue nothing: run
+ * mfm_plan_forward(train = 0) on zeroed copies instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_predict_zeros_klef_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_zeros_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, const float* params, const int64_t* offsets /*host, 78*/,
+                           const float* x, const void* y /*or NULL*/, float* workspace, float* y_hat /*[3, N, output_dim]*/,
+                           float* gen /*3*/, float* disc /*3, or NULL*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Surrogate inference of MFM_missing (csrc/impute.hip; reference mfm_model.py:766-885, evaluated in mfm_mosi.py:572-596 and
  * :1023-1062): a missing modality m and the label from the other two modalities, in the pattern of the entries above -- fp32,
  * dropout the identity, no MfmPlan, no training workspace.  For every case m asked for
