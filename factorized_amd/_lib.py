@@ -15,6 +15,15 @@ MFM_LOSS_SLOTS = 8
 MFM_MAX_SEQ = 6
 ABI_VERSION = 5
 MFM_ERR_UNSUPPORTED = -3
+# slots of mfm_plan_latent_form's out[16] (include/mfm_hip.h): the kernel form the latent stack takes at the plan's sizes --
+# row or staged kernels, floats of the LDS weight panel (0: weights read from L2), rows per workgroup of the staged backward /
+# forward, MFMA or quad products, workgroups per row of the row kernels, tabulated or searched bias gradients, stages, whether
+# the early-fusion fc1 has a stage of its own, floats per row record, largest K / N of a layer, work items of the widest stage
+# forward / backward, biases of all layers together
+LATENT_FORM_SLOTS = ("row_path", "wpanel", "rows_per_wg", "rows_fwd", "mfma", "nch", "bias_tab", "nstages", "split0",
+                     "rec_size", "max_k", "max_n", "items_fwd", "items_bwd", "n_bias")
+# slots of mfm_plan_seq_form's out[4]: 1 = step-by-step path (0: weight-resident recurrence kernels), the widest resident h
+SEQ_FORM_SLOTS = ("stepwise", "max_resident_h")
 
 
 class MfmError(RuntimeError):
@@ -253,6 +262,8 @@ _SIGS = {
     "mfm_plan_clear_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mfm_plan_latent_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mfm_plan_seq_layout": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    "mfm_plan_latent_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "mfm_plan_seq_form": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "mfm_plan_mfn_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mfm_plan_flops_per_step": (C.c_double, [C.c_void_p]),
     "mfm_plan_bytes_per_step": (C.c_double, [C.c_void_p]),

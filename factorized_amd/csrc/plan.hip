@@ -285,6 +285,26 @@ extern "C" int mfm_plan_latent_layout(const MfmPlan* P, int64_t* out) {
   return MFM_OK;
 }
 
+extern "C" int mfm_plan_latent_form(const MfmPlan* P, int64_t* out) {
+  if (!P || !out) { set_error("mfm_plan_latent_form: null argument"); return MFM_ERR_ARG; }
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  const mfm::LatentDev& L = P->lat;
+  out[0] = L.row_path; out[1] = L.wpanel; out[2] = L.rows_per_wg; out[3] = L.rows_fwd; out[4] = L.mfma;
+  out[5] = L.nch; out[6] = L.row_path ? L.bias_tab : 0; out[7] = L.nstages; out[8] = P->lat_split0; out[9] = L.rec_size;
+  for (int i = 0; i < L.nops; ++i) {
+    out[10] = std::max<int64_t>(out[10], P->lat_ops[i].K);
+    out[11] = std::max<int64_t>(out[11], P->lat_ops[i].N);
+    out[14] += P->lat_ops[i].N;
+  }
+  for (int st = 0; st < L.nstages; ++st) {
+    int64_t sn = 0, sk = 0;
+    for (int i = L.stage_begin[st]; i < L.stage_begin[st + 1]; ++i) { sn += P->lat_ops[i].N; sk += P->lat_ops[i].K; }
+    out[12] = std::max(out[12], 4 * sn);
+    out[13] = std::max(out[13], 4 * sk);
+  }
+  return MFM_OK;
+}
+
 extern "C" int mfm_plan_seq_layout(const MfmPlan* P, int32_t which, int64_t* out) {
   if (!P || !out) { set_error("mfm_plan_seq_layout: null argument"); return MFM_ERR_ARG; }
   MFM_REQUIRE(which >= 0 && which < P->n_enc + 3, "mfm_plan_seq_layout: LSTM %d of %d", which, P->n_enc + 3);
@@ -301,6 +321,18 @@ extern "C" int mfm_plan_seq_layout(const MfmPlan* P, int32_t which, int64_t* out
     out[7] = P->h_last[which] >= 0 ? P->h_last[which] * f : -1;
   }
   out[11] = P->seq_bf16 ? 1 : 0;
+  return MFM_OK;
+}
+
+extern "C" int mfm_plan_seq_form(const MfmPlan* P, int32_t which, int64_t* out) {
+  if (!P || !out) { set_error("mfm_plan_seq_form: null argument"); return MFM_ERR_ARG; }
+  MFM_REQUIRE(which >= 0 && which < P->n_enc + 3, "mfm_plan_seq_form: LSTM %d of %d", which, P->n_enc + 3);
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  OptScope _opts(P->opts);
+  const mfm::SeqBuf& sb = which >= P->n_enc ? P->dec[which - P->n_enc] : P->enc[which];
+  // the rule of seq_launch (lstm_seq.hip), which sorts every launch group's LSTMs into the two families
+  out[0] = (sb.h > MFM_SEQ_MAX_RESIDENT_H || opt_get("MFM_SEQ_STEPWISE") != nullptr) ? 1 : 0;
+  out[1] = MFM_SEQ_MAX_RESIDENT_H;
   return MFM_OK;
 }
 

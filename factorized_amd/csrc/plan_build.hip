@@ -215,6 +215,7 @@ int build(MfmPlan* P) {
   const int lat_row_maxb = 256;
   bool split0 = V == 0 && c.B > lat_row_maxb && c.B > 4 * device_cus();   // (up to 4 rows x CUs one round of 4-row workgroups does)
   if (const char* e = opt_get("MFM_LATENT_SPLIT0")) split0 = V == 0 && atoi(e) != 0;
+  P->lat_split0 = split0 ? 1 : 0;
   for (int e = 0; e < nfc; ++e) {
     if (split0 && e == 3) ++st;
     add_op(P->lat_ops, L, st, e, L.in_off[e], last_off[e], in_n[e], in_n[e], o[pi.enc[e] + FC_W], o[pi.enc[e] + FC_B], 0, -1, 0.f);

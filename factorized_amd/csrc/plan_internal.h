@@ -82,6 +82,7 @@ struct MfmPlan {
   mfm::LatOp lat_ops[MFM_LAT_MAXOPS];
   int64_t lat_ops_off, lat_grd, lat_items_off;
   int lay_f1[4], lay_m1[4], lay_c1, lay_mc;   // record offsets kept for mfm_plan_latent_layout
+  int lat_split0 = 0;               // the early-fusion encoder's fc1 has a stage of its own (kept for mfm_plan_latent_form)
   std::vector<int> lat_items;       // row-path item tables: forward then backward, [MAXSTAGES][1024][4] each
   // timing
   int timing_mask, timing_every;

@@ -1028,6 +1028,29 @@ class MFMEngine:
         lay["width"]["fy_to_y"] = int(out[16])
         return rec, grd, lay
 
+    def latent_form(self, T, B):
+        """The kernel form the latent stack takes for the plan at (T,B) (mfm_plan_latent_form): dict with the keys of
+        _lib.LATENT_FORM_SLOTS; row_path, mfma, bias_tab and split0 as bool.  Tests / tuning aids."""
+        p = self.plan(T, B)
+        out = (C.c_int64 * 16)()
+        _lib.check(_lib.lib().mfm_plan_latent_form(p.handle, out), "mfm_plan_latent_form")
+        form = {k: int(out[i]) for i, k in enumerate(_lib.LATENT_FORM_SLOTS)}
+        for k in ("row_path", "mfma", "bias_tab", "split0"):
+            form[k] = bool(form[k])
+        return form
+
+    def seq_form(self, T, B):
+        """Kernel family of every LSTM of the plan at (T,B), encoders in plan order, then the three decoders
+        (mfm_plan_seq_form): list of dicts h, stepwise (False: weight-resident recurrence kernels).  Tests / tuning aids."""
+        p = self.plan(T, B)
+        res = []
+        lay, out = (C.c_int64 * 12)(), (C.c_int64 * 4)()
+        for which in range((4 if self.variant == "kl_ef" else 6) + 3):
+            _lib.check(_lib.lib().mfm_plan_seq_layout(p.handle, which, lay), "mfm_plan_seq_layout")
+            _lib.check(_lib.lib().mfm_plan_seq_form(p.handle, which, out), "mfm_plan_seq_form")
+            res.append(dict(h=int(lay[3]), decoder=bool(lay[6]), stepwise=bool(out[0])))
+        return res
+
     def seq_buffers(self, T, B, which):
         """Saved activations of LSTM `which` (encoders in plan order, then the three decoders) as views of the plan workspace
         (mfm_plan_seq_layout): gates [T,B,4,Hp], hs [T,B,Hp] (bf16 tensors on a bf16-resident plan), cs (fp32); decoders also

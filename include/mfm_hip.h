@@ -849,6 +849,15 @@ int mfm_plan_clear_status(MfmPlan* plan, void* workspace, void* stream);
  * f{l,a,v,y}, out[17..20] f segments (outputs of *_fc2), out[21] y_hat, out[22] 1 if the row-per-workgroup kernels
  * run at this (T,B), out[23..26] mu segments z{l,a,v,y} (inputs of *_fc1), out[27..30] their widths, out[31] reserved. */
 int mfm_plan_latent_layout(const MfmPlan* plan, int64_t* out /*[32]*/);
+/* Which kernel form the latent stack takes at this plan's sizes and (T,B) (tests: a size matrix asserts the form it is there
+ * for).  out[0] 1 = row-per-workgroup kernels, 0 = staged kernels; out[1] floats of the weight panel the staged kernels keep in
+ * LDS (0: they read the weights from L2); out[2] rows per workgroup of the staged backward, out[3] of the staged forward;
+ * out[4] 1 = the staged products run on the fp32 MFMA, 0 = quad form; out[5] workgroups per row of the row kernels (4: one per
+ * modality chain, 1 otherwise); out[6] 1 = the row backward adds its bias gradients from the tabulated list, 0 = it searches
+ * the op table (always 0 off the row path); out[7] stages; out[8] 1 = the early-fusion encoder's fc1 has a stage of its own;
+ * out[9] floats per row record; out[10] / out[11] the largest K / N of a layer; out[12] / out[13] work items of the widest
+ * stage, forward (4 x sum of N) / backward (4 x sum of K); out[14] biases of all layers together; out[15] reserved. */
+int mfm_plan_latent_form(const MfmPlan* plan, int64_t* out /*[16]*/);
 
 /* variants 1, 2: where the Memory Fusion Network keeps its [T*B, .] tensors inside the workspace (tests / tuning aids).
  * Byte offsets: out[0] cStar, out[1] h1 = drop(relu(att1_fc1)), out[2] its relu/dropout mask (0 | 1/(1-p)), out[3] attention,
@@ -864,6 +873,10 @@ int mfm_plan_mfn_layout(const MfmPlan* plan, int64_t* out /*[16]*/);
  * [T,B,Hp], out[8] d x_hat [T*B, out[9]] (out[10] real columns); encoders: out[7] the fp32 copy of h_{T-1} [B,Hp] (-1: none);
  * out[11] 1 when the recurrences run on the bf16 MFMA kernels. */
 int mfm_plan_seq_layout(const MfmPlan* plan, int32_t which, int64_t* out /*[12]*/);
+/* The kernel family of LSTM `which` (numbered as above): out[0] 0 = weight-resident recurrence kernels, 1 = step-by-step path
+ * (recurrent GEMM + cell kernel per time step: h above out[1], or MFM_SEQ_STEPWISE set); out[1] the widest resident h;
+ * out[2..3] reserved. */
+int mfm_plan_seq_form(const MfmPlan* plan, int32_t which, int64_t* out /*[4]*/);
 
 /* Algorithmic work of one training step at this plan's (T,B):
  * 3 x forward FLOPs; activation+input bytes per sample plus 10 P 4 parameter/optimizer bytes. */

@@ -72,6 +72,17 @@ def test_ablation_and_missing_modality_classes_keep_reference_state_dict():
         m.load_state_dict(rd)
 
 
+def test_engine_has_the_form_readers_beside_the_layout_readers():
+    """latent_form / seq_form (which kernel form a plan took) sit beside latent_record / seq_buffers, keyed by the slot names
+    _lib documents"""
+    from factorized_amd import _lib, engine
+    for name in ("latent_record", "seq_buffers", "mfn_buffers", "latent_form", "seq_form"):
+        assert callable(getattr(engine.MFMEngine, name)), name
+    assert len(set(_lib.LATENT_FORM_SLOTS)) == len(_lib.LATENT_FORM_SLOTS) <= 16
+    assert {"row_path", "wpanel", "rows_per_wg", "rows_fwd", "mfma", "nch", "bias_tab", "nstages", "split0"} <= set(_lib.LATENT_FORM_SLOTS)
+    assert _lib.SEQ_FORM_SLOTS[0] == "stepwise"
+
+
 def test_flat_layout_guard_word_sits_behind_every_tensor():
     """The guard word of the guarded optimizers (include/mfm_hip.h, mfm_adam_flat_guarded) is a spare granule of the flat buffer:
     inside it (so that a data-parallel all-reduce carries it), behind every tensor, outside every staged-training span."""
