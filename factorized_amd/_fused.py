@@ -142,15 +142,21 @@ class _FusedEngineMixin:
         return self._engine
 
     # ------------------------------------------------------------------ prediction only
+    def _infer_args(self, x, gauss=True):
+        """what the engine's no-plan entries start from: the engine (MfmError while the parameters are not on the GPU: there is
+        no CPU fallback), a device x as contiguous float32 and, `gauss` set, variant "mmd"'s fixed N(0,1) sample for the fallback"""
+        eng = self.engine
+        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        if gauss and self._engine_variant == "mmd":
+            g = getattr(self, "mmd_gauss", None)
+            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        return eng, x
+
     def _predict(self, x, y):
         """the engine's predict() on this module's parameters: always the deterministic eval computation (dropout off, the
         zy mean), whatever `self.training` says -- which is left as found -- without autograd and without lazy outputs"""
-        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
-        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
-            x = x.contiguous().float()
-        if self._engine_variant == "mmd":
-            g = getattr(self, "mmd_gauss", None)
-            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        eng, x = self._infer_args(x)
         with torch.no_grad():
             return eng.predict(x, y)
 
@@ -179,12 +185,7 @@ class _FusedEngineMixin:
         KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  MFM_KL_EF: engine.objective (no plan, x_hat never written);
         the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must survive it).
         MFM_KL / MFM, and sizes the fused entry refuses: the fused eval forward's loss slots."""
-        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
-        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
-            x = x.contiguous().float()
-        if self._engine_variant == "mmd":
-            g = getattr(self, "mmd_gauss", None)
-            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        eng, x = self._infer_args(x)
         with torch.no_grad():
             return eng.objective(x, y)
 
@@ -199,12 +200,7 @@ class _FusedEngineMixin:
         read.  MFM_KL_EF: engine.predict_zeros (no plan, no zeroed copies, x_hat never written); buffers are kept per (T, N,
         max_rows) and the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must
         survive it).  MFM_KL / MFM, and sizes the fused entry refuses: three fused eval forwards on zeroed copies."""
-        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
-        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
-            x = x.contiguous().float()
-        if self._engine_variant == "mmd":
-            g = getattr(self, "mmd_gauss", None)
-            eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
+        eng, x = self._infer_args(x)
         with torch.no_grad():
             return eng.predict_zeros(x, y)
 
@@ -258,9 +254,7 @@ class _FusedEngineMixin:
         them (clone what must survive it).  MFM_KL, and MFM_KL_EF at sizes the fused entry refuses: the composition of the
         module's own operations.  MFM: likewise; it has no last_to_z* / logvar heads, so zl, za, zv are the encoders' outputs
         and the four logvars are None."""
-        eng = self.engine          # (MfmError while the parameters are not on the GPU: there is no CPU fallback)
-        if torch.is_tensor(x) and x.is_cuda and not (x.dtype == torch.float32 and x.is_contiguous()):
-            x = x.contiguous().float()
+        eng, x = self._infer_args(x, gauss=False)
         with torch.no_grad():
             if self._engine_variant == "kl_ef" and not getattr(eng, "_encode_refused", False):
                 try:
@@ -386,30 +380,25 @@ class _KLEFFn(torch.autograd.Function):
         eng = module.engine
         T, B, _ = x.shape
         plan = ctx.plan
-        if eng.plan(T, B) is not plan or plan.fwd_serial != ctx.serial:
-            raise RuntimeError("MFM_KL_EF backward: another forward with the same (T=%d, B=%d) ran on this model since "
-                               "the graph was built; its activations replaced this one's in the plan workspace.  Call "
-                               "backward() before the next forward (gradient accumulation over several forwards: "
-                               "backward each one first)" % (T, B))
-        if plan.consumed:
-            raise RuntimeError("MFM_KL_EF backward: this graph was already back-propagated (BPTT overwrites the saved "
-                               "gates in place; retain_graph is not supported on the fused plan)")
-        plan.consumed = True
-        d_l, d_a, d_v = eng.cfg["input_dims"]
-        dev = x.device
-
-        def z(t, shape):
-            return torch.zeros(shape, device=dev) if t is None else t.contiguous().float()
-        d_xl, d_xa, d_xv = z(d_xl, (T, B, d_l)), z(d_xa, (T, B, d_a)), z(d_xv, (T, B, d_v))
-        d_y = z(d_y, (B, eng.cfg["output_dim"]))
-        d_kld = z(d_kld, ()).reshape(1)
+        _check_plan_live(plan, eng, ctx.serial, T, B)
         plan.ensure_handover(False)
-        eng.backward_ext(x, d_xl, d_xa, d_xv, d_y, d_kld)
+        eng.backward_ext(x, *_upstream(eng, x, d_xl, d_xa, d_xv, d_y, d_kld))
         # one copy of the flat gradient buffer, handed out as per-parameter views (the plan overwrites its own
         # buffer on the next call; 78 separate clones cost ~0.4 ms of host time per step)
         flat = eng.grads.clone()
         lay = eng.layout
         return (None, None) + tuple(flat[o:o + n].view(shp) for o, n, shp in lay.slots)
+
+
+def _upstream(eng, x, d_xl, d_xa, d_xv, d_y, d_kld):
+    """the five upstream gradients as backward_ext takes them: contiguous float32, zeros where autograd handed None (that
+    output is unused)"""
+    T, B, _ = x.shape
+    shapes = [(T, B, d) for d in eng.cfg["input_dims"]] + [(B, eng.cfg["output_dim"]), ()]
+    ups = [torch.zeros(shp, device=x.device) if g is None else g.contiguous().float()
+           for g, shp in zip((d_xl, d_xa, d_xv, d_y, d_kld), shapes)]
+    ups[4] = ups[4].reshape(1)
+    return ups
 
 
 def _check_plan_live(plan, eng, serial, T, B):
@@ -450,21 +439,14 @@ def _flat_backward_ext(module, plan, serial, x, d_xl, d_xa, d_xv, d_y, d_kld):
     eng = module.engine
     T, B, _ = x.shape
     _check_plan_live(plan, eng, serial, T, B)
-    d_l, d_a, d_v = eng.cfg["input_dims"]
-    dev = x.device
     mk = module._group_masks()
     present = mk["shared"].copy()
     for key, g in (("l", d_xl), ("a", d_xa), ("v", d_xv), ("disc", d_y)):
         if g is not None:
             present |= mk[key]
-
-    def z(t, shape):
-        return torch.zeros(shape, device=dev) if t is None else t.contiguous().float()
-    d_xl, d_xa, d_xv = z(d_xl, (T, B, d_l)), z(d_xa, (T, B, d_a)), z(d_xv, (T, B, d_v))
-    d_y = z(d_y, (B, eng.cfg["output_dim"]))
-    d_kld = z(d_kld, ()).reshape(1)
+    ups = _upstream(eng, x, d_xl, d_xa, d_xv, d_y, d_kld)
     plan.ensure_handover(eng.handover and module._handover_ok())
-    _into_flat(module, eng, present, lambda out: eng.backward_ext(x, d_xl, d_xa, d_xv, d_y, d_kld, out=out))
+    _into_flat(module, eng, present, lambda out: eng.backward_ext(x, *ups, out=out))
 
 
 class _KLEFFastFn(torch.autograd.Function):

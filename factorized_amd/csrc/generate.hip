@@ -120,9 +120,7 @@ int encode_klef_prepare(const char* who, int T, int64_t N, int d_l, int d_a, int
                         const int64_t* offs, float* ws, int64_t max_rows, EncLaunch& L) {
   int rc = infer_check_rows(who, N, max_rows);
   if (rc != MFM_OK) return rc;
-  for (int i = 0; i < ENC_OFFS; ++i)
-    MFM_REQUIRE(offs[i] >= 0 && (i % 10 >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
-                who, i, (long long)offs[i]);
+  if ((rc = infer_check_offsets(who, offs, ENC_OFFS, 10)) != MFM_OK) return rc;
   const int D = d_l + d_a + d_v;
   const int hh[GEN_ENC] = {zl, za, zv, zl + za + zv}, zs[GEN_ENC] = {zl, za, zv, zy};
   const int dd[GEN_ENC] = {d_l, d_a, d_v, D}, col[GEN_ENC] = {0, d_l, d_l + d_a, 0};
@@ -180,10 +178,10 @@ static int encode_klef(int T, int64_t N, int d_l, int d_a, int d_v, int zl, int 
               "%s: sizes must be positive (T %d, N %lld, dims %d %d %d, z %d %d %d %d)", who, T, (long long)N, d_l, d_a, d_v, zl, za, zv, zy);
   MFM_REQUIRE(params && offs && x && ws && out, "%s: bad arguments (params, offsets, x, workspace and outputs must not be null)", who);
   for (int i = 0; i < 8; ++i) MFM_REQUIRE(out[i], "%s: output %d is null", who, i);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  EncLaunch L;
-  int rc = encode_klef_prepare(who, T, N, d_l, d_a, d_v, zl, za, zv, zy, params, offs, ws, max_rows, L);
+  int rc = infer_check_aligned(who, params, x, ws);
   if (rc != MFM_OK) return rc;
+  EncLaunch L;
+  if ((rc = encode_klef_prepare(who, T, N, d_l, d_a, d_v, zl, za, zv, zy, params, offs, ws, max_rows, L)) != MFM_OK) return rc;
   for (int64_t n0 = 0; n0 < N; n0 += L.rows) {
     const int n = (int)std::min<int64_t>(L.rows, N - n0);
     float* o[2 * GEN_ENC];
@@ -200,11 +198,7 @@ int decode_factors_prepare(const char* who, int T, int64_t N, const int32_t* sz,
                            int64_t max_rows, DecLaunch& L) {
   int rc = infer_check_rows(who, N, max_rows);
   if (rc != MFM_OK) return rc;
-  for (int i = 0; i < DEC_OFFS; ++i) {
-    const bool lstm_w = i >= 16 && i < 34 && (i - 16) % 6 < 2;
-    MFM_REQUIRE(offs[i] >= 0 && (!lstm_w || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
-                who, i, (long long)offs[i]);
-  }
+  if ((rc = infer_check_offsets(who, offs, DEC_OFFS, 6, 16, 34)) != MFM_OK) return rc;
   const int zs[GEN_DEC] = {sz[0], sz[1], sz[2]}, zys = sz[3], fm[GEN_DEC] = {sz[4], sz[5], sz[6]}, fy = sz[7];
   const int dm[GEN_DEC] = {sz[8], sz[9], sz[10]}, od = sz[11];
   const int rows = (int)gen_rows(N, max_rows);
@@ -257,13 +251,12 @@ static int decode_factors(int T, int64_t N, const int32_t* sz, const float* para
                           float* ws, float* const* out, int64_t max_rows, hipStream_t stream) {
   static const char* who = "decode factors";
   MFM_REQUIRE(sz && params && offs && z && ws && out, "%s: bad arguments (sizes, params, offsets, factors, workspace and outputs must not be null)", who);
-  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
-  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
+  int rc = infer_check_sizes(who, T, N, sz);
+  if (rc != MFM_OK) return rc;
   for (int i = 0; i < 4; ++i) MFM_REQUIRE(z[i] && out[i], "%s: factor / output %d is null", who, i);
   MFM_REQUIRE((((uintptr_t)params | (uintptr_t)ws) & 15) == 0, "%s: params and workspace must be 16-byte aligned", who);
   DecLaunch L;
-  int rc = decode_factors_prepare(who, T, N, sz, params, offs, ws, max_rows, L);
-  if (rc != MFM_OK) return rc;
+  if ((rc = decode_factors_prepare(who, T, N, sz, params, offs, ws, max_rows, L)) != MFM_OK) return rc;
   const DecodeDev& P = L.P;
   for (int64_t n0 = 0; n0 < N; n0 += L.rows) {
     const int n = (int)std::min<int64_t>(L.rows, N - n0);

@@ -99,7 +99,6 @@ static bool imp_sizes(const int32_t* sz, int cases, ImpSizes& S) {
   return true;
 }
 
-static int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
 
 // workspace of one chunk, in floats, every part a multiple of 4: per case the two encoders' x-projections, the two z rows, the
 // decoder's stored h and the gathered pair
@@ -136,11 +135,10 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
                           float* const* out, int64_t max_rows, hipStream_t stream) {
   static const char* who = "impute missing";
   MFM_REQUIRE(sz && prm && x && ws && out, "%s: bad arguments (sizes, parameter table, x, workspace and outputs must not be null)", who);
-  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
-  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
-  MFM_REQUIRE(cases == 1 || cases == 2 || cases == 4 || cases == 7, "%s: cases = %d (bit 0 l, bit 1 a, bit 2 v: one of them, or all three)", who, cases);
-  int rc = infer_check_rows(who, N, max_rows);
+  int rc = infer_check_sizes(who, T, N, sz);
   if (rc != MFM_OK) return rc;
+  MFM_REQUIRE(cases == 1 || cases == 2 || cases == 4 || cases == 7, "%s: cases = %d (bit 0 l, bit 1 a, bit 2 v: one of them, or all three)", who, cases);
+  if ((rc = infer_check_rows(who, N, max_rows)) != MFM_OK) return rc;
   // (x is read by the gather alone, element by element; the GEMMs and the recurrences read the workspace 16 bytes at a time)
   MFM_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)ws & 15) == 0, "%s: x must be 4-byte aligned, the workspace 16-byte aligned", who);
   ImpSizes S;

@@ -64,15 +64,22 @@ struct Fc1SqItem {
   int d, h, Hp, col_tiles, tile_begin;
 };
 struct Fc1SqDev { Fc1SqItem it[INFER_DEC]; int64_t N; int M, n, D; };
-// fc1_sqerr_kernel on one chunk: `tiles` workgroups in all (the items' tile_begin and partials set by the caller), hmax the
-// widest h among the items.  The kernel stays in objective.hip alone
-int fc1_sqerr_launch(const Fc1SqDev& F, int tiles, int hmax, hipStream_t stream);
 // workgroups (= partial slots) of fc1_sqerr_kernel over a chunk of n rows; dm: the three decoders' output widths
 static int64_t fc1_sqerr_tiles(int64_t T, int64_t n, const int32_t* dm) {
   int64_t t = 0;
   for (int m = 0; m < INFER_DEC; ++m) t += ((T * n + OBJ_BM - 1) / OBJ_BM) * ((dm[m] + OBJ_BN - 1) / OBJ_BN);
   return t;
 }
+// the launch chunk by chunk, behind decode_factors_prepare (below), whose DecLaunch names T, the chunk rows and the d_m.
+// prepare: what does not depend on the chunk -- the decoders' stored h and fc1 into F, the widest h, the column of each modality
+// in x, 1 / (T N d_m) of the WHOLE split -- and the check that a chunk's workgroups can be counted with 32 bits.  The kernel
+// stays in objective.hip alone
+struct DecLaunch;
+struct Fc1SqLaunch { Fc1SqDev F; int T, hmax, col[INFER_DEC]; double inv_gen[INFER_DEC]; };
+int fc1_sqerr_prepare(const char* who, const DecLaunch& L, int64_t N, Fc1SqLaunch& S);
+// x: the whole split [T, N, D], the chunk its rows [n0, n0 + n); one partial per workgroup from `partials` on: modality m's
+// are the npart[m] floats at part[m]
+int fc1_sqerr_chunk(Fc1SqLaunch& S, const float* x, int64_t n0, int n, float* partials, const float** part, int* npart, hipStream_t stream);
 
 // sum over a workgroup of OBJ_THREADS in a fixed order; every thread returns it
 __device__ __forceinline__ double finish_sum(double v, double* red, const int tid) {
@@ -138,6 +145,8 @@ int decode_factors_chunk(const char* who, DecLaunch& L, const float* const* z, f
 // ---------------------------------------------------------------- host: sizes
 static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
 static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }
+// a part of a workspace, in floats: a multiple of 4, so that the next part is 16-byte aligned
+static int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
 static int64_t encode_ws_floats(int64_t T, int64_t N, int64_t zl, int64_t za, int64_t zv, int64_t max_rows) {
   return gen_rows(N, max_rows) * T * 4 * (hp_of(zl) + hp_of(za) + hp_of(zv) + hp_of(zl + za + zv));
 }
@@ -169,7 +178,41 @@ static void seq_fill(SeqDev& s, const float* w_ih, const float* w_hh, const floa
   s.h = h; s.Hp = round_up(h, 16); s.hk4 = gen_hk4(h); s.is_dec = is_dec;
 }
 
+// ---------------------------------------------------------------- host: labels
+// the labels of rows n0 on: y [N, od] floats (loss_kind 0) or [N] int64 class indices (1); null stays null
+static const void* labels_at(const void* y, int loss_kind, int64_t n0, int od) {
+  if (!y) return nullptr;
+  return loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od) : (const void*)(reinterpret_cast<const int64_t*>(y) + n0);
+}
+// what turns the label-loss sum of a whole split into its mean: 1 / (N od) (L1) or 1 / N (CE)
+static double inv_label_count(int loss_kind, int64_t N, int od) {
+  return loss_kind == 0 ? 1.0 / ((double)N * (double)od) : 1.0 / (double)N;
+}
+
 // ---------------------------------------------------------------- host: checks (MFM_OK, or the error set and its code)
+// T, N and the twelve sizes of a size array (zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim)
+static int infer_check_sizes(const char* who, int T, int64_t N, const int32_t* sz) {
+  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
+  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
+  return MFM_OK;
+}
+static int infer_check_loss_kind(const char* who, int loss_kind) {
+  MFM_REQUIRE(loss_kind == 0 || loss_kind == 1, "%s: unknown loss kind %d (0 = L1, 1 = cross entropy)", who, loss_kind);
+  return MFM_OK;
+}
+static int infer_check_aligned(const char* who, const void* params, const void* x, const void* ws) {
+  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
+  return MFM_OK;
+}
+// `count` parameter offsets; those in [lstm_begin, lstm_end) come in groups of `period`, an LSTM's weight_ih and weight_hh first
+static int infer_check_offsets(const char* who, const int64_t* offs, int count, int period, int lstm_begin = 0, int lstm_end = 1 << 30) {
+  for (int i = 0; i < count; ++i) {
+    const bool lstm_w = i >= lstm_begin && i < lstm_end && (i - lstm_begin) % period < 2;
+    MFM_REQUIRE(offs[i] >= 0 && (!lstm_w || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
+                who, i, (long long)offs[i]);
+  }
+  return MFM_OK;
+}
 static int infer_check_rows(const char* who, int64_t N, int64_t max_rows) {
   MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
   MFM_REQUIRE(N < ((int64_t)1 << 24), "%s: N = %lld rows (at most 2^24 - 1)", who, (long long)N);

@@ -131,15 +131,41 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const Obj
 }
 
 // ---------------------------------------------------------------- host
-int fc1_sqerr_launch(const Fc1SqDev& F, int tiles, int hmax, hipStream_t stream) {
-  const size_t lds_bytes = (size_t)(OBJ_BM + OBJ_BN) * (round_up(hmax, 4) + 2) * sizeof(float);
+int fc1_sqerr_prepare(const char* who, const DecLaunch& L, int64_t N, Fc1SqLaunch& S) {
+  const int T = L.P.T;
+  MFM_REQUIRE(fc1_sqerr_tiles(T, L.rows, L.dm) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, L.rows, T);
+  memset(&S, 0, sizeof(S));
+  S.hmax = 1;
+  for (int m = 0; m < INFER_DEC; ++m) {
+    const SeqDev& s = L.P.d[m].seq;
+    Fc1SqItem& I = S.F.it[m];
+    I.hs = s.hs; I.w = L.fcw[m]; I.bias = L.fcb[m];
+    I.d = L.dm[m]; I.h = s.h; I.Hp = s.Hp; I.col_tiles = cdiv(L.dm[m], OBJ_BN);
+    S.hmax = std::max(S.hmax, s.h);
+    S.col[m] = S.F.D;
+    S.F.D += L.dm[m];
+    S.inv_gen[m] = 1.0 / ((double)T * (double)N * (double)L.dm[m]);
+  }
+  S.F.N = N; S.T = T;
+  return MFM_OK;
+}
+
+int fc1_sqerr_chunk(Fc1SqLaunch& S, const float* x, int64_t n0, int n, float* partials, const float** part, int* npart, hipStream_t stream) {
+  Fc1SqDev& F = S.F;
+  F.M = S.T * n; F.n = n;
+  const int row_tiles = cdiv(F.M, OBJ_BM);
+  int tiles = 0;
+  for (int m = 0; m < INFER_DEC; ++m) {
+    Fc1SqItem& I = F.it[m];
+    I.x = x + n0 * F.D + S.col[m];
+    I.tile_begin = tiles; I.partials = partials + tiles;
+    part[m] = I.partials; npart[m] = row_tiles * I.col_tiles;
+    tiles += npart[m];
+  }
+  const size_t lds_bytes = (size_t)(OBJ_BM + OBJ_BN) * (round_up(S.hmax, 4) + 2) * sizeof(float);
   return seq_launch_kernel(fc1_sqerr_kernel, "fc1_sqerr_kernel", dim3(tiles), dim3(OBJ_THREADS), lds_bytes, stream, nullptr, F);
 }
 
-#define OBJ_SIZES 13       // the 12 of mfm_decode_factors, then loss_kind
-#define OBJ_OFFS 78        // the 40 of mfm_encode_klef, then the 38 of mfm_decode_factors
-
-static int64_t r4(int64_t v) { return (v + 3) / 4 * 4; }
 // the workspace, in this order (every part a multiple of 4 floats): the chunk's x-projections and, behind the encoders, the
 // decoders' h in the same place; its eight factors; its y_hat; its squared-error partials; the OBJ_ACC fp64 accumulators
 struct ObjLayout { int64_t seq, z, y_hat, part, total; };
@@ -148,61 +174,48 @@ static ObjLayout objective_layout(int64_t T, int64_t N, const int32_t* sz, int64
   ObjLayout o;
   o.seq = std::max(encode_ws_floats(T, N, sz[0], sz[1], sz[2], max_rows), decode_ws_floats(T, N, sz[7], sz[4], sz[5], sz[6], max_rows));
   o.z = o.seq;
-  o.y_hat = o.z + 2 * (r4(rows * sz[0]) + r4(rows * sz[1]) + r4(rows * sz[2]) + r4(rows * sz[3]));
-  o.part = o.y_hat + r4(rows * sz[11]);
-  o.total = o.part + r4(fc1_sqerr_tiles(T, rows, sz + 8)) + r4(2 * OBJ_ACC);
+  o.y_hat = o.z + 2 * (up4(rows * sz[0]) + up4(rows * sz[1]) + up4(rows * sz[2]) + up4(rows * sz[3]));
+  o.part = o.y_hat + up4(rows * sz[11]);
+  o.total = o.part + up4(fc1_sqerr_tiles(T, rows, sz + 8)) + up4(2 * OBJ_ACC);
   return o;
 }
 
 static int objective_klef(int T, int64_t N, const int32_t* sz, const float* lambdas, const float* params, const int64_t* offs,
                           const float* x, const void* y, float* ws, float* out, int64_t max_rows, hipStream_t stream) {
   static const char* who = "objective klef";
-  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
   MFM_REQUIRE(sz && lambdas && params && offs && x && y && ws && out,
               "%s: bad arguments (sizes, lambdas, params, offsets, x, y, workspace and out must not be null)", who);
-  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
-  MFM_REQUIRE(sz[12] == 0 || sz[12] == 1, "%s: unknown loss kind %d (0 = L1, 1 = cross entropy)", who, sz[12]);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  MFM_REQUIRE(max_rows >= 0, "%s: row cap %lld (0 = the whole split in one chunk)", who, (long long)max_rows);
-  const int zs[INFER_ENC] = {sz[0], sz[1], sz[2], sz[3]}, dm[INFER_DEC] = {sz[8], sz[9], sz[10]};
-  const int od = sz[11], loss_kind = sz[12], D = dm[0] + dm[1] + dm[2];
-  const int col[INFER_DEC] = {0, dm[0], dm[0] + dm[1]};
+  int rc = infer_check_sizes(who, T, N, sz);
+  if (rc != MFM_OK) return rc;
+  if ((rc = infer_check_loss_kind(who, sz[12])) != MFM_OK) return rc;
+  if ((rc = infer_check_aligned(who, params, x, ws)) != MFM_OK) return rc;
+  const int zs[INFER_ENC] = {sz[0], sz[1], sz[2], sz[3]};
+  const int od = sz[11], loss_kind = sz[12];
   EncLaunch E;
   DecLaunch Dl;
-  int rc = encode_klef_prepare(who, T, N, dm[0], dm[1], dm[2], zs[0], zs[1], zs[2], zs[3], params, offs, ws, max_rows, E);
-  if (rc != MFM_OK) return rc;
+  Fc1SqLaunch S;
+  if ((rc = encode_klef_prepare(who, T, N, sz[8], sz[9], sz[10], zs[0], zs[1], zs[2], zs[3], params, offs, ws, max_rows, E)) != MFM_OK) return rc;
   if ((rc = decode_factors_prepare(who, T, N, sz, params, offs + 40, ws, max_rows, Dl)) != MFM_OK) return rc;
+  if ((rc = fc1_sqerr_prepare(who, Dl, N, S)) != MFM_OK) return rc;
   const int rows = E.rows;
-  MFM_REQUIRE(fc1_sqerr_tiles(T, rows, sz + 8) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, rows, T);
-  int hmax = 1;
-  for (int m = 0; m < INFER_DEC; ++m) hmax = std::max(hmax, Dl.P.d[m].seq.h);
 
   const ObjLayout lay = objective_layout(T, N, sz, max_rows);
   float* zbuf[2 * INFER_ENC];
   {
     float* p = ws + lay.z;
     for (int half = 0; half < 2; ++half)
-      for (int i = 0; i < INFER_ENC; ++i) { zbuf[4 * half + i] = p; p += r4((int64_t)rows * zs[i]); }
+      for (int i = 0; i < INFER_ENC; ++i) { zbuf[4 * half + i] = p; p += up4((int64_t)rows * zs[i]); }
   }
   float* y_hat = ws + lay.y_hat;
   float* part = ws + lay.part;
-  double* acc = reinterpret_cast<double*>(ws + lay.total - r4(2 * OBJ_ACC));      // (a multiple of 4 floats from a 16-byte aligned base)
+  double* acc = reinterpret_cast<double*>(ws + lay.total - up4(2 * OBJ_ACC));      // (a multiple of 4 floats from a 16-byte aligned base)
 
-  Fc1SqDev F;
-  memset(&F, 0, sizeof(F));
   ObjFinishDev Q;
   memset(&Q, 0, sizeof(Q));
-  for (int m = 0; m < INFER_DEC; ++m) {
-    const SeqDev& s = Dl.P.d[m].seq;
-    Fc1SqItem& I = F.it[m];
-    I.hs = s.hs; I.w = Dl.fcw[m]; I.bias = Dl.fcb[m];
-    I.d = dm[m]; I.h = s.h; I.Hp = s.Hp; I.col_tiles = cdiv(dm[m], OBJ_BN);
-    Q.inv_gen[m] = 1.0 / ((double)T * (double)N * (double)dm[m]);
-  }
-  F.N = N; F.D = D;
+  for (int m = 0; m < INFER_DEC; ++m) Q.inv_gen[m] = S.inv_gen[m];
   for (int i = 0; i < INFER_ENC; ++i) { Q.mu[i] = zbuf[i]; Q.lv[i] = zbuf[4 + i]; }
   Q.y_hat = y_hat; Q.acc = acc; Q.out = out;
-  Q.inv_disc = loss_kind == 0 ? 1.0 / ((double)N * (double)od) : 1.0 / (double)N;
+  Q.inv_disc = inv_label_count(loss_kind, N, od);
   for (int i = 0; i < 4; ++i) Q.lda[i] = lambdas[i];
   Q.od = od; Q.loss_kind = loss_kind;
 
@@ -211,19 +224,9 @@ static int objective_klef(int T, int64_t N, const int32_t* sz, const float* lamb
     if ((rc = encode_klef_chunk(E, x, N, n0, n, zbuf, stream)) != MFM_OK) return rc;
     // (the x-projections are dead behind the encoders' launch: the decoders' h takes their place)
     if ((rc = decode_factors_chunk(who, Dl, zbuf, y_hat, n, stream)) != MFM_OK) return rc;
-    F.M = T * n; F.n = n;
-    const int row_tiles = cdiv(F.M, OBJ_BM);
-    int tiles = 0;
-    for (int m = 0; m < INFER_DEC; ++m) {
-      Fc1SqItem& I = F.it[m];
-      I.x = x + n0 * D + col[m];
-      I.tile_begin = tiles; I.partials = part + tiles;
-      Q.part[m] = I.partials; Q.npart[m] = row_tiles * I.col_tiles;
-      tiles += Q.npart[m];
-    }
-    if ((rc = fc1_sqerr_launch(F, tiles, hmax, stream)) != MFM_OK) return rc;
+    if ((rc = fc1_sqerr_chunk(S, x, n0, n, part, Q.part, Q.npart, stream)) != MFM_OK) return rc;
     for (int i = 0; i < INFER_ENC; ++i) Q.nz[i] = n * zs[i];
-    Q.y = loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od) : (const void*)(reinterpret_cast<const int64_t*>(y) + n0);
+    Q.y = labels_at(y, loss_kind, n0, od);
     Q.n = n; Q.first = n0 == 0; Q.last = n0 + n == N;
     if ((rc = seq_launch_kernel(objective_finish_kernel, "objective_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q)) != MFM_OK)
       return rc;

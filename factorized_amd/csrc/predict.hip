@@ -110,13 +110,12 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
   static const char* who = "predict klef";
   MFM_REQUIRE(T >= 1 && N >= 1 && D >= 1 && h >= 1 && zy >= 1 && fy >= 1 && od >= 1, "%s: sizes must be positive (T %d, N %lld, D %d, h %d, zy %d, fy %d, output_dim %d)",
               who, T, (long long)N, D, h, zy, fy, od);
-  MFM_REQUIRE(loss_kind == 0 || loss_kind == 1, "%s: unknown loss kind %d (0 = L1, 1 = cross entropy)", who, loss_kind);
-  MFM_REQUIRE(params && offs && x && ws && y_hat, "%s: bad arguments (params, offsets, x, workspace and y_hat must not be null)", who);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  int rc = infer_check_rows(who, N, max_rows);
+  int rc = infer_check_loss_kind(who, loss_kind);
   if (rc != MFM_OK) return rc;
-  for (int i = 0; i < 4 + 2 * PRED_LAYERS; ++i)
-    MFM_REQUIRE(offs[i] >= 0 && (i >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)", who, i, (long long)offs[i]);
+  MFM_REQUIRE(params && offs && x && ws && y_hat, "%s: bad arguments (params, offsets, x, workspace and y_hat must not be null)", who);
+  if ((rc = infer_check_aligned(who, params, x, ws)) != MFM_OK) return rc;
+  if ((rc = infer_check_rows(who, N, max_rows)) != MFM_OK) return rc;
+  if ((rc = infer_check_offsets(who, offs, 4 + 2 * PRED_LAYERS, 4 + 2 * PRED_LAYERS)) != MFM_OK) return rc;
   const int maxw = std::max(std::max(h, zy), std::max(fy, od));
   const int rows = (int)gen_rows(N, max_rows);
   const int R = gen_tile_rows(1, rows), Hp = round_up(h, 16);
@@ -147,7 +146,7 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
   P.T = T; P.od = od; P.loss_kind = loss_kind; P.maxw = maxw;
   P.partials = partials; P.ticket = ticket; P.loss = with_loss ? loss_dev : nullptr;
   P.wg_total = wg_total;
-  P.inv = loss_kind == 0 ? (float)(1.0 / ((double)N * (double)od)) : (float)(1.0 / (double)N);
+  P.inv = (float)inv_label_count(loss_kind, N, od);
   const int threads = std::max(8 * Hp, 64);
 
   int wg_base = 0;
@@ -160,9 +159,7 @@ static int predict_klef(int T, int64_t N, int D, int h, int zy, int fy, int od, 
     });
     if (rc != MFM_OK) return rc;
     P.n = n;
-    P.y = !with_loss ? nullptr
-                     : (loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od)
-                                       : (const void*)(reinterpret_cast<const int64_t*>(y) + n0));
+    P.y = with_loss ? labels_at(y, loss_kind, n0, od) : nullptr;
     P.y_hat = y_hat + n0 * od;
     P.wg_base = wg_base;
     const int grid = cdiv(n, R);

@@ -146,8 +146,6 @@ __global__ __launch_bounds__(OBJ_THREADS) void zeros_finish_kernel(const ZerFini
 // ---------------------------------------------------------------- host
 static const int kZerEnc[4] = {8, 2, 20, 30};      // the canonical sizes: encoders l / a / v h = 32 / 8 / 80, ef h = 120
 
-static int64_t z4(int64_t v) { return (v + 3) / 4 * 4; }
-
 // the workspace, in this order (every part a multiple of 4 floats): the chunk's three partial projections and three gate sets
 // and, behind the recurrences, the decoders' h in the same place; the zeroed encoders' constant gates; their factors, one row per
 // chunk row; zy of the three cases; the squared-error partials; the ZER_ACC fp64 accumulators
@@ -158,10 +156,10 @@ static ZerLayout zeros_layout(int64_t T, int64_t N, const int32_t* sz, int64_t m
   ZerLayout o;
   o.cgates = std::max(rows * T * 4 * hp_of(he) * 2 * ZER_CASES, decode_ws_floats(T, N, sz[7], sz[4], sz[5], sz[6], max_rows));
   o.zc = o.cgates + T * 4 * (hp_of(sz[0]) + hp_of(sz[1]) + hp_of(sz[2]));
-  o.zy = o.zc + z4(rows * sz[0]) + z4(rows * sz[1]) + z4(rows * sz[2]);
-  o.part = o.zy + ZER_CASES * z4(rows * sz[3]);
-  o.acc = o.part + z4(fc1_sqerr_tiles(T, rows, sz + 8));
-  o.total = o.acc + z4(2 * ZER_ACC);
+  o.zy = o.zc + up4(rows * sz[0]) + up4(rows * sz[1]) + up4(rows * sz[2]);
+  o.part = o.zy + ZER_CASES * up4(rows * sz[3]);
+  o.acc = o.part + up4(fc1_sqerr_tiles(T, rows, sz + 8));
+  o.total = o.acc + up4(2 * ZER_ACC);
   return o;
 }
 
@@ -193,21 +191,17 @@ static int zeros_encode_launch(const char* who, ZerEncDev& P, const int* slot, i
 static int predict_zeros_klef(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* x,
                               const void* y, float* ws, float* y_hat, float* gen, float* disc, int64_t max_rows, hipStream_t stream) {
   static const char* who = "predict zeros klef";
-  MFM_REQUIRE(T >= 1 && N >= 1, "%s: sizes must be positive (T %d, N %lld)", who, T, (long long)N);
   MFM_REQUIRE(sz && params && offs && x && ws && y_hat && gen,
               "%s: bad arguments (sizes, params, offsets, x, workspace, y_hat and gen must not be null)", who);
   MFM_REQUIRE((y != nullptr) == (disc != nullptr), "%s: labels and disc come together (both, or both null)", who);
-  for (int i = 0; i < 12; ++i) MFM_REQUIRE(sz[i] >= 1, "%s: sizes must be positive (size %d is %d)", who, i, sz[i]);
-  MFM_REQUIRE(sz[12] == 0 || sz[12] == 1, "%s: unknown loss kind %d (0 = L1, 1 = cross entropy)", who, sz[12]);
-  MFM_REQUIRE((((uintptr_t)params | (uintptr_t)x | (uintptr_t)ws) & 15) == 0, "%s: params, x and workspace must be 16-byte aligned", who);
-  int rc = infer_check_rows(who, N, max_rows);
+  int rc = infer_check_sizes(who, T, N, sz);
   if (rc != MFM_OK) return rc;
-  for (int i = 0; i < 40; ++i)
-    MFM_REQUIRE(offs[i] >= 0 && (i % 10 >= 2 || (offs[i] & 3) == 0), "%s: parameter offset %d is %lld (not negative; the LSTM weights 16-byte aligned)",
-                who, i, (long long)offs[i]);
+  if ((rc = infer_check_loss_kind(who, sz[12])) != MFM_OK) return rc;
+  if ((rc = infer_check_aligned(who, params, x, ws)) != MFM_OK) return rc;
+  if ((rc = infer_check_rows(who, N, max_rows)) != MFM_OK) return rc;
+  if ((rc = infer_check_offsets(who, offs, 40, 10)) != MFM_OK) return rc;
   const int zs[ZER_CASES] = {sz[0], sz[1], sz[2]}, zys = sz[3], dm[ZER_CASES] = {sz[8], sz[9], sz[10]};
   const int od = sz[11], loss_kind = sz[12], D = dm[0] + dm[1] + dm[2], he = zs[0] + zs[1] + zs[2];
-  const int col[ZER_CASES] = {0, dm[0], dm[0] + dm[1]};
   const int hh[4] = {zs[0], zs[1], zs[2], he};
   const int rows = (int)gen_rows(N, max_rows);
   const int R = gen_tile_rows(ZER_CASES, rows);
@@ -223,19 +217,19 @@ static int predict_zeros_klef(int T, int64_t N, const int32_t* sz, const float* 
   const int Hpe = round_up(he, 16);
   if ((rc = infer_check_chunk(who, rows, T, std::max(D, 4 * Hpe), "projection")) != MFM_OK) return rc;
   DecLaunch Dl;
+  Fc1SqLaunch S;
   if ((rc = decode_factors_prepare(who, T, N, sz, params, offs + 40, ws, max_rows, Dl)) != MFM_OK) return rc;
-  MFM_REQUIRE(fc1_sqerr_tiles(T, rows, sz + 8) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, rows, T);
-  int hmax = 1;
-  for (int m = 0; m < ZER_CASES; ++m) hmax = std::max(hmax, Dl.P.d[m].seq.h);
+  if ((rc = fc1_sqerr_prepare(who, Dl, N, S)) != MFM_OK) return rc;
+  const int* col = S.col;                     // the first column of each modality in x
 
   const ZerLayout lay = zeros_layout(T, N, sz, max_rows);
   const int64_t gsz = (int64_t)rows * T * 4 * Hpe;        // one partial projection / one gate set of a full chunk
   float* zc[ZER_CASES]; float* zyb[ZER_CASES];
   {
     float* p = ws + lay.zc;
-    for (int m = 0; m < ZER_CASES; ++m) { zc[m] = p; p += z4((int64_t)rows * zs[m]); }
+    for (int m = 0; m < ZER_CASES; ++m) { zc[m] = p; p += up4((int64_t)rows * zs[m]); }
     p = ws + lay.zy;
-    for (int c = 0; c < ZER_CASES; ++c) { zyb[c] = p; p += z4((int64_t)rows * zys); }
+    for (int c = 0; c < ZER_CASES; ++c) { zyb[c] = p; p += up4((int64_t)rows * zys); }
   }
   float* part = ws + lay.part;
   double* acc = reinterpret_cast<double*>(ws + lay.acc);      // (a multiple of 4 floats from a 16-byte aligned base)
@@ -274,20 +268,11 @@ static int predict_zeros_klef(int T, int64_t N, const int32_t* sz, const float* 
   PE.T = T; PE.maxw = maxw;
   const SeqDev& ef = PE.d[0].seq;
 
-  Fc1SqDev F;
-  memset(&F, 0, sizeof(F));
   ZerFinishDev Q;
   memset(&Q, 0, sizeof(Q));
-  for (int m = 0; m < ZER_CASES; ++m) {
-    const SeqDev& s = Dl.P.d[m].seq;
-    Fc1SqItem& I = F.it[m];
-    I.hs = s.hs; I.w = Dl.fcw[m]; I.bias = Dl.fcb[m];
-    I.d = dm[m]; I.h = s.h; I.Hp = s.Hp; I.col_tiles = cdiv(dm[m], OBJ_BN);
-    Q.inv_gen[m] = 1.0 / ((double)T * (double)N * (double)dm[m]);
-  }
-  F.N = N; F.D = D;
+  for (int m = 0; m < ZER_CASES; ++m) Q.inv_gen[m] = S.inv_gen[m];
   Q.acc = acc; Q.gen = gen; Q.disc = disc;
-  Q.inv_disc = loss_kind == 0 ? 1.0 / ((double)N * (double)od) : 1.0 / (double)N;
+  Q.inv_disc = inv_label_count(loss_kind, N, od);
   Q.od = od; Q.loss_kind = loss_kind;
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
@@ -321,20 +306,9 @@ static int predict_zeros_klef(int T, int64_t N, const int32_t* sz, const float* 
       PD.d[c].y_hat = y_hat + ((int64_t)c * N + n0) * od;
     }
     if ((rc = decode_factors_launch(who, PD, Dl.R, Dl.threads, Dl.lds_bytes, stream)) != MFM_OK) return rc;
-    F.M = T * n; F.n = n;
-    const int row_tiles = cdiv(F.M, OBJ_BM);
-    int tiles = 0;
-    for (int m = 0; m < ZER_CASES; ++m) {
-      Fc1SqItem& I = F.it[m];
-      I.x = x + n0 * D + col[m];
-      I.tile_begin = tiles; I.partials = part + tiles;
-      Q.part[m] = I.partials; Q.npart[m] = row_tiles * I.col_tiles;
-      tiles += Q.npart[m];
-      Q.y_hat[m] = PD.d[m].y_hat;
-    }
-    if ((rc = fc1_sqerr_launch(F, tiles, hmax, stream)) != MFM_OK) return rc;
-    Q.y = !y ? nullptr
-             : (loss_kind == 0 ? (const void*)(reinterpret_cast<const float*>(y) + n0 * od) : (const void*)(reinterpret_cast<const int64_t*>(y) + n0));
+    if ((rc = fc1_sqerr_chunk(S, x, n0, n, part, Q.part, Q.npart, stream)) != MFM_OK) return rc;
+    for (int c = 0; c < ZER_CASES; ++c) Q.y_hat[c] = PD.d[c].y_hat;
+    Q.y = labels_at(y, loss_kind, n0, od);
     Q.n = n; Q.first = first; Q.last = n0 + n == N;
     if ((rc = seq_launch_kernel(zeros_finish_kernel, "zeros_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q)) != MFM_OK)
       return rc;

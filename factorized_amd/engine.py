@@ -8,28 +8,21 @@ Python call = one C call = the whole forward/backward/Adam chain enqueued on the
 current HIP stream (reference: MFM_KL_EF.forward mfm_model.py:619-660 plus the
 hot loop mfm_mosi.py:424-442).
 
+The no-plan inference entries (predict, encode, decode, objective, predict_zeros) are _infer.InferMixin.
+
 PyTorch is used for device memory, streams and torch.distributed only.
 """
 import ctypes as C
 import os
-from collections import OrderedDict, namedtuple
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _flat, _lib
+from ._infer import Factors, InferMixin, Objective, Zeros, _ptr, _stream  # noqa: F401  (the namedtuples: part of this module's interface)
 
 ALIGN = 64  # floats
-
-# what encode() returns: the means and log-variances of the four latent factors, [N, size] each (logvars None for variant "mmd")
-Factors = namedtuple("Factors", ["zl", "za", "zv", "zy", "logvar_zl", "logvar_za", "logvar_zv", "logvar_zy"])
-
-# what objective() returns: the validation objective and its five terms, 0-d float32 device tensors (views of one [6] tensor)
-Objective = namedtuple("Objective", ["loss", "disc", "gen_l", "gen_a", "gen_v", "reg"])
-
-# what predict_zeros() returns, the cases in the reference's order (no l, no a, no v): y_hat [3, N, output_dim], gen [3] (the
-# zeroed modality's reconstruction against the real one), disc [3] or None without labels -- float32 device tensors
-Zeros = namedtuple("Zeros", ["y_hat", "gen", "disc"])
 
 
 def klef_param_shapes(cfg):
@@ -246,16 +239,6 @@ class FlatLayout:
         return out
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    # raw handle of the current stream of the current device: torch.cuda.current_stream() builds a Stream object through
-    # three layers of device-index helpers (~10-20 us of host time per call; measured in the unchanged-loop profile)
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
-
-
 class _Plan:
     def __init__(self, engine, T, B, reg_scale):
         cfg = engine.cfg
@@ -359,7 +342,7 @@ class _Plan:
             pass
 
 
-class MFMEngine:
+class MFMEngine(InferMixin):
     """The fused training / inference step of MFM_KL_EF (variant "kl_ef"), MFM_KL ("kl") or MFM ("mmd") on one MI355X.
     `configs` is the reference's six-dict list."""
 
@@ -538,338 +521,6 @@ class MFMEngine:
         out["y_hat"] = y_hat
         out["losses"] = p.losses
         return out
-
-    # ------------------------------------------------------------------ prediction only
-    PREDICT_MAX_ROWS = 1024      # default row cap of predict(): the x-projections of at most this many rows are alive at once
-
-    _PREDICT_TENSORS = ("ef_encoder.lstm.weight_ih", "ef_encoder.lstm.weight_hh", "ef_encoder.lstm.bias_ih",
-                        "ef_encoder.lstm.bias_hh", "ef_encoder.fc1.weight", "ef_encoder.fc1.bias",
-                        "last_to_zy_fc1.weight", "last_to_zy_fc1.bias", "zy_to_fy_fc1.weight", "zy_to_fy_fc1.bias",
-                        "zy_to_fy_fc2.weight", "zy_to_fy_fc2.bias", "fy_to_y_fc1.weight", "fy_to_y_fc1.bias",
-                        "fy_to_y_fc2.weight", "fy_to_y_fc2.bias")
-
-    def predict_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace predict() keeps for a [T, N, D] split (mfm_predict_klef_workspace_floats)"""
-        c = self.cfg
-        cap = self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
-        return int(_lib.lib().mfm_predict_klef_workspace_floats(int(T), int(N), c["zl_size"] + c["za_size"] + c["zv_size"], cap))
-
-    def predict(self, x, y=None, *, max_rows=None):
-        """x [T, N, D] (, labels) -> {"y_hat": [N, output_dim], "loss": 0-d device tensor or None}: the deterministic eval
-        computation of y_hat and, with labels, the mean L1 / cross-entropy loss, left on the device.
-
-        Variant "kl_ef": mfm_predict_klef -- the ef encoder's recurrence and the six layers behind it, nothing of the
-        generative half, no plan and no training workspace; the split is walked in chunks of at most `max_rows` rows
-        (default PREDICT_MAX_ROWS).  Workspace, y_hat and the loss word are kept per (T, N, max_rows) and REUSED: after the
-        first call for a shape nothing is allocated and nothing synchronises, and the returned tensors are overwritten by the
-        next call for the same shape (clone what must survive it).  Other variants, and sizes the entry refuses (h > 128):
-        the same dictionary from forward(train=False, want_xhat=False)."""
-        self._check_inputs(x, y)
-        T, N, D = x.shape
-        if T < 1 or N < 1:
-            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
-        c = self.cfg
-        od = c["output_dim"]
-        ce = c.get("loss", "l1") == "ce"
-        if y is not None and y.numel() != (N if ce else N * od):
-            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
-                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
-        if max_rows is not None and int(max_rows) < 1:
-            raise _lib.MfmError("max_rows must be at least 1, not %r" % (max_rows,))
-        if self.variant == "kl_ef" and not getattr(self, "_predict_refused", False):
-            cap = self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
-            cache = self.__dict__.setdefault("_predict_bufs", {})
-            st = cache.get((T, N, cap))
-            h = c["zl_size"] + c["za_size"] + c["zv_size"]
-            if st is None:
-                nws = int(_lib.lib().mfm_predict_klef_workspace_floats(T, N, h, cap))
-                offs = (C.c_int64 * 16)(*[self.layout.offsets[n] for n in self._PREDICT_TENSORS])
-                st = (torch.empty(nws, dtype=torch.float32, device=self.device),
-                      torch.empty(N, od, dtype=torch.float32, device=self.device),
-                      torch.zeros((), dtype=torch.float32, device=self.device), offs)
-            ws, y_hat, loss, offs = st
-            rc = _lib.lib().mfm_predict_klef(T, N, D, h, c["zy_size"], c["fy_size"], od, 1 if ce else 0, _ptr(self.params), offs,
-                                             _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat), _ptr(loss) if y is not None else None,
-                                             cap, _stream())
-            if rc == 0:
-                cache[(T, N, cap)] = st
-                return {"y_hat": y_hat, "loss": loss if y is not None else None}
-            if rc != _lib.MFM_ERR_UNSUPPORTED:
-                _lib.check(rc, "mfm_predict_klef")
-            self._predict_refused = True          # (sizes beyond the on-chip recurrence: a property of the configuration)
-        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
-        out = self.forward(x, y, train=False, want_xhat=False, handover=False)
-        return {"y_hat": out["y_hat"], "loss": out["losses"][0].clone() if y is not None else None}
-
-    # ------------------------------------------------------------------ the factorized latents and generation from them
-    _ENCODE_TENSORS = tuple(
-        pre + suf
-        for enc, mu, lv in (("encoder_l", "last_to_zl_fc1", "last_to_logvarzl_fc1"),
-                            ("encoder_a", "last_to_za_fc1", "last_to_logvarza_fc1"),
-                            ("encoder_v", "last_to_zv_fc1", "last_to_logvarzv_fc1"),
-                            ("ef_encoder", "last_to_zy_fc1", "last_to_logvarzy_fc1"))
-        for pre, suf in ((enc, ".lstm.weight_ih"), (enc, ".lstm.weight_hh"), (enc, ".lstm.bias_ih"), (enc, ".lstm.bias_hh"),
-                         (enc, ".fc1.weight"), (enc, ".fc1.bias"), (mu, ".weight"), (mu, ".bias"), (lv, ".weight"), (lv, ".bias")))
-
-    _DECODE_TENSORS = tuple(
-        [mlp + fc + suf for mlp in ("zy_to_fy", "zl_to_fl", "za_to_fa", "zv_to_fv") for fc in ("_fc1", "_fc2")
-         for suf in (".weight", ".bias")]
-        + [dec + suf for dec in ("decoder_l", "decoder_a", "decoder_v")
-           for suf in (".lstm.weight_ih", ".lstm.weight_hh", ".lstm.bias_ih", ".lstm.bias_hh", ".fc1.weight", ".fc1.bias")]
-        + [fc + suf for fc in ("fy_to_y_fc1", "fy_to_y_fc2") for suf in (".weight", ".bias")])
-
-    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
-
-    def _row_cap(self, max_rows):
-        if max_rows is not None and int(max_rows) < 1:
-            raise _lib.MfmError("max_rows must be at least 1, not %r" % (max_rows,))
-        return self.PREDICT_MAX_ROWS if max_rows is None else int(max_rows)
-
-    def encode_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace encode() keeps for a [T, N, D] split (mfm_encode_klef_workspace_floats)"""
-        c = self.cfg
-        return int(_lib.lib().mfm_encode_klef_workspace_floats(int(T), int(N), c["zl_size"], c["za_size"], c["zv_size"],
-                                                               self._row_cap(max_rows)))
-
-    def decode_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace decode() keeps for N rows and T steps (mfm_decode_factors_workspace_floats)"""
-        c = self.cfg
-        return int(_lib.lib().mfm_decode_factors_workspace_floats(int(T), int(N), c["fy_size"], c["fl_size"], c["fa_size"],
-                                                                  c["fv_size"], self._row_cap(max_rows)))
-
-    def encode(self, x, *, max_rows=None):
-        """x [T, N, D] -> Factors(zl, za, zv, zy, logvar_zl, logvar_za, logvar_zv, logvar_zy), float32 device tensors [N, size]:
-        the means and log-variances of the four latent factors (reference mfm_model.py:627-639), the deterministic eval
-        computation.  Variant "kl_ef" only (mfm_encode_klef: the four encoders' recurrences and their heads, no plan and no
-        training workspace; the split is walked in chunks of at most `max_rows` rows, default PREDICT_MAX_ROWS).  Workspace and
-        outputs are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated and nothing
-        synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what must survive
-        it).  Raises MfmUnsupported for another variant or for sizes the entry refuses: the model's encode() then composes the
-        granular operations.  A refusal for a hidden size above 128 is remembered (later calls raise at once); one for the LDS a
-        workgroup would need (very wide layers on four-row tiles: it depends on N and max_rows too) holds for that call alone."""
-        self._check_inputs(x, None)
-        T, N, D = x.shape
-        if T < 1 or N < 1:
-            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
-        cap = self._row_cap(max_rows)
-        if self.variant != "kl_ef":
-            raise _lib.MfmUnsupported("MFMEngine.encode: the fused encoder half exists for variant 'kl_ef' only, not %r" % self.variant)
-        if getattr(self, "_encode_refused", False):
-            raise _lib.MfmUnsupported("MFMEngine.encode: mfm_encode_klef refused this configuration")
-        c = self.cfg
-        cache = self.__dict__.setdefault("_encode_bufs", {})
-        st = cache.get((T, N, cap))
-        zsz = (c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"])
-        if st is None:
-            nws = int(_lib.lib().mfm_encode_klef_workspace_floats(T, N, zsz[0], zsz[1], zsz[2], cap))
-            offs = (C.c_int64 * 40)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS])
-            outs = tuple(torch.empty(N, s, dtype=torch.float32, device=self.device) for s in zsz + zsz)
-            st = (torch.empty(nws, dtype=torch.float32, device=self.device), outs, offs,
-                  (C.c_void_p * 8)(*[t.data_ptr() for t in outs]))
-        ws, outs, offs, optr = st
-        d_l, d_a, d_v = c["input_dims"]
-        rc = _lib.lib().mfm_encode_klef(T, N, d_l, d_a, d_v, zsz[0], zsz[1], zsz[2], zsz[3], _ptr(self.params), offs, _ptr(x),
-                                        _ptr(ws), optr, cap, _stream())
-        if rc == _lib.MFM_ERR_UNSUPPORTED:
-            # a hidden size beyond the on-chip recurrence is a property of the configuration: remembered.  The LDS limit also
-            # depends on the tile rows, hence on N and max_rows: that refusal holds for this call alone
-            self._encode_refused = zsz[0] + zsz[1] + zsz[2] > self.MAX_RESIDENT_H
-            raise _lib.MfmUnsupported("MFMEngine.encode: %s" % _lib.lib().mfm_last_error().decode())
-        _lib.check(rc, "mfm_encode_klef")
-        cache[(T, N, cap)] = st
-        return Factors(*outs)
-
-    def _check_factors(self, zl, za, zv, zy, T):
-        c = self.cfg
-        if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 1:
-            raise _lib.MfmError("decode: T must be an integer >= 1, not %r" % (T,))
-        N = None
-        for name, z, size in (("zl", zl, c["zl_size"]), ("za", za, c["za_size"]), ("zv", zv, c["zv_size"]), ("zy", zy, c["zy_size"])):
-            if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous()):
-                raise _lib.MfmError("decode: %s must be a contiguous float32 CUDA tensor [N, %d]; got %s" % (
-                    name, size, "%s %s %s" % (tuple(z.shape), z.dtype, z.device) if torch.is_tensor(z) else type(z)))
-            if z.shape[1] != size:
-                raise _lib.MfmError("decode: %s has %d columns, the model's %s_size is %d" % (name, z.shape[1], name, size))
-            if self.device.index is not None and z.device != self.device:
-                raise _lib.MfmError("decode: %s lives on %s, the engine on %s" % (name, z.device, self.device))
-            if N is None:
-                N = z.shape[0]
-            if z.shape[0] != N or z.device != zl.device:
-                raise _lib.MfmError("decode: the four factors must have the same number of rows on one device; zl has %d on %s, "
-                                    "%s has %d on %s" % (N, zl.device, name, z.shape[0], z.device))
-        if N < 1:
-            raise _lib.MfmError("decode: no rows")
-        return int(N)
-
-    def decode(self, zl, za, zv, zy, T, *, max_rows=None):
-        """four factors [N, size] (independent arguments: any rows, from encode() or not), T -> [x_l_hat, x_a_hat, x_v_hat,
-        y_hat], x_m_hat [T, N, d_m], y_hat [N, output_dim]: the generative half (reference mfm_model.py:644-657), the
-        deterministic eval computation, for every variant (mfm_decode_factors: the z -> f MLPs, the three decoders' recurrences
-        from [fy | f_m], their fc1 and the classifier; no plan and no training workspace; chunks of at most `max_rows` rows).
-        Workspace and outputs are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated
-        and nothing synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what
-        must survive it).  Raises MfmUnsupported for sizes the entry refuses: the model's decode() then composes the granular
-        operations.  A refusal for a decoder with fy + f_m > 128 is remembered; one for the LDS limit holds for that call alone,
-        as in encode()."""
-        N = self._check_factors(zl, za, zv, zy, T)
-        T = int(T)
-        cap = self._row_cap(max_rows)
-        if getattr(self, "_decode_refused", False):
-            raise _lib.MfmUnsupported("MFMEngine.decode: mfm_decode_factors refused this configuration")
-        c = self.cfg
-        cache = self.__dict__.setdefault("_decode_bufs", {})
-        st = cache.get((T, N, cap))
-        if st is None:
-            nws = int(_lib.lib().mfm_decode_factors_workspace_floats(T, N, c["fy_size"], c["fl_size"], c["fa_size"], c["fv_size"], cap))
-            offs = (C.c_int64 * 38)(*[self.layout.offsets[n] for n in self._DECODE_TENSORS])
-            sizes = (C.c_int32 * 12)(c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], c["fl_size"], c["fa_size"],
-                                     c["fv_size"], c["fy_size"], *c["input_dims"], c["output_dim"])
-            outs = [torch.empty(T, N, d, dtype=torch.float32, device=self.device) for d in c["input_dims"]]
-            outs.append(torch.empty(N, c["output_dim"], dtype=torch.float32, device=self.device))
-            st = (torch.empty(nws, dtype=torch.float32, device=self.device), outs, offs, sizes,
-                  (C.c_void_p * 4)(*[t.data_ptr() for t in outs]))
-        ws, outs, offs, sizes, optr = st
-        zptr = (C.c_void_p * 4)(zl.data_ptr(), za.data_ptr(), zv.data_ptr(), zy.data_ptr())
-        rc = _lib.lib().mfm_decode_factors(T, N, sizes, _ptr(self.params), offs, zptr, _ptr(ws), optr, cap, _stream())
-        if rc == _lib.MFM_ERR_UNSUPPORTED:
-            self._decode_refused = c["fy_size"] + max(c["fl_size"], c["fa_size"], c["fv_size"]) > self.MAX_RESIDENT_H      # (as in encode)
-            raise _lib.MfmUnsupported("MFMEngine.decode: %s" % _lib.lib().mfm_last_error().decode())
-        _lib.check(rc, "mfm_decode_factors")
-        cache[(T, N, cap)] = st
-        return list(outs)
-
-    # ------------------------------------------------------------------ the full validation objective
-    def _objective_sizes(self):
-        c = self.cfg
-        return (C.c_int32 * 13)(c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], c["fl_size"], c["fa_size"], c["fv_size"],
-                                c["fy_size"], *c["input_dims"], c["output_dim"], 1 if c.get("loss", "l1") == "ce" else 0)
-
-    def objective_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace objective() keeps for a [T, N, D] split (mfm_objective_klef_workspace_floats)"""
-        return int(_lib.lib().mfm_objective_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
-
-    def objective(self, x, y, *, max_rows=None):
-        """x [T, N, D], labels -> Objective(loss, disc, gen_l, gen_a, gen_v, reg), 0-d float32 device tensors (views of one [6]
-        tensor): what the reference's drivers validate and report (mfm_mosi.py:319-324, :724-726, :826-845) -- disc the mean L1 /
-        cross entropy as evaluate() defines it, gen_m = F.mse_loss(x_m_hat, x_m), reg the sum of the four loss_KLD(mu, logvar),
-        loss = disc + lda_xl gen_l + lda_xa gen_a + lda_xv gen_v + lda_mmd reg -- from the deterministic eval computation, left
-        on the device.
-
-        Variant "kl_ef": mfm_objective_klef -- the launches of encode(), the recurrence launch of decode(), then the decoders'
-        fc1 fused with the squared error (x_hat is never written) and one small finishing launch; no plan and no training
-        workspace; the split is walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS).  Workspace and the [6]
-        result are kept per (T, N, max_rows) and REUSED: after the first call for a shape nothing is allocated and nothing
-        synchronises, and the returned tensors are overwritten by the next call for the same shape (clone what must survive
-        it).  Other variants, and sizes the entry refuses: the same namedtuple from forward(train=False, handover=False), the
-        total formed on the device.  A refusal for a hidden size above 128 is remembered; one for the LDS limit holds for that
-        call alone, as in encode()."""
-        self._check_inputs(x, y)
-        if y is None:
-            raise _lib.MfmError("objective needs the labels")
-        T, N, D = x.shape
-        if T < 1 or N < 1:
-            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
-        c = self.cfg
-        od = c["output_dim"]
-        ce = c.get("loss", "l1") == "ce"
-        if y.numel() != (N if ce else N * od):
-            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
-                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
-        cap = self._row_cap(max_rows)
-        if self.variant == "kl_ef" and not getattr(self, "_objective_refused", False):
-            cache = self.__dict__.setdefault("_objective_bufs", {})
-            st = cache.get((T, N, cap))
-            if st is None:
-                sizes = self._objective_sizes()
-                nws = int(_lib.lib().mfm_objective_klef_workspace_floats(T, N, sizes, cap))
-                offs = (C.c_int64 * 78)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS + self._DECODE_TENSORS])
-                lda = (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"])
-                out = torch.zeros(6, dtype=torch.float32, device=self.device)
-                st = (torch.empty(nws, dtype=torch.float32, device=self.device), out, Objective(*out.unbind(0)), sizes, offs, lda)
-            ws, out, res, sizes, offs, lda = st
-            rc = _lib.lib().mfm_objective_klef(T, N, sizes, lda, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(out),
-                                               cap, _stream())
-            if rc == 0:
-                cache[(T, N, cap)] = st
-                return res
-            if rc != _lib.MFM_ERR_UNSUPPORTED:
-                _lib.check(rc, "mfm_objective_klef")
-            hs = [c["zl_size"] + c["za_size"] + c["zv_size"]] + [c["fy_size"] + c[k] for k in ("fl_size", "fa_size", "fv_size")]
-            self._objective_refused = max(hs) > self.MAX_RESIDENT_H          # (as in encode)
-        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
-        l = self.forward(x, y, train=False, handover=False)["losses"]
-        out = torch.empty(6, dtype=torch.float32, device=self.device)
-        out[1:6] = l[0:5]
-        out[0] = l[0] + c["lda_xl"] * l[1] + c["lda_xa"] * l[2] + c["lda_xv"] * l[3] + c["lda_mmd"] * l[4]
-        return Objective(*out.unbind(0))
-
-    # ------------------------------------------------------------------ the zeroed-modality test protocol
-    def predict_zeros_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace predict_zeros() keeps for a [T, N, D] split (mfm_predict_zeros_klef_workspace_floats)"""
-        return int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
-
-    def predict_zeros(self, x, y=None, *, max_rows=None):
-        """x [T, N, D] (, labels) -> Zeros(y_hat [3, N, output_dim], gen [3], disc [3] or None), float32 device tensors: the test
-        protocol of the reference's train_mfm_test_zeros (mfm_mosi.py:572-596) -- the split through the deterministic eval forward
-        with modality l, a, v zeroed in turn (the cases in that order); gen[c] = F.mse_loss(x_c_hat of case c, the REAL x_c),
-        unweighted, disc[c] the mean L1 / cross entropy of y_hat[c] as evaluate() defines it (None without labels).  Every mean is
-        over the whole split.
-
-        Variant "kl_ef": mfm_predict_zeros_klef -- no zeroed copy of x, the ef encoder's projection computed once for the three
-        cases, the zeroed encoder one row of work, one decoder per case with its fc1 fused into the squared error (x_hat is
-        never written); no plan and no training workspace; the split is walked in chunks of at most `max_rows` rows (default
-        PREDICT_MAX_ROWS).  Workspace and the three result tensors are kept per (T, N, max_rows) and REUSED: after the first
-        call for a shape nothing is allocated and nothing synchronises, and the returned tensors are overwritten by the next
-        call for the same shape (clone what must survive it).  Other variants, and sizes the entry refuses: the same namedtuple
-        from three forward(train=False, handover=False) calls on zeroed copies, the means formed on the device.  A refusal for a
-        hidden size above 128 is remembered; one for the LDS limit holds for that call alone, as in encode()."""
-        self._check_inputs(x, y)
-        T, N, D = x.shape
-        if T < 1 or N < 1:
-            raise _lib.MfmError("empty split %s" % (tuple(x.shape),))
-        c = self.cfg
-        od = c["output_dim"]
-        ce = c.get("loss", "l1") == "ce"
-        if y is not None and y.numel() != (N if ce else N * od):
-            raise _lib.MfmError("labels must hold %d elements (%s); got shape %s" % (
-                N if ce else N * od, "one class index per row" if ce else "[N, output_dim]", tuple(y.shape)))
-        cap = self._row_cap(max_rows)
-        if self.variant == "kl_ef" and not getattr(self, "_zeros_refused", False):
-            cache = self.__dict__.setdefault("_zeros_bufs", {})
-            st = cache.get((T, N, cap))
-            if st is None:
-                sizes = self._objective_sizes()
-                nws = int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(T, N, sizes, cap))
-                offs = (C.c_int64 * 78)(*[self.layout.offsets[n] for n in self._ENCODE_TENSORS + self._DECODE_TENSORS])
-                st = (torch.empty(nws, dtype=torch.float32, device=self.device),
-                      torch.empty(3, N, od, dtype=torch.float32, device=self.device),
-                      torch.zeros(3, dtype=torch.float32, device=self.device),
-                      torch.zeros(3, dtype=torch.float32, device=self.device), sizes, offs)
-            ws, y_hat, gen, disc, sizes, offs = st
-            rc = _lib.lib().mfm_predict_zeros_klef(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat),
-                                                   _ptr(gen), _ptr(disc) if y is not None else None, cap, _stream())
-            if rc == 0:
-                cache[(T, N, cap)] = st
-                return Zeros(y_hat, gen, disc if y is not None else None)
-            if rc != _lib.MFM_ERR_UNSUPPORTED:
-                _lib.check(rc, "mfm_predict_zeros_klef")
-            hs = [c["zl_size"] + c["za_size"] + c["zv_size"]] + [c["fy_size"] + c[k] for k in ("fl_size", "fa_size", "fv_size")]
-            self._zeros_refused = max(hs) > self.MAX_RESIDENT_H          # (as in encode)
-        # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
-        y_hat = torch.empty(3, N, od, dtype=torch.float32, device=self.device)
-        gen = torch.empty(3, dtype=torch.float32, device=self.device)
-        disc = torch.empty(3, dtype=torch.float32, device=self.device) if y is not None else None
-        d_l, d_a, d_v = c["input_dims"]
-        for i, (a, b, key) in enumerate(((0, d_l, "x_l_hat"), (d_l, d_l + d_a, "x_a_hat"), (d_l + d_a, D, "x_v_hat"))):
-            xz = x.clone()
-            xz[:, :, a:b] = 0
-            out = self.forward(xz, y, train=False, handover=False)
-            y_hat[i].copy_(out["y_hat"])
-            # (the forward's own loss slot is the error against the zeroed columns: the protocol asks for the real ones)
-            gen[i] = (out[key] - x[:, :, a:b]).square().mean()
-            if y is not None:
-                disc[i] = out["losses"][0]
-        return Zeros(y_hat, gen, disc)
 
     def forward_train(self, x, p, grads_to_zero=None):
         """Training-mode forward of the module path's lazy losses (mfm_plan_forward_train): no labels, no output tensors --
