@@ -22,8 +22,9 @@ MFM_ERR_UNSUPPORTED = -3
 # forward / backward, biases of all layers together
 LATENT_FORM_SLOTS = ("row_path", "wpanel", "rows_per_wg", "rows_fwd", "mfma", "nch", "bias_tab", "nstages", "split0",
                      "rec_size", "max_k", "max_n", "items_fwd", "items_bwd", "n_bias")
-# slots of mfm_plan_seq_form's out[4]: 1 = step-by-step path (0: weight-resident recurrence kernels), the widest resident h
-SEQ_FORM_SLOTS = ("stepwise", "max_resident_h")
+# slots of mfm_plan_seq_form's out[4]: 1 = step-by-step path (0: weight-resident recurrence kernels), the widest resident h,
+# 1 = a resident fp32 recurrence on the MFMA kernels (0: the VALU kernels, or one of the other two families)
+SEQ_FORM_SLOTS = ("stepwise", "max_resident_h", "mfma")
 
 
 class MfmError(RuntimeError):

@@ -343,6 +343,7 @@ static bool use_small_path(int B) {
   if (e && e[0] == 's') return true;
   return B <= 512;
 }
+bool seq_mfma_pays(int B) { return !use_small_path(B); }
 
 // bf16 MFMA recurrences (lstm_seq_bf16.hip) work on 16-row batch tiles: 128 x 16 cells of gate math per workgroup and
 // step (~1.4 us per step at h = 120 since the round-5 coalescing, 2.1 before), whatever B is.  Below ~128 rows the chip is

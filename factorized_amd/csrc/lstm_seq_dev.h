@@ -180,6 +180,7 @@ int seq_dec_tail_launch(const MfmSeqDesc* descs, int count, int T, int B, const 
 int seq_dec_bwd_head_launch(const MfmSeqDesc* descs, int count, int T, int B, const float* const* wt_imgs, const LatentDev& lat,
                             const float* params, float* grads, hipStream_t stream);
 bool bf16_seq_pays(int B);     // batch size from which a bf16 plan runs its recurrences on the bf16 kernels
+bool seq_mfma_pays(int B);     // batch size from which the fp32 resident recurrences run on the MFMA kernels (pick path)
 // lstm_seq_small.hip -- fp32 VALU kernels, 1 / 4 rows per workgroup; L as filled by seq_launch, block layout by the launcher
 int seq_small_launch(SeqLaunch& L, bool bwd, hipStream_t stream);      // the plain launch (+ image-writer blocks when L.n_img)
 int seq_small_fold_launch(SeqLaunch& L, bool bwd, const LatentDev& LD, const float* params, float* grads, hipStream_t stream);

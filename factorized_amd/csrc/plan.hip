@@ -333,6 +333,7 @@ extern "C" int mfm_plan_seq_form(const MfmPlan* P, int32_t which, int64_t* out) 
   // the rule of seq_launch (lstm_seq.hip), which sorts every launch group's LSTMs into the two families
   out[0] = (sb.h > MFM_SEQ_MAX_RESIDENT_H || opt_get("MFM_SEQ_STEPWISE") != nullptr) ? 1 : 0;
   out[1] = MFM_SEQ_MAX_RESIDENT_H;
+  out[2] = (!out[0] && !P->seq_bf16 && mfm::seq_mfma_pays(P->B)) ? 1 : 0;
   return MFM_OK;
 }
 

@@ -145,6 +145,12 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
 
   // F0: input projections.  MFM_KL_EF at B <= 32 (fp32 plans on the fold launches): produced
   // by role workgroups of the encoder launch itself (proj_role_dev.h), which also clear the zero spans
+  // bf16 plans round x and W_ih for these products only where the recurrences themselves run on the bf16 kernels (B >= 128).
+  // Below that the recurrences are the fp32 VALU kernels and their gate pre-activations stay fp32 end to end: with unnormalised
+  // features (acoustic inputs of +-600) one bf16 ulp of x moves a pre-activation by +-0.4, and the few gates not saturated carry
+  // the whole gradient -- encoder_a's weight gradients were 31 % off (tests/test_gpu_data_regimes.py, saturated at B = 19);
+  // the role workgroups multiply in fp32 either way, and the tiled GEMM is not the step's bound at these sizes
+  const int proj_prec = seq_bf16 ? c.precision : 0;
   bool proj_in_fold = false;
   const bool capturing = stream_capturing(s);
   if (V == 0 && !seq_bf16 && !st16 && P->n_enc == 4 && P->fold_state >= 0 && P->projfold_state >= 0 && P->pf_flags >= 0 && P->pf_words >= 0 &&
@@ -194,10 +200,10 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
         if (P->pj_pack_call != P->calls) RUN(K_PACK, proj_bf16_pack_launch(PL, P->pj, W + P->pj_wimg, W + P->pj_bimg, s));
         RUN(K_PROJ, proj_bf16_launch(PL, P->pj, W + P->pj_wimg, W + P->pj_bimg, W + P->x16, P->x16_ld, src0, nn, P->x16_off, &zs, s));
         P->x16_call = P->calls;
-      } else if (gemm_panel_pays(PL, c.precision, panel_forced)) RUN(K_PROJ, gemm_panel_launch(PL, &zs, c.precision, panel_forced, s));
-      else RUN(K_PROJ, gemm_group_launch(g, P->n_enc, s, &zs, nullptr, 0, c.precision));
+      } else if (gemm_panel_pays(PL, proj_prec, panel_forced)) RUN(K_PROJ, gemm_panel_launch(PL, &zs, proj_prec, panel_forced, s));
+      else RUN(K_PROJ, gemm_group_launch(g, P->n_enc, s, &zs, nullptr, 0, proj_prec));
     } else {
-      RUN(K_PROJ, gemm_group_launch(g, P->n_enc, s, &zs, nullptr, 0, c.precision));
+      RUN(K_PROJ, gemm_group_launch(g, P->n_enc, s, &zs, nullptr, 0, proj_prec));
     }
     return MFM_OK;
   };
@@ -277,7 +283,7 @@ int forward(MfmPlan* P, const float* params, const float* x, const void* y, int 
     if (PR.fault) P->opt_fault = 0;
     PR.zs = zs;
     PR.loss_ptr = zs.ptr[0]; PR.loss_n = (int)zs.n[0];
-    PR.bf16 = c.precision ? 1 : 0;
+    PR.bf16 = proj_prec ? 1 : 0;
     // training steps: the BPTT launches of this step take their transposed weights from images the role workgroups write
     if (n_wt_items == 7) { for (int i = 0; i < 7; ++i) PR.wt[i] = wt_items[i]; PR.n_wt = 7; }
     // the decoders' steps >= 1 weights in the forward's register order: their launch reloads them with coalesced loads

@@ -692,14 +692,15 @@ class MFMEngine(InferMixin):
 
     def seq_form(self, T, B):
         """Kernel family of every LSTM of the plan at (T,B), encoders in plan order, then the three decoders
-        (mfm_plan_seq_form): list of dicts h, stepwise (False: weight-resident recurrence kernels).  Tests / tuning aids."""
+        (mfm_plan_seq_form): list of dicts h, stepwise (False: weight-resident recurrence kernels), mfma (True: the fp32 MFMA
+        recurrences, 16 rows per workgroup; False: the VALU kernels, or stepwise / bf16).  Tests / tuning aids."""
         p = self.plan(T, B)
         res = []
         lay, out = (C.c_int64 * 12)(), (C.c_int64 * 4)()
         for which in range((4 if self.variant == "kl_ef" else 6) + 3):
             _lib.check(_lib.lib().mfm_plan_seq_layout(p.handle, which, lay), "mfm_plan_seq_layout")
             _lib.check(_lib.lib().mfm_plan_seq_form(p.handle, which, out), "mfm_plan_seq_form")
-            res.append(dict(h=int(lay[3]), decoder=bool(lay[6]), stepwise=bool(out[0])))
+            res.append(dict(h=int(lay[3]), decoder=bool(lay[6]), stepwise=bool(out[0]), mfma=bool(out[2])))
         return res
 
     def seq_buffers(self, T, B, which):

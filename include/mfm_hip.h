@@ -875,7 +875,8 @@ int mfm_plan_mfn_layout(const MfmPlan* plan, int64_t* out /*[16]*/);
 int mfm_plan_seq_layout(const MfmPlan* plan, int32_t which, int64_t* out /*[12]*/);
 /* The kernel family of LSTM `which` (numbered as above): out[0] 0 = weight-resident recurrence kernels, 1 = step-by-step path
  * (recurrent GEMM + cell kernel per time step: h above out[1], or MFM_SEQ_STEPWISE set); out[1] the widest resident h;
- * out[2..3] reserved. */
+ * out[2] 1 when a weight-resident fp32 recurrence runs on the MFMA kernels (16 rows per workgroup: B above 512, or
+ * MFM_SEQ_PATH), 0 on the VALU kernels, the step-by-step path or the bf16 kernels; out[3] reserved. */
 int mfm_plan_seq_form(const MfmPlan* plan, int32_t which, int64_t* out /*[4]*/);
 
 /* Algorithmic work of one training step at this plan's (T,B):

@@ -89,6 +89,7 @@ def test_plan_form_queries_are_host_only():
         for which in range(7):
             assert L.mfm_plan_seq_form(h, which, sq) == 0
             assert dict(zip(_lib.SEQ_FORM_SLOTS, sq))["max_resident_h"] == 128
+            assert dict(zip(_lib.SEQ_FORM_SLOTS, sq))["mfma"] == 0 and sq[3] == 0          # B = 32: the VALU recurrences
             step.append(int(sq[0]))
         assert L.mfm_plan_seq_form(h, 7, sq) == -1 and L.mfm_plan_latent_form(h, None) == -1
         L.mfm_plan_destroy(h)

@@ -119,10 +119,12 @@ def test_gemm_column_sums_with_ones(eng):
 
 
 # ---------------------------------------------------------------------------------- LSTM sequences
-def _cpu_lstm(x, w_ih, w_hh, b_ih, b_hh, dec_init=None, T=None):
-    """torch-CPU recurrence with autograd (reference semantics mfm_model.py:47-58 / 72-88)."""
+def _cpu_lstm(x, w_ih, w_hh, b_ih, b_hh, dec_init=None, T=None, double=False):
+    """torch-CPU recurrence with autograd (reference semantics mfm_model.py:47-58 / 72-88); `double`: the same in float64."""
     h = w_hh.shape[1]
     cell = torch.nn.LSTMCell(w_ih.shape[1], h)
+    if double:
+        return _cpu_lstm64(cell.double(), x, w_ih, w_hh, b_ih, b_hh, dec_init, T)
     with torch.no_grad():
         cell.weight_ih.copy_(torch.from_numpy(w_ih)); cell.weight_hh.copy_(torch.from_numpy(w_hh))
         cell.bias_ih.copy_(torch.from_numpy(b_ih)); cell.bias_hh.copy_(torch.from_numpy(b_hh))
@@ -141,6 +143,30 @@ def _cpu_lstm(x, w_ih, w_hh, b_ih, b_hh, dec_init=None, T=None):
     inp = init
     for t in range(T):
         hx, cx = cell(inp, (hx, cx))
+        inp = hx
+        hs.append(hx); cs.append(cx)
+    return cell, init, torch.stack(hs), torch.stack(cs)
+
+
+def _cpu_lstm64(cell, x, w_ih, w_hh, b_ih, b_hh, dec_init, T):
+    """_cpu_lstm restated with .double(): the reference of the scale = 100 cases, where the fp32 recurrence itself is no
+    longer ten times closer to the truth than TOL"""
+    h = w_hh.shape[1]
+    with torch.no_grad():
+        cell.weight_ih.copy_(torch.from_numpy(w_ih).double()); cell.weight_hh.copy_(torch.from_numpy(w_hh).double())
+        cell.bias_ih.copy_(torch.from_numpy(b_ih).double()); cell.bias_hh.copy_(torch.from_numpy(b_hh).double())
+    hs, cs = [], []
+    init = None
+    if dec_init is None:
+        xt = torch.from_numpy(x).double()
+        B, T = xt.shape[1], xt.shape[0]
+    else:
+        init = torch.from_numpy(dec_init).double().requires_grad_(True)
+        B = init.shape[0]
+    hx, cx = torch.zeros(B, h, dtype=torch.float64), torch.zeros(B, h, dtype=torch.float64)
+    inp = init
+    for t in range(T):
+        hx, cx = cell(xt[t] if init is None else inp, (hx, cx))
         inp = hx
         hs.append(hx); cs.append(cx)
     return cell, init, torch.stack(hs), torch.stack(cs)
@@ -179,8 +205,20 @@ def seq_path(request, monkeypatch):
     return request.param
 
 
-@pytest.mark.parametrize("h,d,B,T", SEQ_SHAPES)
-def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T):
+# scale = 100 (x of the encoder, init of the decoder; gate pre-activations far beyond +-88.7, where the fast activations come back
+# from an inf / exact-0 exponential) at two shapes only, against the float64 recurrence; bounds stay TOL
+ENC_SCALED = [(32, 20, 5, 3), (128, 4, 3, 2)]
+DEC_SCALED = [(32, 5, 3), (128, 3, 2)]
+
+
+def _with_scale(shapes, scaled):
+    """the scale = 1 cases under the ids they always had, then the scaled ones"""
+    return ([pytest.param(*s, 1, id="-".join(map(str, s))) for s in shapes]
+            + [pytest.param(*s, 100, id="-".join(map(str, s)) + "-x100") for s in scaled])
+
+
+@pytest.mark.parametrize("h,d,B,T,scale", _with_scale(SEQ_SHAPES, ENC_SCALED))
+def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T, scale):
     rs = np.random.RandomState(h * 7 + B)
     k = 1.0 / np.sqrt(h)
     w_ih = rs.uniform(-k, k, size=(4 * h, d)).astype(np.float32)
@@ -188,7 +226,9 @@ def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T):
     b_ih = rs.uniform(-k, k, size=4 * h).astype(np.float32)
     b_hh = rs.uniform(-k, k, size=4 * h).astype(np.float32)
     x = rs.normal(size=(T, B, d)).astype(np.float32)
-    cell, _, hs_ref, cs_ref = _cpu_lstm(x, w_ih, w_hh, b_ih, b_hh)
+    if scale != 1:
+        x *= np.float32(scale)
+    cell, _, hs_ref, cs_ref = _cpu_lstm(x, w_ih, w_hh, b_ih, b_hh, double=scale != 1)
     Hp = (h + 15) // 16 * 16
     gx = x.astype(np.float64) @ w_ih.T.astype(np.float64) + b_ih + b_hh
     gates = dev(_pad_gates(gx.astype(np.float32), h, Hp))
@@ -204,7 +244,7 @@ def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T):
 
     # ---- backward: external grad on the last hidden state only (encoder form)
     dh_last = rs.normal(size=(B, h)).astype(np.float32)
-    (hs_ref[-1] * torch.from_numpy(dh_last)).sum().backward()
+    (hs_ref[-1] * torch.from_numpy(dh_last).to(hs_ref.dtype)).sum().backward()
     dh_d = dev(dh_last)
     desc = eng.make_seq(gates, hs, cs, w_d, h, dh_ext=dh_d, ld_dh=h)
     eng.lstm_seq([desc], T, B, backward=True)
@@ -218,8 +258,8 @@ def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T):
     assert rel_err(dW_hh, cell.weight_hh.grad.numpy()) < TOL
 
 
-@pytest.mark.parametrize("h,B,T", [(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7)])
-def test_lstm_seq_decoder_fwd_bwd(eng, seq_path, h, B, T):
+@pytest.mark.parametrize("h,B,T,scale", _with_scale([(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7)], DEC_SCALED))
+def test_lstm_seq_decoder_fwd_bwd(eng, seq_path, h, B, T, scale):
     rs = np.random.RandomState(h + B + T)
     k = 1.0 / np.sqrt(h)
     w_ih = rs.uniform(-k, k, size=(4 * h, h)).astype(np.float32)
@@ -227,7 +267,9 @@ def test_lstm_seq_decoder_fwd_bwd(eng, seq_path, h, B, T):
     b_ih = rs.uniform(-k, k, size=4 * h).astype(np.float32)
     b_hh = rs.uniform(-k, k, size=4 * h).astype(np.float32)
     init = rs.normal(size=(B, h)).astype(np.float32)
-    cell, init_t, hs_ref, cs_ref = _cpu_lstm(None, w_ih, w_hh, b_ih, b_hh, dec_init=init, T=T)
+    if scale != 1:
+        init *= np.float32(scale)
+    cell, init_t, hs_ref, cs_ref = _cpu_lstm(None, w_ih, w_hh, b_ih, b_hh, dec_init=init, T=T, double=scale != 1)
     Hp = (h + 15) // 16 * 16
     gates = torch.full((T, B, 4, Hp), 3.0, device="cuda")
     hs = torch.full((T, B, Hp), 9.0, device="cuda")
@@ -241,7 +283,7 @@ def test_lstm_seq_decoder_fwd_bwd(eng, seq_path, h, B, T):
     assert np.all(hs_o[:, :, h:] == 0.0)
 
     dH = rs.normal(size=(T, B, h)).astype(np.float32)
-    (hs_ref * torch.from_numpy(dH)).sum().backward()
+    (hs_ref * torch.from_numpy(dH).to(hs_ref.dtype)).sum().backward()
     dH_p = np.zeros((T, B, Hp), dtype=np.float32)
     dH_p[:, :, :h] = dH
     dh_d = dev(dH_p)

@@ -20,8 +20,9 @@ def zeroed(x, cfg, c):
     return xz
 
 
-def oracle_zeros(variant, cfgs, weights, xn, yn=None, gauss=None):
-    """-> dict(y_hat [3, N, od] float32, gen [3], disc [3] or None) in float64 where scalar, from the oracle in eval mode"""
+def oracle_zeros(variant, cfgs, weights, xn, yn=None, gauss=None, double=False):
+    """-> dict(y_hat [3, N, od] float32, gen [3], disc [3] or None) in float64 where scalar, from the oracle in eval mode;
+    `double`: the oracle itself computes in float64 (the default is its fp32 forward)"""
     cfg = cfgs[0]
     m = O.build(variant, cfgs)
     O.load_numpy_weights(m, weights)
@@ -30,6 +31,8 @@ def oracle_zeros(variant, cfgs, weights, xn, yn=None, gauss=None):
         m.mmd_gauss = gauss
     torch.set_num_threads(4)
     x = torch.from_numpy(np.ascontiguousarray(xn))
+    if double:
+        m, x = m.double(), x.double()
     y = None if yn is None else torch.from_numpy(np.ascontiguousarray(yn))
     ce = cfg.get("loss", "l1") == "ce"
     y_hat, gen, disc = [], [], []
