@@ -12,6 +12,11 @@ for a hidden size above MAX_RESIDENT_H is a property of the configuration and is
 entry is not asked again); one for the LDS a workgroup would need (very wide layers on four-row tiles) depends on N and
 max_rows too and holds for that call alone.  predict, objective and predict_zeros then compute the same result from
 forward(train=False, handover=False); encode and decode raise MfmUnsupported and the model composes its granular operations.
+
+INPUTS: x is any contiguous float32 CUDA tensor [T, N, D] -- a batch view of a resident dataset, a time crop x[k:] -- at any
+4-byte address; the labels and the four factors of decode() likewise (int64 class labels on 8 bytes, as torch places them).
+The entries check x for 4 bytes and the parameter buffer and workspace, which the engine allocates, for 16: the kernels read x
+with dword loads and with the grouped GEMM's 16-byte buffer loads, which take dword addresses (tests/test_gpu_x_offsets.py).
 """
 import ctypes as C
 from collections import namedtuple

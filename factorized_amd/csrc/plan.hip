@@ -122,6 +122,7 @@ extern "C" int mfm_plan_get_option(const MfmPlan* P, const char* key, int64_t* v
   // read-only: whether the last forward / backward of the plan ran on role workgroups
   else if (!strcmp(key, "proj_roles_active")) *value = P->projfold_state == 1;
   else if (!strcmp(key, "dw_roles_active")) *value = P->dwfold_state == 1;
+  else if (!strcmp(key, "dw_f32_items")) *value = P->dw_f32_items;
   else { set_error("mfm_plan_get_option: unknown key '%s'", key); return MFM_ERR_ARG; }
   return MFM_OK;
 }

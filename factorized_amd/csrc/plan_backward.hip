@@ -490,6 +490,7 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
     if (const char* e = opt_get("MFM_DW_F32_MINROWS")) f32_min_rows = atol(e);
     const bool f32pass = !c.precision && f32_min_rows > 0 && TB >= f32_min_rows && TB > 1;
     bool f32_done[9] = {false, false, false, false, false, false, false, false, false};
+    P->dw_f32_items = 0;
     if (f32pass) {
       DwbLaunch DF;
       memset(&DF, 0, sizeof(DF));
@@ -535,6 +536,7 @@ int backward(MfmPlan* P, const float* params, const float* x, const void* y, int
       if (gen_on)
         for (int m = 0; m < 3; ++m) f32_done[6 + m] = lstm_item32(P->dec[m], P->dec_p[m], nullptr, 0, 0, true);
       if (DF.n_items > 0) RUN(K_DEC_DW, dw_bf16_launch(DF, s));
+      P->dw_f32_items = DF.n_items;
     }
     for (int e = 0; e < P->n_enc && !st16; ++e) {
       if (f32_done[e]) continue;

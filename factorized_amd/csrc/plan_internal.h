@@ -92,6 +92,7 @@ struct MfmPlan {
   const float* grads_prezeroed;     // gradient buffer cleared by the forward pass of the running fused step
   int fold_state = 0;               // encoder + latent fold launches (lstm_seq_small.hip): 0 untried, 1 in use, -1 not applicable
   int projfold_state = 0;           // projection role workgroups in the forward fold launch (proj_role_dev.h): 0 / 1 / -1 alike
+  int dw_f32_items = 0;             // LSTMs whose weight gradients the last backward put on the fp32 one-pass kernel (dw_bf16.hip)
   int64_t pf_flags = -1;            // their flag words [4][T][16] (u32)
   int64_t pf_words = -1;            // the projections they hand over: 64-bit words {value, epoch} [T][B][sum of 4 Hp] (B <= 32 only)
   int64_t wt_img[mfm::MFM_WT_MAX] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};     // transposed-weight images: encoders in plan order, then the 3 decoders (lstm_seq_dev.h)

@@ -458,7 +458,8 @@ int mfm_dataset_gather(float* X, void* y, const float* X_pool, const void* y_poo
  * so this entry runs the ef encoder's input projection (grouped fp32 GEMM) and ONE further launch per row chunk: the T-step
  * recurrence with h / c on chip -- no hs / cs / gate record is stored -- and the six row-wise layers behind it in the same
  * workgroup.  It needs no MfmPlan and no training workspace.  fp32.
- *   sizes    x [T, N, D] time-major and contiguous; h = hidden size of the ef encoder (zl + za + zv); zy, fy, output_dim
+ *   sizes    x [T, N, D] time-major and contiguous (4-byte aligned: any contiguous view); h = hidden size of the ef encoder
+ *            (zl + za + zv); zy, fy, output_dim
  *   params   base of the flat fp32 parameter buffer; `offsets` (host, 16 element offsets into it): ef_encoder.lstm
  *            weight_ih, weight_hh, bias_ih, bias_hh, then weight and bias of ef_encoder.fc1, last_to_zy_fc1, zy_to_fy_fc1,
  *            zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2 (torch layouts; the two LSTM weights 16-byte aligned)
@@ -490,7 +491,8 @@ int mfm_predict_klef(int32_t T, int64_t N, int32_t D, int32_t h, int32_t zy, int
  *   ranges [0, d_l), [d_l, d_l + d_a), [d_l + d_a, D) of x, and zy / logvar_zy likewise from ef_encoder(x).
  * Per row chunk: the four input projections as one grouped fp32 GEMM, then ONE launch whose workgroups are (encoder, row
  * tile): the T-step recurrence, then the encoder's fc1, the mean head and the logvar head on the tile's last hidden states.
- *   sizes    x [T, N, D] time-major and contiguous, D = d_l + d_a + d_v; hidden sizes zl, za, zv and zl + za + zv; zy
+ *   sizes    x [T, N, D] time-major and contiguous (4-byte aligned: any contiguous view), D = d_l + d_a + d_v; hidden sizes
+ *            zl, za, zv and zl + za + zv; zy
  *   params   base of the flat fp32 parameter buffer; `offsets` (host, 40 element offsets into it), per encoder in the order
  *            encoder_l, encoder_a, encoder_v, ef_encoder: lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1 weight, bias, then
  *            weight and bias of its mean head (last_to_zl / za / zv / zy _fc1) and of its logvar head (torch layouts; the LSTM
@@ -511,7 +513,7 @@ int mfm_predict_klef(int32_t T, int64_t N, int32_t D, int32_t h, int32_t zy, int
  *   offsets  host, 38 element offsets: weight and bias of zy_to_fy_fc1, zy_to_fy_fc2, zl_to_fl_fc1, zl_to_fl_fc2, za_to_fa_fc1,
  *            za_to_fa_fc2, zv_to_fv_fc1, zv_to_fv_fc2; per decoder (l, a, v) lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1
  *            weight, bias; weight and bias of fy_to_y_fc1, fy_to_y_fc2 (the LSTM weights 16-byte aligned)
- *   z        host array of 4 device pointers: zl [N, zl], za [N, za], zv [N, zv], zy [N, zy], contiguous
+ *   z        host array of 4 device pointers: zl [N, zl], za [N, za], zv [N, zv], zy [N, zy], contiguous, 4-byte aligned each
  *   out      host array of 4 device pointers: x_l_hat [T, N, d_l], x_a_hat [T, N, d_a], x_v_hat [T, N, d_v], y_hat [N, output_dim]
  *   workspace mfm_decode_factors_workspace_floats(T, N, fy, fl, fa, fv, max_rows) floats, 16-byte aligned, contents arbitrary:
  *            min(N, max_rows) * T * (round_up(fy + fl, 16) + round_up(fy + fa, 16) + round_up(fy + fv, 16)) for the stored h
@@ -547,7 +549,8 @@ int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, 
  *   lambdas  host, 4: lda_xl, lda_xa, lda_xv, lda_mmd
  *   offsets  host, 78 element offsets into the flat fp32 parameter buffer `params`: the 40 of mfm_encode_klef, then the 38 of
  *            mfm_decode_factors
- *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 16-byte aligned
+ *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 4-byte aligned: any contiguous view (a batch of a
+ *            resident dataset, a time crop); params and the workspace alone must be on 16 bytes
  *   y        the labels: float [N, output_dim] (loss_kind 0) / int64 [N] (loss_kind 1)
  *   out      6 device floats (4-byte aligned)
  *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace; every mean is over the whole
@@ -587,7 +590,7 @@ int mfm_objective_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, 
  *   sizes    host, 13: as mfm_objective_klef
  *   offsets  host, 78 element offsets into the flat fp32 parameter buffer `params`: as mfm_objective_klef (the logvar heads'
  *            are not read)
- *   x        [T, N, D] time-major and contiguous, 16-byte aligned; it is read only, all of it
+ *   x        [T, N, D] time-major and contiguous, 4-byte aligned (any contiguous view); it is read only, all of it
  *   y        NULL, or the labels: float [N, output_dim] (loss_kind 0) / int64 [N] (loss_kind 1)
  *   y_hat    out, [3, N, output_dim]; gen: out, 3 device floats; disc: out, 3 device floats -- NULL exactly when y is
  *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace; every mean is over the whole
@@ -823,8 +826,9 @@ int mfm_plan_set_option(MfmPlan* plan, const char* key, int64_t value);
  * MFM_LATENT_*, ...) are read at creation only.  The granular entry points of this header, which have no plan, read the
  * environment at each call. */
 int mfm_plan_set_option_str(MfmPlan* plan, const char* key, const char* value);
-/* also answers two read-only keys: "proj_roles_active" / "dw_roles_active" = 1 when the plan's last forward / backward ran on
- * role workgroups */
+/* also answers three read-only keys: "proj_roles_active" / "dw_roles_active" = 1 when the plan's last forward / backward ran on
+ * role workgroups; "dw_f32_items" = the number of LSTMs whose weight gradients the last backward took on the fp32 one-pass
+ * kernel (MFM_DW_F32_MINROWS; 0: all on the GEMMs) */
 int mfm_plan_get_option(const MfmPlan* plan, const char* key, int64_t* value);
 
 /* Device-side state of a plan inside its workspace: out[0] byte offset of the plan's own loss slots [MFM_LOSS_SLOTS] floats
