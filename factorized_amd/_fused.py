@@ -286,6 +286,49 @@ class _FusedEngineMixin:
             eng._check_factors(*zs, T)
             return self._decode_composed(*zs, int(T))
 
+    # ------------------------------------------------------------------ the gradient-based interpretation
+    def _influence_torch(self, zl, za, zv, zy, T):
+        """influence_factors() with torch operations on this module's parameters (engine.influence_factors_torch); the dropout
+        modules are left out (eval)"""
+        lin, relu = torch.nn.functional.linear, torch.relu
+
+        def mlp(z, fc1, fc2):
+            return relu(lin(relu(lin(z, fc1.weight, fc1.bias)), fc2.weight, fc2.bias))
+
+        decs = [(d.lstm.weight_ih, d.lstm.weight_hh, d.lstm.bias_ih, d.lstm.bias_hh, d.fc1.weight)
+                for d in (self.decoder_l, self.decoder_a, self.decoder_v)]
+        out = E.influence_factors_torch(decs, mlp(zy, self.zy_to_fy_fc1, self.zy_to_fy_fc2),
+                                        [mlp(zl, self.zl_to_fl_fc1, self.zl_to_fl_fc2), mlp(za, self.za_to_fa_fc1, self.za_to_fa_fc2),
+                                         mlp(zv, self.zv_to_fv_fc1, self.zv_to_fv_fc2)], T)
+        return E.Influence(out[0], out[1])
+
+    def influence_factors(self, zl, za, zv, zy, T):
+        """four factors [N, size], T -> Influence(fy, fm) (a namedtuple, engine.Influence) of float32 device tensors [3, T, N],
+        views of one [2, 3, T, N] tensor: the paper's gradient-based interpretation -- fy[m, t, n] = || d x_m_hat[t, n, :] /
+        d fy[n, :] ||_F^2, how strongly the label factor drives the generation of modality m = l, a, v at step t of row n, and
+        fm[m, t, n] the same for the modality's own factor f_m (the derivative is taken with respect to the factors behind the
+        z -> f MLPs) -- always the deterministic eval computation, `self.training` left as found, without autograd.  The
+        factors are independent arguments, as for decode().  All three classes run engine.influence_factors (forward mode: the
+        tangents of a row stay on chip along the decoder's recurrence; no Jacobian is written); the returned tensors are
+        REUSED: the next call with the same shape overwrites them (clone what must survive it).  Sizes the fused entry refuses
+        (a decoder with fy + f_m > 128): the same recursion with torch device operations."""
+        eng = self.engine
+        zs = [z.contiguous().float() if torch.is_tensor(z) and z.is_cuda and not (z.dtype == torch.float32 and z.is_contiguous())
+              else z for z in (zl, za, zv, zy)]
+        with torch.no_grad():
+            if not getattr(eng, "_influence_refused", False):
+                try:
+                    return eng.influence_factors(*zs, T)
+                except _lib.MfmUnsupported:
+                    pass
+            eng._check_factors(*zs, T)
+            return self._influence_torch(*zs, int(T))
+
+    def influence(self, x):
+        """x [T, N, D] -> Influence(fy, fm): influence_factors() of the split's own factors,
+        influence_factors(*self.encode(x)[:4], x.shape[0])"""
+        return self.influence_factors(*self.encode(x)[:4], x.shape[0])
+
     # ------------------------------------------------------------------ flat gradients
     def _flat_grads(self):
         eng = self.engine

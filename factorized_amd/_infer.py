@@ -1,6 +1,7 @@
-"""The engine's no-plan inference entries: predict, encode, decode, objective and predict_zeros (`InferMixin`, a base of
-engine.MFMEngine).  Each is one C call of libmfm_hip.so on the current HIP stream -- no plan, no training workspace, the split
-walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all five go through one host path: the split
+"""The engine's no-plan inference entries: predict, encode, decode, objective, predict_zeros and influence_factors
+(`InferMixin`, a base of engine.MFMEngine).  Each is one C call of libmfm_hip.so on the current HIP stream -- no plan, no
+training workspace, the split walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all six go through
+one host path: the split
 validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
@@ -11,7 +12,8 @@ REFUSALS, likewise: an entry answers MFM_ERR_UNSUPPORTED for sizes its kernels d
 for a hidden size above MAX_RESIDENT_H is a property of the configuration and is remembered in `engine._<entry>_refused` (the
 entry is not asked again); one for the LDS a workgroup would need (very wide layers on four-row tiles) depends on N and
 max_rows too and holds for that call alone.  predict, objective and predict_zeros then compute the same result from
-forward(train=False, handover=False); encode and decode raise MfmUnsupported and the model composes its granular operations.
+forward(train=False, handover=False); encode, decode and influence_factors raise MfmUnsupported and the model composes its
+granular operations (influence: the same recursion with torch device operations, influence_factors_torch below).
 
 INPUTS: x is any contiguous float32 CUDA tensor [T, N, D] -- a batch view of a resident dataset, a time crop x[k:] -- at any
 4-byte address; the labels and the four factors of decode() likewise (int64 class labels on 8 bytes, as torch places them).
@@ -36,6 +38,10 @@ Objective = namedtuple("Objective", ["loss", "disc", "gen_l", "gen_a", "gen_v", 
 # zeroed modality's reconstruction against the real one), disc [3] or None without labels -- float32 device tensors
 Zeros = namedtuple("Zeros", ["y_hat", "gen", "disc"])
 
+# what influence_factors() returns: fy[m, t, n] / fm[m, t, n] = the squared Frobenius norm of d x_m_hat[t, n, :] / d fy[n, :] and
+# / d f_m[n, :], decoders m in the order l, a, v -- float32 device tensors [3, T, N], views of one [2, 3, T, N] tensor
+Influence = namedtuple("Influence", ["fy", "fm"])
+
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
@@ -58,11 +64,50 @@ def _lin(*names):
 # short name of an entry -> (its state cache, its remembered refusal, the library function)
 _ENTRIES = {n: ("_%s_bufs" % n, "_%s_refused" % n, f) for n, f in (
     ("predict", "mfm_predict_klef"), ("encode", "mfm_encode_klef"), ("decode", "mfm_decode_factors"),
-    ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"))}
+    ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"))}
+
+
+def influence_factors_torch(decoders, fy, fms, T):
+    """The forward-mode recursion of influence_factors() with torch operations, on tensors of any device and float dtype:
+    `decoders` three (weight_ih, weight_hh, bias_ih, bias_hh, fc1 weight) of the decoders l, a, v, `fy` [N, fy_size], `fms` the
+    three f_m [N, f_m_size] -> [2, 3, T, N] (block fy / fm, decoder, step, row).  Per decoder with e = [fy | f_m], h columns of
+    tangents J^h, J^c [N, h, h] beside h_t, c_t: J^a = W_ih (step 0) or (W_ih + W_hh) J^h, the gate derivatives as row scalings,
+    J^x = W_fc1 J^h_t, and the sums of its squares over the two column blocks.  What the model runs where the fused entry
+    refuses (a decoder wider than MAX_RESIDENT_H), and an independent implementation to test the kernel against."""
+    nfy = fy.shape[1]
+    out = fy.new_empty(2, 3, T, fy.shape[0])
+    for m, ((w_ih, w_hh, b_ih, b_hh, w_fc), fm) in enumerate(zip(decoders, fms)):
+        e = torch.cat([fy, fm], dim=1)
+        N, h = e.shape
+        w_s, b = w_ih + w_hh, b_ih + b_hh
+        hx = cx = jc = None
+        for t in range(T):
+            if t == 0:
+                a = e @ w_ih.t() + b
+                ja = w_ih.unsqueeze(0).expand(N, 4 * h, h)
+            else:
+                a = hx @ w_s.t() + b
+                ja = torch.matmul(w_s, jh)                      # [4h, h] x [N, h, h] -> [N, 4h, h]
+            i, f, g, o = torch.sigmoid(a[:, :h]), torch.sigmoid(a[:, h:2 * h]), torch.tanh(a[:, 2 * h:3 * h]), torch.sigmoid(a[:, 3 * h:])
+            ja_i, ja_f, ja_g, ja_o = ja[:, :h], ja[:, h:2 * h], ja[:, 2 * h:3 * h], ja[:, 3 * h:]
+            jc_new = (i * (1 - i) * g).unsqueeze(2) * ja_i + (i * (1 - g * g)).unsqueeze(2) * ja_g
+            if t > 0:
+                jc_new = jc_new + (f * (1 - f) * cx).unsqueeze(2) * ja_f + f.unsqueeze(2) * jc
+                cx = f * cx + i * g
+            else:
+                cx = i * g
+            tc = torch.tanh(cx)
+            hx = o * tc
+            jc = jc_new
+            jh = (o * (1 - o) * tc).unsqueeze(2) * ja_o + (o * (1 - tc * tc)).unsqueeze(2) * jc
+            sq = torch.matmul(w_fc, jh).square().sum(dim=1)     # [N, d, h] -> [N, h]
+            out[0, m, t] = sq[:, :nfy].sum(dim=1)
+            out[1, m, t] = sq[:, nfy:].sum(dim=1)
+    return out
 
 
 class InferMixin:
-    """predict / encode / decode / objective / predict_zeros of MFMEngine.  Uses the engine's cfg, variant, layout, params,
+    """predict / encode / decode / objective / predict_zeros / influence_factors of MFMEngine.  Uses the engine's cfg, variant, layout, params,
     device, _check_inputs and forward."""
 
     PREDICT_MAX_ROWS = 1024      # default row cap: the x-projections of at most this many rows are alive at once
@@ -264,6 +309,40 @@ class InferMixin:
             return fn(T, N, sizes, _ptr(self.params), offs, zptr, _ptr(ws), optr, cap, _stream())
 
         return list(self._run_fused_or_raise("decode", (T, N, cap), build, call, self._hidden_sizes()[1:])[1])
+
+    # ------------------------------------------------------------------ the gradient-based interpretation
+    def influence_factors_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace influence_factors() keeps for N rows and T steps (mfm_influence_factors_workspace_floats: the
+        decoders' packed weights)"""
+        sizes = (C.c_int32 * 12)(*self._objective_sizes()[:12])
+        return int(_lib.lib().mfm_influence_factors_workspace_floats(int(T), int(N), sizes, self._row_cap(max_rows)))
+
+    def influence_factors(self, zl, za, zv, zy, T, *, max_rows=None):
+        """four factors [N, size] (independent arguments, as for decode()), T -> Influence(fy, fm), float32 device tensors
+        [3, T, N] (views of one [2, 3, T, N] tensor): how strongly the factors drive the generation of modality m = l, a, v at
+        step t of row n -- fy[m, t, n] = || d x_m_hat[t, n, :] / d fy[n, :] ||_F^2 and fm[m, t, n] the same for the modality's own
+        f_m, the derivative taken with respect to the factors behind the z -> f MLPs -- from the deterministic eval
+        computation, for every variant (mfm_influence_factors: forward mode, the tangents of a row resident in LDS along the
+        decoder's recurrence, the products on the fp32 MFMA; no Jacobian and no x_hat is written).  Workspace and result are
+        reused as the module docstring says; results are bit-identical from run to run and for every max_rows.  Raises
+        MfmUnsupported for sizes the entry refuses (a decoder with fy + f_m > 128 is remembered): the model's
+        influence_factors() then runs influence_factors_torch."""
+        N = self._check_factors(zl, za, zv, zy, T)
+        T = int(T)
+        cap = self._row_cap(max_rows)
+
+        def build():
+            sizes = (C.c_int32 * 12)(*self._objective_sizes()[:12])
+            nws = int(_lib.lib().mfm_influence_factors_workspace_floats(T, N, sizes, cap))
+            out = self._empty(2, 3, T, N)
+            return self._empty(nws), out, Influence(out[0], out[1]), self._offsets(self._DECODE_TENSORS), sizes
+
+        def call(fn, st):
+            ws, out, _, offs, sizes = st
+            zptr = (C.c_void_p * 4)(zl.data_ptr(), za.data_ptr(), zv.data_ptr(), zy.data_ptr())
+            return fn(T, N, sizes, _ptr(self.params), offs, zptr, _ptr(ws), _ptr(out), cap, _stream())
+
+        return self._run_fused_or_raise("influence", (T, N, cap), build, call, self._hidden_sizes()[1:])[2]
 
     # ------------------------------------------------------------------ the full validation objective
     def objective_workspace_floats(self, T, N, max_rows=None):

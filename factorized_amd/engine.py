@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _flat, _lib
-from ._infer import Factors, InferMixin, Objective, Zeros, _ptr, _stream  # noqa: F401  (the namedtuples: part of this module's interface)
+from ._infer import Factors, InferMixin, Influence, Objective, Zeros, _ptr, _stream, influence_factors_torch  # noqa: F401  (the namedtuples: part of this module's interface)
 
 ALIGN = 64  # floats
 

@@ -610,6 +610,34 @@ int mfm_predict_zeros_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13
                            float* gen /*3*/, float* disc /*3, or NULL*/, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The gradient-based interpretation of the factorized model (csrc/influence.hip): how strongly the factors drive the generation
+ * of each modality at each time step.  For decoder m = l, a, v with embedding e = [fy | f_m] of width h = fy + f_m
+ * (mfm_model.py:644-656, decoderLSTM :64-91), from the deterministic eval computation (dropout the identity),
+ *   out[0][m][t][n] = sum_{i < d_m} sum_{j < fy}       (d x_m_hat[t][n][i] / d e[n][j])^2      ("fy")
+ *   out[1][m][t][n] = sum_{i < d_m} sum_{fy <= j < h}  (d x_m_hat[t][n][i] / d e[n][j])^2      ("fm")
+ * The derivative is with respect to the factors f, behind the z -> f MLPs.  Forward mode: the h tangent columns of a row are
+ * carried along the decoder's recurrence, J^a = (W_ih + W_hh) J^h (step 0: W_ih itself) and J^x = W_fc1 J^h on
+ * v_mfma_f32_16x16x4_f32, the gate-derivative scalings on the VALU, h, c, J^h and J^c in LDS; fp32 throughout.  One small launch
+ * per call packs the decoders' weights into the workspace (gate-interleaved rows, padded to the MFMA tile with exact zeros);
+ * then per row chunk ONE launch whose workgroups are (decoder, row tile): fy and f_m of the tile's rows on the code path of
+ * mfm_decode_factors (bit-identical embedding), the T steps, and per step the sums of squares reduced inside the workgroup in
+ * a fixed order.  Every out element is stored once by one workgroup; no Jacobian and no x_hat leaves the chip; no atomics:
+ * results are bit-identical from run to run and for every max_rows.
+ *   sizes, offsets, z   exactly the arguments of mfm_decode_factors (the classifier's offsets are not read)
+ *   out      [2, 3, T, N] device floats (4-byte aligned): block (fy, fm), decoder (l, a, v)
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk)
+ *   workspace mfm_influence_factors_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary: per
+ *            decoder, with Hp = round_up(fy + f_m, 16), 8 Hp^2 + 4 Hp + round_up(d_m, 16) Hp for the packed weights -- it does
+ *            not depend on T, N or max_rows
+ * Nothing outside the workspace and `out` is written.  T < 1, N < 1, a null pointer or max_rows < 0 return MFM_ERR_ARG before
+ * anything touches the GPU.  A decoder with fy + f_m > 128, or more LDS than a CU has, returns MFM_ERR_UNSUPPORTED with the
+ * size in the error text and enqueues nothing.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_influence_factors_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_influence_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, const float* params, const int64_t* offsets /*host, 38*/,
+                          const float* const* z /*host, 4*/, float* workspace, float* out /*[2, 3, T, N]*/, int64_t max_rows,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Surrogate inference of MFM_missing (csrc/impute.hip; reference mfm_model.py:766-885, evaluated in mfm_mosi.py:572-596 and
  * :1023-1062): a missing modality m and the label from the other two modalities, in the pattern of the entries above -- fp32,
  * dropout the identity, no MfmPlan, no training workspace.  For every case m asked for
