@@ -249,14 +249,16 @@ class _FusedEngineMixin:
         """x [T, N, D] -> Factors(zl, za, zv, zy, logvar_zl, logvar_za, logvar_zv, logvar_zy) (a namedtuple, engine.Factors) of
         float32 device tensors [N, size]: the means and log-variances of the four latent factors (reference
         mfm_model.py:627-639) -- always the deterministic eval computation (dropout off, no sampling), `self.training` left as
-        found, without autograd and without lazy outputs.  MFM_KL_EF: engine.encode (one projection launch and one launch for
-        the four recurrences and their heads); the returned tensors are REUSED: the next call with the same shape overwrites
-        them (clone what must survive it).  MFM_KL, and MFM_KL_EF at sizes the fused entry refuses: the composition of the
-        module's own operations.  MFM: likewise; it has no last_to_z* / logvar heads, so zl, za, zv are the encoders' outputs
-        and the four logvars are None."""
+        found, without autograd and without lazy outputs.  All three classes run engine.encode -- MFM_KL_EF: one projection
+        launch and one launch for the four recurrences and their heads; MFM_KL and MFM: one projection launch, then the six
+        recurrences, the MFN's attention chain and its memory recurrence with the label head as one launch each, nothing of
+        cStar, attention or attended written to memory -- and the returned tensors are REUSED: the next call with the same
+        shape overwrites them (clone what must survive it).  Sizes the fused entry refuses: the composition of the module's
+        own operations.  MFM has no last_to_z* / logvar heads, so zl, za, zv are the encoders' outputs and the four logvars
+        are None."""
         eng, x = self._infer_args(x, gauss=False)
         with torch.no_grad():
-            if self._engine_variant == "kl_ef" and not getattr(eng, "_encode_refused", False):
+            if not getattr(eng, "_encode_refused" if self._engine_variant == "kl_ef" else "_encode_mfn_refused", False):
                 try:
                     return eng.encode(x)
                 except _lib.MfmUnsupported:
@@ -326,7 +328,7 @@ class _FusedEngineMixin:
 
     def influence(self, x):
         """x [T, N, D] -> Influence(fy, fm): influence_factors() of the split's own factors,
-        influence_factors(*self.encode(x)[:4], x.shape[0])"""
+        influence_factors(*self.encode(x)[:4], x.shape[0]) -- two fused entries for all three classes, no plan"""
         return self.influence_factors(*self.encode(x)[:4], x.shape[0])
 
     # ------------------------------------------------------------------ flat gradients

@@ -1,7 +1,9 @@
 """The engine's no-plan inference entries: predict, encode, decode, objective, predict_zeros and influence_factors
 (`InferMixin`, a base of engine.MFMEngine).  Each is one C call of libmfm_hip.so on the current HIP stream -- no plan, no
 training workspace, the split walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all six go through
-one host path: the split
+one host path (encode has two library entries behind it: mfm_encode_klef for variant "kl_ef", mfm_encode_mfn for the variants
+"kl" and "mmd", whose label factor comes from the Memory Fusion Network; the latter keeps its state in
+`engine._encode_mfn_bufs` / `engine._encode_mfn_refused`): the split
 validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
@@ -64,7 +66,8 @@ def _lin(*names):
 # short name of an entry -> (its state cache, its remembered refusal, the library function)
 _ENTRIES = {n: ("_%s_bufs" % n, "_%s_refused" % n, f) for n, f in (
     ("predict", "mfm_predict_klef"), ("encode", "mfm_encode_klef"), ("decode", "mfm_decode_factors"),
-    ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"))}
+    ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"),
+    ("encode_mfn", "mfm_encode_mfn"))}
 
 
 def influence_factors_torch(decoders, fy, fms, T):
@@ -117,6 +120,16 @@ class InferMixin:
     _PREDICT_TENSORS = _lstm("ef_encoder") + _lin("last_to_zy_fc1", "zy_to_fy_fc1", "zy_to_fy_fc2", "fy_to_y_fc1", "fy_to_y_fc2")
     _ENCODE_TENSORS = tuple(n for enc, z in (("encoder_l", "zl"), ("encoder_a", "za"), ("encoder_v", "zv"), ("ef_encoder", "zy"))
                             for n in _lstm(enc) + _lin("last_to_%s_fc1" % z, "last_to_logvar%s_fc1" % z))
+    # mfm_encode_mfn, per variant: the encoders (with their heads for "kl"), the MFN's LSTM cells, its attention and gamma
+    # networks, the label head(s)
+    _MFN_TENSORS = (tuple("mfn_encoder.lstm_%s.%s" % (m, n) for m in "lav" for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                    + _lin(*["mfn_encoder." + n for n in ("att1_fc1", "att1_fc2", "att2_fc1", "att2_fc2", "gamma1_fc1", "gamma1_fc2",
+                                                          "gamma2_fc1", "gamma2_fc2")]))
+    _ENCODE_MFN_TENSORS = {
+        "kl": (tuple(n for m in "lav" for n in _lstm("encoder_" + m) + _lin("last_to_z%s_fc1" % m, "last_to_logvarz%s_fc1" % m))
+               + _MFN_TENSORS + _lin("last_to_zy_fc1", "last_to_logvarzy_fc1")),
+        "mmd": tuple(n for m in "lav" for n in _lstm("encoder_" + m)) + _MFN_TENSORS + _lin("last_to_zy_fc1"),
+    }
     _DECODE_TENSORS = (_lin(*[mlp + fc for mlp in ("zy_to_fy", "zl_to_fl", "za_to_fa", "zv_to_fv") for fc in ("_fc1", "_fc2")])
                        + _lstm("decoder_l") + _lstm("decoder_a") + _lstm("decoder_v") + _lin("fy_to_y_fc1", "fy_to_y_fc2"))
 
@@ -227,9 +240,18 @@ class InferMixin:
         return {"y_hat": out["y_hat"], "loss": out["losses"][0].clone() if y is not None else None}
 
     # ------------------------------------------------------------------ the factorized latents and generation from them
-    def encode_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace encode() keeps for a [T, N, D] split (mfm_encode_klef_workspace_floats)"""
+    def _encode_mfn_sizes(self):
+        """the 17 sizes of mfm_encode_mfn (include/mfm_hip.h)"""
         c = self.cfg
+        return (C.c_int32 * 17)(*c["input_dims"], c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], *c["h_dims"], c["memsize"],
+                                c.get("windowsize", 2), *[k["shapes"] for k in self.configs[1:5]], 1 if self.variant == "kl" else 0)
+
+    def encode_workspace_floats(self, T, N, max_rows=None):
+        """floats of workspace encode() keeps for a [T, N, D] split (mfm_encode_klef_workspace_floats; variants "kl" and "mmd":
+        mfm_encode_mfn_workspace_floats)"""
+        c = self.cfg
+        if self.variant != "kl_ef":
+            return int(_lib.lib().mfm_encode_mfn_workspace_floats(int(T), int(N), self._encode_mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_encode_klef_workspace_floats(int(T), int(N), c["zl_size"], c["za_size"], c["zv_size"],
                                                                self._row_cap(max_rows)))
 
@@ -241,14 +263,17 @@ class InferMixin:
 
     def encode(self, x, *, max_rows=None):
         """x [T, N, D] -> Factors(zl, za, zv, zy, logvar_zl, logvar_za, logvar_zv, logvar_zy), float32 device tensors [N, size]:
-        the means and log-variances of the four latent factors (reference mfm_model.py:627-639), the deterministic eval
-        computation.  Variant "kl_ef" only (mfm_encode_klef: the four encoders' recurrences and their heads).  Workspace and
-        outputs are reused as the module docstring says.  Raises MfmUnsupported for another variant or for sizes the entry
-        refuses: the model's encode() then composes the granular operations."""
+        the means and log-variances of the four latent factors (reference mfm_model.py:627-639, :723-743), the deterministic eval
+        computation.  Variant "kl_ef": mfm_encode_klef (the four encoders' recurrences and their heads).  Variants "kl" and
+        "mmd": mfm_encode_mfn (the three encoders and the Memory Fusion Network -- its LSTMs, the attention chain with cStar,
+        attention and attended on chip, the memory recurrence and the label head); "mmd" has no heads on the encoders and no
+        log-variances: zl, za, zv are the encoders' outputs and the four logvars None.  Workspace and outputs are reused as the
+        module docstring says.  Raises MfmUnsupported for sizes the entry refuses (an h_dims entry or encoder size above 128 is
+        remembered): the model's encode() then composes the granular operations."""
         T, N, D = self._check_split(x)
         cap = self._row_cap(max_rows)
         if self.variant != "kl_ef":
-            raise _lib.MfmUnsupported("MFMEngine.encode: the fused encoder half exists for variant 'kl_ef' only, not %r" % self.variant)
+            return self._encode_mfn(x, T, N, cap)
         c = self.cfg
         zsz = (c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"])
 
@@ -262,6 +287,25 @@ class InferMixin:
             return fn(T, N, *c["input_dims"], *zsz, _ptr(self.params), offs, _ptr(x), _ptr(ws), optr, cap, _stream())
 
         return Factors(*self._run_fused_or_raise("encode", (T, N, cap), build, call, self._hidden_sizes()[:1])[1])
+
+    def _encode_mfn(self, x, T, N, cap):
+        c = self.cfg
+        kl = self.variant == "kl"
+        zsz = (c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"])
+
+        def build():
+            sizes = self._encode_mfn_sizes()
+            nws = int(_lib.lib().mfm_encode_mfn_workspace_floats(T, N, sizes, cap))
+            outs = tuple(self._empty(N, s) for s in (zsz + zsz if kl else zsz))
+            optr = (C.c_void_p * 8)(*[t.data_ptr() for t in outs])
+            return self._empty(nws), outs + (None,) * (8 - len(outs)), self._offsets(self._ENCODE_MFN_TENSORS[self.variant]), optr, sizes
+
+        def call(fn, st):
+            ws, _, offs, optr, sizes = st
+            return fn(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(ws), optr, cap, _stream())
+
+        hidden = tuple(c["h_dims"]) + zsz[:3]
+        return Factors(*self._run_fused_or_raise("encode_mfn", (T, N, cap), build, call, hidden)[1])
 
     def _check_factors(self, zl, za, zv, zy, T):
         c = self.cfg

@@ -201,6 +201,10 @@ _SIGS = {
     "mfm_encode_klef": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int64,
                                   C.c_void_p]),
+    "mfm_encode_mfn_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
+    "mfm_encode_mfn_tile_rows": (C.c_int, [C.c_int64, C.c_int64]),
+    "mfm_encode_mfn": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),
     "mfm_decode_factors_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "mfm_decode_factors": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64),
                                      C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),

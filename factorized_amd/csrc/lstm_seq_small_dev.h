@@ -193,7 +193,10 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // back from the h buffer the step just filled by Hp * R / 64 full waves behind the step's barrier -- row b0 + r of step t at
 // d.hs[t * hs_step + (b0 + r) * Hp + unit], all Hp units (the pad units exact zeros: a GEMM over the rows masks its K tail by
 // multiplication and must not meet whatever the buffer held).
-template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true, bool HS = false>
+// CS (with REC = false; encode_mfn.hip: the MFN's LSTMs, whose cell states feed the attention chain behind the launch): c_t alone
+// leaves for HBM -- the owners drop it into slot 4 of the record buffer, Hp * R / 64 full waves write it out behind the step's
+// barrier: row b0 + r of step t at d.cs[(t * B + b0 + r) * Hp + unit], all Hp units (the pad units exact zeros).
+template <int KQ, int R, bool FLG = false, bool BF = false, bool REC = true, bool HS = false, bool CS = false>
 __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const int T, const int B, const int tile, float* lds,
                                                const unsigned long long* pw = nullptr, const unsigned epoch = 0, const int pw_ld = 0,
                                                const HoCtl ctl = HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u},
@@ -221,6 +224,7 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
   constexpr int HX = (R == 1) ? HKB : HK;          // extent of one h buffer
   static_assert(!BF || R == 1, "bf16 dot products: one-row tiles only");
   static_assert(!HS || (!REC && !BF), "h-only record: fp32 inference bodies");
+  static_assert(!CS || (!REC && !BF && !HS), "c-only record: fp32 inference bodies");
   static_assert(!FLG || R == 1, "projection words: one-row tiles only (one word per fetching lane)");
   float* hbuf = lds;                       // [2][HX][R]
   __bf16* hb16 = reinterpret_cast<__bf16*>(lds);   // BF: the same two buffers as bf16 (half the bytes)
@@ -393,6 +397,16 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     hs_p = p_hs + (int64_t)min(b0 + r, B - 1) * Hp + (hs_ok ? unit : 0);
     hs_l = (hs_ok && unit < HX) ? unit * R + r : -1;          // (-1: a pad unit beyond the h buffer's extent)
   }
+  // CS: element tid -> (row r, unit), unit fastest
+  gfloat* cs_p = p_cs;
+  int cs_l = 0;
+  bool cs_ok = false;
+  if constexpr (CS) {
+    const int r = tid / HKB, unit = tid - r * HKB;
+    cs_ok = tid < HKB * R && b0 + r < B;
+    cs_p = p_cs + (int64_t)min(b0 + r, B - 1) * Hp + (cs_ok ? unit : 0);
+    cs_l = cs_ok ? (4 * HKB + unit) * R + r : 0;
+  }
   const int ucl = min(u, HKB - 1);
   const int my_o = (2 * gp * HKB + ucl) * R + myrow;       // this lane's slots: 2gp, 2gp+1 and 4+gp
   const float sc0 = gp ? 2.0f : 1.0f;                      // gate 0 of the pair: sigmoid(i) / tanh(g)
@@ -545,6 +559,9 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
         ob[0] = a0; ob[HKB * R] = a1;
         ob[(4 - gp) * HKB * R] = gp ? hv : c;        // slot 4 (c) from gp 0, slot 5 (h) from gp 1
       }
+      if constexpr (CS) {
+        if (gp == 0) obuf[par * (6 * HKB * R) + 4 * HKB * R + ucl * R + myrow] = c;
+      }
       if (gp == 0 && u < HX) {
         const float hn = (b < B) ? hv : 0.0f;
         if constexpr (BF) hb16[(cur ^ 1) * HX + u] = (__bf16)hn; else hbuf[(cur ^ 1) * (HX * R) + u * R + myrow] = hn;
@@ -583,6 +600,10 @@ __device__ __forceinline__ const float* small_fwd_body(const SeqDev& d, const in
     if constexpr (HS) {
       if (hs_ok) *hs_p = hs_l >= 0 ? hbuf[(cur ^ 1) * (HX * R) + hs_l] : 0.0f;
       hs_p += hs_step;
+    }
+    if constexpr (CS) {
+      if (cs_ok) *cs_p = obuf[par * (6 * HKB * R) + cs_l];
+      cs_p += sstep;
     }
 #pragma unroll
     for (int i = 0; i < NXL; ++i) { xpf[i] = xn[i]; xpw[i] = xnw[i]; }

@@ -532,6 +532,52 @@ int mfm_decode_factors(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, 
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * mfm_encode_mfn (csrc/encode_mfn.hip): the encoder half of MFM_KL and MFM, whose label factor comes from the Memory Fusion
+ * Network (mfm_model.py:140-199, :723-743), in the pattern and under the contract of mfm_encode_klef: fp32, dropout the
+ * identity, the means used, no MfmPlan and no training workspace.
+ *   m_last = encoder_m(x_m) (the recurrence, then the encoder's fc1) for m = l, a, v.  heads = 1 (MFM_KL): z_m =
+ *   last_to_z{m}_fc1(m_last), logvar_z_m = last_to_logvarz{m}_fc1(m_last).  heads = 0 (MFM): z_m = m_last, no logvars.
+ *   MFN: the three LSTMCell recurrences on x_l, x_a, x_v; cStar_t = [c_{t-1} | c_t], c_{-1} = 0; attended = softmax(att1_fc2(
+ *   relu(att1_fc1(cStar)))) * cStar; cHat = tanh(att2_fc2(relu(att2_fc1(attended)))); gamma_g = sigmoid(gamma{g}_fc2(relu(
+ *   gamma{g}_fc1([attended | mem])))); mem = gamma1 * mem + gamma2 * cHat; zy = last_to_zy_fc1([h_l,T | h_a,T | h_v,T | mem_T])
+ *   and, heads = 1, logvar_zy = last_to_logvarzy_fc1 of the same.  The MFN's out_fc* layers are not used, as in the reference.
+ * Per row chunk four launches behind one grouped fp32 GEMM for the six input projections: the six recurrences as (LSTM, row
+ * tile) workgroups (the encoders with their fc1 and heads; the MFN's LSTMs store their cell states and last hidden state, no h
+ * record and no gates); the attention chain row-wise over the T * n pairs (t, row) on the fp32 MFMA with cStar, attention and
+ * attended in LDS only -- per pair cHat and the attended part of the two gamma pre-activations are written; the memory
+ * recurrence with one workgroup per row, mem on chip, ending with the label head(s).
+ *   sizes    host, 17: d_l, d_a, d_v; zl, za, zv (the encoders' hidden sizes); zy; h_l, h_a, h_v (h_dims); memsize; windowsize;
+ *            the hidden widths of att1, att2, gamma1, gamma2; heads (1: MFM_KL, 0: MFM)
+ *   offsets  host, element offsets into the flat fp32 parameter buffer `params`.  Per encoder l, a, v: lstm weight_ih,
+ *            weight_hh, bias_ih, bias_hh, fc1 weight, bias and, heads = 1, weight and bias of its mean head and of its logvar
+ *            head (10 or 6 each); per MFN LSTM l, a, v: weight_ih, weight_hh, bias_ih, bias_hh (12); weight and bias of att1_fc1,
+ *            att1_fc2, att2_fc1, att2_fc2, gamma1_fc1, gamma1_fc2, gamma2_fc1, gamma2_fc2 (16); of last_to_zy_fc1 and, heads = 1,
+ *            last_to_logvarzy_fc1.  62 offsets with heads, 48 without (torch layouts; the LSTM weights 16-byte aligned)
+ *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 4-byte aligned: any contiguous view
+ *   out      host array of 8 device pointers in the order zl [N, zl], za, zv, zy [N, zy], then the four logvars alike; heads = 0:
+ *            the last four are not read and may be NULL
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_encode_mfn_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary.  With
+ *            rows = min(N, max_rows), Hp(h) = round_up(h, 16), up4(v) = round_up(v, 4):
+ *              rows * T * 4 * (Hp(zl) + Hp(za) + Hp(zv) + Hp(h_l) + Hp(h_a) + Hp(h_v))      the x-projections
+ *            + rows * T * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                     the MFN LSTMs' cell states
+ *            + up4(rows * h_l) + up4(rows * h_a) + up4(rows * h_v)                          their last hidden states
+ *            + up4(rows * T * memsize) + up4(rows * T * gamma1) + up4(rows * T * gamma2)    cHat and the gamma partials
+ * Determinism: bit-identical from run to run.  The recurrence launch runs on one-row tiles while 6 * rows < 6 * CUs and on
+ * four-row tiles from there (mfm_encode_mfn_tile_rows tells which; host only, -1 for bad arguments); the other launches have
+ * one form (the attention chain takes 16 or 32 pairs per workgroup, and a pair's arithmetic is the same in both).  For a
+ * fixed tile-row form the results are bit-identical for every row chunking.
+ * Nothing outside the workspace and the outputs is written.  Any N >= 1, T >= 1.  MFM_ERR_UNSUPPORTED with the size in the
+ * error text, nothing enqueued: an h_dims entry or an encoder hidden size above 128; a windowsize other than 2 (the reference's
+ * forward reads exactly two steps); attention widths whose tile needs more than the 160 KB of LDS of a CU; memsize or gamma
+ * widths beyond the register-resident memory recurrence (more than 1024 threads, or a reduction longer than 512).  Compose
+ * the granular entries instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_encode_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 17*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_encode_mfn_tile_rows(int64_t N, int64_t max_rows);
+int mfm_encode_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 17*/, const float* params, const int64_t* offsets /*host, 62 or 48*/,
+                   const float* x, float* workspace, float* const* out /*host, 8*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The full validation objective of MFM_KL_EF (csrc/objective.hip; reference mfm_mosi.py:319-324, :724-726, :826-845): the six
  * numbers every driver reports for a validation split, from the deterministic eval forward, in the pattern of the entries
  * above -- fp32, dropout the identity, z = the mean heads, no MfmPlan, no training workspace, and no x_hat in memory.
