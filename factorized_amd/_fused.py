@@ -197,9 +197,10 @@ class _FusedEngineMixin:
         F.mse_loss of the zeroed modality's reconstruction against the real one (what the reference prints, unweighted), disc
         [3] the mean L1 / cross entropy per case as evaluate() defines it, None without labels.  Always the deterministic eval
         computation (dropout off, z = the mean heads), `self.training` left as found, without autograd, lazy outputs or a host
-        read.  MFM_KL_EF: engine.predict_zeros (no plan, no zeroed copies, x_hat never written); buffers are kept per (T, N,
-        max_rows) and the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must
-        survive it).  MFM_KL / MFM, and sizes the fused entry refuses: three fused eval forwards on zeroed copies."""
+        read.  Every class: engine.predict_zeros (no plan, no zeroed copies, x_hat never written -- MFM_KL_EF through
+        mfm_predict_zeros_klef, MFM_KL / MFM through mfm_predict_zeros_mfn, the Memory Fusion Network's label path on chip);
+        buffers are kept per (T, N, max_rows) and the returned tensors are REUSED: the next call with the same shape overwrites
+        them (clone what must survive it).  Sizes the fused entry refuses: three fused eval forwards on zeroed copies."""
         eng, x = self._infer_args(x)
         with torch.no_grad():
             return eng.predict_zeros(x, y)

@@ -3,7 +3,8 @@
 training workspace, the split walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all six go through
 one host path (encode has two library entries behind it: mfm_encode_klef for variant "kl_ef", mfm_encode_mfn for the variants
 "kl" and "mmd", whose label factor comes from the Memory Fusion Network; the latter keeps its state in
-`engine._encode_mfn_bufs` / `engine._encode_mfn_refused`): the split
+`engine._encode_mfn_bufs` / `engine._encode_mfn_refused`; predict_zeros likewise: mfm_predict_zeros_klef, and
+mfm_predict_zeros_mfn with its state in `engine._zeros_mfn_bufs` / `engine._zeros_mfn_refused`): the split
 validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
@@ -67,7 +68,7 @@ def _lin(*names):
 _ENTRIES = {n: ("_%s_bufs" % n, "_%s_refused" % n, f) for n, f in (
     ("predict", "mfm_predict_klef"), ("encode", "mfm_encode_klef"), ("decode", "mfm_decode_factors"),
     ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"),
-    ("encode_mfn", "mfm_encode_mfn"))}
+    ("encode_mfn", "mfm_encode_mfn"), ("zeros_mfn", "mfm_predict_zeros_mfn"))}
 
 
 def influence_factors_torch(decoders, fy, fms, T):
@@ -430,8 +431,17 @@ class InferMixin:
         return Objective(*out.unbind(0))
 
     # ------------------------------------------------------------------ the zeroed-modality test protocol
+    def _zeros_mfn_sizes(self):
+        """the 23 sizes of mfm_predict_zeros_mfn (include/mfm_hip.h): the 17 of mfm_encode_mfn, the f sizes, output_dim, loss kind"""
+        c = self.cfg
+        return (C.c_int32 * 23)(*self._encode_mfn_sizes(), c["fl_size"], c["fa_size"], c["fv_size"], c["fy_size"], c["output_dim"],
+                                1 if c.get("loss", "l1") == "ce" else 0)
+
     def predict_zeros_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace predict_zeros() keeps for a [T, N, D] split (mfm_predict_zeros_klef_workspace_floats)"""
+        """floats of workspace predict_zeros() keeps for a [T, N, D] split (mfm_predict_zeros_klef_workspace_floats; variants
+        "kl" and "mmd": mfm_predict_zeros_mfn_workspace_floats)"""
+        if self.variant != "kl_ef":
+            return int(_lib.lib().mfm_predict_zeros_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
 
     def predict_zeros(self, x, y=None, *, max_rows=None):
@@ -443,26 +453,40 @@ class InferMixin:
 
         Variant "kl_ef": mfm_predict_zeros_klef -- no zeroed copy of x, the ef encoder's projection computed once for the three
         cases, the zeroed encoder one row of work, one decoder per case with its fc1 fused into the squared error (x_hat is
-        never written).  Workspace and the three result tensors are reused and a refusal falls back as the module docstring
-        says.  Other variants: the same namedtuple from three forward(train=False, handover=False) calls on zeroed copies, the
-        means formed on the device."""
+        never written).  Variants "kl" and "mmd": mfm_predict_zeros_mfn -- the MFN's three LSTMs on the real columns once for
+        the three cases, the zeroed modality's MFN LSTM and encoder one row of work each, the attention chain and the memory
+        recurrence of encode() over the (case, row) pairs, then the same decoders' launches; its state is a cache of its own,
+        `_zeros_mfn_bufs`.  Workspace and the three result tensors are reused and a refusal falls back as the module docstring
+        says (remembered for an h_dims entry, an encoder or a decoder above 128): the same namedtuple from three
+        forward(train=False, handover=False) calls on zeroed copies, the means formed on the device."""
         T, N, D = self._check_split(x, y)
         cap = self._row_cap(max_rows)
         c = self.cfg
         od = c["output_dim"]
+        klef = self.variant == "kl_ef"
 
         def build():
-            sizes = self._objective_sizes()
-            nws = int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(T, N, sizes, cap))
+            if klef:
+                sizes = self._objective_sizes()
+                nws = int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(T, N, sizes, cap))
+                offs = self._offsets(self._ENCODE_TENSORS + self._DECODE_TENSORS)
+            else:
+                sizes = self._zeros_mfn_sizes()
+                nws = int(_lib.lib().mfm_predict_zeros_mfn_workspace_floats(T, N, sizes, cap))
+                offs = self._offsets(self._ENCODE_MFN_TENSORS[self.variant] + self._DECODE_TENSORS)
             return (self._empty(nws), self._empty(3, N, od), torch.zeros(3, dtype=torch.float32, device=self.device),
-                    torch.zeros(3, dtype=torch.float32, device=self.device), sizes, self._offsets(self._ENCODE_TENSORS + self._DECODE_TENSORS))
+                    torch.zeros(3, dtype=torch.float32, device=self.device), sizes, offs)
 
         def call(fn, st):
             ws, y_hat, gen, disc, sizes, offs = st
             return fn(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat), _ptr(gen),
                       _ptr(disc) if y is not None else None, cap, _stream())
 
-        st = self._run_fused("zeros", (T, N, cap), build, call, self._hidden_sizes()) if self.variant == "kl_ef" else None
+        if klef:
+            st = self._run_fused("zeros", (T, N, cap), build, call, self._hidden_sizes())
+        else:
+            hidden = tuple(c["h_dims"]) + (c["zl_size"], c["za_size"], c["zv_size"]) + self._hidden_sizes()[1:]
+            st = self._run_fused("zeros_mfn", (T, N, cap), build, call, hidden)
         if st is not None:
             return Zeros(st[1], st[2], st[3] if y is not None else None)
         # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)

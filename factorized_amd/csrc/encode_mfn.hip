@@ -16,15 +16,10 @@
 //      its records -- and ends with last_to_zy_fc1 (and the logvar head) on [h_l | h_a | h_v | mem].
 // A pair's and a row's arithmetic does not depend on its place in a tile or a chunk, nothing is accumulated across workgroups:
 // results are bit-identical from run to run, and for every chunking within one tile-row form of launch 2 (gen_tile_rows).
-#include "infer_dev.h"
+// Launches 3 and 4 live in encode_mfn_dev.h: mfm_predict_zeros_mfn (zeros_mfn.hip) runs them too, on another gather.
+#include "encode_mfn_dev.h"
 
 namespace mfm {
-
-#define EMFN_LSTMS 6          // encoder l, a, v, then the MFN's lstm l, a, v
-#define EMFN_SIZES 17
-#define EMFN_ATT_THREADS 512
-#define EMFN_SPARTS 16        // threads per pair in the softmax: fixed, the sums' order must not depend on the tile width
-#define EMFN_MAXW 32          // weights per thread and matrix of the memory recurrence
 
 struct EmfnOne {
   SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4; an MFN LSTM: cs [T, n, Hp]
@@ -71,300 +66,8 @@ __global__ __launch_bounds__(1024) void encode_mfn_seq_kernel(const EmfnSeqDev P
   store_rows<R>(act2, E.lv, h, b0, P.n, tid);
 }
 
-// ---------------------------------------------------------------- the attention chain
-struct EmfnAttDev {
-  const float* cs[3];                          // the MFN LSTMs' c records [T, n, Hp]
-  const float* w[6]; const float* b[6];        // att1_fc1, att1_fc2, att2_fc1, att2_fc2, gamma1_fc1, gamma2_fc1
-  float* chat; float* g1p; float* g2p;         // [T n, M], [T n, H1], [T n, H2]
-  int hm[3], Hpm[3];
-  int T, n, tot, KC, KCp, h1, h2, hbp, M, H1, H2;
-};
-
-// Y[o][pair] = sum_k W[o][k] X[k][pair] over the tile's 16 CT pairs: wave w takes the 16-unit output tiles w, w + waves, ...;
-// X in LDS as [Kp][LDP] (rows K .. Kp exact zeros), LDP = 16 CT + 4 (the four k a B fragment reads fall on different banks).
-// MFMA step s of chunk c multiplies k = 16 c + 4 (lane >> 4) + s on both sides: a lane's four A values are one 16-byte load of
-// its weight row (K and the row stride multiples of 4 and an aligned base; else four guarded dword loads), the next chunk's
-// while this one multiplies.  Rows beyond Nout and columns beyond K read as zeros.  epi(o, pair, value) for the lane's
-// 4 x CT results: o = 16 tile + 4 (lane >> 4) + r, pair = 16 ct + (lane & 15)
-template <int CT, class Epi>
-__device__ __forceinline__ void emfn_layer(const float* __restrict__ W, const int ldw, const int K, const int Kp, const int Nout,
-                                           const int out_tiles, const float* Xs, Epi epi) {
-  constexpr int LDP = 16 * CT + 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int col = lane & 15, q = lane >> 4;
-  const bool vec = (ldw & 3) == 0 && (K & 3) == 0 && (((uintptr_t)W) & 15) == 0;
-  const int kchunks = Kp / 16;
-  for (int ot = wave; ot < out_tiles; ot += nw) {
-    const int orow = 16 * ot + col;
-    const bool rok = orow < Nout;
-    const float* wr = W + (int64_t)min(orow, Nout - 1) * ldw;
-    auto lda = [&](const int c) {
-      const int k0 = 16 * c + 4 * q;
-      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (vec) {
-        if (rok && k0 < K) v = *reinterpret_cast<const f32x4*>(wr + k0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (rok && k0 + i < K) v[i] = wr[k0 + i];
-      }
-      return v;
-    };
-    f32x4 acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    f32x4 a4 = lda(0);
-    for (int c = 0; c < kchunks; ++c) {
-      const f32x4 an = lda(c + 1 < kchunks ? c + 1 : c);
-      const float* bc = Xs + (16 * c + 4 * q) * LDP + col;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[ct] = mma16x16x4(a4[s], bc[s * LDP + 16 * ct], acc[ct]);
-      }
-      a4 = an;
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) epi(16 * ot + 4 * q + r, 16 * ct + col, acc[ct][r]);
-  }
-}
-
-template <int CT>
-__global__ __launch_bounds__(EMFN_ATT_THREADS) void encode_mfn_att_kernel(const EmfnAttDev P) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int MT = 16 * CT, LDP = MT + 4;
-  const int tid = threadIdx.x;
-  const int KC = P.KC, KCp = P.KCp, tot = P.tot;
-  const int64_t pairs = (int64_t)P.T * P.n, p0 = (int64_t)blockIdx.x * MT;
-  float* Xc = lds;                             // [KCp][LDP] cStar
-  float* Lg = Xc + KCp * LDP;                  // [KCp][LDP] the attention's logits, then attended
-  float* Hb = Lg + KCp * LDP;                  // [hbp][LDP] the hidden layer of att1, then of att2
-  float* red = Hb + P.hbp * LDP;               // [2][EMFN_SPARTS][MT]
-
-  // ---- cStar of the tile's pairs: k < tot from step t - 1 (zeros at t = 0), the rest from step t; unit fastest
-  const int n0 = P.hm[0], n1 = n0 + P.hm[1];
-  for (int e = tid; e < KCp * MT; e += EMFN_ATT_THREADS) {
-    const int j = e / KCp, k = e - j * KCp;
-    const int64_t p = p0 + j;
-    float v = 0.0f;
-    if (k < KC && p < pairs) {
-      const int t = (int)(p / P.n), i = (int)(p - (int64_t)t * P.n);
-      const int prev = k < tot, u = prev ? k : k - tot;
-      const int m = u < n0 ? 0 : (u < n1 ? 1 : 2);
-      const int um = u - (m == 0 ? 0 : (m == 1 ? n0 : n1));
-      if (!prev || t > 0) v = P.cs[m][((int64_t)(t - prev) * P.n + i) * P.Hpm[m] + um];
-    }
-    Xc[k * LDP + j] = v;
-  }
-  lds_barrier();
-
-  // ---- att1: hidden = relu(fc1 cStar), logits = fc2 hidden
-  emfn_layer<CT>(P.w[0], KC, KC, KCp, P.h1, P.hbp / 16, Xc, [&](const int o, const int j, const float v) {
-    Hb[o * LDP + j] = o < P.h1 ? fmaxf(v + P.b[0][o], 0.0f) : 0.0f;
-  });
-  lds_barrier();
-  emfn_layer<CT>(P.w[1], P.h1, P.h1, (P.h1 + 15) / 16 * 16, KC, KCp / 16, Hb, [&](const int o, const int j, const float v) {
-    Lg[o * LDP + j] = o < KC ? v + P.b[1][o] : 0.0f;
-  });
-  lds_barrier();
-
-  // ---- attended = softmax(logits) * cStar per pair: EMFN_SPARTS threads per pair, every sum in a fixed order
-  {
-    const int j = tid % MT, part = tid / MT;
-    const bool on = tid < EMFN_SPARTS * MT;
-    float mx = -INFINITY;
-    if (on)
-      for (int k = part; k < KC; k += EMFN_SPARTS) mx = fmaxf(mx, Lg[k * LDP + j]);
-    if (on) red[part * MT + j] = mx;
-    lds_barrier();
-    if (on) {
-#pragma unroll
-      for (int s = 0; s < EMFN_SPARTS; ++s) mx = fmaxf(mx, red[s * MT + j]);
-    }
-    float sum = 0.0f;
-    if (on)
-      for (int k = part; k < KC; k += EMFN_SPARTS) {
-        const float ev = expf(Lg[k * LDP + j] - mx);
-        Lg[k * LDP + j] = ev;
-        sum += ev;
-      }
-    float* red2 = red + EMFN_SPARTS * MT;
-    if (on) red2[part * MT + j] = sum;
-    lds_barrier();
-    if (on) {
-      float tsum = red2[j];
-#pragma unroll
-      for (int s = 1; s < EMFN_SPARTS; ++s) tsum += red2[s * MT + j];
-      for (int k = part; k < KC; k += EMFN_SPARTS) Lg[k * LDP + j] = Lg[k * LDP + j] / tsum * Xc[k * LDP + j];
-    }
-  }
-  lds_barrier();
-
-  // ---- att2: cHat = tanh(fc2 relu(fc1 attended))
-  emfn_layer<CT>(P.w[2], KC, KC, KCp, P.h2, P.hbp / 16, Lg, [&](const int o, const int j, const float v) {
-    Hb[o * LDP + j] = o < P.h2 ? fmaxf(v + P.b[2][o], 0.0f) : 0.0f;
-  });
-  lds_barrier();
-  emfn_layer<CT>(P.w[3], P.h2, P.h2, (P.h2 + 15) / 16 * 16, P.M, (P.M + 15) / 16, Hb, [&](const int o, const int j, const float v) {
-    if (o < P.M && p0 + j < pairs) P.chat[(p0 + j) * P.M + o] = tanhf(v + P.b[3][o]);
-  });
-  // ---- the attended columns of gamma1_fc1 / gamma2_fc1 (their rows are KC + M wide), with the bias
-  emfn_layer<CT>(P.w[4], KC + P.M, KC, KCp, P.H1, (P.H1 + 15) / 16, Lg, [&](const int o, const int j, const float v) {
-    if (o < P.H1 && p0 + j < pairs) P.g1p[(p0 + j) * P.H1 + o] = v + P.b[4][o];
-  });
-  emfn_layer<CT>(P.w[5], KC + P.M, KC, KCp, P.H2, (P.H2 + 15) / 16, Lg, [&](const int o, const int j, const float v) {
-    if (o < P.H2 && p0 + j < pairs) P.g2p[(p0 + j) * P.H2 + o] = v + P.b[5][o];
-  });
-}
-
-// ---------------------------------------------------------------- the memory recurrence and the label head
-struct EmfnMemDev {
-  const float* g1p; const float* g2p; const float* chat;      // [T, n, H1], [T, n, H2], [T, n, M]
-  const float* w1m; const float* w2m;                          // the memory columns of gamma*_fc1, rows ldw apart
-  const float* w1b; const float* b1b; const float* w2b; const float* b2b;      // gamma*_fc2
-  const float* hl[3];                                          // the MFN LSTMs' last hidden states [n, h_m]
-  const float* wz[2]; const float* bz[2]; float* oz[2];        // last_to_zy_fc1, last_to_logvarzy_fc1; the chunk's rows [n, zy]
-  int hn[3];
-  int T, n, M, H1, H2, QA, QB, MP, HP, ldw, tot, zy, nheads;
-};
-
-// all-reduce over groups of Q adjacent lanes, Q in {1, 2, 4, 8, 16}
-__device__ __forceinline__ float emfn_group_sum(float v, const int Q) {
-  if (Q >= 2) v += dpp_f<DPP_QUAD_XOR1>(v);
-  if (Q >= 4) v += dpp_f<DPP_QUAD_XOR2>(v);
-  if (Q >= 8) v += dpp_f<DPP_ROW_HALF_MIRROR>(v);
-  if (Q >= 16) v += dpp_f<DPP_ROW_MIRROR>(v);
-  return v;
-}
-
-// a thread's resident weights: elements [k0, k0 + 32) of one weight row, zeros beyond n; whole aligned slices as 16-byte loads
-__device__ __forceinline__ void emfn_wslice(float (&w)[EMFN_MAXW], const float* __restrict__ row, const int k0, const int n, const bool act) {
-  const float* src = row + k0;
-  if (act && k0 + EMFN_MAXW <= n && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-#pragma unroll
-    for (int i = 0; i < EMFN_MAXW / 4; ++i) {
-      const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
-      w[4 * i] = v[0]; w[4 * i + 1] = v[1]; w[4 * i + 2] = v[2]; w[4 * i + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < EMFN_MAXW; ++i) w[i] = (act && k0 + i < n) ? row[min(k0 + i, n - 1)] : 0.0f;
-  }
-}
-
-// The thread roles, the operand layout (lane q of a group owns the contiguous slice [32 q, 32 q + 32) of the reduction) and the
-// two barriers per step are those of mfn_mem_fwd_kernel (mfn_mem.hip); nothing of a step is stored
-template <int MAXT>
-__global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const EmfnMemDev P) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int T = P.T, n = P.n, M = P.M, H1 = P.H1, H2 = P.H2, QA = P.QA, QB = P.QB, MP = P.MP, HP = P.HP;
-  float* memb = lds;                 // [2][MP]
-  float* ab = lds + 2 * MP;          // [2][HP] the relu activations of the two gates
-  const int row = blockIdx.x, tid = threadIdx.x;
-
-  // phase A: (gate, j, q): u[j] = relu(partial[t][j] + sum_k Wm[j][k] mem[k])
-  const int nA = (H1 + H2) * QA;
-  const bool actA = tid < nA;
-  const int ja = min(tid, nA - 1) / QA, qa = tid % QA;
-  const int netA = ja >= H1;
-  const int jn = netA ? ja - H1 : ja;
-  const int Hn = netA ? H2 : H1;
-  float wA[EMFN_MAXW];
-  emfn_wslice(wA, (netA ? P.w2m : P.w1m) + (int64_t)jn * P.ldw, EMFN_MAXW * qa, M, actA);
-  const float* abuf = netA ? P.g2p : P.g1p;
-  // phase B: (m, q): gamma_g[m] = sigmoid(b[m] + sum_k Wb_g[m][k] u_g[k]), both gates
-  const int nB = M * QB;
-  const bool actB = tid < nB;
-  const int mb = min(tid, nB - 1) / QB, qb = tid % QB;
-  float wB1[EMFN_MAXW], wB2[EMFN_MAXW];
-  emfn_wslice(wB1, P.w1b + (int64_t)mb * H1, EMFN_MAXW * qb, H1, actB);
-  emfn_wslice(wB2, P.w2b + (int64_t)mb * H2, EMFN_MAXW * qb, H2, actB);
-  const float bb1 = P.b1b[mb], bb2 = P.b2b[mb];
-
-  for (int i = tid; i < 2 * MP + 2 * HP; i += blockDim.x) lds[i] = 0.0f;
-  float memr = 0.0f;                              // mem[mb], the same in every lane of the phase-B group
-  const int64_t arow = (int64_t)row * Hn + jn, mrow = (int64_t)row * M + mb;
-  float att_n = abuf[arow], ch_n = P.chat[mrow];
-  lds_barrier();
-  const bool stA = actA && qa == 0, stB = actB && qb == 0;
-  int cur = 0;
-  for (int t = 0; t < T; ++t) {
-    const float att = att_n, ch = ch_n;
-    const int tn = min(t + 1, T - 1);
-    att_n = abuf[(int64_t)tn * n * Hn + arow];     // unconditional prefetch (clamped at the tail)
-    ch_n = P.chat[(int64_t)tn * n * M + mrow];
-    {
-      const f32x4* mp = reinterpret_cast<const f32x4*>(memb + cur * MP + EMFN_MAXW * qa);
-      float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-      for (int i = 0; i < EMFN_MAXW / 4; ++i) {
-        const f32x4 v = mp[i];
-        s0 = fmaf(wA[4 * i], v[0], s0); s1 = fmaf(wA[4 * i + 1], v[1], s1);
-        s0 = fmaf(wA[4 * i + 2], v[2], s0); s1 = fmaf(wA[4 * i + 3], v[3], s1);
-      }
-      const float u = fmaxf(emfn_group_sum(s0 + s1, QA) + att, 0.0f);
-      if (stA) ab[netA ? HP + jn : jn] = u;
-    }
-    lds_barrier();
-    {
-      const f32x4* a1p = reinterpret_cast<const f32x4*>(ab + EMFN_MAXW * qb);
-      const f32x4* a2p = reinterpret_cast<const f32x4*>(ab + HP + EMFN_MAXW * qb);
-      float z1 = 0.0f, z2 = 0.0f;
-#pragma unroll
-      for (int i = 0; i < EMFN_MAXW / 4; ++i) {
-        const f32x4 v1 = a1p[i], v2 = a2p[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { z1 = fmaf(wB1[4 * i + e], v1[e], z1); z2 = fmaf(wB2[4 * i + e], v2[e], z2); }
-      }
-      const float g1 = act_sigmoid(emfn_group_sum(z1, QB) + bb1), g2 = act_sigmoid(emfn_group_sum(z2, QB) + bb2);
-      memr = g1 * memr + g2 * ch;
-      if (stB) memb[(cur ^ 1) * MP + mb] = memr;
-    }
-    lds_barrier();
-    cur ^= 1;
-  }
-
-  // ---- the heads on [h_l | h_a | h_v | mem_T]: the vector into LDS (over the recurrence's buffers, which nobody reads any
-  // more), then 8 lanes per output
-  const int KT = P.tot + M, nout = P.nheads * P.zy;
-  float* vec = lds;
-  const int m0 = P.hn[0], m1 = m0 + P.hn[1];
-  for (int k = tid; k < P.tot; k += blockDim.x) {
-    const int m = k < m0 ? 0 : (k < m1 ? 1 : 2);
-    const int km = k - (m == 0 ? 0 : (m == 1 ? m0 : m1));
-    vec[k] = P.hl[m][(int64_t)row * P.hn[m] + km];
-  }
-  if (stB) vec[P.tot + mb] = memr;
-  lds_barrier();
-  const int q8 = tid & 7;
-  for (int o = tid >> 3; o < nout; o += (int)blockDim.x >> 3) {
-    const int hd = o / P.zy, c = o - hd * P.zy;
-    const float* wr = P.wz[hd] + (int64_t)c * KT;
-    float s = 0.0f;
-    for (int k = q8; k < KT; k += 8) s = fmaf(wr[k], vec[k], s);
-    s = emfn_group_sum(s, 8);
-    if (q8 == 0) P.oz[hd][(int64_t)row * P.zy + c] = s + P.bz[hd][c];
-  }
-}
-
 // ---------------------------------------------------------------- host
 static const int kEmfnCanon[EMFN_LSTMS] = {8, 2, 20, 22, 16, 12};      // encoders h = 32 / 8 / 80, the MFN's LSTMs h = 88 / 64 / 48
-
-struct EmfnSizes { int d[3], z[3], zy, hm[3], M, win, h1, h2, H1, H2, heads; };
-
-static bool emfn_sizes(const int32_t* sz, EmfnSizes& S) {
-  if (!sz) return false;
-  for (int i = 0; i < 16; ++i)
-    if (sz[i] < 1) return false;
-  if (sz[16] != 0 && sz[16] != 1) return false;
-  for (int i = 0; i < 3; ++i) { S.d[i] = sz[i]; S.z[i] = sz[3 + i]; S.hm[i] = sz[7 + i]; }
-  S.zy = sz[6]; S.M = sz[10]; S.win = sz[11]; S.h1 = sz[12]; S.h2 = sz[13]; S.H1 = sz[14]; S.H2 = sz[15]; S.heads = sz[16];
-  return true;
-}
-
-static int emfn_pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 // the parts of the workspace, in floats, for chunks of `rows` rows
 struct EmfnWs { int64_t gates[EMFN_LSTMS], cs[3], hl[3], chat, g1p, g2p, total; };
@@ -374,12 +77,6 @@ static void emfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, EmfnWs& W) {
   for (int m = 0; m < 3; ++m) { W.cs[m] = rows * T * hp_of(S.hm[m]); W.hl[m] = up4(rows * S.hm[m]); W.total += W.cs[m] + W.hl[m]; }
   W.chat = up4(rows * T * S.M); W.g1p = up4(rows * T * S.H1); W.g2p = up4(rows * T * S.H2);
   W.total += W.chat + W.g1p + W.g2p;
-}
-
-static size_t emfn_att_lds_floats(const EmfnSizes& S, int CT) {
-  const size_t MT = 16 * (size_t)CT, LDP = MT + 4;
-  const size_t KCp = round_up(2 * (S.hm[0] + S.hm[1] + S.hm[2]), 16), hbp = round_up(std::max(S.h1, S.h2), 16);
-  return (2 * KCp + hbp) * LDP + 2 * EMFN_SPARTS * MT;
 }
 
 template <int R>
@@ -431,7 +128,7 @@ static int encode_mfn(int T, int64_t N, const int32_t* sz, const float* params, 
     if ((rc = infer_check_resident(who, S.z[i])) != MFM_OK) return rc;
     if ((rc = infer_check_resident(who, S.hm[i])) != MFM_OK) return rc;
   }
-  const int D = S.d[0] + S.d[1] + S.d[2], tot = S.hm[0] + S.hm[1] + S.hm[2], KC = 2 * tot;
+  const int D = S.d[0] + S.d[1] + S.d[2];
   const int rows = (int)gen_rows(N, max_rows);
   const int R = gen_tile_rows(EMFN_LSTMS, rows);
   int maxw = 1, threads = 64;
@@ -445,41 +142,18 @@ static int encode_mfn(int T, int64_t N, const int32_t* sz, const float* params, 
     seq_floats = std::max(seq_floats, i < 3 ? enc_lds_floats(S.z[i], R, 3, maxw) : seq_lds_floats(S.hm[i - 3], R));
   const size_t seq_lds = lds_bytes_of(seq_floats);
   if ((rc = infer_check_lds(who, seq_lds, maxw, R)) != MFM_OK) return rc;
-  // the attention chain: 32 pairs per workgroup once 16 would give every CU more than four workgroups, where the LDS allows
-  const int64_t pairs = (int64_t)T * rows;
-  int CT = ((pairs + 15) / 16 > 4L * device_cus()) ? 2 : 1;
-  if (CT == 2 && lds_bytes_of(emfn_att_lds_floats(S, 2)) > 160 * 1024) CT = 1;
-  const size_t att_lds = lds_bytes_of(emfn_att_lds_floats(S, CT));
-  if (att_lds > 160 * 1024) {
-    set_error("%s: %zu bytes of LDS per workgroup of the attention chain (cStar %d wide, hidden layers %d and %d) exceed the 160 KB of a CU",
-              who, att_lds, KC, S.h1, S.h2);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  // the memory recurrence: its four matrices in registers
-  const int QA = emfn_pow2_ge(cdiv(S.M, EMFN_MAXW)), QB = emfn_pow2_ge(cdiv(std::max(S.H1, S.H2), EMFN_MAXW));
-  const int nA = (S.H1 + S.H2) * QA, nB = S.M * QB;
-  if (QA > 16 || QB > 16 || nA > 1024 || nB > 1024) {
-    set_error("%s: memory %d / gamma hidden sizes %d, %d do not fit the register-resident memory recurrence", who, S.M, S.H1, S.H2);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  const int mem_threads = round_up(std::max(nA, nB), 64);
-  const int MP = EMFN_MAXW * QA, HP = EMFN_MAXW * QB;
-  const size_t mem_lds = lds_bytes_of(std::max(2 * MP + 2 * HP, tot + S.M));
-  if (mem_lds > 160 * 1024) {
-    set_error("%s: the label head's input of %d + %d floats does not fit the LDS of a CU", who, tot, S.M);
-    return MFM_ERR_UNSUPPORTED;
-  }
+  // the attention chain and the memory recurrence (encode_mfn_dev.h)
+  EmfnChain C;
+  if ((rc = emfn_chain_check(who, S, (int64_t)T * rows, C)) != MFM_OK) return rc;
+  EmfnAttDev& A = C.A;
+  EmfnMemDev& Mm = C.Mm;
   if ((rc = infer_check_chunk(who, rows, T, std::max(std::max(D, 4 * round_up(maxw, 16)), std::max(S.M, std::max(S.H1, S.H2))), "projection")) != MFM_OK) return rc;
 
   // ---- everything that does not depend on the chunk
   EmfnWs W;
   emfn_ws(S, T, rows, W);
   EmfnSeqDev P;
-  EmfnAttDev A;
-  EmfnMemDev Mm;
   memset(&P, 0, sizeof(P));
-  memset(&A, 0, sizeof(A));
-  memset(&Mm, 0, sizeof(Mm));
   float* w0 = ws;
   int col[EMFN_LSTMS], dd[EMFN_LSTMS];
   for (int i = 0; i < EMFN_LSTMS; ++i) {
@@ -498,19 +172,7 @@ static int encode_mfn(int T, int64_t N, const int32_t* sz, const float* params, 
   A.g1p = w0; w0 += W.g1p;
   A.g2p = w0; w0 += W.g2p;
   P.count = EMFN_LSTMS; P.T = T; P.maxw = maxw; P.heads = S.heads;
-  // att1_fc1, att1_fc2, att2_fc1, att2_fc2, then gamma1_fc1 and gamma2_fc1 (offsets 8 and 12 of the MFN's sixteen)
-  static const int att_off[6] = {0, 2, 4, 6, 8, 12};
-  for (int l = 0; l < 6; ++l) { A.w[l] = params + offs[o_att + att_off[l]]; A.b[l] = params + offs[o_att + att_off[l] + 1]; }
-  for (int m = 0; m < 3; ++m) { A.hm[m] = S.hm[m]; A.Hpm[m] = round_up(S.hm[m], 16); Mm.hn[m] = S.hm[m]; }
-  A.T = T; A.tot = tot; A.KC = KC; A.KCp = round_up(KC, 16); A.h1 = S.h1; A.h2 = S.h2; A.hbp = round_up(std::max(S.h1, S.h2), 16);
-  A.M = S.M; A.H1 = S.H1; A.H2 = S.H2;
-  Mm.g1p = A.g1p; Mm.g2p = A.g2p; Mm.chat = A.chat;
-  Mm.w1m = A.w[4] + KC; Mm.w2m = A.w[5] + KC; Mm.ldw = KC + S.M;
-  Mm.w1b = params + offs[o_att + 10]; Mm.b1b = params + offs[o_att + 11];
-  Mm.w2b = params + offs[o_att + 14]; Mm.b2b = params + offs[o_att + 15];
-  for (int hd = 0; hd < (S.heads ? 2 : 1); ++hd) { Mm.wz[hd] = params + offs[o_zy + 2 * hd]; Mm.bz[hd] = params + offs[o_zy + 2 * hd + 1]; }
-  Mm.T = T; Mm.M = S.M; Mm.H1 = S.H1; Mm.H2 = S.H2; Mm.QA = QA; Mm.QB = QB; Mm.MP = MP; Mm.HP = HP; Mm.tot = tot; Mm.zy = S.zy;
-  Mm.nheads = S.heads ? 2 : 1;
+  emfn_chain_fill(C, S, T, params, offs + o_att, offs + o_zy, S.heads ? 2 : 1);
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
@@ -526,21 +188,9 @@ static int encode_mfn(int T, int64_t N, const int32_t* sz, const float* params, 
     for (int i = 0; i < 3; ++i) { P.d[i].mu = out[i] + n0 * S.z[i]; P.d[i].lv = S.heads ? out[4 + i] + n0 * S.z[i] : nullptr; }
     rc = (R == 1) ? emfn_seq_launch<1>(P, threads, seq_lds, stream) : emfn_seq_launch<4>(P, threads, seq_lds, stream);
     if (rc != MFM_OK) return rc;
-    A.n = n;
-    const int64_t np = (int64_t)T * n;
-    if (CT == 2)
-      rc = seq_launch_kernel(encode_mfn_att_kernel<2>, "encode_mfn_att_kernel", dim3((unsigned)((np + 31) / 32)), dim3(EMFN_ATT_THREADS), att_lds, stream, nullptr, A);
-    else
-      rc = seq_launch_kernel(encode_mfn_att_kernel<1>, "encode_mfn_att_kernel", dim3((unsigned)((np + 15) / 16)), dim3(EMFN_ATT_THREADS), att_lds, stream, nullptr, A);
-    if (rc != MFM_OK) return rc;
-    Mm.n = n;
     Mm.oz[0] = out[3] + n0 * S.zy;
     Mm.oz[1] = S.heads ? out[7] + n0 * S.zy : nullptr;
-    if (mem_threads <= 512)
-      rc = seq_launch_kernel(encode_mfn_mem_kernel<512>, "encode_mfn_mem_kernel", dim3(n), dim3(mem_threads), mem_lds, stream, nullptr, Mm);
-    else
-      rc = seq_launch_kernel(encode_mfn_mem_kernel<1024>, "encode_mfn_mem_kernel", dim3(n), dim3(mem_threads), mem_lds, stream, nullptr, Mm);
-    if (rc != MFM_OK) return rc;
+    if ((rc = emfn_chain_launch<false>(C, T, n, stream)) != MFM_OK) return rc;
   }
   return MFM_OK;
 }

@@ -1,0 +1,410 @@
+// The Memory Fusion Network behind the MFN LSTMs, shared by encode_mfn.hip and zeros_mfn.hip: the attention chain
+// (encode_mfn_att_kernel) and the memory recurrence with the label head (encode_mfn_mem_kernel), the size array they are
+// described by and the host-side sizing of the two launches.  Template parameter ZC of both kernels: false, the rows of the
+// chain are the chunk's n rows (mfm_encode_mfn); true, they are the 3 n (case c, row i) of the zeroed-modality protocol, case
+// major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from the ONE row the MFN's LSTM c computes
+// on zero input (cz / hz), the other two modalities' from the real records.  Only the gather differs; the arithmetic of a row is
+// the same code.  Each .hip instantiates one value of ZC.
+#pragma once
+#include "infer_dev.h"
+
+namespace mfm {
+
+#define EMFN_LSTMS 6          // encoder l, a, v, then the MFN's lstm l, a, v
+#define EMFN_SIZES 17
+#define EMFN_ATT_THREADS 512
+#define EMFN_SPARTS 16        // threads per pair in the softmax: fixed, the sums' order must not depend on the tile width
+#define EMFN_MAXW 32          // weights per thread and matrix of the memory recurrence
+
+// ---------------------------------------------------------------- the attention chain
+struct EmfnAttDev {
+  const float* cs[3];                          // the MFN LSTMs' c records [T, n, Hp]
+  const float* cz[3];                          // ZC: the one-row c records [T, 1, Hp] of the MFN LSTMs on zero input
+  const float* w[6]; const float* b[6];        // att1_fc1, att1_fc2, att2_fc1, att2_fc2, gamma1_fc1, gamma2_fc1
+  float* chat; float* g1p; float* g2p;         // [T nv, M], [T nv, H1], [T nv, H2]; nv = n (ZC: 3 n) rows of the chain
+  int hm[3], Hpm[3];
+  int T, n, tot, KC, KCp, h1, h2, hbp, M, H1, H2;
+};
+
+// Y[o][pair] = sum_k W[o][k] X[k][pair] over the tile's 16 CT pairs: wave w takes the 16-unit output tiles w, w + waves, ...;
+// X in LDS as [Kp][LDP] (rows K .. Kp exact zeros), LDP = 16 CT + 4 (the four k a B fragment reads fall on different banks).
+// MFMA step s of chunk c multiplies k = 16 c + 4 (lane >> 4) + s on both sides: a lane's four A values are one 16-byte load of
+// its weight row (K and the row stride multiples of 4 and an aligned base; else four guarded dword loads), the next chunk's
+// while this one multiplies.  Rows beyond Nout and columns beyond K read as zeros.  epi(o, pair, value) for the lane's
+// 4 x CT results: o = 16 tile + 4 (lane >> 4) + r, pair = 16 ct + (lane & 15)
+template <int CT, class Epi>
+__device__ __forceinline__ void emfn_layer(const float* __restrict__ W, const int ldw, const int K, const int Kp, const int Nout,
+                                           const int out_tiles, const float* Xs, Epi epi) {
+  constexpr int LDP = 16 * CT + 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int col = lane & 15, q = lane >> 4;
+  const bool vec = (ldw & 3) == 0 && (K & 3) == 0 && (((uintptr_t)W) & 15) == 0;
+  const int kchunks = Kp / 16;
+  for (int ot = wave; ot < out_tiles; ot += nw) {
+    const int orow = 16 * ot + col;
+    const bool rok = orow < Nout;
+    const float* wr = W + (int64_t)min(orow, Nout - 1) * ldw;
+    auto lda = [&](const int c) {
+      const int k0 = 16 * c + 4 * q;
+      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (vec) {
+        if (rok && k0 < K) v = *reinterpret_cast<const f32x4*>(wr + k0);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (rok && k0 + i < K) v[i] = wr[k0 + i];
+      }
+      return v;
+    };
+    f32x4 acc[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 a4 = lda(0);
+    for (int c = 0; c < kchunks; ++c) {
+      const f32x4 an = lda(c + 1 < kchunks ? c + 1 : c);
+      const float* bc = Xs + (16 * c + 4 * q) * LDP + col;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[ct] = mma16x16x4(a4[s], bc[s * LDP + 16 * ct], acc[ct]);
+      }
+      a4 = an;
+    }
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) epi(16 * ot + 4 * q + r, 16 * ct + col, acc[ct][r]);
+  }
+}
+
+template <int CT, bool ZC>
+__global__ __launch_bounds__(EMFN_ATT_THREADS) void encode_mfn_att_kernel(const EmfnAttDev P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int MT = 16 * CT, LDP = MT + 4;
+  const int tid = threadIdx.x;
+  const int KC = P.KC, KCp = P.KCp, tot = P.tot;
+  const int64_t pairs = (int64_t)P.T * (ZC ? 3 : 1) * P.n, p0 = (int64_t)blockIdx.x * MT;
+  float* Xc = lds;                             // [KCp][LDP] cStar
+  float* Lg = Xc + KCp * LDP;                  // [KCp][LDP] the attention's logits, then attended
+  float* Hb = Lg + KCp * LDP;                  // [hbp][LDP] the hidden layer of att1, then of att2
+  float* red = Hb + P.hbp * LDP;               // [2][EMFN_SPARTS][MT]
+
+  // ---- cStar of the tile's pairs: k < tot from step t - 1 (zeros at t = 0), the rest from step t; unit fastest
+  const int n0 = P.hm[0], n1 = n0 + P.hm[1];
+  for (int e = tid; e < KCp * MT; e += EMFN_ATT_THREADS) {
+    const int j = e / KCp, k = e - j * KCp;
+    const int64_t p = p0 + j;
+    float v = 0.0f;
+    if (k < KC && p < pairs) {
+      const int prev = k < tot, u = prev ? k : k - tot;
+      const int m = u < n0 ? 0 : (u < n1 ? 1 : 2);
+      const int um = u - (m == 0 ? 0 : (m == 1 ? n0 : n1));
+      if constexpr (ZC) {
+        // pair p = (t, case c, row i): the zeroed modality's columns from its one-row record, the same for every row
+        const int nv = 3 * P.n;
+        const int t = (int)(p / nv), r = (int)(p - (int64_t)t * nv);
+        const int c = r / P.n, i = r - c * P.n;
+        if (!prev || t > 0)
+          v = (m == c) ? P.cz[m][(int64_t)(t - prev) * P.Hpm[m] + um] : P.cs[m][((int64_t)(t - prev) * P.n + i) * P.Hpm[m] + um];
+      } else {
+        const int t = (int)(p / P.n), i = (int)(p - (int64_t)t * P.n);
+        if (!prev || t > 0) v = P.cs[m][((int64_t)(t - prev) * P.n + i) * P.Hpm[m] + um];
+      }
+    }
+    Xc[k * LDP + j] = v;
+  }
+  lds_barrier();
+
+  // ---- att1: hidden = relu(fc1 cStar), logits = fc2 hidden
+  emfn_layer<CT>(P.w[0], KC, KC, KCp, P.h1, P.hbp / 16, Xc, [&](const int o, const int j, const float v) {
+    Hb[o * LDP + j] = o < P.h1 ? fmaxf(v + P.b[0][o], 0.0f) : 0.0f;
+  });
+  lds_barrier();
+  emfn_layer<CT>(P.w[1], P.h1, P.h1, (P.h1 + 15) / 16 * 16, KC, KCp / 16, Hb, [&](const int o, const int j, const float v) {
+    Lg[o * LDP + j] = o < KC ? v + P.b[1][o] : 0.0f;
+  });
+  lds_barrier();
+
+  // ---- attended = softmax(logits) * cStar per pair: EMFN_SPARTS threads per pair, every sum in a fixed order
+  {
+    const int j = tid % MT, part = tid / MT;
+    const bool on = tid < EMFN_SPARTS * MT;
+    float mx = -INFINITY;
+    if (on)
+      for (int k = part; k < KC; k += EMFN_SPARTS) mx = fmaxf(mx, Lg[k * LDP + j]);
+    if (on) red[part * MT + j] = mx;
+    lds_barrier();
+    if (on) {
+#pragma unroll
+      for (int s = 0; s < EMFN_SPARTS; ++s) mx = fmaxf(mx, red[s * MT + j]);
+    }
+    float sum = 0.0f;
+    if (on)
+      for (int k = part; k < KC; k += EMFN_SPARTS) {
+        const float ev = expf(Lg[k * LDP + j] - mx);
+        Lg[k * LDP + j] = ev;
+        sum += ev;
+      }
+    float* red2 = red + EMFN_SPARTS * MT;
+    if (on) red2[part * MT + j] = sum;
+    lds_barrier();
+    if (on) {
+      float tsum = red2[j];
+#pragma unroll
+      for (int s = 1; s < EMFN_SPARTS; ++s) tsum += red2[s * MT + j];
+      for (int k = part; k < KC; k += EMFN_SPARTS) Lg[k * LDP + j] = Lg[k * LDP + j] / tsum * Xc[k * LDP + j];
+    }
+  }
+  lds_barrier();
+
+  // ---- att2: cHat = tanh(fc2 relu(fc1 attended))
+  emfn_layer<CT>(P.w[2], KC, KC, KCp, P.h2, P.hbp / 16, Lg, [&](const int o, const int j, const float v) {
+    Hb[o * LDP + j] = o < P.h2 ? fmaxf(v + P.b[2][o], 0.0f) : 0.0f;
+  });
+  lds_barrier();
+  emfn_layer<CT>(P.w[3], P.h2, P.h2, (P.h2 + 15) / 16 * 16, P.M, (P.M + 15) / 16, Hb, [&](const int o, const int j, const float v) {
+    if (o < P.M && p0 + j < pairs) P.chat[(p0 + j) * P.M + o] = tanhf(v + P.b[3][o]);
+  });
+  // ---- the attended columns of gamma1_fc1 / gamma2_fc1 (their rows are KC + M wide), with the bias
+  emfn_layer<CT>(P.w[4], KC + P.M, KC, KCp, P.H1, (P.H1 + 15) / 16, Lg, [&](const int o, const int j, const float v) {
+    if (o < P.H1 && p0 + j < pairs) P.g1p[(p0 + j) * P.H1 + o] = v + P.b[4][o];
+  });
+  emfn_layer<CT>(P.w[5], KC + P.M, KC, KCp, P.H2, (P.H2 + 15) / 16, Lg, [&](const int o, const int j, const float v) {
+    if (o < P.H2 && p0 + j < pairs) P.g2p[(p0 + j) * P.H2 + o] = v + P.b[5][o];
+  });
+}
+
+// ---------------------------------------------------------------- the memory recurrence and the label head
+struct EmfnMemDev {
+  const float* g1p; const float* g2p; const float* chat;      // [T, n, H1], [T, n, H2], [T, n, M]
+  const float* w1m; const float* w2m;                          // the memory columns of gamma*_fc1, rows ldw apart
+  const float* w1b; const float* b1b; const float* w2b; const float* b2b;      // gamma*_fc2
+  const float* hl[3];                                          // the MFN LSTMs' last hidden states [n, h_m] (ZC: [nreal, h_m])
+  const float* hz[3];                                          // ZC: the last hidden state [h_m] of MFN LSTM m on zero input
+  const float* wz[2]; const float* bz[2]; float* oz[2];        // last_to_zy_fc1, last_to_logvarzy_fc1; the chunk's rows [n, zy]
+  int hn[3];
+  int T, n, M, H1, H2, QA, QB, MP, HP, ldw, tot, zy, nheads;   // n: the rows of the recurrence (ZC: 3 nreal, case major)
+  int nreal;                                                   // ZC: the chunk's rows
+};
+
+// all-reduce over groups of Q adjacent lanes, Q in {1, 2, 4, 8, 16}
+__device__ __forceinline__ float emfn_group_sum(float v, const int Q) {
+  if (Q >= 2) v += dpp_f<DPP_QUAD_XOR1>(v);
+  if (Q >= 4) v += dpp_f<DPP_QUAD_XOR2>(v);
+  if (Q >= 8) v += dpp_f<DPP_ROW_HALF_MIRROR>(v);
+  if (Q >= 16) v += dpp_f<DPP_ROW_MIRROR>(v);
+  return v;
+}
+
+// a thread's resident weights: elements [k0, k0 + 32) of one weight row, zeros beyond n; whole aligned slices as 16-byte loads
+__device__ __forceinline__ void emfn_wslice(float (&w)[EMFN_MAXW], const float* __restrict__ row, const int k0, const int n, const bool act) {
+  const float* src = row + k0;
+  if (act && k0 + EMFN_MAXW <= n && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+#pragma unroll
+    for (int i = 0; i < EMFN_MAXW / 4; ++i) {
+      const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
+      w[4 * i] = v[0]; w[4 * i + 1] = v[1]; w[4 * i + 2] = v[2]; w[4 * i + 3] = v[3];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < EMFN_MAXW; ++i) w[i] = (act && k0 + i < n) ? row[min(k0 + i, n - 1)] : 0.0f;
+  }
+}
+
+// The thread roles, the operand layout (lane q of a group owns the contiguous slice [32 q, 32 q + 32) of the reduction) and the
+// two barriers per step are those of mfn_mem_fwd_kernel (mfn_mem.hip); nothing of a step is stored
+template <int MAXT, bool ZC>
+__global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const EmfnMemDev P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int T = P.T, n = P.n, M = P.M, H1 = P.H1, H2 = P.H2, QA = P.QA, QB = P.QB, MP = P.MP, HP = P.HP;
+  float* memb = lds;                 // [2][MP]
+  float* ab = lds + 2 * MP;          // [2][HP] the relu activations of the two gates
+  const int row = blockIdx.x, tid = threadIdx.x;
+
+  // phase A: (gate, j, q): u[j] = relu(partial[t][j] + sum_k Wm[j][k] mem[k])
+  const int nA = (H1 + H2) * QA;
+  const bool actA = tid < nA;
+  const int ja = min(tid, nA - 1) / QA, qa = tid % QA;
+  const int netA = ja >= H1;
+  const int jn = netA ? ja - H1 : ja;
+  const int Hn = netA ? H2 : H1;
+  float wA[EMFN_MAXW];
+  emfn_wslice(wA, (netA ? P.w2m : P.w1m) + (int64_t)jn * P.ldw, EMFN_MAXW * qa, M, actA);
+  const float* abuf = netA ? P.g2p : P.g1p;
+  // phase B: (m, q): gamma_g[m] = sigmoid(b[m] + sum_k Wb_g[m][k] u_g[k]), both gates
+  const int nB = M * QB;
+  const bool actB = tid < nB;
+  const int mb = min(tid, nB - 1) / QB, qb = tid % QB;
+  float wB1[EMFN_MAXW], wB2[EMFN_MAXW];
+  emfn_wslice(wB1, P.w1b + (int64_t)mb * H1, EMFN_MAXW * qb, H1, actB);
+  emfn_wslice(wB2, P.w2b + (int64_t)mb * H2, EMFN_MAXW * qb, H2, actB);
+  const float bb1 = P.b1b[mb], bb2 = P.b2b[mb];
+
+  for (int i = tid; i < 2 * MP + 2 * HP; i += blockDim.x) lds[i] = 0.0f;
+  float memr = 0.0f;                              // mem[mb], the same in every lane of the phase-B group
+  const int64_t arow = (int64_t)row * Hn + jn, mrow = (int64_t)row * M + mb;
+  float att_n = abuf[arow], ch_n = P.chat[mrow];
+  lds_barrier();
+  const bool stA = actA && qa == 0, stB = actB && qb == 0;
+  int cur = 0;
+  for (int t = 0; t < T; ++t) {
+    const float att = att_n, ch = ch_n;
+    const int tn = min(t + 1, T - 1);
+    att_n = abuf[(int64_t)tn * n * Hn + arow];     // unconditional prefetch (clamped at the tail)
+    ch_n = P.chat[(int64_t)tn * n * M + mrow];
+    {
+      const f32x4* mp = reinterpret_cast<const f32x4*>(memb + cur * MP + EMFN_MAXW * qa);
+      float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+      for (int i = 0; i < EMFN_MAXW / 4; ++i) {
+        const f32x4 v = mp[i];
+        s0 = fmaf(wA[4 * i], v[0], s0); s1 = fmaf(wA[4 * i + 1], v[1], s1);
+        s0 = fmaf(wA[4 * i + 2], v[2], s0); s1 = fmaf(wA[4 * i + 3], v[3], s1);
+      }
+      const float u = fmaxf(emfn_group_sum(s0 + s1, QA) + att, 0.0f);
+      if (stA) ab[netA ? HP + jn : jn] = u;
+    }
+    lds_barrier();
+    {
+      const f32x4* a1p = reinterpret_cast<const f32x4*>(ab + EMFN_MAXW * qb);
+      const f32x4* a2p = reinterpret_cast<const f32x4*>(ab + HP + EMFN_MAXW * qb);
+      float z1 = 0.0f, z2 = 0.0f;
+#pragma unroll
+      for (int i = 0; i < EMFN_MAXW / 4; ++i) {
+        const f32x4 v1 = a1p[i], v2 = a2p[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { z1 = fmaf(wB1[4 * i + e], v1[e], z1); z2 = fmaf(wB2[4 * i + e], v2[e], z2); }
+      }
+      const float g1 = act_sigmoid(emfn_group_sum(z1, QB) + bb1), g2 = act_sigmoid(emfn_group_sum(z2, QB) + bb2);
+      memr = g1 * memr + g2 * ch;
+      if (stB) memb[(cur ^ 1) * MP + mb] = memr;
+    }
+    lds_barrier();
+    cur ^= 1;
+  }
+
+  // ---- the heads on [h_l | h_a | h_v | mem_T]: the vector into LDS (over the recurrence's buffers, which nobody reads any
+  // more), then 8 lanes per output
+  const int KT = P.tot + M, nout = P.nheads * P.zy;
+  float* vec = lds;
+  const int m0 = P.hn[0], m1 = m0 + P.hn[1];
+  for (int k = tid; k < P.tot; k += blockDim.x) {
+    const int m = k < m0 ? 0 : (k < m1 ? 1 : 2);
+    const int km = k - (m == 0 ? 0 : (m == 1 ? m0 : m1));
+    if constexpr (ZC) {
+      const int c = row / P.nreal, i = row - c * P.nreal;      // row = (case c, row i): h_c is the zero row's
+      vec[k] = (m == c) ? P.hz[m][km] : P.hl[m][(int64_t)i * P.hn[m] + km];
+    } else {
+      vec[k] = P.hl[m][(int64_t)row * P.hn[m] + km];
+    }
+  }
+  if (stB) vec[P.tot + mb] = memr;
+  lds_barrier();
+  const int q8 = tid & 7;
+  for (int o = tid >> 3; o < nout; o += (int)blockDim.x >> 3) {
+    const int hd = o / P.zy, c = o - hd * P.zy;
+    const float* wr = P.wz[hd] + (int64_t)c * KT;
+    float s = 0.0f;
+    for (int k = q8; k < KT; k += 8) s = fmaf(wr[k], vec[k], s);
+    s = emfn_group_sum(s, 8);
+    if (q8 == 0) P.oz[hd][(int64_t)row * P.zy + c] = s + P.bz[hd][c];
+  }
+}
+
+struct EmfnSizes { int d[3], z[3], zy, hm[3], M, win, h1, h2, H1, H2, heads; };
+
+static bool emfn_sizes(const int32_t* sz, EmfnSizes& S) {
+  if (!sz) return false;
+  for (int i = 0; i < 16; ++i)
+    if (sz[i] < 1) return false;
+  if (sz[16] != 0 && sz[16] != 1) return false;
+  for (int i = 0; i < 3; ++i) { S.d[i] = sz[i]; S.z[i] = sz[3 + i]; S.hm[i] = sz[7 + i]; }
+  S.zy = sz[6]; S.M = sz[10]; S.win = sz[11]; S.h1 = sz[12]; S.h2 = sz[13]; S.H1 = sz[14]; S.H2 = sz[15]; S.heads = sz[16];
+  return true;
+}
+
+static int emfn_pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+
+static size_t emfn_att_lds_floats(const EmfnSizes& S, int CT) {
+  const size_t MT = 16 * (size_t)CT, LDP = MT + 4;
+  const size_t KCp = round_up(2 * (S.hm[0] + S.hm[1] + S.hm[2]), 16), hbp = round_up(std::max(S.h1, S.h2), 16);
+  return (2 * KCp + hbp) * LDP + 2 * EMFN_SPARTS * MT;
+}
+
+// ---------------------------------------------------------------- host: the two launches behind the MFN's LSTMs
+struct EmfnChain { EmfnAttDev A; EmfnMemDev Mm; int CT, mem_threads; size_t att_lds, mem_lds; };
+
+// what the two kernels do not cover (MFM_ERR_UNSUPPORTED with the size in the error text), and their sizing into a zeroed C;
+// pairs: the (step, row) pairs of a full chunk's attention chain
+static int emfn_chain_check(const char* who, const EmfnSizes& S, int64_t pairs, EmfnChain& C) {
+  memset(&C, 0, sizeof(C));
+  const int tot = S.hm[0] + S.hm[1] + S.hm[2], KC = 2 * tot;
+  // the attention chain: 32 pairs per workgroup once 16 would give every CU more than four workgroups, where the LDS allows
+  C.CT = ((pairs + 15) / 16 > 4L * device_cus()) ? 2 : 1;
+  if (C.CT == 2 && lds_bytes_of(emfn_att_lds_floats(S, 2)) > 160 * 1024) C.CT = 1;
+  C.att_lds = lds_bytes_of(emfn_att_lds_floats(S, C.CT));
+  if (C.att_lds > 160 * 1024) {
+    set_error("%s: %zu bytes of LDS per workgroup of the attention chain (cStar %d wide, hidden layers %d and %d) exceed the 160 KB of a CU",
+              who, C.att_lds, KC, S.h1, S.h2);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  // the memory recurrence: its four matrices in registers
+  const int QA = emfn_pow2_ge(cdiv(S.M, EMFN_MAXW)), QB = emfn_pow2_ge(cdiv(std::max(S.H1, S.H2), EMFN_MAXW));
+  const int nA = (S.H1 + S.H2) * QA, nB = S.M * QB;
+  if (QA > 16 || QB > 16 || nA > 1024 || nB > 1024) {
+    set_error("%s: memory %d / gamma hidden sizes %d, %d do not fit the register-resident memory recurrence", who, S.M, S.H1, S.H2);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  C.mem_threads = round_up(std::max(nA, nB), 64);
+  const int MP = EMFN_MAXW * QA, HP = EMFN_MAXW * QB;
+  C.mem_lds = lds_bytes_of(std::max(2 * MP + 2 * HP, tot + S.M));
+  if (C.mem_lds > 160 * 1024) {
+    set_error("%s: the label head's input of %d + %d floats does not fit the LDS of a CU", who, tot, S.M);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  C.Mm.QA = QA; C.Mm.QB = QB; C.Mm.MP = MP; C.Mm.HP = HP;
+  return MFM_OK;
+}
+
+// sizes and parameters of the two launches: att, the sixteen offsets of the MFN's attention and gamma networks; zyo, those of
+// the label head(s).  The caller sets the records (A.cs / cz, Mm.hl / hz), the chain's buffers (chat, g1p, g2p) and Mm.oz
+static void emfn_chain_fill(EmfnChain& C, const EmfnSizes& S, int T, const float* params, const int64_t* att, const int64_t* zyo, int nheads) {
+  EmfnAttDev& A = C.A;
+  EmfnMemDev& Mm = C.Mm;
+  const int tot = S.hm[0] + S.hm[1] + S.hm[2], KC = 2 * tot;
+  // att1_fc1, att1_fc2, att2_fc1, att2_fc2, then gamma1_fc1 and gamma2_fc1 (offsets 8 and 12 of the MFN's sixteen)
+  static const int att_off[6] = {0, 2, 4, 6, 8, 12};
+  for (int l = 0; l < 6; ++l) { A.w[l] = params + att[att_off[l]]; A.b[l] = params + att[att_off[l] + 1]; }
+  for (int m = 0; m < 3; ++m) { A.hm[m] = S.hm[m]; A.Hpm[m] = round_up(S.hm[m], 16); Mm.hn[m] = S.hm[m]; }
+  A.T = T; A.tot = tot; A.KC = KC; A.KCp = round_up(KC, 16); A.h1 = S.h1; A.h2 = S.h2; A.hbp = round_up(std::max(S.h1, S.h2), 16);
+  A.M = S.M; A.H1 = S.H1; A.H2 = S.H2;
+  Mm.w1m = A.w[4] + KC; Mm.w2m = A.w[5] + KC; Mm.ldw = KC + S.M;
+  Mm.w1b = params + att[10]; Mm.b1b = params + att[11];
+  Mm.w2b = params + att[14]; Mm.b2b = params + att[15];
+  for (int hd = 0; hd < nheads; ++hd) { Mm.wz[hd] = params + zyo[2 * hd]; Mm.bz[hd] = params + zyo[2 * hd + 1]; }
+  Mm.T = T; Mm.M = S.M; Mm.H1 = S.H1; Mm.H2 = S.H2; Mm.tot = tot; Mm.zy = S.zy;
+  Mm.nheads = nheads;
+}
+
+// the two launches on a chunk of n rows (ZC: the 3 n rows (case, row) behind them)
+template <bool ZC>
+static int emfn_chain_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
+  EmfnAttDev& A = C.A;
+  EmfnMemDev& Mm = C.Mm;
+  const int nv = (ZC ? 3 : 1) * n;
+  A.n = n;
+  Mm.g1p = A.g1p; Mm.g2p = A.g2p; Mm.chat = A.chat;
+  const int64_t np = (int64_t)T * nv;
+  int rc;
+  if (C.CT == 2)
+    rc = seq_launch_kernel(encode_mfn_att_kernel<2, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 31) / 32)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
+  else
+    rc = seq_launch_kernel(encode_mfn_att_kernel<1, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 15) / 16)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
+  if (rc != MFM_OK) return rc;
+  Mm.n = nv; Mm.nreal = n;
+  if (C.mem_threads <= 512)
+    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+}
+
+}  // namespace mfm

@@ -118,6 +118,21 @@ __device__ __forceinline__ double label_loss_part(const float* y_hat, const void
   return disc;
 }
 
+// ---------------------------------------------------------------- the finish of the zeroed-modality protocol (zeros.hip; zeros_mfn.hip launches it too)
+#define ZER_CASES INFER_DEC
+#define ZER_ACC (2 * ZER_CASES)        // squared errors l, a, v; label-loss sums of the cases no l, no a, no v
+struct ZerFinishDev {
+  const float* part[ZER_CASES]; int npart[ZER_CASES];      // this chunk's squared-error partials
+  const float* y_hat[ZER_CASES]; const void* y;            // this chunk's [n, od] per case and its labels (null: no label loss)
+  double* acc;                                             // ZER_ACC running sums over the chunks so far
+  float* gen; float* disc;                                 // 3 floats each; disc null without labels
+  double inv_gen[ZER_CASES], inv_disc;                     // 1 / (T N d_m), 1 / (N od) (L1) or 1 / N (CE): the WHOLE split
+  int n, od, loss_kind, first, last;
+};
+// zeros_finish_kernel, one workgroup: the chunk's sums in a fixed order in fp64 into acc (the first chunk stores, the others
+// add); behind the last chunk gen and disc.  The kernel stays in zeros.hip alone
+int zeros_finish_launch(const ZerFinishDev& Q, hipStream_t stream);
+
 // ---------------------------------------------------------------- the encoders' launch (generate.hip)
 #define INFER_ENC 4
 struct EncOne {

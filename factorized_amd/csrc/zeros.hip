@@ -28,9 +28,7 @@
 
 namespace mfm {
 
-#define ZER_CASES INFER_DEC
 #define ZER_LSTMS (2 * ZER_CASES)      // the ef encoder once per case, then the three zeroed encoders
-#define ZER_ACC (2 * ZER_CASES)        // squared errors l, a, v; label-loss sums of the cases no l, no a, no v
 
 struct ZerOne {
   SeqDev seq;                                  // gates (read only), w_hh, h, Hp, hk4
@@ -105,15 +103,6 @@ __global__ __launch_bounds__(256) void zeros_gates_kernel(const ZerGatesDev G) {
   }
 }
 
-struct ZerFinishDev {
-  const float* part[ZER_CASES]; int npart[ZER_CASES];      // this chunk's squared-error partials
-  const float* y_hat[ZER_CASES]; const void* y;            // this chunk's [n, od] per case and its labels (null: no label loss)
-  double* acc;                                             // ZER_ACC running sums over the chunks so far
-  float* gen; float* disc;                                 // 3 floats each; disc null without labels
-  double inv_gen[ZER_CASES], inv_disc;                     // 1 / (T N d_m), 1 / (N od) (L1) or 1 / N (CE): the WHOLE split
-  int n, od, loss_kind, first, last;
-};
-
 __global__ __launch_bounds__(OBJ_THREADS) void zeros_finish_kernel(const ZerFinishDev P) {
   __shared__ double red[OBJ_THREADS];
   const int tid = threadIdx.x;
@@ -144,6 +133,10 @@ __global__ __launch_bounds__(OBJ_THREADS) void zeros_finish_kernel(const ZerFini
 }
 
 // ---------------------------------------------------------------- host
+int zeros_finish_launch(const ZerFinishDev& Q, hipStream_t stream) {
+  return seq_launch_kernel(zeros_finish_kernel, "zeros_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q);
+}
+
 static const int kZerEnc[4] = {8, 2, 20, 30};      // the canonical sizes: encoders l / a / v h = 32 / 8 / 80, ef h = 120
 
 // the workspace, in this order (every part a multiple of 4 floats): the chunk's three partial projections and three gate sets
@@ -310,8 +303,7 @@ static int predict_zeros_klef(int T, int64_t N, const int32_t* sz, const float* 
     for (int c = 0; c < ZER_CASES; ++c) Q.y_hat[c] = PD.d[c].y_hat;
     Q.y = labels_at(y, loss_kind, n0, od);
     Q.n = n; Q.first = first; Q.last = n0 + n == N;
-    if ((rc = seq_launch_kernel(zeros_finish_kernel, "zeros_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q)) != MFM_OK)
-      return rc;
+    if ((rc = zeros_finish_launch(Q, stream)) != MFM_OK) return rc;
   }
   return MFM_OK;
 }

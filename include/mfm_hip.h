@@ -656,6 +656,56 @@ int mfm_predict_zeros_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13
                            float* gen /*3*/, float* disc /*3, or NULL*/, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * mfm_predict_zeros_mfn (csrc/zeros_mfn.hip): the same protocol, with the same results y_hat[c], gen[c], disc[c] and under the
+ * same contract, for MFM_KL and MFM, whose label factor comes from the Memory Fusion Network (mfm_model.py:140-199, :723-743).
+ * Only what the results depend on runs: the MFN's three LSTMs on the real columns of x ONCE for the three cases (they are
+ * independent of each other); the MFN LSTM and the encoder of a zeroed modality on the all-zero row, one row of work each;
+ * decoder c of case c; the classifier.  The present modalities' own encoders reach none of the results and do not run; no
+ * log-variance head, no KLD and no MMD is computed.  heads = 1 (MFM_KL): z_c^0 = last_to_z{c}_fc1(encoder_c(0)); heads = 0
+ * (MFM): z_c^0 = encoder_c(0), its fc1 output.  Per row chunk of n rows: ONE grouped fp32 GEMM for the three input projections;
+ * ONE launch of (MFN LSTM, row tile) workgroups that store the cell states and the last hidden state, which in the first chunk
+ * carries six more one-row workgroups on the constant gates b_ih + b_hh (a small launch fills them in front) -- the three MFN
+ * LSTMs on zero input (a one-row cell-state record and last h) and the three encoders on zero input (fc1, the mean head with
+ * heads: z_c^0); the attention chain of mfm_encode_mfn over the 3 * T * n triples (t, case, row), cStar gathered with modality
+ * c's columns from the one-row record; its memory recurrence per (case, row) ending with last_to_zy_fc1 on [h_l | h_a | h_v |
+ * mem], h_c the zero row's -> zy_c; then the launches of mfm_predict_zeros_klef from the decoders on: decoder c on (zy_c,
+ * z_c^0) with the classifier -> y_hat[c], the fused fc1 / squared-error launch against the real x, and the fp64 finish.
+ *   sizes    host, 23: the 17 of mfm_encode_mfn (d_l, d_a, d_v; zl, za, zv; zy; h_l, h_a, h_v; memsize; windowsize; the hidden
+ *            widths of att1, att2, gamma1, gamma2; heads), then fl, fa, fv, fy, output_dim, loss_kind (0 = L1, 1 = cross entropy)
+ *   offsets  host, element offsets into the flat fp32 parameter buffer `params`: the 62 (heads = 1) or 48 (heads = 0) of
+ *            mfm_encode_mfn in its order (the logvar heads' are not read), then the 38 of mfm_decode_factors: 100 or 86
+ *   x, y, y_hat, gen, disc, max_rows   as mfm_predict_zeros_klef
+ *   workspace mfm_predict_zeros_mfn_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary.  With
+ *            rows = min(N, max_rows), Hp(h) = round_up(h, 16), up4(v) = round_up(v, 4):
+ *              max(rows * T * 4 * (Hp(h_l) + Hp(h_a) + Hp(h_v)),                              the x-projections, and in their
+ *                  rows * T * (Hp(fy + fl) + Hp(fy + fa) + Hp(fy + fv)))                      place the decoders' stored h
+ *            + rows * T * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                       the MFN LSTMs' cell states
+ *            + up4(rows * h_l) + up4(rows * h_a) + up4(rows * h_v)                            their last hidden states
+ *            + up4(3 * rows * T * memsize) + up4(3 * rows * T * gamma1) + up4(3 * rows * T * gamma2)    cHat, the gamma partials
+ *            + T * 4 * (Hp(h_l) + Hp(h_a) + Hp(h_v) + Hp(zl) + Hp(za) + Hp(zv))               the six constant gate sets
+ *            + T * (Hp(h_l) + Hp(h_a) + Hp(h_v)) + up4(h_l) + up4(h_a) + up4(h_v)             the one-row records and last h
+ *            + up4(rows * zl) + up4(rows * za) + up4(rows * zv)                               z_c^0, one row per chunk row
+ *            + up4(3 * rows * zy)                                                             zy of the three cases
+ *            + up4(sum over m of ceil(T * rows / 64) * ceil(d_m / 64))                        the squared-error partials
+ *            + 12                                                                             six fp64 accumulators
+ * Determinism: no float atomics; bit-identical from run to run for a given (T, N, max_rows).  The recurrence launch and the
+ * decoders' run on one-row tiles while 3 * rows < 6 * CUs and on four-row tiles from there (mfm_predict_zeros_mfn_tile_rows
+ * tells which; host only, -1 for bad arguments); the attention chain takes 16 or 32 triples per workgroup, a triple's
+ * arithmetic the same in both.  For a fixed tile-row form y_hat is bit-identical for every row chunking; gen and disc are fp64
+ * sums in a fixed order per chunking, over the counts of the WHOLE split.
+ * Nothing outside the workspace, y_hat, gen and disc is written.  T < 1, N < 1, a null pointer or max_rows < 0 return MFM_ERR_ARG
+ * before anything touches the GPU.  MFM_ERR_UNSUPPORTED with the size in the error text, nothing enqueued: what mfm_encode_mfn
+ * refuses (an h_dims entry or an encoder hidden size above 128, a windowsize other than 2, attention widths beyond the LDS,
+ * memsize or gamma widths beyond the register-resident memory recurrence) and what mfm_decode_factors refuses (a decoder with
+ * fy + f_m > 128, more LDS than a CU has): run mfm_plan_forward(train = 0) on zeroed copies instead.  Stream-ordered, no host
+ * synchronisation, legal inside a stream capture. */
+int64_t mfm_predict_zeros_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_zeros_mfn_tile_rows(int64_t N, int64_t max_rows);
+int mfm_predict_zeros_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, const float* params, const int64_t* offsets /*host, 100 or 86*/,
+                          const float* x, const void* y /*or NULL*/, float* workspace, float* y_hat /*[3, N, output_dim]*/,
+                          float* gen /*3*/, float* disc /*3, or NULL*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The gradient-based interpretation of the factorized model (csrc/influence.hip): how strongly the factors drive the generation
  * of each modality at each time step.  For decoder m = l, a, v with embedding e = [fy | f_m] of width h = fy + f_m
  * (mfm_model.py:644-656, decoderLSTM :64-91), from the deterministic eval computation (dropout the identity),
