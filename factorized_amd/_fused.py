@@ -182,9 +182,11 @@ class _FusedEngineMixin:
         (mfm_mosi.py:319-324, :724-726, :826-845), loss = disc + lda_xl gen_l + lda_xa gen_a + lda_xv gen_v + lda_mmd reg with the
         config's lambdas (default 1) -- always the deterministic eval computation (dropout off, z = the mean heads),
         `self.training` left as found, without autograd, lazy outputs or a host read; `.loss` is accepted as is by
-        KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  MFM_KL_EF: engine.objective (no plan, x_hat never written);
-        the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must survive it).
-        MFM_KL / MFM, and sizes the fused entry refuses: the fused eval forward's loss slots."""
+        KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  Every class: engine.objective (no plan, x_hat never written --
+        MFM_KL_EF through mfm_objective_klef, MFM_KL / MFM through mfm_objective_mfn, the Memory Fusion Network on chip; MFM's
+        reg is the deterministic value-only MMD over all N^2 pairs against `self.mmd_gauss` when set, else against a fresh N(0, 1)
+        sample per call); the returned tensors are REUSED: the next call with the same shape overwrites them (clone what must
+        survive it).  Sizes the fused entry refuses: the fused eval forward's loss slots."""
         eng, x = self._infer_args(x)
         with torch.no_grad():
             return eng.objective(x, y)

@@ -4,7 +4,8 @@ training workspace, the split walked in chunks of at most `max_rows` rows (defau
 one host path (encode has two library entries behind it: mfm_encode_klef for variant "kl_ef", mfm_encode_mfn for the variants
 "kl" and "mmd", whose label factor comes from the Memory Fusion Network; the latter keeps its state in
 `engine._encode_mfn_bufs` / `engine._encode_mfn_refused`; predict_zeros likewise: mfm_predict_zeros_klef, and
-mfm_predict_zeros_mfn with its state in `engine._zeros_mfn_bufs` / `engine._zeros_mfn_refused`): the split
+mfm_predict_zeros_mfn with its state in `engine._zeros_mfn_bufs` / `engine._zeros_mfn_refused`; objective likewise:
+mfm_objective_klef, and mfm_objective_mfn with its state in `engine._objective_mfn_bufs` / `engine._objective_mfn_refused`): the split
 validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
@@ -68,7 +69,7 @@ def _lin(*names):
 _ENTRIES = {n: ("_%s_bufs" % n, "_%s_refused" % n, f) for n, f in (
     ("predict", "mfm_predict_klef"), ("encode", "mfm_encode_klef"), ("decode", "mfm_decode_factors"),
     ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"),
-    ("encode_mfn", "mfm_encode_mfn"), ("zeros_mfn", "mfm_predict_zeros_mfn"))}
+    ("encode_mfn", "mfm_encode_mfn"), ("zeros_mfn", "mfm_predict_zeros_mfn"), ("objective_mfn", "mfm_objective_mfn"))}
 
 
 def influence_factors_torch(decoders, fy, fms, T):
@@ -391,7 +392,10 @@ class InferMixin:
 
     # ------------------------------------------------------------------ the full validation objective
     def objective_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace objective() keeps for a [T, N, D] split (mfm_objective_klef_workspace_floats)"""
+        """floats of workspace objective() keeps for a [T, N, D] split (mfm_objective_klef_workspace_floats; variants "kl" and
+        "mmd": mfm_objective_mfn_workspace_floats)"""
+        if self.variant != "kl_ef":
+            return int(_lib.lib().mfm_objective_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_objective_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
 
     def objective(self, x, y, *, max_rows=None):
@@ -402,12 +406,22 @@ class InferMixin:
         on the device.
 
         Variant "kl_ef": mfm_objective_klef -- the launches of encode(), the recurrence launch of decode(), then the decoders'
-        fc1 fused with the squared error (x_hat is never written) and one small finishing launch.  Workspace and the [6] result
-        are reused and a refusal falls back as the module docstring says.  Other variants: the same namedtuple from
-        forward(train=False, handover=False), the total formed on the device."""
+        fc1 fused with the squared error (x_hat is never written) and one small finishing launch.  Variants "kl" and "mmd":
+        mfm_objective_mfn -- the launches of encode() for these classes (the Memory Fusion Network on chip), then the same
+        decoder, squared-error and finishing launches; its state is a cache of its own, `_objective_mfn_bufs`.  For "mmd" reg
+        is the sum of the four maximum mean discrepancies over all N^2 pairs of the split against a Gaussian sample [N, zl + za
+        + zv + zy]: `self.gauss` when set, else a buffer of the entry's state refilled with .normal_() on every call; the
+        value-only MMD launch writes one partial per workgroup and a last launch adds them in fp64 (no float atomics: reg is
+        bit-identical from run to run for a given sample).  Workspace and the [6] result are reused and a refusal falls back as
+        the module docstring says (remembered for an h_dims entry, an encoder or a decoder above 128): the same namedtuple
+        from forward(train=False, handover=False), the total formed on the device."""
         T, N, D = self._check_split(x, y, need_labels="objective")
         cap = self._row_cap(max_rows)
         c = self.cfg
+        if self.variant != "kl_ef":
+            st = self._objective_mfn(x, y, T, N, cap)
+            if st is not None:
+                return st[2]
 
         def build():
             sizes = self._objective_sizes()
@@ -429,6 +443,37 @@ class InferMixin:
         out[1:6] = l[0:5]
         out[0] = l[0] + c["lda_xl"] * l[1] + c["lda_xa"] * l[2] + c["lda_xv"] * l[3] + c["lda_mmd"] * l[4]
         return Objective(*out.unbind(0))
+
+    def _objective_mfn(self, x, y, T, N, cap):
+        """objective() of the variants "kl" and "mmd" through mfm_objective_mfn -> the entry's state, or None: refused.  A given
+        `self.gauss` is checked here in front of the entry, so also when the entry is remembered as refused: a sample of the
+        wrong shape, dtype or device raises MfmError before the fallback's plan would trip over it with an assert"""
+        c = self.cfg
+        mmd = self.variant == "mmd"
+        gl = c["zl_size"] + c["za_size"] + c["zv_size"] + c["zy_size"]
+        given = self.gauss if mmd else None
+        if given is not None and not (torch.is_tensor(given) and given.is_cuda and given.dtype == torch.float32 and given.is_contiguous()
+                                      and tuple(given.shape) == (N, gl) and given.device == x.device):
+            raise _lib.MfmError("objective: gauss must be a contiguous float32 CUDA tensor [%d, %d] on %s; got %s" % (
+                N, gl, x.device, "%s %s %s" % (tuple(given.shape), given.dtype, given.device) if torch.is_tensor(given) else type(given)))
+
+        def build():
+            sizes = self._zeros_mfn_sizes()
+            nws = int(_lib.lib().mfm_objective_mfn_workspace_floats(T, N, sizes, cap))
+            out = torch.zeros(6, dtype=torch.float32, device=self.device)
+            return (self._empty(nws), out, Objective(*out.unbind(0)), sizes,
+                    self._offsets(self._ENCODE_MFN_TENSORS[self.variant] + self._DECODE_TENSORS),
+                    (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"]), self._empty(N, gl) if mmd else None)
+
+        def call(fn, st):
+            ws, out, _, sizes, offs, lda, drawn = st
+            g = given
+            if mmd and g is None:
+                g = drawn.normal_()
+            return fn(T, N, sizes, lda, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(g), _ptr(ws), _ptr(out), cap, _stream())
+
+        hidden = tuple(c["h_dims"]) + (c["zl_size"], c["za_size"], c["zv_size"]) + self._hidden_sizes()[1:]
+        return self._run_fused("objective_mfn", (T, N, cap), build, call, hidden)
 
     # ------------------------------------------------------------------ the zeroed-modality test protocol
     def _zeros_mfn_sizes(self):

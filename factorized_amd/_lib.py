@@ -211,6 +211,11 @@ _SIGS = {
     "mfm_objective_klef_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
     "mfm_objective_klef": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p,
                                      C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mfm_objective_mfn_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
+    "mfm_objective_mfn_tile_rows": (C.c_int, [C.c_int64, C.c_int64]),
+    "mfm_objective_mfn": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p,
+                                    C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
     "mfm_predict_zeros_klef_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
     "mfm_predict_zeros_klef": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -4,7 +4,10 @@
 // chain are the chunk's n rows (mfm_encode_mfn); true, they are the 3 n (case c, row i) of the zeroed-modality protocol, case
 // major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from the ONE row the MFN's LSTM c computes
 // on zero input (cz / hz), the other two modalities' from the real records.  Only the gather differs; the arithmetic of a row is
-// the same code.  Each .hip instantiates one value of ZC.
+// the same code.  encode_mfn.hip and objective_mfn.hip instantiate ZC = false, zeros_mfn.hip ZC = true.
+// At the end of the file: the launch in front of the chain as mfm_encode_mfn runs it -- the six recurrences (encoder l, a, v with
+// their heads, the MFN's LSTMs with their cell-state records) in one launch, encode_mfn_seq_kernel, its workspace parts and its
+// launcher; encode_mfn_front.h walks them chunk by chunk for mfm_encode_mfn and mfm_objective_mfn (objective_mfn.hip).
 #pragma once
 #include "infer_dev.h"
 
@@ -405,6 +408,90 @@ static int emfn_chain_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
   if (C.mem_threads <= 512)
     return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
   return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+}
+
+// ---------------------------------------------------------------- the six recurrences (mfm_encode_mfn; mfm_objective_mfn launches them too)
+struct EmfnOne {
+  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4; an MFN LSTM: cs [T, n, Hp]
+  const float* w[3]; const float* b[3];        // an encoder: fc1, the mean head, the logvar head
+  float* mu; float* lv;                        // an encoder: this chunk's rows [n, h] (no heads: mu takes fc1's output)
+  float* h_last;                               // an MFN LSTM: this chunk's last hidden states [n, h]
+  int block_begin;
+};
+struct EmfnSeqDev { EmfnOne d[EMFN_LSTMS]; int count, T, n, maxw, heads; };
+
+// MFN0: the LSTM at index 0 is one of the MFN's (the launches of one LSTM each); indices 3 .. 5 always are
+template <int R, bool MFN0, int K0, int K1, int K2, int K3, int K4, int K5>
+__global__ __launch_bounds__(1024) void encode_mfn_seq_kernel(const EmfnSeqDev P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, bid = blockIdx.x;
+  MFM_SEQ_BLOCK_LSTM(P, bid, di)
+  const EmfnOne& E = P.d[di];
+  const int tile = bid - E.block_begin, b0 = tile * R;
+  const int h = E.seq.h;
+  const float* hT = nullptr;
+  if ((MFN0 && di == 0) || di >= 3) {
+    if constexpr (MFN0) { MFM_TUPLE_ONE(0, K0, (hT = small_fwd_body<KQ, R, false, false, false, false, true>(E.seq, P.T, P.n, tile, lds))) }
+    MFM_TUPLE_ONE(3, K3, (hT = small_fwd_body<KQ, R, false, false, false, false, true>(E.seq, P.T, P.n, tile, lds)))
+    MFM_TUPLE_ONE(4, K4, (hT = small_fwd_body<KQ, R, false, false, false, false, true>(E.seq, P.T, P.n, tile, lds)))
+    MFM_TUPLE_ONE(5, K5, (hT = small_fwd_body<KQ, R, false, false, false, false, true>(E.seq, P.T, P.n, tile, lds)))
+    store_rows<R>(hT, E.h_last, h, b0, P.n, tid);
+    return;
+  }
+  if constexpr (!MFN0) { MFM_TUPLE_ONE(0, K0, (hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds))) }
+  MFM_TUPLE_ONE(1, K1, (hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds)))
+  MFM_TUPLE_ONE(2, K2, (hT = small_fwd_body<KQ, R, false, false, false>(E.seq, P.T, P.n, tile, lds)))
+  // the two h buffers stay where they are; fc1's output and the two heads' behind them ([maxw][R] each)
+  float* act0 = lds + 2 * E.seq.Hp * R;
+  float* act1 = act0 + P.maxw * R;
+  float* act2 = act1 + P.maxw * R;
+  dense_rows<R>(E.w[0], E.b[0], h, h, hT, act0, false);
+  if (!P.heads) {
+    store_rows<R>(act0, E.mu, h, b0, P.n, tid);
+    return;
+  }
+  dense_rows<R>(E.w[1], E.b[1], h, h, act0, act1, false);
+  dense_rows<R>(E.w[2], E.b[2], h, h, act0, act2, false);
+  store_rows<R>(act1, E.mu, h, b0, P.n, tid);
+  store_rows<R>(act2, E.lv, h, b0, P.n, tid);
+}
+
+// ---------------------------------------------------------------- host: the six recurrences
+static const int kEmfnCanon[EMFN_LSTMS] = {8, 2, 20, 22, 16, 12};      // encoders h = 32 / 8 / 80, the MFN's LSTMs h = 88 / 64 / 48
+
+// the parts of the workspace, in floats, for chunks of `rows` rows
+struct EmfnWs { int64_t gates[EMFN_LSTMS], cs[3], hl[3], chat, g1p, g2p, total; };
+static void emfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, EmfnWs& W) {
+  W.total = 0;
+  for (int i = 0; i < EMFN_LSTMS; ++i) { W.gates[i] = rows * T * 4 * hp_of(i < 3 ? S.z[i] : S.hm[i - 3]); W.total += W.gates[i]; }
+  for (int m = 0; m < 3; ++m) { W.cs[m] = rows * T * hp_of(S.hm[m]); W.hl[m] = up4(rows * S.hm[m]); W.total += W.cs[m] + W.hl[m]; }
+  W.chat = up4(rows * T * S.M); W.g1p = up4(rows * T * S.H1); W.g2p = up4(rows * T * S.H2);
+  W.total += W.chat + W.g1p + W.g2p;
+}
+
+// the launch(es) of the six recurrences on a chunk of P.n rows: P.d[0 .. EMFN_LSTMS) filled but for block_begin
+template <int R>
+static int emfn_seq_launch(const char* who, EmfnSeqDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
+  static const char* name = "encode_mfn_seq_kernel";
+  bool canon = true;
+  for (int i = 0; i < EMFN_LSTMS; ++i) canon = canon && P.d[i].seq.hk4 == kEmfnCanon[i];
+  const int tiles = cdiv(P.n, R);
+  if (canon) {
+    for (int i = 0; i < EMFN_LSTMS; ++i) P.d[i].block_begin = i * tiles;
+    return seq_launch_kernel(encode_mfn_seq_kernel<R, false, 8, 2, 20, 22, 16, 12>, name, dim3(EMFN_LSTMS * tiles), dim3(threads), lds_bytes,
+                             stream, nullptr, P);
+  }
+  // other sizes: one launch per LSTM of the kernel instantiated for its size alone (the launch rules of infer_dev.h)
+  for (int i = 0; i < EMFN_LSTMS; ++i) {
+    EmfnSeqDev Q = P;
+    Q.d[0] = P.d[i]; Q.d[0].block_begin = 0; Q.count = 1;
+    const int th = std::max(8 * Q.d[0].seq.Hp, 64);
+    const int rc = (i < 3)
+      ? infer_launch_hk4(who, name, Q.d[0].seq, [](auto kk) { return encode_mfn_seq_kernel<R, false, decltype(kk)::value, 0, 0, 0, 0, 0>; }, Q, tiles, th, lds_bytes, stream)
+      : infer_launch_hk4(who, name, Q.d[0].seq, [](auto kk) { return encode_mfn_seq_kernel<R, true, decltype(kk)::value, 0, 0, 0, 0, 0>; }, Q, tiles, th, lds_bytes, stream);
+    if (rc != MFM_OK) return rc;
+  }
+  return MFM_OK;
 }
 
 }  // namespace mfm

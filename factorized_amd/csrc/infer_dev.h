@@ -118,6 +118,22 @@ __device__ __forceinline__ double label_loss_part(const float* y_hat, const void
   return disc;
 }
 
+// ---------------------------------------------------------------- the finish of the objective (objective.hip; objective_mfn.hip launches it too)
+#define OBJ_ACC 5          // squared errors l, a, v; KLD sum; label-loss sum
+struct ObjFinishDev {
+  const float* part[INFER_DEC]; int npart[INFER_DEC];      // this chunk's squared-error partials
+  const float* mu[4]; const float* lv[4]; int nz[4];       // this chunk's factors, n * size elements each (0: no KLD term)
+  const float* y_hat; const void* y;                       // this chunk's [n, od] and labels
+  double* acc;                                             // OBJ_ACC running sums over the chunks so far
+  float* out;                                              // loss, disc, gen_l, gen_a, gen_v, reg
+  double inv_gen[INFER_DEC], inv_disc;                     // 1 / (T N d_m), 1 / (N od) (L1) or 1 / N (CE): the WHOLE split
+  float lda[4];                                            // lda_xl, lda_xa, lda_xv, lda_mmd
+  int n, od, loss_kind, first, last;                       // last 0 on every chunk: acc is left for the caller's own finish
+};
+// objective_finish_kernel, one workgroup: the chunk's sums in a fixed order in fp64 into acc (the first chunk stores, the others
+// add); behind the last chunk the six floats, reg = -0.5 * the KLD sum.  The kernel stays in objective.hip alone
+int objective_finish_launch(const ObjFinishDev& Q, hipStream_t stream);
+
 // ---------------------------------------------------------------- the finish of the zeroed-modality protocol (zeros.hip; zeros_mfn.hip launches it too)
 #define ZER_CASES INFER_DEC
 #define ZER_ACC (2 * ZER_CASES)        // squared errors l, a, v; label-loss sums of the cases no l, no a, no v

@@ -24,7 +24,6 @@
 
 namespace mfm {
 
-#define OBJ_ACC 5          // squared errors l, a, v; KLD sum; label-loss sum
 static_assert(OBJ_BM == OBJ_BN && OBJ_BM * 4 == OBJ_THREADS, "one staging loop fills both LDS tiles; a wave owns 16 rows");
 
 __global__ __launch_bounds__(OBJ_THREADS) void fc1_sqerr_kernel(const Fc1SqDev P) {
@@ -85,17 +84,6 @@ __global__ __launch_bounds__(OBJ_THREADS) void fc1_sqerr_kernel(const Fc1SqDev P
   if (tid == 0) I.partials[tile] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-struct ObjFinishDev {
-  const float* part[INFER_DEC]; int npart[INFER_DEC];      // this chunk's squared-error partials
-  const float* mu[INFER_ENC]; const float* lv[INFER_ENC]; int nz[INFER_ENC];   // this chunk's factors, n * size elements each
-  const float* y_hat; const void* y;                       // this chunk's [n, od] and labels
-  double* acc;                                             // OBJ_ACC running sums over the chunks so far
-  float* out;                                              // loss, disc, gen_l, gen_a, gen_v, reg
-  double inv_gen[INFER_DEC], inv_disc;                     // 1 / (T N d_m), 1 / (N od) (L1) or 1 / N (CE): the WHOLE split
-  float lda[4];                                            // lda_xl, lda_xa, lda_xv, lda_mmd
-  int n, od, loss_kind, first, last;
-};
-
 __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const ObjFinishDev P) {
   __shared__ double red[OBJ_THREADS];
   const int tid = threadIdx.x;
@@ -131,6 +119,10 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_finish_kernel(const Obj
 }
 
 // ---------------------------------------------------------------- host
+int objective_finish_launch(const ObjFinishDev& Q, hipStream_t stream) {
+  return seq_launch_kernel(objective_finish_kernel, "objective_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q);
+}
+
 int fc1_sqerr_prepare(const char* who, const DecLaunch& L, int64_t N, Fc1SqLaunch& S) {
   const int T = L.P.T;
   MFM_REQUIRE(fc1_sqerr_tiles(T, L.rows, L.dm) < ((int64_t)1 << 31), "%s: a chunk of %d rows x %d steps is too large; pass a row cap", who, L.rows, T);
@@ -228,8 +220,7 @@ static int objective_klef(int T, int64_t N, const int32_t* sz, const float* lamb
     for (int i = 0; i < INFER_ENC; ++i) Q.nz[i] = n * zs[i];
     Q.y = labels_at(y, loss_kind, n0, od);
     Q.n = n; Q.first = n0 == 0; Q.last = n0 + n == N;
-    if ((rc = seq_launch_kernel(objective_finish_kernel, "objective_finish_kernel", dim3(1), dim3(OBJ_THREADS), 0, stream, nullptr, Q)) != MFM_OK)
-      return rc;
+    if ((rc = objective_finish_launch(Q, stream)) != MFM_OK) return rc;
   }
   return MFM_OK;
 }

@@ -615,6 +615,58 @@ int mfm_objective_klef(int32_t T, int64_t N, const int32_t* sizes /*host, 13*/, 
                        int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * mfm_objective_mfn (csrc/objective_mfn.hip): the same six numbers, under the same contract, for MFM_KL and MFM, whose label
+ * factor comes from the Memory Fusion Network (mfm_model.py:140-199, :723-743).  heads = 1 (MFM_KL): reg as above, over the four
+ * (mean, logvar) pairs.  heads = 0 (MFM): the factors are the encoders' fc1 outputs and last_to_zy_fc1, and
+ *   out[5] reg    sum over the four factors z [N, dim] of mean K(g, g) + mean K(z, z) - 2 mean K(g, z),
+ *                 K(a, b) = exp(-|a - b|^2 / dim^2) (mfm_model.py:14-34), the means over all N^2 pairs of the WHOLE split, g the
+ *                 factor's columns of `gauss`
+ * Per row chunk of n rows: the launches of mfm_encode_mfn as that entry launches them (the grouped projection GEMM, the six
+ * recurrences in one launch, the attention chain, the memory recurrence with the label head(s)), the factors into the workspace
+ * -- with heads the chunk's means and log-variances, without heads the means into their rows of four whole-split arrays
+ * [N, size]; the recurrence launch of mfm_decode_factors on the chunk's means (the stored h takes the place of the
+ * projections); the fused fc1 / squared-error launch and the single-workgroup fp64 finish of mfm_objective_klef.  With heads that
+ * finish writes `out` behind the last chunk.  Without heads two more launches follow the last chunk: the MMD, value only --
+ * workgroup (factor, tile of 8 rows i for N <= 256, else 32) walks j in tiles of 32 rows staged in LDS, forms the three kernel
+ * values per pair with expf, adds kzz + kgg - 2 kgz per pair, reduces lane -> wave -> workgroup in a fixed order and writes ONE
+ * partial to its own slot -- and a finish that adds each factor's partials in ascending order in fp64, scales by 1 / N^2, forms
+ * the total and writes `out`.  No gradient, no [N, N] scratch, no float atomics.
+ *   sizes    host, 23: as mfm_predict_zeros_mfn (entry 16, heads, tells MFM_KL from MFM)
+ *   lambdas  host, 4: lda_xl, lda_xa, lda_xv, lda_mmd
+ *   offsets  host, 100 (heads = 1) or 86 (heads = 0): as mfm_predict_zeros_mfn (with heads the logvar heads' are read here)
+ *   x, y, out, max_rows   as mfm_objective_klef
+ *   gauss    heads = 0: the N(0, 1) sample, [N, zl + za + zv + zy] contiguous (columns in that order), 4-byte aligned, read
+ *            only; heads = 1: must be NULL.  Either the other way round is MFM_ERR_ARG
+ *   workspace mfm_objective_mfn_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary.  With
+ *            rows = min(N, max_rows), Hp(h) = round_up(h, 16), up4(v) = round_up(v, 4):
+ *              max(rows * T * 4 * (Hp(zl) + Hp(za) + Hp(zv) + Hp(h_l) + Hp(h_a) + Hp(h_v)),   the six x-projections, and in their
+ *                  rows * T * (Hp(fy + fl) + Hp(fy + fa) + Hp(fy + fv)))                      place the decoders' stored h
+ *            + rows * T * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                       the MFN LSTMs' cell states
+ *            + up4(rows * h_l) + up4(rows * h_a) + up4(rows * h_v)                            their last hidden states
+ *            + up4(rows * T * memsize) + up4(rows * T * gamma1) + up4(rows * T * gamma2)      cHat, the gamma partials
+ *            + heads = 1: 2 * (up4(rows * zl) + up4(rows * za) + up4(rows * zv) + up4(rows * zy))   the chunk's means, logvars
+ *              heads = 0: up4(N * zl) + up4(N * za) + up4(N * zv) + up4(N * zy)               the whole split's means
+ *            + up4(rows * output_dim)                                                         the chunk's y_hat
+ *            + up4(sum over m of ceil(T * rows / 64) * ceil(d_m / 64))                        the squared-error partials
+ *            + heads = 0: up4(4 * ceil(N / (N <= 256 ? 8 : 32)))                              the MMD's partials
+ *            + 12                                                                             five fp64 accumulators
+ *            Beyond the row cap it grows with N by the whole-split means and the MMD's partials alone (heads = 0).
+ * Determinism: the six values are bit-identical from run to run for a given (T, N, max_rows) and, heads = 0, a given gauss.
+ * The recurrence launches run on one-row tiles while 6 * rows < 6 * CUs and on four-row tiles from there
+ * (mfm_objective_mfn_tile_rows tells which; host only, -1 for bad arguments); the sums are fp64 in a fixed order per chunking.
+ * Nothing outside the workspace and `out` is written.  T < 1, N < 1, a null pointer or max_rows < 0 return MFM_ERR_ARG before
+ * anything touches the GPU.  MFM_ERR_UNSUPPORTED with the size in the error text, nothing enqueued: what mfm_encode_mfn refuses
+ * (an h_dims entry or an encoder hidden size above 128, a windowsize other than 2, attention widths beyond the LDS, memsize or
+ * gamma widths beyond the register-resident memory recurrence), what mfm_decode_factors refuses (a decoder with fy + f_m > 128,
+ * more LDS than a CU has) and, heads = 0, a factor too wide for the MMD's LDS tiles (above about 300): run
+ * mfm_plan_forward(train = 0) instead.  Stream-ordered, no host synchronisation, legal inside a stream capture. */
+int64_t mfm_objective_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_objective_mfn_tile_rows(int64_t N, int64_t max_rows);
+int mfm_objective_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, const float* lambdas /*host, 4*/, const float* params,
+                      const int64_t* offsets /*host, 100 or 86*/, const float* x, const void* y, const float* gauss /*[N, zl + za + zv + zy], or NULL*/,
+                      float* workspace, float* out /*6*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The zeroed-modality test protocol of MFM_KL_EF (csrc/zeros.hip; reference mfm_mosi.py:572-596, `predict` of
  * train_mfm_test_zeros): the split through the deterministic eval forward three times, each time with one modality's columns
  * taken as zero -- case 0: no l ([0, d_l)), 1: no a ([d_l, d_l + d_a)), 2: no v ([d_l + d_a, D)) -- in the pattern of the entries
