@@ -153,28 +153,33 @@ class _FusedEngineMixin:
             eng.gauss = None if g is None else torch.cat([t.to(x.device).float() for t in g], dim=1).contiguous()
         return eng, x
 
-    def _predict(self, x, y):
+    def _predict(self, x, y, label_only=False):
         """the engine's predict() on this module's parameters: always the deterministic eval computation (dropout off, the
         zy mean), whatever `self.training` says -- which is left as found -- without autograd and without lazy outputs"""
         eng, x = self._infer_args(x)
         with torch.no_grad():
-            return eng.predict(x, y)
+            return eng.predict(x, y, label_only=label_only)
 
-    def predict(self, x):
+    def predict(self, x, *, label_only=False):
         """x [T, N, D] -> y_hat [N, output_dim], the reference's `predict(model, X)` (mfm_mosi.py:360-365) without the
         generative half.  MFM_KL_EF: one recurrence and six row-wise layers (engine.predict); the buffer is reused by the next
-        call with the same shape.  MFM_KL / MFM: the fused eval forward."""
-        return self._predict(x, None)["y_hat"]
+        call with the same shape.  MFM_KL / MFM: by default the fused eval forward on a plan, bit for bit.  label_only=True
+        takes these two classes through mfm_predict_mfn instead: the Memory Fusion Network's label path on chip and nothing else
+        -- no plan and its workspace, no encoder, decoder or regulariser -- with y_hat equal to the default's to fp32 rounding
+        (not bit for bit) and reused by the next call with the same shape; for MFM_KL_EF the keyword changes nothing."""
+        return self._predict(x, None, label_only)["y_hat"]
 
-    def evaluate(self, x, y, loss_fn=None):
+    def evaluate(self, x, y, loss_fn=None, *, label_only=False):
         """x, labels -> the loss as a 0-d tensor on the device (no host read), the reference's `evaluate(model, X, y)`
         (mfm_mosi.py:349-357); accepted as is by KeepBest.update and lr_scheduler.ReduceLROnPlateau.step.  loss_fn=None: the
         config's loss (nn.L1Loss(), or nn.CrossEntropyLoss() for loss="ce"), reduced inside the prediction launch; any other
-        `loss_fn` is applied with torch to the returned y_hat."""
+        `loss_fn` is applied with torch to the returned y_hat.  `label_only` as for predict(): the default is the eval forward's
+        bits for MFM_KL / MFM; True computes the loss on the label path alone (mfm_predict_mfn), the mean formed on the device
+        in a fixed order, equal to the default's to fp32 rounding."""
         if loss_fn is None:
-            return self._predict(x, y)["loss"]
+            return self._predict(x, y, label_only)["loss"]
         with torch.no_grad():
-            return loss_fn(self._predict(x, None)["y_hat"], y)
+            return loss_fn(self._predict(x, None, label_only)["y_hat"], y)
 
     def objective(self, x, y):
         """x [T, N, D], labels -> Objective(loss, disc, gen_l, gen_a, gen_v, reg) (a namedtuple, engine.Objective) of 0-d float32

@@ -5,7 +5,9 @@ one host path (encode has two library entries behind it: mfm_encode_klef for var
 "kl" and "mmd", whose label factor comes from the Memory Fusion Network; the latter keeps its state in
 `engine._encode_mfn_bufs` / `engine._encode_mfn_refused`; predict_zeros likewise: mfm_predict_zeros_klef, and
 mfm_predict_zeros_mfn with its state in `engine._zeros_mfn_bufs` / `engine._zeros_mfn_refused`; objective likewise:
-mfm_objective_klef, and mfm_objective_mfn with its state in `engine._objective_mfn_bufs` / `engine._objective_mfn_refused`): the split
+mfm_objective_klef, and mfm_objective_mfn with its state in `engine._objective_mfn_bufs` / `engine._objective_mfn_refused`; predict
+with label_only=True likewise: mfm_predict_klef, and mfm_predict_mfn with its state in `engine._predict_mfn_bufs` /
+`engine._predict_mfn_refused` -- without the keyword predict of the variants "kl" and "mmd" is the eval forward on a plan): the split
 validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
@@ -69,7 +71,8 @@ def _lin(*names):
 _ENTRIES = {n: ("_%s_bufs" % n, "_%s_refused" % n, f) for n, f in (
     ("predict", "mfm_predict_klef"), ("encode", "mfm_encode_klef"), ("decode", "mfm_decode_factors"),
     ("objective", "mfm_objective_klef"), ("zeros", "mfm_predict_zeros_klef"), ("influence", "mfm_influence_factors"),
-    ("encode_mfn", "mfm_encode_mfn"), ("zeros_mfn", "mfm_predict_zeros_mfn"), ("objective_mfn", "mfm_objective_mfn"))}
+    ("encode_mfn", "mfm_encode_mfn"), ("zeros_mfn", "mfm_predict_zeros_mfn"), ("objective_mfn", "mfm_objective_mfn"),
+    ("predict_mfn", "mfm_predict_mfn"))}
 
 
 def influence_factors_torch(decoders, fy, fms, T):
@@ -132,6 +135,8 @@ class InferMixin:
                + _MFN_TENSORS + _lin("last_to_zy_fc1", "last_to_logvarzy_fc1")),
         "mmd": tuple(n for m in "lav" for n in _lstm("encoder_" + m)) + _MFN_TENSORS + _lin("last_to_zy_fc1"),
     }
+    # mfm_predict_mfn: the MFN, the label head and the four layers behind it -- the same 38 for both variants
+    _PREDICT_MFN_TENSORS = _MFN_TENSORS + _lin("last_to_zy_fc1", "zy_to_fy_fc1", "zy_to_fy_fc2", "fy_to_y_fc1", "fy_to_y_fc2")
     _DECODE_TENSORS = (_lin(*[mlp + fc for mlp in ("zy_to_fy", "zl_to_fl", "za_to_fa", "zv_to_fv") for fc in ("_fc1", "_fc2")])
                        + _lstm("decoder_l") + _lstm("decoder_a") + _lstm("decoder_v") + _lin("fy_to_y_fc1", "fy_to_y_fc2"))
 
@@ -208,21 +213,35 @@ class InferMixin:
         return st
 
     # ------------------------------------------------------------------ prediction only
-    def predict_workspace_floats(self, T, N, max_rows=None):
-        """floats of workspace predict() keeps for a [T, N, D] split (mfm_predict_klef_workspace_floats)"""
+    def predict_workspace_floats(self, T, N, max_rows=None, label_only=False):
+        """floats of workspace predict() keeps for a [T, N, D] split (mfm_predict_klef_workspace_floats; variants "kl" and "mmd"
+        with label_only=True: mfm_predict_mfn_workspace_floats)"""
+        if label_only and self.variant != "kl_ef":
+            return int(_lib.lib().mfm_predict_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_predict_klef_workspace_floats(int(T), int(N), self._hidden_sizes()[0], self._row_cap(max_rows)))
 
-    def predict(self, x, y=None, *, max_rows=None):
+    def predict(self, x, y=None, *, max_rows=None, label_only=False):
         """x [T, N, D] (, labels) -> {"y_hat": [N, output_dim], "loss": 0-d device tensor or None}: the deterministic eval
         computation of y_hat and, with labels, the mean L1 / cross-entropy loss, left on the device.
 
         Variant "kl_ef": mfm_predict_klef -- the ef encoder's recurrence and the six layers behind it, nothing of the
         generative half.  Workspace, y_hat and the loss word are reused and a refusal falls back as the module docstring says.
-        Other variants: the same dictionary from forward(train=False, want_xhat=False)."""
+        `label_only` changes nothing here: this path already is label-only.
+        Variants "kl" and "mmd": by default the same dictionary from forward(train=False, want_xhat=False), bit for bit the
+        eval forward on a plan.  With label_only=True: mfm_predict_mfn -- the Memory Fusion Network's three recurrences, its
+        attention chain and memory recurrence on chip, the label head and the classifier in the memory recurrence's workgroup,
+        the loss reduced behind it; no plan, none of the encoders, decoders or regularisers.  Its state is a cache of its own,
+        `_predict_mfn_bufs`; workspace, y_hat and the loss word are reused and a refusal (remembered for an h_dims entry above
+        128) falls back to the default path, as the module docstring says.  The results agree with the default's to fp32
+        rounding, not bit for bit."""
         T, N, D = self._check_split(x, y)
         cap = self._row_cap(max_rows)
         c = self.cfg
         od, h = c["output_dim"], self._hidden_sizes()[0]
+        if label_only and self.variant != "kl_ef":
+            st = self._predict_mfn(x, y, T, N, cap)
+            if st is not None:
+                return {"y_hat": st[1], "loss": st[2] if y is not None else None}
 
         def build():
             nws = int(_lib.lib().mfm_predict_klef_workspace_floats(T, N, h, cap))
@@ -240,6 +259,22 @@ class InferMixin:
         # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)
         out = self.forward(x, y, train=False, want_xhat=False, handover=False)
         return {"y_hat": out["y_hat"], "loss": out["losses"][0].clone() if y is not None else None}
+
+    def _predict_mfn(self, x, y, T, N, cap):
+        """predict(label_only=True) of the variants "kl" and "mmd" through mfm_predict_mfn -> the entry's state (workspace,
+        y_hat, the loss word, sizes, offsets), or None: refused"""
+        def build():
+            sizes = self._zeros_mfn_sizes()
+            nws = int(_lib.lib().mfm_predict_mfn_workspace_floats(T, N, sizes, cap))
+            return (self._empty(nws), self._empty(N, self.cfg["output_dim"]), torch.zeros((), dtype=torch.float32, device=self.device),
+                    sizes, self._offsets(self._PREDICT_MFN_TENSORS))
+
+        def call(fn, st):
+            ws, y_hat, loss, sizes, offs = st
+            return fn(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat),
+                      _ptr(loss) if y is not None else None, cap, _stream())
+
+        return self._run_fused("predict_mfn", (T, N, cap), build, call, tuple(self.cfg["h_dims"]))
 
     # ------------------------------------------------------------------ the factorized latents and generation from them
     def _encode_mfn_sizes(self):

@@ -223,6 +223,10 @@ _SIGS = {
     "mfm_predict_zeros_mfn_tile_rows": (C.c_int, [C.c_int64, C.c_int64]),
     "mfm_predict_zeros_mfn": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mfm_predict_mfn_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
+    "mfm_predict_mfn_tile_rows": (C.c_int, [C.c_int64, C.c_int64]),
+    "mfm_predict_mfn": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mfm_influence_factors_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
     "mfm_influence_factors": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64),
                                         C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

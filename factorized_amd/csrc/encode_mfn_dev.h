@@ -5,6 +5,9 @@
 // major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from the ONE row the MFN's LSTM c computes
 // on zero input (cz / hz), the other two modalities' from the real records.  Only the gather differs; the arithmetic of a row is
 // the same code.  encode_mfn.hip and objective_mfn.hip instantiate ZC = false, zeros_mfn.hip ZC = true.
+// Template parameter TAIL of the memory recurrence (off by default; predict_mfn.hip alone turns it on, with ZC = false): zy stays
+// in LDS and the same workgroup goes on with zy_to_fy and the classifier, writes the row of y_hat and, with labels, the row's
+// loss contribution (EmfnTailDev); the other instantiations do not see any of it.
 // At the end of the file: the launch in front of the chain as mfm_encode_mfn runs it -- the six recurrences (encoder l, a, v with
 // their heads, the MFN's LSTMs with their cell-state records) in one launch, encode_mfn_seq_kernel, its workspace parts and its
 // launcher; encode_mfn_front.h walks them chunk by chunk for mfm_encode_mfn and mfm_objective_mfn (objective_mfn.hip).
@@ -189,7 +192,6 @@ struct EmfnMemDev {
   int T, n, M, H1, H2, QA, QB, MP, HP, ldw, tot, zy, nheads;   // n: the rows of the recurrence (ZC: 3 nreal, case major)
   int nreal;                                                   // ZC: the chunk's rows
 };
-
 // all-reduce over groups of Q adjacent lanes, Q in {1, 2, 4, 8, 16}
 __device__ __forceinline__ float emfn_group_sum(float v, const int Q) {
   if (Q >= 2) v += dpp_f<DPP_QUAD_XOR1>(v);
@@ -214,10 +216,35 @@ __device__ __forceinline__ void emfn_wslice(float (&w)[EMFN_MAXW], const float* 
   }
 }
 
+// TAIL: what the label tail behind the recurrence adds (mfm_predict_mfn); wz[0] / bz[0] are read, oz is not
+struct EmfnTailDev : EmfnMemDev {
+  const float* wt[4]; const float* bt[4];      // zy_to_fy_fc1, zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2
+  const void* y; float* y_hat;                 // this chunk's labels (null: no loss) and outputs [n, od]
+  float* rowloss; double* acc; int* ticket;    // workspace: one contribution per row of the chunk, the running sum, the ticket word
+  float* loss;                                 // the result (null: no loss)
+  double inv;                                  // 1 / (N od) (L1) or 1 / N (CE) over the WHOLE split
+  int fy, od, loss_kind, tailw, first, last;   // tailw: floats of one tail activation in LDS; first / last chunk of the call
+};
+
+// one layer of the tail on LDS vectors, 8 lanes per output as the head: out[o] = (relu)(b[o] + sum_k W[o][k] in[k])
+__device__ __forceinline__ void emfn_tail_layer(const float* __restrict__ W, const float* __restrict__ b, const int K, const int Nout,
+                                                const float* in, float* out, const bool relu, const int tid) {
+  const int q8 = tid & 7;
+  for (int o = tid >> 3; o < Nout; o += (int)blockDim.x >> 3) {
+    const float* wr = W + (int64_t)o * K;
+    float s = 0.0f;
+    for (int k = q8; k < K; k += 8) s = fmaf(wr[k], in[k], s);
+    s = emfn_group_sum(s, 8) + b[o];
+    if (q8 == 0) out[o] = relu ? fmaxf(s, 0.0f) : s;
+  }
+  lds_barrier();
+}
+
 // The thread roles, the operand layout (lane q of a group owns the contiguous slice [32 q, 32 q + 32) of the reduction) and the
 // two barriers per step are those of mfn_mem_fwd_kernel (mfn_mem.hip); nothing of a step is stored
-template <int MAXT, bool ZC>
-__global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const EmfnMemDev P) {
+template <int MAXT, bool ZC, bool TAIL = false>
+__global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const std::conditional_t<TAIL, EmfnTailDev, EmfnMemDev> P) {
+  static_assert(!(TAIL && ZC), "the label tail runs on the chunk's own rows");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int T = P.T, n = P.n, M = P.M, H1 = P.H1, H2 = P.H2, QA = P.QA, QB = P.QB, MP = P.MP, HP = P.HP;
   float* memb = lds;                 // [2][MP]
@@ -303,14 +330,64 @@ __global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const EmfnMemDev P
   }
   if (stB) vec[P.tot + mb] = memr;
   lds_barrier();
-  const int q8 = tid & 7;
-  for (int o = tid >> 3; o < nout; o += (int)blockDim.x >> 3) {
-    const int hd = o / P.zy, c = o - hd * P.zy;
-    const float* wr = P.wz[hd] + (int64_t)c * KT;
-    float s = 0.0f;
-    for (int k = q8; k < KT; k += 8) s = fmaf(wr[k], vec[k], s);
-    s = emfn_group_sum(s, 8);
-    if (q8 == 0) P.oz[hd][(int64_t)row * P.zy + c] = s + P.bz[hd][c];
+  if constexpr (!TAIL) {
+    const int q8 = tid & 7;
+    for (int o = tid >> 3; o < nout; o += (int)blockDim.x >> 3) {
+      const int hd = o / P.zy, c = o - hd * P.zy;
+      const float* wr = P.wz[hd] + (int64_t)c * KT;
+      float s = 0.0f;
+      for (int k = q8; k < KT; k += 8) s = fmaf(wr[k], vec[k], s);
+      s = emfn_group_sum(s, 8);
+      if (q8 == 0) P.oz[hd][(int64_t)row * P.zy + c] = s + P.bz[hd][c];
+    }
+  } else {
+    // ---- the label tail: zy (the mean head alone) stays in LDS behind the vector; the four small layers ping-pong between two
+    // activations [tailw]; y_hat ends in act0
+    float* act0 = lds + (KT + 3) / 4 * 4;
+    float* act1 = act0 + P.tailw;
+    const int fy = P.fy, od = P.od;
+    emfn_tail_layer(P.wz[0], P.bz[0], KT, P.zy, vec, act0, false, tid);
+    emfn_tail_layer(P.wt[0], P.bt[0], P.zy, fy, act0, act1, true, tid);
+    emfn_tail_layer(P.wt[1], P.bt[1], fy, fy, act1, act0, true, tid);
+    emfn_tail_layer(P.wt[2], P.bt[2], fy, fy, act0, act1, true, tid);
+    emfn_tail_layer(P.wt[3], P.bt[3], fy, od, act1, act0, false, tid);
+    for (int o = tid; o < od; o += blockDim.x) P.y_hat[(int64_t)row * od + o] = act0[o];
+    if (!P.y || !P.loss || tid >= 64) return;      // (the first wave alone goes on)
+    // the row's contribution in a fixed order by one lane; then the arrival ticket of predict_klef_kernel, per chunk: the
+    // workgroup that draws the chunk's last ticket adds the chunk's contributions in a fixed order in fp64 -- lane l takes rows
+    // l, l + 64, ... ascending, then one fixed butterfly --, carries the running sum of the chunks so far (the launches of a
+    // call are stream-ordered), writes the mean behind the last chunk and puts the ticket back to 0.  Nobody waits or spins
+    int drawn = 0;
+    if (tid == 0) {
+      float part = 0.0f;
+      if (P.loss_kind == 0) {
+        const float* yt = reinterpret_cast<const float*>(P.y) + (int64_t)row * od;
+        for (int o = 0; o < od; ++o) part += fabsf(act0[o] - yt[o]);
+      } else {
+        const int64_t lab = reinterpret_cast<const int64_t*>(P.y)[row];
+        float mx = act0[0];
+        for (int o = 1; o < od; ++o) mx = fmaxf(mx, act0[o]);
+        float se = 0.0f;
+        for (int o = 0; o < od; ++o) se += expf(act0[o] - mx);
+        const int lc = (int)min(max(lab, (int64_t)0), (int64_t)(od - 1));      // (a label outside [0, od) must not index outside LDS)
+        part = (logf(se) + mx) - act0[lc];
+      }
+      __hip_atomic_store(P.rowloss + row, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      drawn = __hip_atomic_fetch_add(P.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    drawn = __builtin_amdgcn_readfirstlane(drawn);
+    if (drawn != n - 1) return;
+    // the last arriver of the chunk: every contribution was stored in front of its workgroup's draw
+    double s = 0.0;
+    for (int i = tid; i < n; i += 64) s += (double)__hip_atomic_load(P.rowloss + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (tid == 0) {
+      if (!P.first) s += __hip_atomic_load(P.acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(P.acc, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (P.last) __hip_atomic_store(P.loss, (float)(s * P.inv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(P.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
@@ -339,7 +416,8 @@ struct EmfnChain { EmfnAttDev A; EmfnMemDev Mm; int CT, mem_threads; size_t att_
 
 // what the two kernels do not cover (MFM_ERR_UNSUPPORTED with the size in the error text), and their sizing into a zeroed C;
 // pairs: the (step, row) pairs of a full chunk's attention chain
-static int emfn_chain_check(const char* who, const EmfnSizes& S, int64_t pairs, EmfnChain& C) {
+// tailw: floats of one activation of the label tail (TAIL; 0: none), two of which lie behind the head's input
+static int emfn_chain_check(const char* who, const EmfnSizes& S, int64_t pairs, EmfnChain& C, int tailw = 0) {
   memset(&C, 0, sizeof(C));
   const int tot = S.hm[0] + S.hm[1] + S.hm[2], KC = 2 * tot;
   // the attention chain: 32 pairs per workgroup once 16 would give every CU more than four workgroups, where the LDS allows
@@ -360,9 +438,13 @@ static int emfn_chain_check(const char* who, const EmfnSizes& S, int64_t pairs, 
   }
   C.mem_threads = round_up(std::max(nA, nB), 64);
   const int MP = EMFN_MAXW * QA, HP = EMFN_MAXW * QB;
-  C.mem_lds = lds_bytes_of(std::max(2 * MP + 2 * HP, tot + S.M));
+  C.mem_lds = lds_bytes_of(std::max(2 * MP + 2 * HP, round_up(tot + S.M, 4) + 2 * tailw));
   if (C.mem_lds > 160 * 1024) {
-    set_error("%s: the label head's input of %d + %d floats does not fit the LDS of a CU", who, tot, S.M);
+    if (tailw)
+      set_error("%s: the label head's input of %d + %d floats and two activations of the label tail of %d do not fit the LDS of a CU",
+                who, tot, S.M, tailw);
+    else
+      set_error("%s: the label head's input of %d + %d floats does not fit the LDS of a CU", who, tot, S.M);
     return MFM_ERR_UNSUPPORTED;
   }
   C.Mm.QA = QA; C.Mm.QB = QB; C.Mm.MP = MP; C.Mm.HP = HP;
@@ -389,25 +471,30 @@ static void emfn_chain_fill(EmfnChain& C, const EmfnSizes& S, int T, const float
   Mm.nheads = nheads;
 }
 
-// the two launches on a chunk of n rows (ZC: the 3 n rows (case, row) behind them)
+// the attention chain on a chunk of n rows (ZC: the 3 n rows (case, row)); the memory recurrence reads what it leaves
 template <bool ZC>
-static int emfn_chain_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
+static int emfn_att_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
   EmfnAttDev& A = C.A;
   EmfnMemDev& Mm = C.Mm;
   const int nv = (ZC ? 3 : 1) * n;
   A.n = n;
   Mm.g1p = A.g1p; Mm.g2p = A.g2p; Mm.chat = A.chat;
-  const int64_t np = (int64_t)T * nv;
-  int rc;
-  if (C.CT == 2)
-    rc = seq_launch_kernel(encode_mfn_att_kernel<2, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 31) / 32)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
-  else
-    rc = seq_launch_kernel(encode_mfn_att_kernel<1, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 15) / 16)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
-  if (rc != MFM_OK) return rc;
   Mm.n = nv; Mm.nreal = n;
+  const int64_t np = (int64_t)T * nv;
+  if (C.CT == 2)
+    return seq_launch_kernel(encode_mfn_att_kernel<2, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 31) / 32)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
+  return seq_launch_kernel(encode_mfn_att_kernel<1, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 15) / 16)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
+}
+
+// the two launches on a chunk of n rows (ZC: the 3 n rows (case, row) behind them)
+template <bool ZC>
+static int emfn_chain_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
+  const int rc = emfn_att_launch<ZC>(C, T, n, stream);
+  if (rc != MFM_OK) return rc;
+  const EmfnMemDev& Mm = C.Mm;
   if (C.mem_threads <= 512)
-    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
-  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC>, "encode_mfn_mem_kernel", dim3(nv), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
 }
 
 // ---------------------------------------------------------------- the six recurrences (mfm_encode_mfn; mfm_objective_mfn launches them too)

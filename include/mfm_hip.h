@@ -758,6 +758,58 @@ int mfm_predict_zeros_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 23*
                           float* gen /*3*/, float* disc /*3, or NULL*/, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * mfm_predict_mfn (csrc/predict_mfn.hip): the prediction-only path of MFM_KL and MFM -- what mfm_predict_klef is for MFM_KL_EF,
+ * under its contract, for the classes whose label factor comes from the Memory Fusion Network (mfm_model.py:140-199, :723-743):
+ *   zy = last_to_zy_fc1([h_l,T | h_a,T | h_v,T | mem_T]) of the MFN as mfm_encode_mfn defines it (the mean; nothing is sampled),
+ *   fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy)))), y_hat = fy_to_y_fc2(relu(fy_to_y_fc1(fy))),
+ *   *loss = mean |y_hat - y| over N * output_dim (loss_kind 0) / mean cross entropy over N (1), as mfm_predict_klef defines it.
+ * Only what these depend on runs: the three modality encoders and their heads, every log-variance head, KLD / MMD, the
+ * modalities' z -> f MLPs, the decoders and their fc1 do not, and their parameters are not read.  Per row chunk of n rows, on the
+ * one stream given: ONE grouped fp32 GEMM for the three input projections; ONE launch of (MFN LSTM, row tile) workgroups that
+ * store the cell states and the last hidden state; the attention chain of mfm_encode_mfn over the T * n pairs; its memory
+ * recurrence per row, which keeps zy in LDS and goes on, in the same workgroup, with the four small layers -- it writes the row
+ * of y_hat and, with labels, the row's loss contribution.  The workgroup that draws the LAST arrival ticket of a chunk adds the
+ * chunk's contributions in a fixed order in fp64 onto the running sum of the chunks before it and, behind the last chunk,
+ * divides by the counts of the WHOLE split; it puts the ticket word back to 0.  Nobody waits or spins, no float atomics touch
+ * the result.
+ *   sizes    host, 23: as mfm_predict_zeros_mfn.  zl, za, zv and fl, fa, fv must be positive and are otherwise unused; heads
+ *            (entry 16) must be 0 or 1 and is otherwise unused: the label path is the same for MFM_KL and MFM
+ *   offsets  host, 38 element offsets into the flat fp32 parameter buffer `params`: per MFN LSTM l, a, v weight_ih, weight_hh,
+ *            bias_ih, bias_hh (12); weight and bias of att1_fc1, att1_fc2, att2_fc1, att2_fc2, gamma1_fc1, gamma1_fc2, gamma2_fc1,
+ *            gamma2_fc2 (16); of last_to_zy_fc1 (2); of zy_to_fy_fc1, zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2 (8) (torch layouts; the
+ *            LSTM weights 16-byte aligned)
+ *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 4-byte aligned: any contiguous view; read only
+ *   y        NULL, or the labels: float [N, output_dim] (loss_kind 0) / int64 [N] (loss_kind 1, class indices)
+ *   y_hat    out, [N, output_dim]; loss: out, one device float -- NULL exactly when y is (then no loss is computed or written)
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace; the loss is the mean over all N
+ *            rows whatever the chunking
+ *   workspace mfm_predict_mfn_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary.  With
+ *            rows = min(N, max_rows), Hp(h) = round_up(h, 16), up4(v) = round_up(v, 4), in this order:
+ *              rows * T * 4 * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                   the x-projections
+ *            + rows * T * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                       the MFN LSTMs' cell states
+ *            + up4(rows * h_l) + up4(rows * h_a) + up4(rows * h_v)                            their last hidden states
+ *            + up4(rows * T * memsize) + up4(rows * T * gamma1) + up4(rows * T * gamma2)      cHat, the gamma partials
+ *            + up4(rows)                                                                      one loss contribution per chunk row
+ *            + 4                                                                              the fp64 running sum, the ticket word, a pad
+ *            It does not grow with N beyond the row cap.  With labels the call clears the ticket word itself (a memset on the
+ *            stream) and leaves it at 0: it is the third of the last four floats.
+ * Determinism: bit-identical from run to run for a given (T, N, max_rows).  The recurrence launch runs on one-row tiles while
+ * 3 * rows < 6 * CUs and on four-row tiles from there (mfm_predict_mfn_tile_rows tells which; host only, -1 for bad arguments);
+ * the attention chain takes 16 or 32 pairs per workgroup, a pair's arithmetic the same in both.  For a fixed tile-row form y_hat
+ * is bit-identical for every row chunking; the loss is an fp64 sum in a fixed order per chunking.
+ * Nothing outside the workspace, y_hat and *loss is written; rows beyond a chunk are neither read nor written.  T < 1, N < 1, a
+ * null pointer, y without loss or loss without y, or max_rows < 0 return MFM_ERR_ARG before anything touches the GPU.
+ * MFM_ERR_UNSUPPORTED with the size in the error text, nothing enqueued: an h_dims entry above 128, a windowsize other than 2,
+ * attention widths beyond the LDS, memsize or gamma widths beyond the register-resident memory recurrence, a label head's input
+ * and tail activations (the widest of zy, fy, output_dim, twice) beyond the LDS: run mfm_plan_forward(train = 0) instead.
+ * Stream-ordered, no host synchronisation, no allocation, legal inside a stream capture (no forked branches). */
+int64_t mfm_predict_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_mfn_tile_rows(int64_t N, int64_t max_rows);
+int mfm_predict_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, const float* params, const int64_t* offsets /*host, 38*/,
+                    const float* x, const void* y /*or NULL*/, float* workspace, float* y_hat /*[N, output_dim]*/,
+                    float* loss /*or NULL*/, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The gradient-based interpretation of the factorized model (csrc/influence.hip): how strongly the factors drive the generation
  * of each modality at each time step.  For decoder m = l, a, v with embedding e = [fy | f_m] of width h = fy + f_m
  * (mfm_model.py:644-656, decoderLSTM :64-91), from the deterministic eval computation (dropout the identity),
