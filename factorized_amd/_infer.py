@@ -1,14 +1,20 @@
 """The engine's no-plan inference entries: predict, encode, decode, objective, predict_zeros and influence_factors
 (`InferMixin`, a base of engine.MFMEngine).  Each is one C call of libmfm_hip.so on the current HIP stream -- no plan, no
-training workspace, the split walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all six go through
-one host path (encode has two library entries behind it: mfm_encode_klef for variant "kl_ef", mfm_encode_mfn for the variants
-"kl" and "mmd", whose label factor comes from the Memory Fusion Network; the latter keeps its state in
-`engine._encode_mfn_bufs` / `engine._encode_mfn_refused`; predict_zeros likewise: mfm_predict_zeros_klef, and
-mfm_predict_zeros_mfn with its state in `engine._zeros_mfn_bufs` / `engine._zeros_mfn_refused`; objective likewise:
-mfm_objective_klef, and mfm_objective_mfn with its state in `engine._objective_mfn_bufs` / `engine._objective_mfn_refused`; predict
-with label_only=True likewise: mfm_predict_klef, and mfm_predict_mfn with its state in `engine._predict_mfn_bufs` /
-`engine._predict_mfn_refused` -- without the keyword predict of the variants "kl" and "mmd" is the eval forward on a plan): the split
-validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner (`_run_fused`).
+training workspace, the split walked in chunks of at most `max_rows` rows (default PREDICT_MAX_ROWS) -- and all go through one
+host path: the split validation (`_check_split`), the parameter offsets table (`_offsets`) and the fused-entry runner
+(`_run_fused`).  The variants "kl" and "mmd", whose label factor comes from the Memory Fusion Network, have library functions and
+state caches of their own:
+
+    entry               "kl_ef"                    "kl", "mmd"                cache ("kl_ef" / "kl", "mmd")            refused
+    predict             mfm_predict_klef           the eval forward on a plan _predict_bufs / (the plan)               falls back
+      label_only=True   mfm_predict_klef           mfm_predict_mfn            _predict_bufs / _predict_mfn_bufs        falls back
+    encode              mfm_encode_klef            mfm_encode_mfn             _encode_bufs / _encode_mfn_bufs          raises
+    decode              mfm_decode_factors         mfm_decode_factors         _decode_bufs                             raises
+    objective           mfm_objective_klef         mfm_objective_mfn          _objective_bufs / _objective_mfn_bufs    falls back
+    predict_zeros       mfm_predict_zeros_klef     mfm_predict_zeros_mfn      _zeros_bufs / _zeros_mfn_bufs            falls back
+    influence_factors   mfm_influence_factors      mfm_influence_factors      _influence_bufs                          raises
+
+A cache `_<name>_bufs` remembers its refusal in `_<name>_refused` (`_ENTRIES` below).
 
 THE REUSE CONTRACT, the same for every entry: workspace and result tensors are kept per (T, N, max_rows) in
 `engine._<entry>_bufs` and REUSED.  After the first call for a shape nothing is allocated and nothing synchronises, and the
@@ -180,6 +186,16 @@ class InferMixin:
         return (C.c_int32 * 13)(c["zl_size"], c["za_size"], c["zv_size"], c["zy_size"], c["fl_size"], c["fa_size"], c["fv_size"],
                                 c["fy_size"], *c["input_dims"], c["output_dim"], 1 if c.get("loss", "l1") == "ce" else 0)
 
+    def _mfn_hidden(self, encoders, decoders):
+        """the recurrences of an MFN entry (variants "kl", "mmd"): the MFN's LSTMs, then the encoders and / or the decoders"""
+        c = self.cfg
+        return (tuple(c["h_dims"]) + ((c["zl_size"], c["za_size"], c["zv_size"]) if encoders else ())
+                + (self._hidden_sizes()[1:] if decoders else ()))
+
+    def _lambdas(self):
+        c = self.cfg
+        return (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"])
+
     def _run_fused(self, name, key, build, call, hidden):
         """One call of the fused entry `name` (a key of _ENTRIES) -> its state, or None: refused, now or remembered.  The state
         (workspace, result tensors, native tables) lives in `self._<name>_bufs[key]`: `build()` allocates it on a miss and it is
@@ -217,7 +233,7 @@ class InferMixin:
         """floats of workspace predict() keeps for a [T, N, D] split (mfm_predict_klef_workspace_floats; variants "kl" and "mmd"
         with label_only=True: mfm_predict_mfn_workspace_floats)"""
         if label_only and self.variant != "kl_ef":
-            return int(_lib.lib().mfm_predict_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
+            return int(_lib.lib().mfm_predict_mfn_workspace_floats(int(T), int(N), self._mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_predict_klef_workspace_floats(int(T), int(N), self._hidden_sizes()[0], self._row_cap(max_rows)))
 
     def predict(self, x, y=None, *, max_rows=None, label_only=False):
@@ -264,7 +280,7 @@ class InferMixin:
         """predict(label_only=True) of the variants "kl" and "mmd" through mfm_predict_mfn -> the entry's state (workspace,
         y_hat, the loss word, sizes, offsets), or None: refused"""
         def build():
-            sizes = self._zeros_mfn_sizes()
+            sizes = self._mfn_sizes()
             nws = int(_lib.lib().mfm_predict_mfn_workspace_floats(T, N, sizes, cap))
             return (self._empty(nws), self._empty(N, self.cfg["output_dim"]), torch.zeros((), dtype=torch.float32, device=self.device),
                     sizes, self._offsets(self._PREDICT_MFN_TENSORS))
@@ -274,7 +290,7 @@ class InferMixin:
             return fn(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(ws), _ptr(y_hat),
                       _ptr(loss) if y is not None else None, cap, _stream())
 
-        return self._run_fused("predict_mfn", (T, N, cap), build, call, tuple(self.cfg["h_dims"]))
+        return self._run_fused("predict_mfn", (T, N, cap), build, call, self._mfn_hidden(False, False))
 
     # ------------------------------------------------------------------ the factorized latents and generation from them
     def _encode_mfn_sizes(self):
@@ -341,8 +357,7 @@ class InferMixin:
             ws, _, offs, optr, sizes = st
             return fn(T, N, sizes, _ptr(self.params), offs, _ptr(x), _ptr(ws), optr, cap, _stream())
 
-        hidden = tuple(c["h_dims"]) + zsz[:3]
-        return Factors(*self._run_fused_or_raise("encode_mfn", (T, N, cap), build, call, hidden)[1])
+        return Factors(*self._run_fused_or_raise("encode_mfn", (T, N, cap), build, call, self._mfn_hidden(True, False))[1])
 
     def _check_factors(self, zl, za, zv, zy, T):
         c = self.cfg
@@ -430,7 +445,7 @@ class InferMixin:
         """floats of workspace objective() keeps for a [T, N, D] split (mfm_objective_klef_workspace_floats; variants "kl" and
         "mmd": mfm_objective_mfn_workspace_floats)"""
         if self.variant != "kl_ef":
-            return int(_lib.lib().mfm_objective_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
+            return int(_lib.lib().mfm_objective_mfn_workspace_floats(int(T), int(N), self._mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_objective_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
 
     def objective(self, x, y, *, max_rows=None):
@@ -463,7 +478,7 @@ class InferMixin:
             nws = int(_lib.lib().mfm_objective_klef_workspace_floats(T, N, sizes, cap))
             out = torch.zeros(6, dtype=torch.float32, device=self.device)
             return (self._empty(nws), out, Objective(*out.unbind(0)), sizes, self._offsets(self._ENCODE_TENSORS + self._DECODE_TENSORS),
-                    (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"]))
+                    self._lambdas())
 
         def call(fn, st):
             ws, out, _, sizes, offs, lda = st
@@ -493,12 +508,12 @@ class InferMixin:
                 N, gl, x.device, "%s %s %s" % (tuple(given.shape), given.dtype, given.device) if torch.is_tensor(given) else type(given)))
 
         def build():
-            sizes = self._zeros_mfn_sizes()
+            sizes = self._mfn_sizes()
             nws = int(_lib.lib().mfm_objective_mfn_workspace_floats(T, N, sizes, cap))
             out = torch.zeros(6, dtype=torch.float32, device=self.device)
             return (self._empty(nws), out, Objective(*out.unbind(0)), sizes,
-                    self._offsets(self._ENCODE_MFN_TENSORS[self.variant] + self._DECODE_TENSORS),
-                    (C.c_float * 4)(c["lda_xl"], c["lda_xa"], c["lda_xv"], c["lda_mmd"]), self._empty(N, gl) if mmd else None)
+                    self._offsets(self._ENCODE_MFN_TENSORS[self.variant] + self._DECODE_TENSORS), self._lambdas(),
+                    self._empty(N, gl) if mmd else None)
 
         def call(fn, st):
             ws, out, _, sizes, offs, lda, drawn = st
@@ -507,21 +522,23 @@ class InferMixin:
                 g = drawn.normal_()
             return fn(T, N, sizes, lda, _ptr(self.params), offs, _ptr(x), _ptr(y), _ptr(g), _ptr(ws), _ptr(out), cap, _stream())
 
-        hidden = tuple(c["h_dims"]) + (c["zl_size"], c["za_size"], c["zv_size"]) + self._hidden_sizes()[1:]
-        return self._run_fused("objective_mfn", (T, N, cap), build, call, hidden)
+        return self._run_fused("objective_mfn", (T, N, cap), build, call, self._mfn_hidden(True, True))
 
     # ------------------------------------------------------------------ the zeroed-modality test protocol
-    def _zeros_mfn_sizes(self):
-        """the 23 sizes of mfm_predict_zeros_mfn (include/mfm_hip.h): the 17 of mfm_encode_mfn, the f sizes, output_dim, loss kind"""
+    def _mfn_sizes(self):
+        """the 23 sizes of mfm_predict_zeros_mfn, mfm_objective_mfn and mfm_predict_mfn (include/mfm_hip.h): the 17 of
+        mfm_encode_mfn, the f sizes, output_dim, loss kind"""
         c = self.cfg
         return (C.c_int32 * 23)(*self._encode_mfn_sizes(), c["fl_size"], c["fa_size"], c["fv_size"], c["fy_size"], c["output_dim"],
                                 1 if c.get("loss", "l1") == "ce" else 0)
+
+    _zeros_mfn_sizes = _mfn_sizes      # the name from when predict_zeros alone used it: callers outside this file keep working
 
     def predict_zeros_workspace_floats(self, T, N, max_rows=None):
         """floats of workspace predict_zeros() keeps for a [T, N, D] split (mfm_predict_zeros_klef_workspace_floats; variants
         "kl" and "mmd": mfm_predict_zeros_mfn_workspace_floats)"""
         if self.variant != "kl_ef":
-            return int(_lib.lib().mfm_predict_zeros_mfn_workspace_floats(int(T), int(N), self._zeros_mfn_sizes(), self._row_cap(max_rows)))
+            return int(_lib.lib().mfm_predict_zeros_mfn_workspace_floats(int(T), int(N), self._mfn_sizes(), self._row_cap(max_rows)))
         return int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(int(T), int(N), self._objective_sizes(), self._row_cap(max_rows)))
 
     def predict_zeros(self, x, y=None, *, max_rows=None):
@@ -551,7 +568,7 @@ class InferMixin:
                 nws = int(_lib.lib().mfm_predict_zeros_klef_workspace_floats(T, N, sizes, cap))
                 offs = self._offsets(self._ENCODE_TENSORS + self._DECODE_TENSORS)
             else:
-                sizes = self._zeros_mfn_sizes()
+                sizes = self._mfn_sizes()
                 nws = int(_lib.lib().mfm_predict_zeros_mfn_workspace_floats(T, N, sizes, cap))
                 offs = self._offsets(self._ENCODE_MFN_TENSORS[self.variant] + self._DECODE_TENSORS)
             return (self._empty(nws), self._empty(3, N, od), torch.zeros(3, dtype=torch.float32, device=self.device),
@@ -565,8 +582,7 @@ class InferMixin:
         if klef:
             st = self._run_fused("zeros", (T, N, cap), build, call, self._hidden_sizes())
         else:
-            hidden = tuple(c["h_dims"]) + (c["zl_size"], c["za_size"], c["zv_size"]) + self._hidden_sizes()[1:]
-            st = self._run_fused("zeros_mfn", (T, N, cap), build, call, hidden)
+            st = self._run_fused("zeros_mfn", (T, N, cap), build, call, self._mfn_hidden(True, True))
         if st is not None:
             return Zeros(st[1], st[2], st[3] if y is not None else None)
         # (separate launches, as the eval-mode forward of the module path: inference has no optimizer guard to lean on)

@@ -16,9 +16,8 @@
 //      its records -- and ends with last_to_zy_fc1 (and the logvar head) on [h_l | h_a | h_v | mem].
 // A pair's and a row's arithmetic does not depend on its place in a tile or a chunk, nothing is accumulated across workgroups:
 // results are bit-identical from run to run, and for every chunking within one tile-row form of launch 2 (gen_tile_rows).
-// The kernels live in encode_mfn_dev.h: mfm_predict_zeros_mfn (zeros_mfn.hip) runs launches 3 and 4 too, on another gather.  The
-// host side of the four launches (emfn_front_prepare / emfn_front_chunk) lives in encode_mfn_front.h: mfm_objective_mfn
-// (objective_mfn.hip) runs them as they are run here.
+// The kernels and the host side every MFN entry shares live in encode_mfn_dev.h (its file head lists them); the walk over the four
+// launches (emfn_front_prepare / emfn_front_chunk) in encode_mfn_front.h, which mfm_objective_mfn (objective_mfn.hip) runs too.
 #include "encode_mfn_front.h"
 
 namespace mfm {
@@ -35,10 +34,8 @@ static int encode_mfn(int T, int64_t N, const int32_t* sz, const float* params, 
   if (rc != MFM_OK) return rc;
   EmfnWs W;
   emfn_ws(S, T, gen_rows(N, max_rows), W);
-  int64_t gates = 0;
-  for (int i = 0; i < EMFN_LSTMS; ++i) gates += W.gates[i];
   EmfnFront F;
-  if ((rc = emfn_front_prepare(who, T, N, S, params, offs, ws, ws + gates, max_rows, F)) != MFM_OK) return rc;
+  if ((rc = emfn_front_prepare(who, T, N, S, params, offs, ws, ws + W.all_gates, max_rows, F)) != MFM_OK) return rc;
   for (int64_t n0 = 0; n0 < N; n0 += F.rows) {
     const int n = (int)std::min<int64_t>(F.rows, N - n0);
     float* oc[8];

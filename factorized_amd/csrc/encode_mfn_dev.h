@@ -1,16 +1,21 @@
-// The Memory Fusion Network behind the MFN LSTMs, shared by encode_mfn.hip and zeros_mfn.hip: the attention chain
-// (encode_mfn_att_kernel) and the memory recurrence with the label head (encode_mfn_mem_kernel), the size array they are
-// described by and the host-side sizing of the two launches.  Template parameter ZC of both kernels: false, the rows of the
-// chain are the chunk's n rows (mfm_encode_mfn); true, they are the 3 n (case c, row i) of the zeroed-modality protocol, case
-// major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from the ONE row the MFN's LSTM c computes
-// on zero input (cz / hz), the other two modalities' from the real records.  Only the gather differs; the arithmetic of a row is
-// the same code.  encode_mfn.hip and objective_mfn.hip instantiate ZC = false, zeros_mfn.hip ZC = true.
+// The Memory Fusion Network behind the MFN LSTMs, shared by the four no-plan entries of MFM_KL and MFM (encode_mfn.hip,
+// objective_mfn.hip, zeros_mfn.hip, predict_mfn.hip): the attention chain (encode_mfn_att_kernel) and the memory recurrence with
+// the label head (encode_mfn_mem_kernel), the size arrays they are described by and the host side the entries have in common.
+// Template parameter ZC of both kernels: false, the rows of the chain are the chunk's n rows; true, they are the 3 n (case c, row
+// i) of the zeroed-modality protocol, case major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from
+// the ONE row the MFN's LSTM c computes on zero input (cz / hz), the other two modalities' from the real records.  Only the gather
+// differs; the arithmetic of a row is the same code.  zeros_mfn.hip alone instantiates ZC = true.
 // Template parameter TAIL of the memory recurrence (off by default; predict_mfn.hip alone turns it on, with ZC = false): zy stays
 // in LDS and the same workgroup goes on with zy_to_fy and the classifier, writes the row of y_hat and, with labels, the row's
 // loss contribution (EmfnTailDev); the other instantiations do not see any of it.
+// Host, shared by all four: the two size parsers (emfn_sizes, the 17 of mfm_encode_mfn; mfn_sizes, the MFN_SIZES of the other
+// three), the refusals (mfn_check_covered), the sizing of the two launches (emfn_chain_check / emfn_chain_fill) and the launches
+// themselves (emfn_att_launch, emfn_mem_launch, emfn_chain_launch), the workspace parts behind the x-projections (mfn_ws), the
+// MFN's three LSTMs of a call (MfnLstm, mfn_lstms_fill) and a chunk's grouped projection GEMM (mfn_xproj_chunk).
 // At the end of the file: the launch in front of the chain as mfm_encode_mfn runs it -- the six recurrences (encoder l, a, v with
 // their heads, the MFN's LSTMs with their cell-state records) in one launch, encode_mfn_seq_kernel, its workspace parts and its
-// launcher; encode_mfn_front.h walks them chunk by chunk for mfm_encode_mfn and mfm_objective_mfn (objective_mfn.hip).
+// launcher; encode_mfn_front.h walks them chunk by chunk for mfm_encode_mfn and mfm_objective_mfn.  Nothing above that section
+// names it: zeros_mfn.hip and predict_mfn.hip include this header and must not instantiate that kernel.
 #pragma once
 #include "infer_dev.h"
 
@@ -18,6 +23,7 @@ namespace mfm {
 
 #define EMFN_LSTMS 6          // encoder l, a, v, then the MFN's lstm l, a, v
 #define EMFN_SIZES 17
+#define MFN_SIZES 23          // the sizes of the entries with a back end: the 17, then fl, fa, fv, fy, output_dim, the loss kind
 #define EMFN_ATT_THREADS 512
 #define EMFN_SPARTS 16        // threads per pair in the softmax: fixed, the sums' order must not depend on the tile width
 #define EMFN_MAXW 32          // weights per thread and matrix of the memory recurrence
@@ -403,6 +409,22 @@ static bool emfn_sizes(const int32_t* sz, EmfnSizes& S) {
   return true;
 }
 
+// the MFN_SIZES sizes of mfm_predict_zeros_mfn, mfm_objective_mfn and mfm_predict_mfn: every one positive (those an entry does not
+// use too), heads and the loss kind 0 or 1.  dec: the twelve sizes of mfm_decode_factors
+struct MfnSizes { EmfnSizes E; int32_t dec[12]; int fy, od, loss_kind; };
+
+static bool mfn_sizes(const int32_t* sz, MfnSizes& Z) {
+  if (!emfn_sizes(sz, Z.E)) return false;
+  for (int i = 17; i < 22; ++i)
+    if (sz[i] < 1) return false;
+  if (sz[22] != 0 && sz[22] != 1) return false;
+  const EmfnSizes& S = Z.E;
+  const int32_t dec[12] = {S.z[0], S.z[1], S.z[2], S.zy, sz[17], sz[18], sz[19], sz[20], S.d[0], S.d[1], S.d[2], sz[21]};
+  memcpy(Z.dec, dec, sizeof(dec));
+  Z.fy = sz[20]; Z.od = sz[21]; Z.loss_kind = sz[22];
+  return true;
+}
+
 static int emfn_pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 static size_t emfn_att_lds_floats(const EmfnSizes& S, int CT) {
@@ -413,6 +435,21 @@ static size_t emfn_att_lds_floats(const EmfnSizes& S, int CT) {
 
 // ---------------------------------------------------------------- host: the two launches behind the MFN's LSTMs
 struct EmfnChain { EmfnAttDev A; EmfnMemDev Mm; int CT, mem_threads; size_t att_lds, mem_lds; };
+
+// what no kernel of an entry covers (MFM_ERR_UNSUPPORTED with the size in the error text): another window, an LSTM beyond the
+// resident recurrence.  enc: the entry runs the modality encoders too (z[i] is checked in front of hm[i])
+static int mfn_check_covered(const char* who, const EmfnSizes& S, bool enc) {
+  if (S.win != 2) {
+    set_error("%s: windowsize %d (the attention reads the cell states of exactly 2 steps)", who, S.win);
+    return MFM_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < 3; ++i) {
+    int rc;
+    if (enc && (rc = infer_check_resident(who, S.z[i])) != MFM_OK) return rc;
+    if ((rc = infer_check_resident(who, S.hm[i])) != MFM_OK) return rc;
+  }
+  return MFM_OK;
+}
 
 // what the two kernels do not cover (MFM_ERR_UNSUPPORTED with the size in the error text), and their sizing into a zeroed C;
 // pairs: the (step, row) pairs of a full chunk's attention chain
@@ -486,15 +523,70 @@ static int emfn_att_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
   return seq_launch_kernel(encode_mfn_att_kernel<1, ZC>, "encode_mfn_att_kernel", dim3((unsigned)((np + 15) / 16)), dim3(EMFN_ATT_THREADS), C.att_lds, stream, nullptr, A);
 }
 
+// the memory recurrence on the rows the attention chain was launched on; Mm: C.Mm, or (TAIL) the caller's copy of it with the tail
+template <bool ZC, bool TAIL = false>
+static int emfn_mem_launch(const EmfnChain& C, const std::conditional_t<TAIL, EmfnTailDev, EmfnMemDev>& Mm, hipStream_t stream) {
+  if (C.mem_threads <= 512)
+    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC, TAIL>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC, TAIL>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+}
+
 // the two launches on a chunk of n rows (ZC: the 3 n rows (case, row) behind them)
 template <bool ZC>
 static int emfn_chain_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
   const int rc = emfn_att_launch<ZC>(C, T, n, stream);
-  if (rc != MFM_OK) return rc;
-  const EmfnMemDev& Mm = C.Mm;
-  if (C.mem_threads <= 512)
-    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
-  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+  return rc != MFM_OK ? rc : emfn_mem_launch<ZC>(C, C.Mm, stream);
+}
+
+// ---------------------------------------------------------------- host: the MFN's three LSTMs of a call and what lies behind them
+// the workspace parts behind the x-projections, in floats and in this order, for chunks of `rows` rows: the c records and last
+// hidden states of the MFN's LSTMs, then cHat and the gamma partials of the chain's rows (cases: 1, or the 3 of the zeroed protocol)
+struct MfnWs { int64_t cs[3], hl[3], chat, g1p, g2p, total; };
+static MfnWs mfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, int cases) {
+  MfnWs W;
+  W.chat = up4(cases * rows * T * S.M); W.g1p = up4(cases * rows * T * S.H1); W.g2p = up4(cases * rows * T * S.H2);
+  W.total = W.chat + W.g1p + W.g2p;
+  for (int m = 0; m < 3; ++m) { W.cs[m] = rows * T * hp_of(S.hm[m]); W.hl[m] = up4(rows * S.hm[m]); W.total += W.cs[m] + W.hl[m]; }
+  return W;
+}
+
+// the first column of modality m in a row of x
+static int mfn_col(const EmfnSizes& S, int m) { return m == 0 ? 0 : (m == 1 ? S.d[0] : S.d[0] + S.d[1]); }
+
+// one LSTM of a call as the host walks it: where the caller's kernel argument keeps its SeqDev and (an MFN LSTM) its last hidden
+// states -- the entries' *One structs differ --, and the d columns of x from col on that it projects
+struct MfnLstm { SeqDev* seq; float** h_last; int col, d; };
+
+// the MFN's lstm l, a, v of a call, L[0 .. 3) with seq / h_last set by the caller: the cells from their twelve offsets, their
+// projections from `gates` on, their c records (A.cs) and last hidden states (Mm.hl) and the chain's buffers from `rest` on in
+// the order of mfn_ws; returns the end of those parts
+static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64_t T, int64_t rows, int cases, const float* params,
+                             const int64_t* cells, float* gates, float* rest) {
+  const MfnWs W = mfn_ws(S, T, rows, cases);
+  for (int m = 0; m < 3; ++m) {
+    const int64_t* o = cells + 4 * m;
+    seq_fill(*L[m].seq, params + o[0], params + o[1], params + o[2], params + o[3], S.hm[m], 0);
+    L[m].seq->gates = gates; gates += rows * T * 4 * hp_of(S.hm[m]);
+    L[m].col = mfn_col(S, m); L[m].d = S.d[m];
+  }
+  for (int m = 0; m < 3; ++m) { L[m].seq->cs = rest; C.A.cs[m] = rest; rest += W.cs[m]; }
+  for (int m = 0; m < 3; ++m) { *L[m].h_last = rest; C.Mm.hl[m] = rest; rest += W.hl[m]; }
+  C.A.chat = rest; rest += W.chat;
+  C.A.g1p = rest; rest += W.g1p;
+  C.A.g2p = rest; rest += W.g2p;
+  return rest;
+}
+
+// the x-projections of a chunk, rows [n0, n0 + n) of the split x [T, N, D], as ONE grouped GEMM: gates_e[t][i][g][u] =
+// x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh, pad units u >= h exact zeros.  One chunk: the T * N rows of x are one matrix and
+// an LSTM one problem; else one problem per LSTM and step
+static int mfn_xproj_chunk(int count, const MfnLstm* L, const float* x, int T, int64_t N, int D, int64_t n0, int n, hipStream_t stream) {
+  const bool whole = n == N;
+  return gemm_group_each(count * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
+    const int e = p % count, t = p / count;
+    const SeqDev& s = *L[e].seq;
+    xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + L[e].col, D, L[e].d, whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
+  });
 }
 
 // ---------------------------------------------------------------- the six recurrences (mfm_encode_mfn; mfm_objective_mfn launches them too)
@@ -546,14 +638,12 @@ __global__ __launch_bounds__(1024) void encode_mfn_seq_kernel(const EmfnSeqDev P
 // ---------------------------------------------------------------- host: the six recurrences
 static const int kEmfnCanon[EMFN_LSTMS] = {8, 2, 20, 22, 16, 12};      // encoders h = 32 / 8 / 80, the MFN's LSTMs h = 88 / 64 / 48
 
-// the parts of the workspace, in floats, for chunks of `rows` rows
-struct EmfnWs { int64_t gates[EMFN_LSTMS], cs[3], hl[3], chat, g1p, g2p, total; };
+// the parts of the workspace, in floats, for chunks of `rows` rows: the six x-projections, then mfn_ws
+struct EmfnWs { int64_t gates[EMFN_LSTMS], all_gates, total; };
 static void emfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, EmfnWs& W) {
-  W.total = 0;
-  for (int i = 0; i < EMFN_LSTMS; ++i) { W.gates[i] = rows * T * 4 * hp_of(i < 3 ? S.z[i] : S.hm[i - 3]); W.total += W.gates[i]; }
-  for (int m = 0; m < 3; ++m) { W.cs[m] = rows * T * hp_of(S.hm[m]); W.hl[m] = up4(rows * S.hm[m]); W.total += W.cs[m] + W.hl[m]; }
-  W.chat = up4(rows * T * S.M); W.g1p = up4(rows * T * S.H1); W.g2p = up4(rows * T * S.H2);
-  W.total += W.chat + W.g1p + W.g2p;
+  W.all_gates = 0;
+  for (int i = 0; i < EMFN_LSTMS; ++i) { W.gates[i] = rows * T * 4 * hp_of(i < 3 ? S.z[i] : S.hm[i - 3]); W.all_gates += W.gates[i]; }
+  W.total = W.all_gates + mfn_ws(S, T, rows, 1).total;
 }
 
 // the launch(es) of the six recurrences on a chunk of P.n rows: P.d[0 .. EMFN_LSTMS) filled but for block_begin

@@ -20,12 +20,11 @@
 //      a fixed order, ONE partial into its own slot -- and objective_mfn_mmd_finish_kernel, which adds the partials of each term
 //      in ascending order in fp64, scales by 1 / N^2, forms the total and writes the six floats.
 // No gradient, no [N, N] scratch, no float atomics: the six results are bit-identical from run to run for a given (T, N,
-// max_rows) and, without heads, a given gauss.
+// max_rows) and, without heads, a given gauss.  The parser of the MFN_SIZES sizes (mfn_sizes) is that of encode_mfn_dev.h.
 #include "encode_mfn_front.h"
 
 namespace mfm {
 
-#define OMFN_SIZES 23
 #define OMFN_JT 32          // rows j per LDS tile of the MMD
 
 struct OmfnMmdTerm { const float* z; const float* g; int dim, pad_; };      // z [N, dim] contiguous; g: rows ldg apart
@@ -123,20 +122,6 @@ __global__ __launch_bounds__(64) void objective_mfn_mmd_finish_kernel(const Omfn
 }
 
 // ---------------------------------------------------------------- host
-struct OmfnSizes { EmfnSizes E; int32_t dec[12]; int loss_kind; };      // dec: the twelve sizes of mfm_decode_factors
-
-static bool omfn_sizes(const int32_t* sz, OmfnSizes& Z) {
-  if (!emfn_sizes(sz, Z.E)) return false;
-  for (int i = 17; i < 22; ++i)
-    if (sz[i] < 1) return false;
-  if (sz[22] != 0 && sz[22] != 1) return false;
-  const EmfnSizes& S = Z.E;
-  const int32_t dec[12] = {S.z[0], S.z[1], S.z[2], S.zy, sz[17], sz[18], sz[19], sz[20], S.d[0], S.d[1], S.d[2], sz[21]};
-  memcpy(Z.dec, dec, sizeof(dec));
-  Z.loss_kind = sz[22];
-  return true;
-}
-
 // rows i per workgroup of the MMD, and its workgroups (= partial slots) per term
 static int omfn_mmd_rows(int64_t N) { return N <= 256 ? 8 : 32; }
 static int64_t omfn_mmd_tiles(int64_t N) { return (N + omfn_mmd_rows(N) - 1) / omfn_mmd_rows(N); }
@@ -146,16 +131,15 @@ static int64_t omfn_mmd_tiles(int64_t N) { return (N + omfn_mmd_rows(N) - 1) / o
 // projections (c records, last hidden states, cHat, the gamma partials); the factors -- with heads the chunk's four means and
 // four log-variances, without the four whole-split means; the chunk's y_hat; its squared-error partials; without heads the
 // MMD's partials; the fp64 accumulators
-struct OmfnLayout { EmfnWs W; int64_t gates, o_cs, zpart[4], o_z, o_yhat, o_part, o_mmd, o_acc, total; };
-static OmfnLayout omfn_layout(const OmfnSizes& Z, int64_t T, int64_t N, int64_t max_rows) {
+struct OmfnLayout { int64_t o_cs, zpart[4], o_z, o_yhat, o_part, o_mmd, o_acc, total; };
+static OmfnLayout omfn_layout(const MfnSizes& Z, int64_t T, int64_t N, int64_t max_rows) {
   const EmfnSizes& S = Z.E;
   const int64_t rows = gen_rows(N, max_rows);
   OmfnLayout L;
-  emfn_ws(S, T, rows, L.W);
-  L.gates = 0;
-  for (int i = 0; i < EMFN_LSTMS; ++i) L.gates += L.W.gates[i];
-  L.o_cs = std::max(L.gates, decode_ws_floats(T, N, Z.dec[7], Z.dec[4], Z.dec[5], Z.dec[6], max_rows));
-  L.o_z = L.o_cs + (L.W.total - L.gates);
+  EmfnWs W;
+  emfn_ws(S, T, rows, W);
+  L.o_cs = std::max(W.all_gates, decode_ws_floats(T, N, Z.dec[7], Z.dec[4], Z.dec[5], Z.dec[6], max_rows));
+  L.o_z = L.o_cs + (W.total - W.all_gates);
   int64_t zf = 0;
   for (int i = 0; i < 4; ++i) { L.zpart[i] = up4((S.heads ? rows : N) * Z.dec[i]); zf += L.zpart[i]; }
   L.o_yhat = L.o_z + (S.heads ? 2 : 1) * zf;
@@ -169,9 +153,9 @@ static OmfnLayout omfn_layout(const OmfnSizes& Z, int64_t T, int64_t N, int64_t 
 static int objective_mfn(int T, int64_t N, const int32_t* sz, const float* lambdas, const float* params, const int64_t* offs,
                          const float* x, const void* y, const float* gauss, float* ws, float* out, int64_t max_rows, hipStream_t stream) {
   static const char* who = "objective mfn";
-  OmfnSizes Z;
-  MFM_REQUIRE(T >= 1 && N >= 1 && omfn_sizes(sz, Z),
-              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, OMFN_SIZES);
+  MfnSizes Z;
+  MFM_REQUIRE(T >= 1 && N >= 1 && mfn_sizes(sz, Z),
+              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, MFN_SIZES);
   MFM_REQUIRE(lambdas && params && offs && x && y && ws && out,
               "%s: bad arguments (lambdas, params, offsets, x, y, workspace and out must not be null)", who);
   const EmfnSizes& S = Z.E;
@@ -185,7 +169,7 @@ static int objective_mfn(int T, int64_t N, const int32_t* sz, const float* lambd
   const OmfnLayout lay = omfn_layout(Z, T, N, max_rows);
   EmfnFront F;
   if ((rc = emfn_front_prepare(who, T, N, S, params, offs, ws, ws + lay.o_cs, max_rows, F)) != MFM_OK) return rc;
-  const int od = Z.dec[11], loss_kind = Z.loss_kind, rows = F.rows, o_dec = F.n_offs;
+  const int od = Z.od, loss_kind = Z.loss_kind, rows = F.rows, o_dec = F.n_offs;
   DecLaunch Dl;
   Fc1SqLaunch Sq;
   if ((rc = decode_factors_prepare(who, T, N, Z.dec, params, offs + o_dec, ws, max_rows, Dl)) != MFM_OK) return rc;
@@ -267,8 +251,8 @@ static int objective_mfn(int T, int64_t N, const int32_t* sz, const float* lambd
 }  // namespace mfm
 
 extern "C" int64_t mfm_objective_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes, int64_t max_rows) {
-  mfm::OmfnSizes Z;
-  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::omfn_sizes(sizes, Z)) return 0;
+  mfm::MfnSizes Z;
+  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::mfn_sizes(sizes, Z)) return 0;
   return mfm::omfn_layout(Z, T, N, max_rows).total;
 }
 

@@ -18,12 +18,13 @@
 // waits or spins: y_hat and the loss are bit-identical from run to run for a given (T, N, max_rows); a row's arithmetic does not
 // depend on its place in a tile or a chunk, so y_hat is bit-identical for every chunking within one tile-row form of launch 2.
 // Launch 2 follows the launch rules of infer_dev.h: the per-block switch for the canonical size tuple only, else one launch per LSTM.
+// The host side of launches 1, 3 and 4, the size parser, the refusals and the workspace parts behind the projections are the
+// shared ones of encode_mfn_dev.h (its file head lists them); here: launch 2, the tail's arguments and the loss words.
 #include "encode_mfn_dev.h"
 
 namespace mfm {
 
 #define PMFN_LSTMS 3
-#define PMFN_SIZES 23
 #define PMFN_OFFS 38          // 12 of the MFN's LSTM cells, 16 of its attention and gamma networks, 2 of last_to_zy_fc1, 8 of the tail
 
 struct PmfnOne {
@@ -48,33 +49,15 @@ __global__ __launch_bounds__(1024) void predict_mfn_seq_kernel(const PmfnSeqDev 
 // ---------------------------------------------------------------- host
 static const int kPmfnCanon[PMFN_LSTMS] = {22, 16, 12};      // the MFN's LSTMs h = 88 / 64 / 48
 
-struct PmfnSizes { EmfnSizes E; int fy, od, loss_kind, tailw; };
-
-// the encoders' z sizes and fl / fa / fv: positive, otherwise unused; heads: 0 or 1, otherwise unused
-static bool pmfn_sizes(const int32_t* sz, PmfnSizes& Z) {
-  if (!emfn_sizes(sz, Z.E)) return false;
-  for (int i = 17; i < 22; ++i)
-    if (sz[i] < 1) return false;
-  if (sz[22] != 0 && sz[22] != 1) return false;
-  Z.fy = sz[20]; Z.od = sz[21]; Z.loss_kind = sz[22];
-  Z.tailw = round_up(std::max(Z.E.zy, std::max(Z.fy, Z.od)), 4);      // the widest activation of the tail
-  return true;
-}
-
 // the workspace, in this order (every part a multiple of 4 floats; include/mfm_hip.h states it term by term): the chunk's three
-// x-projections; the c records and last hidden states; cHat and the gamma partials; one loss contribution per chunk row; the
-// fp64 running sum, the ticket word and a pad
-struct PmfnLayout { int64_t gates[PMFN_LSTMS], cs[PMFN_LSTMS], hl[PMFN_LSTMS], chat, g1p, g2p, o_row, o_acc, total; };
-static PmfnLayout pmfn_layout(const PmfnSizes& Z, int64_t T, int64_t N, int64_t max_rows) {
-  const EmfnSizes& S = Z.E;
+// x-projections; the parts of mfn_ws; one loss contribution per chunk row; the fp64 running sum, the ticket word and a pad
+struct PmfnLayout { int64_t o_cs, o_row, o_acc, total; };
+static PmfnLayout pmfn_layout(const EmfnSizes& S, int64_t T, int64_t N, int64_t max_rows) {
   const int64_t rows = gen_rows(N, max_rows);
   PmfnLayout L;
-  int64_t o = 0;
-  for (int m = 0; m < PMFN_LSTMS; ++m) { L.gates[m] = rows * T * 4 * hp_of(S.hm[m]); o += L.gates[m]; }
-  for (int m = 0; m < PMFN_LSTMS; ++m) { L.cs[m] = rows * T * hp_of(S.hm[m]); L.hl[m] = up4(rows * S.hm[m]); o += L.cs[m] + L.hl[m]; }
-  L.chat = up4(rows * T * S.M); L.g1p = up4(rows * T * S.H1); L.g2p = up4(rows * T * S.H2);
-  o += L.chat + L.g1p + L.g2p;
-  L.o_row = o;
+  L.o_cs = 0;
+  for (int m = 0; m < PMFN_LSTMS; ++m) L.o_cs += rows * T * 4 * hp_of(S.hm[m]);
+  L.o_row = L.o_cs + mfn_ws(S, T, rows, 1).total;
   L.o_acc = L.o_row + up4(rows);
   L.total = L.o_acc + 4;
   return L;
@@ -91,9 +74,9 @@ static int pmfn_seq_launch(const char* who, PmfnSeqDev& P, int threads, size_t l
 static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* x, const void* y,
                        float* ws, float* y_hat, float* loss, int64_t max_rows, hipStream_t stream) {
   static const char* who = "predict mfn";
-  PmfnSizes Z;
-  MFM_REQUIRE(T >= 1 && N >= 1 && pmfn_sizes(sz, Z),
-              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, PMFN_SIZES);
+  MfnSizes Z;      // (the encoders' z sizes, fl / fa / fv and heads: checked, otherwise unused)
+  MFM_REQUIRE(T >= 1 && N >= 1 && mfn_sizes(sz, Z),
+              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, MFN_SIZES);
   MFM_REQUIRE(params && offs && x && ws && y_hat, "%s: bad arguments (params, offsets, x, workspace and y_hat must not be null)", who);
   MFM_REQUIRE((y != nullptr) == (loss != nullptr), "%s: labels and loss come together (both, or both null)", who);
   const EmfnSizes& S = Z.E;
@@ -102,18 +85,10 @@ static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params,
   if ((rc = infer_check_rows(who, N, max_rows)) != MFM_OK) return rc;
   const int o_att = 4 * PMFN_LSTMS, o_zy = o_att + 16, o_tail = o_zy + 2;
   if ((rc = infer_check_offsets(who, offs, PMFN_OFFS, 4, 0, o_att)) != MFM_OK) return rc;
-
-  // ---- what the kernels do not cover
-  if (S.win != 2) {
-    set_error("%s: windowsize %d (the attention reads the cell states of exactly 2 steps)", who, S.win);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  int hmax = 1;
-  for (int m = 0; m < PMFN_LSTMS; ++m) {
-    if ((rc = infer_check_resident(who, S.hm[m])) != MFM_OK) return rc;
-    hmax = std::max(hmax, S.hm[m]);
-  }
+  if ((rc = mfn_check_covered(who, S, false)) != MFM_OK) return rc;
+  const int hmax = std::max(S.hm[0], std::max(S.hm[1], S.hm[2]));
   const int D = S.d[0] + S.d[1] + S.d[2], od = Z.od, loss_kind = Z.loss_kind;
+  const int tailw = round_up(std::max(S.zy, std::max(Z.fy, od)), 4);      // the widest activation of the tail
   const int rows = (int)gen_rows(N, max_rows);
   const int R = gen_tile_rows(PMFN_LSTMS, rows);
   const int threads = std::max(64, 8 * round_up(hmax, 16));
@@ -122,29 +97,18 @@ static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params,
   const size_t seq_lds = lds_bytes_of(seq_floats);
   if ((rc = infer_check_lds(who, seq_lds, hmax, R)) != MFM_OK) return rc;
   EmfnChain C;
-  if ((rc = emfn_chain_check(who, S, (int64_t)T * rows, C, Z.tailw)) != MFM_OK) return rc;
+  if ((rc = emfn_chain_check(who, S, (int64_t)T * rows, C, tailw)) != MFM_OK) return rc;
   if ((rc = infer_check_chunk(who, rows, T, std::max(std::max(D, 4 * round_up(hmax, 16)), std::max(S.M, std::max(S.H1, S.H2))), "projection")) != MFM_OK)
     return rc;
 
   // ---- everything that does not depend on the chunk
-  const PmfnLayout lay = pmfn_layout(Z, T, N, max_rows);
+  const PmfnLayout lay = pmfn_layout(S, T, N, max_rows);
   PmfnSeqDev P;
   memset(&P, 0, sizeof(P));
-  EmfnAttDev& A = C.A;
   emfn_chain_fill(C, S, T, params, offs + o_att, offs + o_zy, 1);
-  int col[PMFN_LSTMS];
-  float* w0 = ws;
-  for (int m = 0; m < PMFN_LSTMS; ++m) {
-    const int64_t* o = offs + 4 * m;
-    seq_fill(P.d[m].seq, params + o[0], params + o[1], params + o[2], params + o[3], S.hm[m], 0);
-    P.d[m].seq.gates = w0; w0 += lay.gates[m];
-    col[m] = m == 0 ? 0 : (m == 1 ? S.d[0] : S.d[0] + S.d[1]);
-  }
-  for (int m = 0; m < PMFN_LSTMS; ++m) { P.d[m].seq.cs = w0; A.cs[m] = w0; w0 += lay.cs[m]; }
-  for (int m = 0; m < PMFN_LSTMS; ++m) { P.d[m].h_last = w0; C.Mm.hl[m] = w0; w0 += lay.hl[m]; }
-  A.chat = w0; w0 += lay.chat;
-  A.g1p = w0; w0 += lay.g1p;
-  A.g2p = w0; w0 += lay.g2p;
+  MfnLstm L[PMFN_LSTMS];
+  for (int m = 0; m < PMFN_LSTMS; ++m) L[m] = MfnLstm{&P.d[m].seq, &P.d[m].h_last, 0, 0};
+  mfn_lstms_fill(L, C, S, T, rows, 1, params, offs, ws, ws + lay.o_cs);
   P.count = PMFN_LSTMS; P.T = T;
 
   EmfnTailDev Q;
@@ -155,19 +119,13 @@ static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params,
   Q.ticket = reinterpret_cast<int*>(ws + lay.o_acc + 2);
   Q.loss = loss;
   Q.inv = inv_label_count(loss_kind, N, od);
-  Q.fy = Z.fy; Q.od = od; Q.loss_kind = loss_kind; Q.tailw = Z.tailw;
+  Q.fy = Z.fy; Q.od = od; Q.loss_kind = loss_kind; Q.tailw = tailw;
   // (a call that ended in an error between two launches may have left arrivals behind)
   if (loss) MFM_HIP_CHECK(hipMemsetAsync(Q.ticket, 0, sizeof(int), stream));
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
-    const bool whole = n == N;           // one chunk: the T * N rows of x are one matrix
-    // gates_m[t][i][g][u] = x_m[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
-    rc = gemm_group_each(PMFN_LSTMS * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
-      const int m = p % PMFN_LSTMS, t = p / PMFN_LSTMS;
-      const SeqDev& s = P.d[m].seq;
-      xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + col[m], D, S.d[m], whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
-    });
+    rc = mfn_xproj_chunk(PMFN_LSTMS, L, x, T, N, D, n0, n, stream);
     if (rc != MFM_OK) return rc;
     P.n = n;
     rc = (R == 1) ? pmfn_seq_launch<1>(who, P, threads, seq_lds, stream) : pmfn_seq_launch<4>(who, P, threads, seq_lds, stream);
@@ -177,9 +135,7 @@ static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params,
     Q.y = labels_at(y, loss_kind, n0, od);
     Q.y_hat = y_hat + n0 * od;
     Q.first = n0 == 0; Q.last = n0 + n == N;
-    rc = (C.mem_threads <= 512)
-      ? seq_launch_kernel(encode_mfn_mem_kernel<512, false, true>, "encode_mfn_mem_kernel", dim3(n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Q)
-      : seq_launch_kernel(encode_mfn_mem_kernel<1024, false, true>, "encode_mfn_mem_kernel", dim3(n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Q);
+    rc = emfn_mem_launch<false, true>(C, Q, stream);
     if (rc != MFM_OK) return rc;
   }
   return MFM_OK;
@@ -188,9 +144,9 @@ static int predict_mfn(int T, int64_t N, const int32_t* sz, const float* params,
 }  // namespace mfm
 
 extern "C" int64_t mfm_predict_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes, int64_t max_rows) {
-  mfm::PmfnSizes Z;
-  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::pmfn_sizes(sizes, Z)) return 0;
-  return mfm::pmfn_layout(Z, T, N, max_rows).total;
+  mfm::MfnSizes Z;
+  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::mfn_sizes(sizes, Z)) return 0;
+  return mfm::pmfn_layout(Z.E, T, N, max_rows).total;
 }
 
 extern "C" int mfm_predict_mfn_tile_rows(int64_t N, int64_t max_rows) {

@@ -25,12 +25,13 @@
 // No float atomics: the results are bit-identical from run to run for a given (T, N, max_rows); a row's arithmetic does not
 // depend on its place in a tile or a chunk, so y_hat is bit-identical for every chunking within one tile-row form.  Launch 2
 // follows the launch rules of infer_dev.h: the per-block switch for the canonical size tuple only, else one launch per LSTM.
+// The host side of launches 1, 3 and 4, the size parser, the refusals and the workspace parts behind the projections are the
+// shared ones of encode_mfn_dev.h (its file head lists them); here: launch 2 with its one-row recurrences and the back end.
 #include "encode_mfn_dev.h"
 
 namespace mfm {
 
 #define ZMFN_LSTMS 9          // the MFN's lstm l, a, v on x; the same three on zero input; encoder l, a, v on zero input
-#define ZMFN_SIZES 23
 
 struct ZmfnOne {
   SeqDev seq;                                  // gates (read only), w_hh, h, Hp, hk4; an MFN LSTM: cs [T, n, Hp]
@@ -93,36 +94,19 @@ __global__ __launch_bounds__(256) void zeros_mfn_cgates_kernel(const ZmfnGatesDe
 // ---------------------------------------------------------------- host
 static const int kZmfnCanon[6] = {22, 16, 12, 8, 2, 20};      // the MFN's LSTMs h = 88 / 64 / 48, encoders h = 32 / 8 / 80
 
-struct ZmfnSizes { EmfnSizes E; int32_t dec[12]; int loss_kind; };      // dec: the twelve sizes of mfm_decode_factors
-
-static bool zmfn_sizes(const int32_t* sz, ZmfnSizes& Z) {
-  if (!emfn_sizes(sz, Z.E)) return false;
-  for (int i = 17; i < 22; ++i)
-    if (sz[i] < 1) return false;
-  if (sz[22] != 0 && sz[22] != 1) return false;
-  const EmfnSizes& S = Z.E;
-  const int32_t dec[12] = {S.z[0], S.z[1], S.z[2], S.zy, sz[17], sz[18], sz[19], sz[20], S.d[0], S.d[1], S.d[2], sz[21]};
-  memcpy(Z.dec, dec, sizeof(dec));
-  Z.loss_kind = sz[22];
-  return true;
-}
-
 // the workspace, in this order (every part a multiple of 4 floats; include/mfm_hip.h states it term by term): the chunk's three
-// x-projections and, behind the recurrences, the decoders' h in the same place; the real c records and last hidden states; cHat
-// and the gamma partials of the 3 rows T triples; the six constant gate sets; the one-row c records and last hidden states; the
-// zeroed encoders' factors, one row per chunk row; zy of the three cases; the squared-error partials; the fp64 accumulators
-struct ZmfnLayout { int64_t gates[3], cs[3], hl[3], chat, g1p, g2p, cg[6], cz[3], hz[3], zc[3], o_cs, o_zy, o_part, o_acc, total; };
-static ZmfnLayout zmfn_layout(const ZmfnSizes& Z, int64_t T, int64_t N, int64_t max_rows) {
+// x-projections and, behind the recurrences, the decoders' h in the same place; the parts of mfn_ws, the chain's buffers for the 3
+// rows T triples; the six constant gate sets; the one-row c records and last hidden states; the zeroed encoders' factors, one row
+// per chunk row; zy of the three cases; the squared-error partials; the fp64 accumulators
+struct ZmfnLayout { int64_t cg[6], cz[3], hz[3], zc[3], o_cs, o_zy, o_part, o_acc, total; };
+static ZmfnLayout zmfn_layout(const MfnSizes& Z, int64_t T, int64_t N, int64_t max_rows) {
   const EmfnSizes& S = Z.E;
   const int64_t rows = gen_rows(N, max_rows);
   ZmfnLayout L;
   int64_t g = 0;
-  for (int m = 0; m < 3; ++m) { L.gates[m] = rows * T * 4 * hp_of(S.hm[m]); g += L.gates[m]; }
+  for (int m = 0; m < 3; ++m) g += rows * T * 4 * hp_of(S.hm[m]);
   L.o_cs = std::max(g, decode_ws_floats(T, N, Z.dec[7], Z.dec[4], Z.dec[5], Z.dec[6], max_rows));
-  int64_t o = L.o_cs;
-  for (int m = 0; m < 3; ++m) { L.cs[m] = rows * T * hp_of(S.hm[m]); L.hl[m] = up4(rows * S.hm[m]); o += L.cs[m] + L.hl[m]; }
-  L.chat = up4(3 * rows * T * S.M); L.g1p = up4(3 * rows * T * S.H1); L.g2p = up4(3 * rows * T * S.H2);
-  o += L.chat + L.g1p + L.g2p;
+  int64_t o = L.o_cs + mfn_ws(S, T, rows, 3).total;
   for (int i = 0; i < 6; ++i) { L.cg[i] = T * 4 * hp_of(i < 3 ? S.hm[i] : S.z[i - 3]); o += L.cg[i]; }
   for (int m = 0; m < 3; ++m) { L.cz[m] = T * hp_of(S.hm[m]); L.hz[m] = up4(S.hm[m]); L.zc[m] = up4(rows * S.z[m]); o += L.cz[m] + L.hz[m] + L.zc[m]; }
   L.o_zy = o;
@@ -162,9 +146,9 @@ static int zmfn_seq_launch(const char* who, ZmfnSeqDev& P, bool canon, int threa
 static int predict_zeros_mfn(int T, int64_t N, const int32_t* sz, const float* params, const int64_t* offs, const float* x,
                              const void* y, float* ws, float* y_hat, float* gen, float* disc, int64_t max_rows, hipStream_t stream) {
   static const char* who = "predict zeros mfn";
-  ZmfnSizes Z;
-  MFM_REQUIRE(T >= 1 && N >= 1 && zmfn_sizes(sz, Z),
-              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, ZMFN_SIZES);
+  MfnSizes Z;
+  MFM_REQUIRE(T >= 1 && N >= 1 && mfn_sizes(sz, Z),
+              "%s: sizes must be positive (T %d, N %lld, and the %d sizes; heads and the loss kind 0 or 1)", who, T, (long long)N, MFN_SIZES);
   MFM_REQUIRE(params && offs && x && ws && y_hat && gen,
               "%s: bad arguments (params, offsets, x, workspace, y_hat and gen must not be null)", who);
   MFM_REQUIRE((y != nullptr) == (disc != nullptr), "%s: labels and disc come together (both, or both null)", who);
@@ -176,17 +160,8 @@ static int predict_zeros_mfn(int T, int64_t N, const int32_t* sz, const float* p
   const int EO = S.heads ? 10 : 6, o_mfn = 3 * EO, o_att = o_mfn + 12, o_zy = o_att + 16, o_dec = o_zy + (S.heads ? 4 : 2);
   if ((rc = infer_check_offsets(who, offs, o_mfn, EO)) != MFM_OK) return rc;
   if ((rc = infer_check_offsets(who, offs + o_mfn, o_dec - o_mfn, 4, 0, 12)) != MFM_OK) return rc;
-
-  // ---- what the kernels do not cover
-  if (S.win != 2) {
-    set_error("%s: windowsize %d (the attention reads the cell states of exactly 2 steps)", who, S.win);
-    return MFM_ERR_UNSUPPORTED;
-  }
-  for (int i = 0; i < 3; ++i) {
-    if ((rc = infer_check_resident(who, S.z[i])) != MFM_OK) return rc;
-    if ((rc = infer_check_resident(who, S.hm[i])) != MFM_OK) return rc;
-  }
-  const int D = S.d[0] + S.d[1] + S.d[2], od = Z.dec[11], loss_kind = Z.loss_kind;
+  if ((rc = mfn_check_covered(who, S, true)) != MFM_OK) return rc;
+  const int D = S.d[0] + S.d[1] + S.d[2], od = Z.od, loss_kind = Z.loss_kind;
   const int rows = (int)gen_rows(N, max_rows);
   const int R = gen_tile_rows(3, rows);
   int maxw = 1, hmax = 1, threads = 64;
@@ -219,24 +194,14 @@ static int predict_zeros_mfn(int T, int64_t N, const int32_t* sz, const float* p
   EmfnAttDev& A = C.A;
   EmfnMemDev& Mm = C.Mm;
   emfn_chain_fill(C, S, T, params, offs + o_att, offs + o_zy, 1);
-  int col[3];
+  MfnLstm L[3];
   float* zc[3];
   {
-    float* w0 = ws;
-    for (int m = 0; m < 3; ++m) {          // the MFN's LSTMs on x
-      ZmfnOne& E = P.d[m];
-      const int64_t* o = offs + o_mfn + 4 * m;
-      seq_fill(E.seq, params + o[0], params + o[1], params + o[2], params + o[3], S.hm[m], 0);
-      E.seq.gates = w0; w0 += lay.gates[m];
-      E.slot = m;
-      col[m] = m == 0 ? 0 : (m == 1 ? S.d[0] : S.d[0] + S.d[1]);
+    for (int m = 0; m < 3; ++m) {          // the MFN's LSTMs on x; the chain's buffers hold the 3 cases
+      L[m] = MfnLstm{&P.d[m].seq, &P.d[m].h_last, 0, 0};
+      P.d[m].slot = m;
     }
-    w0 = ws + lay.o_cs;
-    for (int m = 0; m < 3; ++m) { P.d[m].seq.cs = w0; A.cs[m] = w0; w0 += lay.cs[m]; }
-    for (int m = 0; m < 3; ++m) { P.d[m].h_last = w0; Mm.hl[m] = w0; w0 += lay.hl[m]; }
-    A.chat = w0; w0 += lay.chat;
-    A.g1p = w0; w0 += lay.g1p;
-    A.g2p = w0; w0 += lay.g2p;
+    float* w0 = mfn_lstms_fill(L, C, S, T, rows, 3, params, offs + o_mfn, ws, ws + lay.o_cs);
     for (int i = 0; i < 6; ++i) {          // the six one-row recurrences: the MFN's LSTMs, then the encoders, on zero input
       ZmfnOne& E = P.d[3 + i];
       const int m = i % 3;
@@ -276,13 +241,8 @@ static int predict_zeros_mfn(int T, int64_t N, const int32_t* sz, const float* p
 
   for (int64_t n0 = 0; n0 < N; n0 += rows) {
     const int n = (int)std::min<int64_t>(rows, N - n0);
-    const bool whole = n == N, first = n0 == 0;
-    // gates_m[t][i][g][u] = x_m[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros
-    rc = gemm_group_each(3 * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
-      const int m = p % 3, t = p / 3;
-      const SeqDev& s = P.d[m].seq;
-      xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + col[m], D, S.d[m], whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
-    });
+    const bool first = n0 == 0;
+    rc = mfn_xproj_chunk(3, L, x, T, N, D, n0, n, stream);
     if (rc != MFM_OK) return rc;
     if (first) {
       zeros_mfn_cgates_kernel<<<dim3(8), dim3(256), 0, stream>>>(G);
@@ -313,8 +273,8 @@ static int predict_zeros_mfn(int T, int64_t N, const int32_t* sz, const float* p
 }  // namespace mfm
 
 extern "C" int64_t mfm_predict_zeros_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes, int64_t max_rows) {
-  mfm::ZmfnSizes Z;
-  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::zmfn_sizes(sizes, Z)) return 0;
+  mfm::MfnSizes Z;
+  if (T < 1 || N < 1 || max_rows < 0 || !sizes || !mfm::mfn_sizes(sizes, Z)) return 0;
   return mfm::zmfn_layout(Z, T, N, max_rows).total;
 }
 

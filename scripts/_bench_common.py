@@ -1,6 +1,6 @@
 """What the feature bench scripts share (bench_dropin, bench_keepbest, bench_plateau, bench_predict, bench_swa, bench_clip,
-bench_shuffle): the MOSI set-up, the reference's unchanged training loop, the host-clock timers and the recorder of what a
-script prints.  Importing it puts the repository on sys.path."""
+bench_shuffle, and bench_zeros, bench_objective and their *_mfn kin): the MOSI set-up, the reference's unchanged training loop, the
+host-clock timers, what the inference benches measure with (peak_of, median, captured) and the recorder of what a script prints.  Importing it puts the repository on sys.path."""
 import os
 import sys
 import time
@@ -77,6 +77,34 @@ def timed(fn, n, warmup):
         for _ in range(k):
             fn()
     return timed_steps(run, n, min(warmup, n))
+
+
+def peak_of(fn):
+    """peak device memory of a first call of `fn` (its buffers included) beyond what is allocated now, in bytes"""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    keep = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del keep
+    return peak
+
+
+def median(v):
+    """(the median of the rounds, their spread max - min)"""
+    v = sorted(v)
+    return v[len(v) // 2], v[-1] - v[0]
+
+
+def captured(fn):
+    """one call of `fn` captured as a graph on the current device"""
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        fn()
+    return graph
 
 
 # ---------------------------------------------------------------------- the record of a run

@@ -18,7 +18,7 @@ import argparse
 
 import torch
 
-from _bench_common import batch, cfgs, need_gpu, say, timed, write_out
+from _bench_common import batch, captured, cfgs, need_gpu, peak_of, say, timed, write_out
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
 
 FORMS = ["ref_forward", "new_eager", "new_graph"]
@@ -45,19 +45,6 @@ def six(l):
     return out
 
 
-def peak_of(fn):
-    """peak device memory of a first call of `fn` (its buffers included) beyond what is allocated now, in bytes"""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del keep
-    return peak
-
-
 med_all = {}
 for N, T in SHAPES:
     X, y = batch(N, T, 9)
@@ -75,10 +62,7 @@ for N, T in SHAPES:
     got = [float(v) for v in torch.stack(list(new_eager())).cpu()]
     for g, r in zip(got, ref):
         assert abs(g - r) <= 1e-4 * max(abs(r), 1e-3), (got, ref)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        new_eager()
+    graph = captured(new_eager)
     RUN = {"ref_forward": ref_forward, "new_eager": new_eager, "new_graph": graph.replay}
     seen = {f: [] for f in FORMS}
     for r in range(args.rounds):

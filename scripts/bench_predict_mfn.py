@@ -20,7 +20,7 @@ import argparse
 
 import torch
 
-from _bench_common import batch, cfgs, need_gpu, say, timed, write_out
+from _bench_common import batch, captured, cfgs, median, need_gpu, peak_of, say, timed, write_out
 from factorized_amd import mfm_model as M  # noqa: E402
 
 FORMS = ["default_eager", "default_graph", "label_eager", "label_graph"]
@@ -37,32 +37,6 @@ if args.rounds < 5:
     ap.error("--rounds must be at least 5: the medians are compared against the spread of the rounds")
 
 need_gpu("bench_predict_mfn.py")
-
-
-def peak_of(fn):
-    """peak device memory of a first call of `fn` (its buffers included) beyond what is allocated now, in bytes"""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del keep
-    return peak
-
-
-def median(v):
-    v = sorted(v)
-    return v[len(v) // 2], v[-1] - v[0]
-
-
-def captured(fn):
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        fn()
-    return graph
 
 
 verdicts = []

@@ -30,7 +30,7 @@ import argparse
 import torch
 import torch.nn.functional as F
 
-from _bench_common import batch, cfgs, d_a, d_l, d_v, need_gpu, say, timed, write_out
+from _bench_common import batch, captured, cfgs, d_a, d_l, d_v, median, need_gpu, peak_of, say, timed, write_out
 from factorized_amd import engine as E  # noqa: E402
 from factorized_amd.mfm_model import MFM_KL_EF  # noqa: E402
 
@@ -55,24 +55,6 @@ he = c["zl_size"] + c["za_size"] + c["zv_size"]
 Hp = (he + 15) // 16 * 16
 views = eng.param_views()
 W, b_ih, b_hh = views["ef_encoder.lstm.weight_ih"], views["ef_encoder.lstm.bias_ih"], views["ef_encoder.lstm.bias_hh"]
-
-
-def peak_of(fn):
-    """peak device memory of a first call of `fn` (its buffers included) beyond what is allocated now, in bytes"""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del keep
-    return peak
-
-
-def median(v):
-    v = sorted(v)
-    return v[len(v) // 2], v[-1] - v[0]
 
 
 def proj_forms(X, rows, T):
@@ -139,10 +121,7 @@ for N, T in SHAPES:
     got = [t.cpu() for t in new_eager()]
     for g, r in zip(got, ref):
         assert float((g - r).abs().max()) <= 1e-4 * max(float(r.abs().max()), 1e-3), (g, r)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        new_eager()
+    graph = captured(new_eager)
     RUN = {"ref_route": ref_route, "new_eager": new_eager, "new_graph": graph.replay}
     seen = {f: [] for f in FORMS}
     for r in range(args.rounds):

@@ -21,7 +21,7 @@ import argparse
 
 import torch
 
-from _bench_common import batch, cfgs, need_gpu, say, timed, write_out
+from _bench_common import batch, captured, cfgs, median, need_gpu, peak_of, say, timed, write_out
 from factorized_amd import mfm_model as M  # noqa: E402
 
 FORMS = ["old_route", "new_eager", "new_graph"]
@@ -38,24 +38,6 @@ if args.rounds < 5:
     ap.error("--rounds must be at least 5: the medians are compared against the spread of the rounds")
 
 need_gpu("bench_zeros_mfn.py")
-
-
-def peak_of(fn):
-    """peak device memory of a first call of `fn` (its buffers included) beyond what is allocated now, in bytes"""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    keep = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    del keep
-    return peak
-
-
-def median(v):
-    v = sorted(v)
-    return v[len(v) // 2], v[-1] - v[0]
 
 
 verdicts = []
@@ -84,10 +66,7 @@ for cls, variant in CLS:
         got = [t.cpu() for t in new_eager()]
         for g, r in zip(got, ref):
             assert float((g - r).abs().max()) <= 1e-4 * max(float(r.abs().max()), 1e-3), (g, r)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            new_eager()
+        graph = captured(new_eager)
         RUN = {"old_route": old_route, "new_eager": new_eager, "new_graph": graph.replay}
         seen = {f: [] for f in FORMS}
         for r in range(args.rounds):

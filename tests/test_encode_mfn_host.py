@@ -5,18 +5,10 @@ import ctypes as C
 import pytest
 
 from factorized_amd import _lib, configs, engine
+from tests.mfn_entries import CANON_SIZES, hp as _hp, ODD_SIZES, up4 as _up4
 
 NEW = ["mfm_encode_mfn", "mfm_encode_mfn_tile_rows", "mfm_encode_mfn_workspace_floats"]
-CANON = (300, 5, 20, 32, 8, 80, 32, 88, 64, 48, 64, 2, 128, 128, 128, 128, 1)
-ODD = (7, 3, 5, 6, 3, 7, 5, 9, 6, 7, 5, 2, 10, 11, 12, 13, 0)
-
-
-def _hp(h):
-    return (h + 15) // 16 * 16
-
-
-def _up4(v):
-    return (v + 3) // 4 * 4
+CANON, ODD = CANON_SIZES[:17], ODD_SIZES[:17]
 
 
 def _formula(T, N, sz, max_rows):

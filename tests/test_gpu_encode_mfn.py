@@ -13,39 +13,11 @@ from oracle import mfm_oracle as O
 from factorized_amd import _lib, configs, synth
 from tests import cases
 from tests import data_regimes as DR
+from tests.mfn_entries import bits as _bits, CANARY, canary as _canary, intact as _intact, model as _model, odd_cfgs as _odd_cfgs, ptr as _p
 from tests.cases import rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-CANARY = 0x7FC0DEAD                   # a NaN with a payload: any store over it shows
-CLS = {"kl": "MFM_KL", "mmd": "MFM"}
-# nothing a multiple of 4 or of a tile
-ODD = dict(input_dims=[7, 3, 5], h_dims=[9, 6, 7], memsize=5, zy_size=5, zl_size=6, za_size=3, zv_size=7)
-ODD_ATT = (10, 11, 12, 13)
-
-
-def _odd_cfgs(**over):
-    cfgs = configs.canonical_configs(dropout=False, **dict(ODD, **over))
-    for k, w in zip(cfgs[1:5], ODD_ATT):
-        k["shapes"] = w
-    return cfgs
-
-
-def _model(cfgs, variant):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from factorized_amd import mfm_model as M
-    model = getattr(M, CLS[variant])(*cfgs)
-    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    w = synth.make_weights(shapes, seed=1234)
-    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return model.to("cuda"), w
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
 def _same(a, b):
     return all((p is None and q is None) or torch.equal(_bits(p), _bits(q)) for p, q in zip(a, b))
 
@@ -173,19 +145,6 @@ def test_row_chunks_and_two_calls_are_bit_equal(variant):
 
 
 # ----------------------------------------------------------------------------------- 5. containment, x off a 16-byte boundary
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _canary(n, pad=256):
-    big = torch.full((pad + n + pad,), CANARY, dtype=torch.int32, device="cuda")
-    return big, big[pad:pad + n].view(torch.float32)
-
-
-def _intact(big, n, pad=256):
-    return bool((big[:pad] == CANARY).all()) and bool((big[pad + n:] == CANARY).all())
-
-
 def _abi(s, variant, x, cap):
     """mfm_encode_mfn through the C ABI on a canary-framed workspace and outputs -> the factors; nothing outside is touched"""
     from factorized_amd import engine

@@ -14,37 +14,13 @@ from oracle import mfm_oracle as O
 from factorized_amd import _lib, configs, synth
 from tests import cases
 from tests import data_regimes as DR
+from tests.mfn_entries import bits as _bits, CANARY, model as _model, odd_cfgs as _odd_cfgs, ptr as _p
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-CANARY = 0x7FC0DEAD                   # a NaN with a payload: any store over it shows
 FIELDS = ("loss", "disc", "gen_l", "gen_a", "gen_v", "reg")
 GOLD_KEYS = ("fwd_loss", "fwd_disc", "fwd_gen_l", "fwd_gen_a", "fwd_gen_v", "fwd_reg")
-CLS = {"kl": "MFM_KL", "mmd": "MFM"}
 VARIANTS = ["kl", "mmd"]
-# nothing a multiple of 4 or of a tile (the sizes of tests/test_gpu_encode_mfn.py)
-ODD = dict(input_dims=[7, 3, 5], h_dims=[9, 6, 7], memsize=5, zy_size=5, zl_size=6, za_size=3, zv_size=7)
-ODD_ATT = (10, 11, 12, 13)
-
-
-def _odd_cfgs(**over):
-    cfgs = configs.canonical_configs(dropout=False, **dict(ODD, **over))
-    for k, w in zip(cfgs[1:5], ODD_ATT):
-        k["shapes"] = w
-    return cfgs
-
-
-def _model(cfgs, variant):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from factorized_amd import mfm_model as M
-    model = getattr(M, CLS[variant])(*cfgs)
-    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    w = synth.make_weights(shapes, seed=1234)
-    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return model.to("cuda"), w
-
-
 def _zsizes(cfg):
     return [cfg["zl_size"], cfg["za_size"], cfg["zv_size"], cfg["zy_size"]]
 
@@ -89,10 +65,6 @@ def _oracle(variant, cfgs, w, xn, yn, g=None, double=False):
     with torch.no_grad():
         ref = O.loss_terms(m, x, y, cfg, "ce" if ce else "l1")
     return [float(ref[k]) for k in FIELDS]
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
 
 
 def _obits(obj):
@@ -340,10 +312,6 @@ def test_lambdas_weigh_the_total(variant):
 
 
 # ----------------------------------------------------------------------------------- 9. containment, x off a 16-byte boundary
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _abi(s, variant, x, y, cap, sizes=None, expect=0):
     """mfm_objective_mfn through the C ABI on a canary-framed workspace and output -> the bits of the six floats after checking
     that nothing outside them was touched; expect != 0: the return code, and nothing at all was touched"""
@@ -352,7 +320,7 @@ def _abi(s, variant, x, y, cap, sizes=None, expect=0):
     c = e.cfg
     L = _lib.lib()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    good = e._zeros_mfn_sizes()
+    good = e._mfn_sizes()
     nws = int(L.mfm_objective_mfn_workspace_floats(T, N, good, cap))
     assert nws > 0 and nws == e.objective_workspace_floats(T, N, max_rows=cap or N)
     PAD = 256
@@ -492,7 +460,7 @@ def test_data_regimes_against_the_float64_oracle(variant, regime):
 # ----------------------------------------------------------------------------------- 12. refusals
 def test_windowsize_3_is_refused_nothing_is_enqueued_and_it_is_not_remembered(monkeypatch):
     s = _canon("kl")
-    sizes = s["e"]._zeros_mfn_sizes()
+    sizes = s["e"]._mfn_sizes()
     sizes[11] = 3
     _abi(s, "kl", s["x"], s["y"], 0, sizes=sizes, expect=_lib.MFM_ERR_UNSUPPORTED)
     assert "windowsize 3" in _lib.lib().mfm_last_error().decode()

@@ -16,37 +16,13 @@ from oracle import mfm_oracle as O
 from factorized_amd import _lib, configs, synth
 from tests import cases
 from tests import data_regimes as DR
+from tests.mfn_entries import bits as _bits, CANARY, model as _model, odd_cfgs as _odd_cfgs, ptr as _p
 from tests import offset_views as OV
 from tests.cases import rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-CANARY = 0x7FC0DEAD                   # a NaN with a payload: any store over it shows
-CLS = {"kl": "MFM_KL", "mmd": "MFM", "kl_ef": "MFM_KL_EF"}
 VARIANTS = ["kl", "mmd"]
-# nothing a multiple of 4 or of a tile (the sizes of tests/test_gpu_encode_mfn.py)
-ODD = dict(input_dims=[7, 3, 5], h_dims=[9, 6, 7], memsize=5, zy_size=5, zl_size=6, za_size=3, zv_size=7)
-ODD_ATT = (10, 11, 12, 13)
-
-
-def _odd_cfgs(**over):
-    cfgs = configs.canonical_configs(dropout=False, **dict(ODD, **over))
-    for k, w in zip(cfgs[1:5], ODD_ATT):
-        k["shapes"] = w
-    return cfgs
-
-
-def _model(cfgs, variant):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from factorized_amd import mfm_model as M
-    model = getattr(M, CLS[variant])(*cfgs)
-    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    w = synth.make_weights(shapes, seed=1234)
-    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return model.to("cuda"), w
-
-
 def _oracle(variant, cfgs, w, xn, yn, double=False):
     """(y_hat [N, od], the label loss) of the oracle in eval mode (float64 throughout with `double`)"""
     cfg = cfgs[0]
@@ -65,10 +41,6 @@ def _oracle(variant, cfgs, w, xn, yn, double=False):
     else:
         loss = float((y_hat.double() - y.double().view_as(y_hat)).abs().mean())
     return y_hat.numpy(), loss
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32).clone()
 
 
 def _run(e, x, y=None, cap=None):
@@ -291,10 +263,6 @@ def test_parameters_off_the_label_path_are_not_read(variant):
 
 
 # ----------------------------------------------------------------------------------- 6. containment, x off a 16-byte boundary
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _abi(e, x, y, cap, sizes=None, expect=0, with_loss=True):
     """mfm_predict_mfn through the C ABI on canary-framed workspace, y_hat and loss -> (bits of y_hat, bits of the loss word, the
     workspace) after checking that nothing outside them was touched; expect != 0: the return code, and nothing at all was touched"""
@@ -303,7 +271,7 @@ def _abi(e, x, y, cap, sizes=None, expect=0, with_loss=True):
     od = e.cfg["output_dim"]
     L = _lib.lib()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    good = e._zeros_mfn_sizes()
+    good = e._mfn_sizes()
     nws = int(L.mfm_predict_mfn_workspace_floats(T, N, good, cap))
     assert nws > 0 and nws == e.predict_workspace_floats(T, N, max_rows=cap or N, label_only=True)
     PAD = 256
@@ -414,7 +382,7 @@ def test_a_refusal_at_resident_sizes_falls_back_and_is_not_remembered(monkeypatc
 
 def test_windowsize_3_is_refused_and_nothing_is_enqueued():
     s = _canon("kl")
-    sizes = s["e"]._zeros_mfn_sizes()
+    sizes = s["e"]._mfn_sizes()
     sizes[11] = 3
     _abi(s["e"], s["x"], s["y"], 0, sizes=sizes, expect=_lib.MFM_ERR_UNSUPPORTED)
     assert "windowsize 3" in _lib.lib().mfm_last_error().decode()

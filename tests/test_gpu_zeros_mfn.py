@@ -14,40 +14,12 @@ import torch
 from factorized_amd import _lib, configs, synth
 from tests import cases, zeros_ref
 from tests import data_regimes as DR
+from tests.mfn_entries import bits as _bits, CANARY, canary as _canary, intact as _intact, model as _model, odd_cfgs as _odd_cfgs, ptr as _p
 from tests.cases import rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-CANARY = 0x7FC0DEAD                   # a NaN with a payload: any store over it shows
-CLS = {"kl": "MFM_KL", "mmd": "MFM"}
 VARIANTS = ["kl", "mmd"]
-# nothing a multiple of 4 or of a tile (the sizes of tests/test_gpu_encode_mfn.py)
-ODD = dict(input_dims=[7, 3, 5], h_dims=[9, 6, 7], memsize=5, zy_size=5, zl_size=6, za_size=3, zv_size=7)
-ODD_ATT = (10, 11, 12, 13)
-
-
-def _odd_cfgs(**over):
-    cfgs = configs.canonical_configs(dropout=False, **dict(ODD, **over))
-    for k, w in zip(cfgs[1:5], ODD_ATT):
-        k["shapes"] = w
-    return cfgs
-
-
-def _model(cfgs, variant):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from factorized_amd import mfm_model as M
-    model = getattr(M, CLS[variant])(*cfgs)
-    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    w = synth.make_weights(shapes, seed=1234)
-    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in w.items()})
-    return model.to("cuda"), w
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
 def _zbits(z):
     return [_bits(z.y_hat), _bits(z.gen)] + ([] if z.disc is None else [_bits(z.disc)])
 
@@ -225,19 +197,6 @@ def test_four_row_tiles_on_odd_sizes_take_a_launch_per_lstm():
 
 
 # ----------------------------------------------------------------------------------- 7. containment, x off a 16-byte boundary
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _canary(n, pad=256):
-    big = torch.full((pad + n + pad,), CANARY, dtype=torch.int32, device="cuda")
-    return big, big[pad:pad + n].view(torch.float32)
-
-
-def _intact(big, n, pad=256):
-    return bool((big[:pad] == CANARY).all()) and bool((big[pad + n:] == CANARY).all())
-
-
 def _abi(s, variant, x, y, cap, sizes=None, expect=0):
     """mfm_predict_zeros_mfn through the C ABI on canary-framed workspace and outputs -> (bits of y_hat, gen, disc) after checking
     that nothing outside them was touched; expect != 0: the return code, and nothing at all was touched"""
@@ -246,7 +205,7 @@ def _abi(s, variant, x, y, cap, sizes=None, expect=0):
     od = c["output_dim"]
     L = _lib.lib()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    good = e._zeros_mfn_sizes()
+    good = e._mfn_sizes()
     nws = int(L.mfm_predict_zeros_mfn_workspace_floats(T, N, good, cap))
     assert nws > 0 and nws == e.predict_zeros_workspace_floats(T, N, max_rows=cap or N)
     big_ws, ws = _canary(nws)
@@ -383,7 +342,7 @@ def test_data_regimes_against_the_float64_oracle(variant, regime):
 # ----------------------------------------------------------------------------------- 10. refusals
 def test_windowsize_3_is_refused_and_nothing_is_enqueued():
     s = _canon("kl")
-    sizes = s["e"]._zeros_mfn_sizes()
+    sizes = s["e"]._mfn_sizes()
     sizes[11] = 3
     _abi(s, "kl", s["x"], s["y"], 0, sizes=sizes, expect=_lib.MFM_ERR_UNSUPPORTED)
     assert "windowsize 3" in _lib.lib().mfm_last_error().decode()

@@ -8,19 +8,9 @@ import torch
 
 from factorized_amd import _lib, configs, engine
 from factorized_amd import mfm_model as M
+from tests.mfn_entries import CANON_SIZES as CANON, hp as _hp, ODD_SIZES as ODD, up4 as _up4
 
 NEW = ["mfm_predict_mfn", "mfm_predict_mfn_tile_rows", "mfm_predict_mfn_workspace_floats"]
-# d_l d_a d_v | zl za zv | zy | h_l h_a h_v | memsize | windowsize | att1 att2 gamma1 gamma2 | heads | fl fa fv fy | od | loss kind
-CANON = (300, 5, 20, 32, 8, 80, 32, 88, 64, 48, 64, 2, 128, 128, 128, 128, 1, 88, 8, 8, 16, 1, 0)
-ODD = (7, 3, 5, 6, 3, 7, 5, 9, 6, 7, 5, 2, 10, 11, 12, 13, 0, 88, 8, 8, 16, 3, 1)
-
-
-def _hp(h):
-    return (h + 15) // 16 * 16
-
-
-def _up4(v):
-    return (v + 3) // 4 * 4
 
 
 def _formula(T, N, sz, max_rows):

@@ -9,21 +9,9 @@ import pytest
 
 from factorized_amd import _lib, configs, engine, synth
 from tests import cases, zeros_ref
+from tests.mfn_entries import CANON_SIZES as CANON, hp as _hp, odd_cfgs, ODD_SIZES as ODD, up4 as _up4
 
 NEW = ["mfm_predict_zeros_mfn", "mfm_predict_zeros_mfn_tile_rows", "mfm_predict_zeros_mfn_workspace_floats"]
-# d_l d_a d_v | zl za zv | zy | h_l h_a h_v | memsize | windowsize | att1 att2 gamma1 gamma2 | heads | fl fa fv fy | od | loss kind
-CANON = (300, 5, 20, 32, 8, 80, 32, 88, 64, 48, 64, 2, 128, 128, 128, 128, 1, 88, 8, 8, 16, 1, 0)
-ODD = (7, 3, 5, 6, 3, 7, 5, 9, 6, 7, 5, 2, 10, 11, 12, 13, 0, 88, 8, 8, 16, 3, 1)
-ODD_CFG = dict(input_dims=[7, 3, 5], h_dims=[9, 6, 7], memsize=5, zy_size=5, zl_size=6, za_size=3, zv_size=7)
-ODD_ATT = (10, 11, 12, 13)
-
-
-def _hp(h):
-    return (h + 15) // 16 * 16
-
-
-def _up4(v):
-    return (v + 3) // 4 * 4
 
 
 def _formula(T, N, sz, max_rows):
@@ -149,9 +137,7 @@ def test_entries_table_keeps_a_cache_of_its_own():
 @pytest.mark.parametrize("variant", ["kl", "mmd"])
 def test_oracle_on_zeroed_inputs_reproduces_the_fixture(variant):
     """pins the fixtures (the reference's own run, tests/golden/make_golden_zeros_mfn.py) and the oracle to each other"""
-    cfgs = configs.canonical_configs(dropout=False, **ODD_CFG)
-    for k, w in zip(cfgs[1:5], ODD_ATT):
-        k["shapes"] = w
+    cfgs = odd_cfgs()
     cfg = cfgs[0]
     gold = np.load(os.path.join(cases.GOLDEN, "%s_zeros_b19_t9.npz" % variant))
     B, T = [int(v) for v in gold["meta"]]
