@@ -19,7 +19,8 @@ constexpr int BK = 32;   // K depth of one LDS stage: 8 MFMA k-steps between bar
 
 // VEC: every operand of every problem in the group is unit-stride along its 4-element load groups
 // (true for all products of the MFM step); the 16-byte path is then unconditional.  A launch with
-// an oddly strided operand uses the VEC=false instantiation (dword buffer loads) for the whole group.
+// an oddly strided operand uses the VEC=false instantiation (dword buffer loads) for the whole group: the m-/n-
+// and k-contiguous operands of such a group keep their LDS images and masks, and every dword is clamped into the operand.
 // Occupancy target (second launch-bounds argument = waves per SIMD): a K step is a chain of latencies (LDS
 // write -> barrier -> fragment reads -> 8 MFMAs), so resident waves are what keeps the MFMA pipe fed.  88
 // registers / 5 workgroups per CU for the 32x32 tiles, 158 / 3 for the 64x64 tiles, no spills; measured
@@ -95,7 +96,8 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
   constexpr int GA = EPT_A / 4, GB = EPT_B / 4;
   float ra[DEPTH][EPT_A], rb[DEPTH][EPT_B];
   const int a_sm = (int)d.a_sm, a_sk = (int)d.a_sk, b_sk = (int)d.b_sk, b_sn = (int)d.b_sn;
-  // extents in bytes for the bounds-checked descriptors (host guarantees < 2^31)
+  // extents in bytes for the bounds-checked descriptors; these and every `off * 4` below are 32-bit ints: the host
+  // refuses operands whose span in BYTES does not fit one (gemm_group_launch)
   const int a_bytes = ((d.m - 1) * a_sm + (max(d.k, 1) - 1) * a_sk + 1) * 4;
   const int b_bytes = ((max(d.k, 1) - 1) * b_sk + (max(d.n_valid, 1) - 1) * b_sn + 1) * 4;
   const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, a_bytes, 0x00020000);
@@ -129,9 +131,11 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
         v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ares, off * 4, 0, 0));
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                     ares, (a_base[g] + min(gk + e, klast) * a_sk) * 4, 0, 0));
+        for (int e = 0; e < 4; ++e) {       // the group runs along m for an m-contiguous operand (as the mask and a_st have it), along k otherwise
+          const int off = a_mcontig ? min(gm + e, d.m - 1) * a_sm + min(gk, klast) * a_sk
+                                    : a_base[g] + min(gk + e, klast) * a_sk;
+          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ares, off * 4, 0, 0));
+        }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -148,9 +152,11 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
         v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(bres, off * 4, 0, 0));
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                     bres, (b_base[g] + min(gk + e, klast) * b_sk) * 4, 0, 0));
+        for (int e = 0; e < 4; ++e) {       // along n for an n-contiguous operand, along k otherwise
+          const int off = b_ncontig ? min(gn + e, max(d.n_valid - 1, 0)) * b_sn + min(gk, klast) * b_sk
+                                    : b_base[g] + min(gk + e, klast) * b_sk;
+          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bres, off * 4, 0, 0));
+        }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -321,10 +327,22 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
     MFM_REQUIRE(d.n_valid >= 0 && d.n_valid <= d.n, "gemm[%d]: n_valid %d > n %d", i, d.n_valid, d.n);
     MFM_REQUIRE(d.split_k <= 1 || d.accumulate, "gemm[%d]: split_k needs accumulate", i);
     {
-      const int64_t lim = (int64_t)1 << 31;
-      const int64_t ea = (int64_t)(d.m - 1) * d.a_sm + (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.a_sk;
-      const int64_t eb = (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.b_sk + (int64_t)(d.n_valid > 0 ? d.n_valid - 1 : 0) * d.b_sn;
-      MFM_REQUIRE(ea < lim && eb < lim && ea >= 0 && eb >= 0, "gemm[%d]: operand spans >= 2^31 elements (32-bit tile offsets)", i);
+      // The kernels form an operand's extent (a_bytes, b_bytes) and every load offset (off * 4) in BYTES in 32-bit ints:
+      // the span of one batch member, first to last element, is held to what those carry, 2^31 - 1 bytes (2^29 - 1 fp32
+      // elements).  Beyond it the extent wraps and the loads return zeros or another row without any error.
+      const int64_t lim = ((int64_t)1 << 31) - 1;
+      MFM_REQUIRE(d.a_sm >= 0 && d.a_sk >= 0 && d.b_sk >= 0 && d.b_sn >= 0 && d.a_sm <= lim && d.a_sk <= lim && d.b_sk <= lim && d.b_sn <= lim,
+                  "gemm[%d]: operand strides must lie in [0, 2^31) (a_sm=%lld a_sk=%lld b_sk=%lld b_sn=%lld)", i,
+                  (long long)d.a_sm, (long long)d.a_sk, (long long)d.b_sk, (long long)d.b_sn);
+      const int64_t sa = (int64_t)(d.m - 1) * d.a_sm + (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.a_sk + 1;
+      const int64_t sb = (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.b_sk + (int64_t)(d.n_valid > 0 ? d.n_valid - 1 : 0) * d.b_sn + 1;
+      const int64_t ba = d.a_bf16 ? ((sa * 2 + 3) & ~(int64_t)3) : sa * 4;      // (bf16: whole dwords, as the kernel rounds it)
+      MFM_REQUIRE(ba <= lim,
+                  "gemm[%d]: operand a spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
+                  i, (long long)sa, (long long)ba);
+      MFM_REQUIRE(sb * 4 <= lim,
+                  "gemm[%d]: operand b spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
+                  i, (long long)sb, (long long)(sb * 4));
     }
     blocks64 += (long)cdiv(d.m, 64) * cdiv(d.n, 64) * d.batch;
   }
@@ -345,6 +363,7 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
   bool vec = true;
   for (int i = 0; i < count; ++i) {
     const MfmGemmDesc& d = descs[i];
+    if (d.k == 0) continue;        // no element of a or b is part of the product (its strides are replaced below)
     const bool a_mcontig = (d.a_sm == 1 && d.a_sk != 1), b_ncontig = (d.b_sn == 1 && d.b_sk != 1);
     if (!(a_mcontig || d.a_sk == 1) || !(b_ncontig || d.b_sk == 1)) vec = false;
   }
@@ -358,6 +377,10 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
   for (int i = 0; i < count; ++i) {
     GemmProblem& P = g.p[i];
     P.d = descs[i];
+    if (P.d.k == 0) {              // C = bias: the kernel's clamped, masked tile fetches stay on element 0 of a and b
+      P.d.a_sz = P.d.a_sm = 0; P.d.a_sk = 1;
+      P.d.b_sz = P.d.b_sn = 0; P.d.b_sk = 1;
+    }
     P.tiles_m = cdiv(P.d.m, BT);
     P.tiles_n = cdiv(P.d.n, BT);
     int split = P.d.split_k;

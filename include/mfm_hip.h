@@ -50,8 +50,21 @@ int mfm_device_cus(void);
  * Grouped fp32 GEMM on the f32 MFMA (v_mfma_f32_16x16x4_f32), exact fp32 FMA chains.
  *   for z in [0,batch):  C[z][m][n] (+)= alpha * sum_k A(z,m,k) * B(z,k,n) + bias[z][n] + bias2[z][n]
  * A(z,m,k) = a[z*a_sz + m*a_sm + k*a_sk], B(z,k,n) = b[z*b_sz + k*b_sk + n*b_sn],
- * C element at c[z*c_sz + m*ldc + n].  Columns n in [n_valid, n) are produced as exact zeros
- * (pad units).  accumulate!=0 -> atomic += into c (and c2 if non-null), needed for split_k>1.
+ * C element at c[z*c_sz + m*ldc + n].  Columns n in [n_valid, n) (pad units) are produced as exact zeros
+ * by a plain product and are left untouched when accumulate!=0; columns [n, ldc) are never written.
+ * accumulate!=0 -> atomic += into c (and c2 if non-null), needed for split_k>1.  The biases are added once
+ * whatever the split, and alpha scales the product only, not the biases.  k = 0 is a valid problem
+ * (C = bias, or C += bias): a and b must still be non-null and address at least one element.
+ * Operands: strides are >= 0, and the span of one batch member of a or b, first to last element, is at most
+ * 2^31 - 1 BYTES (2^29 - 1 fp32 elements): the tile loads carry 32-bit byte offsets; a larger span is refused
+ * (MFM_ERR_ARG) with the operand and its span in the message.  fp32 base pointers need 4-byte alignment only.
+ * What the loads touch: an operand that is unit-stride along k (or along m for a, n for b) is fetched 16 bytes
+ * at a time, so up to three elements BEHIND a row's K range, or behind m / n_valid of an m-/n-contiguous
+ * operand, are read when they lie inside the operand's span (the columns of a wider matrix an operand is a
+ * slice of, the next row), and are then multiplied by zero.  Those elements must be FINITE: an inf or NaN
+ * there survives the multiply and poisons the output row / column.  Where they may not be finite (missing
+ * values next to observed ones), gather the operand into a zero-padded matrix of its own first, as
+ * csrc/impute.hip does.  Nothing is read outside the span.
  * Replaces every nn.Linear / LSTMCell addmm and its AddmmBackward on the path:
  * mfm_model.py:56,83,85 (x W_ih^T hoisted over all T), :61,90 (fc1), autograd of the same.
  */
@@ -76,7 +89,9 @@ int mfm_gemm_grouped_f32(const MfmGemmDesc* descs /*host*/, int count, void* str
 /* The same products with bf16 MFMA operands (v_mfma_f32_16x16x32_bf16) and fp32 accumulation: a and b are still
  * fp32 buffers, rounded to bf16 (nearest even) on the way from the global tile to LDS; c, bias, alpha, the
  * epilogue and the atomics are fp32 exactly as above.  "bf16 compute, fp32 master weights" of BASELINE.json
- * configs 2-4.  A group holding an operand that is not unit-stride along m/n or k runs on the fp32 kernel. */
+ * configs 2-4.  A group holding an operand that is not unit-stride along m/n or k runs on the fp32 kernel -- every
+ * problem of that launch (at most MFM_GEMM_MAXP consecutive descriptors), with fp32 results -- and is refused if it
+ * also holds an a_bf16 / c_bf16 descriptor. */
 int mfm_gemm_grouped_bf16(const MfmGemmDesc* descs /*host*/, int count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
