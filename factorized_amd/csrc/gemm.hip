@@ -22,65 +22,36 @@ constexpr int BK = 32;   // K depth of one LDS stage: 8 MFMA k-steps between bar
 // an oddly strided operand uses the VEC=false instantiation (dword buffer loads) for the whole group: the m-/n-
 // and k-contiguous operands of such a group keep their LDS images and masks, and every dword is clamped into the operand.
 // Occupancy target (second launch-bounds argument = waves per SIMD): a K step is a chain of latencies (LDS
-// write -> barrier -> fragment reads -> 8 MFMAs), so resident waves are what keeps the MFMA pipe fed.  88
-// registers / 5 workgroups per CU for the 32x32 tiles, 158 / 3 for the 64x64 tiles, no spills; measured
-// against the compiler's default (108 / 4 and 188 / 2): +4 % on the whole step at B=2048, +1 % at B=32;
-// 6 waves (80 registers, 4 spilled) gains nothing more.
+// write -> barrier -> fragment reads -> 8 MFMAs), so resident waves are what keeps the MFMA pipe fed.  The compiler
+// reports 89 registers (VEC; 94 without) / 5 workgroups per CU for the 32x32 tiles and 157 (160) / 3 for the 64x64
+// tiles, all four without scratch (profiles/gemm_family_refactor.txt); measured against the compiler's default (108 / 4
+// and 188 / 2): +4 % on the whole step at B=2048, +1 % at B=32; 6 waves (80 registers, 4 spilled) gains nothing more.
 // FR = 4: 128x128 tiles (each wave 64x64 = 16 accumulators) for launches with thousands of 64x64 tiles: twice the MFMA
-// work per staged byte and per barrier of the FR = 2 variant; 2 workgroups per CU (73 KB of LDS, <= 256 registers).
+// work per staged byte and per barrier of the FR = 2 variant; 2 workgroups per CU (73 KB of LDS).  Both FR = 4 forms
+// spill: about 220 registers and 272 bytes of scratch per lane are reported for them, and 256 registers with 304 bytes
+// for the bf16-operand kernel's FR = 4 form.
 // It carries no squared-error epilogue (64 more live registers): launches that need one stay on FR <= 2.
 template <int FR, bool VEC>
 __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2)) void gemm_f32_kernel(const GemmGroup g) {
-  constexpr int BM = 32 * FR, BN = 32 * FR;
-  constexpr int LDA = BM + 16, LDB = BN + 16;     // [k][m] layout (m-/n-contiguous operands)
-  constexpr int LDK = BK + 4;                     // [m][k] layout (k-contiguous operands)
-  constexpr int EPT_A = BM * BK / 256, EPT_B = BN * BK / 256;
-  constexpr int ASZ = (BK * LDA > BM * LDK) ? BK * LDA : BM * LDK;
-  constexpr int BSZ = (BK * LDB > BN * LDK) ? BK * LDB : BN * LDK;
+  constexpr int BT = 32 * FR;                     // tile edge, m and n alike
+  constexpr int LDR = BT + 16;                    // [k][row] layout (m-/n-contiguous operands)
+  constexpr int LDK = BK + 4;                     // [row][k] layout (k-contiguous operands)
+  constexpr int EPT = BT * BK / 256;              // elements per thread and operand tile
+  constexpr int SZ = (BK * LDR > BT * LDK) ? BK * LDR : BT * LDK;
   // two LDS images per operand: while the MFMAs of K-tile kt read image kt&1, the registers of tile kt+1 are
   // written to the other one, so a K step costs ONE barrier instead of two
-  __shared__ __attribute__((aligned(16))) float As2[2][ASZ];
-  __shared__ __attribute__((aligned(16))) float Bs2[2][BSZ];
+  __shared__ __attribute__((aligned(16))) float As2[2][SZ];
+  __shared__ __attribute__((aligned(16))) float Bs2[2][SZ];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int bi = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // ---- locate problem / tile (wave-uniform)
-  // Workgroups are dealt to the 8 XCDs round-robin by id, and each XCD has its own L2.  Tiles that share
-  // an operand panel (same m-tile across n, same n-tile across m / gates) are neighbours in the LOGICAL
-  // order, so inside every problem each XCD is given one contiguous run of logical tiles: a panel is then
-  // fetched from HBM once per XCD that needs it instead of once per tile (the LSTM weight-gradient launch
-  // read 37.7 MB for ~6 MB of operands before this), while every XCD still gets an equal
-  // share of every problem (a whole-launch remap left the XCDs with the long-K problems as stragglers).
-  int pi = 0;
-  const int bid = blockIdx.x;
-#pragma unroll
-  for (int i = 1; i < MFM_GEMM_MAXP; ++i) pi += (bid >= g.begins[i]) ? 1 : 0;
-  const GemmProblem& P = g.p[pi];
-  const MfmGemmDesc& d = P.d;
-  int local = bid - P.block_begin;
-  {
-    constexpr int NX = 8;
-    const int nb = ((pi + 1 < g.count) ? g.begins[pi + 1] : (int)gridDim.x) - P.block_begin;
-    const int x = local % NX, j = local / NX;
-    const int per = nb / NX, rem = nb % NX;
-    local = x * per + (x < rem ? x : rem) + j;
-  }
-  const int tn = local % P.tiles_n; local /= P.tiles_n;
-  const int tm = local % P.tiles_m; local /= P.tiles_m;
-  const int z = local % d.batch;
-  const int split = local / d.batch;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kbeg = split * P.k_per_split;
-  const int kend = min(d.k, kbeg + P.k_per_split);
-  if (kbeg >= kend && split > 0) return;
-
-  const float* __restrict__ A = d.a + (int64_t)z * d.a_sz;
-  const float* __restrict__ Bm = d.b + (int64_t)z * d.b_sz;
-  const bool a_mcontig = (d.a_sm == 1 && d.a_sk != 1);
-  const bool b_ncontig = (d.b_sn == 1 && d.b_sk != 1);
+  const GemmTile t = gemm_locate(g, BT, BT);
+  const MfmGemmDesc& d = g.p[t.pi].d;
+  const int kbeg = t.kbeg, kend = t.kend;
+  if (kbeg >= kend && t.split > 0) return;
 
   // Register ring of DEPTH K-tiles in flight.  At these sizes (K = 300..640, 8 MFMAs per wave and
   // tile) one workgroup's K loop is a chain of latencies and, above all, of vector-memory instructions:
@@ -93,129 +64,80 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
   //   (b) the barriers are LDS-only (lds_barrier): __syncthreads() drains the ring with vmcnt(0);
   //   (c) the operand fragments of a tile are read from LDS before the first MFMA.
   constexpr int DEPTH = (FR == 1) ? 3 : (FR == 2 ? 2 : 1);
-  constexpr int GA = EPT_A / 4, GB = EPT_B / 4;
-  float ra[DEPTH][EPT_A], rb[DEPTH][EPT_B];
-  const int a_sm = (int)d.a_sm, a_sk = (int)d.a_sk, b_sk = (int)d.b_sk, b_sn = (int)d.b_sn;
-  // extents in bytes for the bounds-checked descriptors; these and every `off * 4` below are 32-bit ints: the host
-  // refuses operands whose span in BYTES does not fit one (gemm_group_launch)
-  const int a_bytes = ((d.m - 1) * a_sm + (max(d.k, 1) - 1) * a_sk + 1) * 4;
-  const int b_bytes = ((max(d.k, 1) - 1) * b_sk + (max(d.n_valid, 1) - 1) * b_sn + 1) * 4;
-  const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bres = __builtin_amdgcn_make_buffer_rsrc((void*)Bm, 0, b_bytes, 0x00020000);
-  // loop-invariant group coordinates
-  int a_base[GA], a_gk[GA], a_gm[GA], b_base[GB], b_gk[GB], b_gn[GB];
-#pragma unroll
-  for (int g = 0; g < GA; ++g) {
-    const int idx = (tid * GA + g) * 4;
-    const int k = a_mcontig ? idx / BM : idx % BK;
-    const int m = a_mcontig ? idx % BM : idx / BK;
-    a_gk[g] = k; a_gm[g] = m0 + m;
-    a_base[g] = min(m0 + m, d.m - 1) * a_sm;
-  }
-#pragma unroll
-  for (int g = 0; g < GB; ++g) {
-    const int idx = (tid * GB + g) * 4;
-    const int k = b_ncontig ? idx / BN : idx % BK;
-    const int n = b_ncontig ? idx % BN : idx / BK;
-    b_gk[g] = k; b_gn[g] = n0 + n;
-    b_base[g] = min(n0 + n, max(d.n_valid - 1, 0)) * b_sn;
-  }
+  constexpr int G = EPT / 4;
+  float ra[DEPTH][EPT], rb[DEPTH][EPT];
   const int klast = max(kend - 1, 0);
-  auto load_tiles = [&](int slot, int k0) {
+
+  // One operand as this thread sees it: a for its rows m, b for its "rows" n.
+  struct Operand {
+    __amdgpu_buffer_rsrc_t res;
+    bool rowcontig;                       // unit-stride along the rows: the 4-element groups and the LDS image run along them
+    int rlim, s_row, s_k;                 // rows that exist (m / n_valid), element strides
+    int l_row, l_k;                       // LDS strides of the image (block-uniform values, no divergent control flow)
+    int gk[G], gr[G], base[G], st[G];     // loop-invariant, per group: k in the tile, row, offset of the clamped row, place in the image
+  };
+  // the extent in bytes for the bounds-checked descriptor and every `off * 4` below are 32-bit ints: the host refuses
+  // operands whose span in BYTES does not fit one (gemm_check_problem)
+  auto operand = [&](const float* p, const int bytes, const GemmForm form, const int r0, const int rlim, const int s_row, const int s_k) {
+    Operand o;
+    o.res = __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, bytes, 0x00020000);
+    o.rowcontig = form == GEMM_ROW_CONTIG;
+    o.rlim = rlim; o.s_row = s_row; o.s_k = s_k;
+    o.l_row = o.rowcontig ? 1 : LDK; o.l_k = o.rowcontig ? LDR : 1;
 #pragma unroll
-    for (int g = 0; g < GA; ++g) {
-      const int gk = k0 + a_gk[g], gm = a_gm[g];
+    for (int g = 0; g < G; ++g) {
+      const int idx = (tid * G + g) * 4;
+      const int k = o.rowcontig ? idx / BT : idx % BK;
+      const int r = o.rowcontig ? idx % BT : idx / BK;
+      o.gk[g] = k; o.gr[g] = r0 + r;
+      o.base[g] = min(r0 + r, max(rlim - 1, 0)) * s_row;
+      o.st[g] = r * o.l_row + k * o.l_k;
+    }
+    return o;
+  };
+  const int a_sm = (int)d.a_sm, a_sk = (int)d.a_sk, b_sk = (int)d.b_sk, b_sn = (int)d.b_sn;
+  const Operand oa = operand(d.a + (int64_t)t.z * d.a_sz, gemm_operand_bytes(d.m, d.k, a_sm, a_sk, 4),
+                             gemm_operand_form(d.a_sm, d.a_sk), t.m0, d.m, a_sm, a_sk);
+  const Operand ob = operand(d.b + (int64_t)t.z * d.b_sz, gemm_operand_bytes(d.k, d.n_valid, b_sk, b_sn, 4),
+                             gemm_operand_form(d.b_sn, d.b_sk), t.n0, d.n_valid, b_sn, b_sk);
+  auto load_op = [&](float (&r)[EPT], const Operand& o, const int k0) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int gk = k0 + o.gk[g], gr = o.gr[g];
       f32x4 v;
       if constexpr (VEC) {
-        const int off = a_base[g] + min(gk, klast) * a_sk;
-        v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ares, off * 4, 0, 0));
+        const int off = o.base[g] + min(gk, klast) * o.s_k;
+        v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(o.res, off * 4, 0, 0));
       } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {       // the group runs along m for an m-contiguous operand (as the mask and a_st have it), along k otherwise
-          const int off = a_mcontig ? min(gm + e, d.m - 1) * a_sm + min(gk, klast) * a_sk
-                                    : a_base[g] + min(gk + e, klast) * a_sk;
-          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ares, off * 4, 0, 0));
+        for (int e = 0; e < 4; ++e) {       // the group runs along the rows for a row-contiguous operand (as the mask and st have it), along k otherwise
+          const int off = o.rowcontig ? min(gr + e, max(o.rlim - 1, 0)) * o.s_row + min(gk, klast) * o.s_k
+                                      : o.base[g] + min(gk + e, klast) * o.s_k;
+          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(o.res, off * 4, 0, 0));
         }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int em = a_mcontig ? gm + e : gm, ek = a_mcontig ? gk : gk + e;
-        ra[slot][4 * g + e] = v[e] * (float)((int)(em < d.m) & (int)(ek < kend));
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-      const int gk = k0 + b_gk[g], gn = b_gn[g];
-      f32x4 v;
-      if constexpr (VEC) {
-        const int off = b_base[g] + min(gk, klast) * b_sk;
-        v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(bres, off * 4, 0, 0));
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {       // along n for an n-contiguous operand, along k otherwise
-          const int off = b_ncontig ? min(gn + e, max(d.n_valid - 1, 0)) * b_sn + min(gk, klast) * b_sk
-                                    : b_base[g] + min(gk + e, klast) * b_sk;
-          v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(bres, off * 4, 0, 0));
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int en = b_ncontig ? gn + e : gn, ek = b_ncontig ? gk : gk + e;
-        rb[slot][4 * g + e] = v[e] * (float)((int)(en < d.n_valid) & (int)(ek < kend));
+        const int er = o.rowcontig ? gr + e : gr, ek = o.rowcontig ? gk : gk + e;
+        r[4 * g + e] = v[e] * (float)((int)(er < o.rlim) & (int)(ek < kend));
       }
     }
   };
-  // LDS strides of the two images (block-uniform values, no divergent control flow)
-  const int a_lm = a_mcontig ? 1 : LDK, a_lk = a_mcontig ? LDA : 1;
-  const int b_ln = b_ncontig ? 1 : LDK, b_lk = b_ncontig ? LDB : 1;
-  int a_st[GA], b_st[GB];
+  auto store_op = [&](const float (&r)[EPT], const Operand& o, float* img) {
 #pragma unroll
-  for (int g = 0; g < GA; ++g) {
-    const int idx = (tid * GA + g) * 4;
-    const int k = a_mcontig ? idx / BM : idx % BK;
-    const int m = a_mcontig ? idx % BM : idx / BK;
-    a_st[g] = m * a_lm + k * a_lk;
-  }
-#pragma unroll
-  for (int g = 0; g < GB; ++g) {
-    const int idx = (tid * GB + g) * 4;
-    const int k = b_ncontig ? idx / BN : idx % BK;
-    const int n = b_ncontig ? idx % BN : idx / BK;
-    b_st[g] = n * b_ln + k * b_lk;
-  }
-  auto store_tiles = [&](int slot, int img) {
-    float* As = As2[img];
-    float* Bs = Bs2[img];
-#pragma unroll
-    for (int g = 0; g < GA; ++g)
-      *reinterpret_cast<f32x4*>(As + a_st[g]) = f32x4{ra[slot][4 * g], ra[slot][4 * g + 1], ra[slot][4 * g + 2], ra[slot][4 * g + 3]};
-#pragma unroll
-    for (int g = 0; g < GB; ++g)
-      *reinterpret_cast<f32x4*>(Bs + b_st[g]) = f32x4{rb[slot][4 * g], rb[slot][4 * g + 1], rb[slot][4 * g + 2], rb[slot][4 * g + 3]};
+    for (int g = 0; g < G; ++g)
+      *reinterpret_cast<f32x4*>(img + o.st[g]) = f32x4{r[4 * g], r[4 * g + 1], r[4 * g + 2], r[4 * g + 3]};
   };
+  auto load_tiles = [&](int slot, int k0) { load_op(ra[slot], oa, k0); load_op(rb[slot], ob, k0); };
+  auto store_tiles = [&](int slot, int img) { store_op(ra[slot], oa, As2[img]); store_op(rb[slot], ob, Bs2[img]); };
 
   // squared-error epilogue: the targets of this thread's outputs are requested before the K loop
-  const bool do_mse = (FR <= 2) && pi < g.mse_count;          // wave-uniform
-  const MseEpi& me = g.mse[do_mse ? pi : 0];
+  const bool do_mse = (FR <= 2) && t.pi < g.mse_count;          // wave-uniform
   constexpr int TF = (FR <= 2) ? FR : 1;            // FR = 4 has no squared-error epilogue: no target registers
   float tgt[TF][TF][4];
-  if constexpr (FR <= 2) if (do_mse) {
-#pragma unroll
-    for (int fm = 0; fm < FR; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < FR; ++fn)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = min(m0 + wm * 16 * FR + fm * 16 + q * 4 + r, d.m - 1);
-          const int col = min(n0 + wn * 16 * FR + fn * 16 + bi, max(d.n_valid - 1, 0));
-          tgt[fm][fn][r] = me.x[(int64_t)row * me.ldx + col];
-        }
-  }
+  gemm_mse_targets<FR, TF>(g.mse[do_mse ? t.pi : 0], do_mse, d, t, wm, wn, bi, q, tgt);
   f32x4 acc[FR][FR];
-#pragma unroll
-  for (int i = 0; i < FR; ++i)
-#pragma unroll
-    for (int j = 0; j < FR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  gemm_clear_acc<FR>(acc);
 
   const int nkt = (kend - kbeg + BK - 1) / BK;
   // the ring is always filled DEPTH deep (tiles past the end load clamped addresses and are masked
@@ -244,8 +166,8 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
         for (int ks = 0; ks < KSB; ++ks)
 #pragma unroll
           for (int f = 0; f < FR; ++f) {
-            af[ks][f] = As[((kb + ks) * 4 + q) * a_lk + (wm * 16 * FR + f * 16 + bi) * a_lm];
-            bf[ks][f] = Bs[((kb + ks) * 4 + q) * b_lk + (wn * 16 * FR + f * 16 + bi) * b_ln];
+            af[ks][f] = As[((kb + ks) * 4 + q) * oa.l_k + (wm * 16 * FR + f * 16 + bi) * oa.l_row];
+            bf[ks][f] = Bs[((kb + ks) * 4 + q) * ob.l_k + (wn * 16 * FR + f * 16 + bi) * ob.l_row];
           }
 #pragma unroll
         for (int ks = 0; ks < KSB; ++ks)
@@ -263,7 +185,7 @@ __global__ __launch_bounds__(256, (FR == 1) ? (VEC ? 5 : 4) : (FR == 2 ? 3 : 2))
     }
   }
 
-  gemm_epilogue<FR, TF>(g, d, pi, z, split, m0, n0, wm, wn, bi, q, tid, lane, wave, acc, tgt, do_mse);
+  gemm_epilogue<FR, TF>(g, d, t, wm, wn, bi, q, tid, lane, wave, acc, tgt, do_mse);
 }
 
 static int g_cus = 0;
@@ -278,75 +200,48 @@ int device_cus() {
   return g_cus;
 }
 
-// Host-side launch of one group (count <= MFM_GEMM_MAXP).
-int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, const ZeroSpans* zs, const MseEpi* mse,
-                      int mse_count, int precision, const GemmEpiSet* epis) {
-  MFM_REQUIRE(count >= 1 && count <= MFM_GEMM_MAXP, "gemm group: count %d out of range", count);
-  const int cus = device_cus();
-  GemmGroup g;
-  memset(&g, 0, sizeof(g));
-  g.count = count;
-  MFM_REQUIRE(mse_count >= 0 && mse_count <= 3 && mse_count <= count && (mse_count == 0 || mse), "gemm group: bad mse epilogue count %d", mse_count);
-  g.mse_count = mse_count;
-  for (int i = 0; i < mse_count; ++i) {
-    MFM_REQUIRE(mse[i].x && !descs[i].accumulate && descs[i].batch == 1, "gemm group: mse epilogue %d needs a plain (non-accumulating, unbatched) product", i);
-    g.mse[i] = mse[i];
+// What one descriptor (problem i of its group) must satisfy.  has_mse: a squared-error epilogue rides on the problem and may
+// stand in for its c.
+static int gemm_check_problem(const MfmGemmDesc& d, int i, int precision, bool has_mse) {
+  MFM_REQUIRE(d.m > 0 && d.n > 0 && d.k >= 0 && d.batch > 0, "gemm[%d]: bad dims m=%d n=%d k=%d batch=%d", i, d.m, d.n, d.k, d.batch);
+  MFM_REQUIRE(d.a && d.b && (d.c || (has_mse && !d.accumulate && !d.c_bf16)), "gemm[%d]: null operand", i);
+  if (d.a_bf16 || d.c_bf16) {
+    MFM_REQUIRE(precision == 1, "gemm[%d]: bf16-resident operands (a_bf16 / c_bf16) are taken by the bf16 entry point only", i);
+    MFM_REQUIRE(!d.c_bf16 || (!d.accumulate && d.split_k <= 1), "gemm[%d]: c_bf16 needs a plain (non-accumulating, unsplit) product", i);
+    const GemmForm fa = gemm_operand_form(d.a_sm, d.a_sk);
+    MFM_REQUIRE(!d.a_bf16 || ((((uintptr_t)d.a) & 15) == 0 && (d.a_sz & 7) == 0 &&
+                              ((fa == GEMM_K_CONTIG && (d.a_sm & 7) == 0) || (fa == GEMM_ROW_CONTIG && (d.a_sk & 7) == 0))),
+                "gemm[%d]: a_bf16 needs a unit-stride axis on 16-byte boundaries (a_sm=%lld a_sk=%lld a_sz=%lld)", i,
+                (long long)d.a_sm, (long long)d.a_sk, (long long)d.a_sz);
   }
-  if (epis && epis->count > 0) {
-    MFM_REQUIRE(epis->count <= MFM_GEMM_NEPI && epis->count <= count && epis->epi, "gemm group: %d output transforms (max %d)", epis->count, MFM_GEMM_NEPI);
-    for (int i = 0; i < epis->count; ++i) {
-      const GemmEpi& e = epis->epi[i];
-      MFM_REQUIRE(e.kind >= 0 && e.kind <= 3 && (e.kind == 0 || e.kind == 2 || e.aux), "gemm group: bad output transform %d", i);
-      MFM_REQUIRE(e.kind == 0 || (!descs[i].accumulate && descs[i].split_k <= 1 && descs[i].batch == 1),
-                  "gemm group: output transform %d needs a plain (non-accumulating, unbatched) product", i);
-      g.epi[i] = e;
-    }
-    g.epi_count = epis->count; g.epi_train = epis->train; g.epi_seed = epis->seed; g.epi_tick = epis->tick;
-  }
-  if (zs) {
-    for (int i = 0; i < MFM_GEMM_ZSPANS; ++i) {
-      if (zs->n[i] <= 0) continue;
-      MFM_REQUIRE((zs->n[i] & 3) == 0 && (((uintptr_t)zs->ptr[i]) & 15) == 0, "gemm group: zero span %d not 16-byte shaped", i);
-      g.zero_ptr[i] = zs->ptr[i]; g.zero_n[i] = zs->n[i];
-    }
-  }
-  // pass 1: block count with 64x64 tiles and no split; decide tile size
+  MFM_REQUIRE(d.n_valid >= 0 && d.n_valid <= d.n, "gemm[%d]: n_valid %d > n %d", i, d.n_valid, d.n);
+  MFM_REQUIRE(d.split_k <= 1 || d.accumulate, "gemm[%d]: split_k needs accumulate", i);
+  // The kernels form an operand's extent (gemm_operand_bytes) and every load offset (off * 4) in BYTES in 32-bit ints:
+  // the span of one batch member, first to last element, is held to what those carry, 2^31 - 1 bytes (2^29 - 1 fp32
+  // elements).  Beyond it the extent wraps and the loads return zeros or another row without any error.
+  const int64_t lim = ((int64_t)1 << 31) - 1;
+  MFM_REQUIRE(d.a_sm >= 0 && d.a_sk >= 0 && d.b_sk >= 0 && d.b_sn >= 0 && d.a_sm <= lim && d.a_sk <= lim && d.b_sk <= lim && d.b_sn <= lim,
+              "gemm[%d]: operand strides must lie in [0, 2^31) (a_sm=%lld a_sk=%lld b_sk=%lld b_sn=%lld)", i,
+              (long long)d.a_sm, (long long)d.a_sk, (long long)d.b_sk, (long long)d.b_sn);
+  const int64_t sa = gemm_operand_elems<int64_t>(d.m, d.k, d.a_sm, d.a_sk), ba = gemm_operand_bytes<int64_t>(d.m, d.k, d.a_sm, d.a_sk, d.a_bf16 ? 2 : 4);
+  const int64_t sb = gemm_operand_elems<int64_t>(d.k, d.n_valid, d.b_sk, d.b_sn), bb = gemm_operand_bytes<int64_t>(d.k, d.n_valid, d.b_sk, d.b_sn, 4);
+  MFM_REQUIRE(ba <= lim,
+              "gemm[%d]: operand a spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
+              i, (long long)sa, (long long)ba);
+  MFM_REQUIRE(bb <= lim,
+              "gemm[%d]: operand b spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
+              i, (long long)sb, (long long)bb);
+  return MFM_OK;
+}
+
+// The launch plan of a group of checked problems on a device of `cus` CUs: tile size 32 FR, kernel form (vec: no oddly
+// strided operand; bf16: the bf16-operand kernel), and per problem the tiles, K split and first workgroup in g.p / g.begins.
+static int gemm_plan_group(const MfmGemmDesc* descs, int count, int cus, int precision, int mse_count, GemmGroup& g, int& FR, bool& vec,
+                           bool& bf16, int& total) {
+  // tile size from the block count with 64x64 tiles and no split
   long blocks64 = 0;
-  for (int i = 0; i < count; ++i) {
-    const MfmGemmDesc& d = descs[i];
-    MFM_REQUIRE(d.m > 0 && d.n > 0 && d.k >= 0 && d.batch > 0, "gemm[%d]: bad dims m=%d n=%d k=%d batch=%d", i, d.m, d.n, d.k, d.batch);
-    MFM_REQUIRE(d.a && d.b && (d.c || (i < mse_count && !d.accumulate && !d.c_bf16)), "gemm[%d]: null operand", i);
-    if (d.a_bf16 || d.c_bf16) {
-      MFM_REQUIRE(precision == 1, "gemm[%d]: bf16-resident operands (a_bf16 / c_bf16) are taken by the bf16 entry point only", i);
-      MFM_REQUIRE(!d.c_bf16 || (!d.accumulate && d.split_k <= 1), "gemm[%d]: c_bf16 needs a plain (non-accumulating, unsplit) product", i);
-      MFM_REQUIRE(!d.a_bf16 || ((((uintptr_t)d.a) & 15) == 0 && (d.a_sz & 7) == 0 &&
-                                ((d.a_sk == 1 && (d.a_sm & 7) == 0) || (d.a_sm == 1 && d.a_sk != 1 && (d.a_sk & 7) == 0))),
-                  "gemm[%d]: a_bf16 needs a unit-stride axis on 16-byte boundaries (a_sm=%lld a_sk=%lld a_sz=%lld)", i,
-                  (long long)d.a_sm, (long long)d.a_sk, (long long)d.a_sz);
-    }
-    MFM_REQUIRE(d.n_valid >= 0 && d.n_valid <= d.n, "gemm[%d]: n_valid %d > n %d", i, d.n_valid, d.n);
-    MFM_REQUIRE(d.split_k <= 1 || d.accumulate, "gemm[%d]: split_k needs accumulate", i);
-    {
-      // The kernels form an operand's extent (a_bytes, b_bytes) and every load offset (off * 4) in BYTES in 32-bit ints:
-      // the span of one batch member, first to last element, is held to what those carry, 2^31 - 1 bytes (2^29 - 1 fp32
-      // elements).  Beyond it the extent wraps and the loads return zeros or another row without any error.
-      const int64_t lim = ((int64_t)1 << 31) - 1;
-      MFM_REQUIRE(d.a_sm >= 0 && d.a_sk >= 0 && d.b_sk >= 0 && d.b_sn >= 0 && d.a_sm <= lim && d.a_sk <= lim && d.b_sk <= lim && d.b_sn <= lim,
-                  "gemm[%d]: operand strides must lie in [0, 2^31) (a_sm=%lld a_sk=%lld b_sk=%lld b_sn=%lld)", i,
-                  (long long)d.a_sm, (long long)d.a_sk, (long long)d.b_sk, (long long)d.b_sn);
-      const int64_t sa = (int64_t)(d.m - 1) * d.a_sm + (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.a_sk + 1;
-      const int64_t sb = (int64_t)(d.k > 0 ? d.k - 1 : 0) * d.b_sk + (int64_t)(d.n_valid > 0 ? d.n_valid - 1 : 0) * d.b_sn + 1;
-      const int64_t ba = d.a_bf16 ? ((sa * 2 + 3) & ~(int64_t)3) : sa * 4;      // (bf16: whole dwords, as the kernel rounds it)
-      MFM_REQUIRE(ba <= lim,
-                  "gemm[%d]: operand a spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
-                  i, (long long)sa, (long long)ba);
-      MFM_REQUIRE(sb * 4 <= lim,
-                  "gemm[%d]: operand b spans %lld elements (%lld bytes); the 32-bit byte offsets of the tile loads hold 2^31 - 1 bytes",
-                  i, (long long)sb, (long long)(sb * 4));
-    }
-    blocks64 += (long)cdiv(d.m, 64) * cdiv(d.n, 64) * d.batch;
-  }
-  int FR = (blocks64 >= 2L * cus) ? 2 : 1;
+  for (int i = 0; i < count; ++i) blocks64 += (long)cdiv(descs[i].m, 64) * cdiv(descs[i].n, 64) * descs[i].batch;
+  FR = (blocks64 >= 2L * cus) ? 2 : 1;
   // 128x128 tiles (FR = 4) are opt-in: on single large forward-layout products they add ~10 % over 64x64 (fp32:
   // 61 -> 69 TF/s on the projection shape, 86 -> 99 TF/s at 4096^3), but the step's grouped launches mix in small-K
   // and weight-gradient problems that lose more than that (proj launch at B=2048: 457 -> 514 us), and the bf16-operand
@@ -360,20 +255,18 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
   for (int i = 0; i < count; ++i)
     base_blocks += (long)cdiv(descs[i].m, BT) * cdiv(descs[i].n, BT) * descs[i].batch;
   const long kdepth = 2048;      // K elements one workgroup walks at most (accumulating problems; measured 256..4096 at B=512/2048)
-  bool vec = true;
+  vec = true;
   for (int i = 0; i < count; ++i) {
     const MfmGemmDesc& d = descs[i];
     if (d.k == 0) continue;        // no element of a or b is part of the product (its strides are replaced below)
-    const bool a_mcontig = (d.a_sm == 1 && d.a_sk != 1), b_ncontig = (d.b_sn == 1 && d.b_sk != 1);
-    if (!(a_mcontig || d.a_sk == 1) || !(b_ncontig || d.b_sk == 1)) vec = false;
+    if (gemm_operand_form(d.a_sm, d.a_sk) == GEMM_ODD || gemm_operand_form(d.b_sn, d.b_sk) == GEMM_ODD) vec = false;
   }
   // bf16 MFMA operands (precision 1) need every operand unit-stride along its 16-byte load groups; a group with an
   // oddly strided operand runs on the fp32 kernel's dword path instead
-  const bool bf16 = (precision == 1) && vec;
+  bf16 = (precision == 1) && vec;
   for (int i = 0; i < count; ++i)
     MFM_REQUIRE(bf16 || !(descs[i].a_bf16 || descs[i].c_bf16), "gemm[%d]: bf16-resident operands need unit-stride operands in the whole group", i);
   const int bk = bf16 ? BKB : BK;
-  int total = 0;
   for (int i = 0; i < count; ++i) {
     GemmProblem& P = g.p[i];
     P.d = descs[i];
@@ -403,68 +296,93 @@ int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, c
     split = cdiv(P.d.k > 0 ? P.d.k : 1, kps);
     P.d.split_k = split;
     P.k_per_split = kps;
-    P.block_begin = total;
-    g.begins[i] = total;
-    total += P.tiles_m * P.tiles_n * P.d.batch * split;
+    g.begins[i] = P.tiles_m * P.tiles_n * P.d.batch * split;
   }
-  for (int i = count; i < MFM_GEMM_MAXP; ++i) g.begins[i] = 0x7fffffff;
-  if (bf16) return gemm_bf16_launch_kernel(g, FR, total, stream);
-  if (FR == 4) {
-    if (vec) MFM_LAUNCH_TIMED((gemm_f32_kernel<4, true>), dim3(total), dim3(256), 0, stream, g);
-    else MFM_LAUNCH_TIMED((gemm_f32_kernel<4, false>), dim3(total), dim3(256), 0, stream, g);
-  } else if (FR == 2) {
-    if (vec) MFM_LAUNCH_TIMED((gemm_f32_kernel<2, true>), dim3(total), dim3(256), 0, stream, g);
-    else MFM_LAUNCH_TIMED((gemm_f32_kernel<2, false>), dim3(total), dim3(256), 0, stream, g);
-  } else {
-    if (vec) MFM_LAUNCH_TIMED((gemm_f32_kernel<1, true>), dim3(total), dim3(256), 0, stream, g);
-    else MFM_LAUNCH_TIMED((gemm_f32_kernel<1, false>), dim3(total), dim3(256), 0, stream, g);
-  }
-  MFM_LAUNCH_CHECK("gemm_f32_kernel");
+  total = gemm_assign_blocks(g);
   return MFM_OK;
+}
+
+// The one place that names the instantiations: (bf16, FR, vec) -> kernel.
+static int gemm_dispatch(const GemmGroup& g, bool bf16, int FR, bool vec, int total, hipStream_t stream) {
+  static const GemmKernel f32[3][2] = {{gemm_f32_kernel<1, false>, gemm_f32_kernel<1, true>},
+                                       {gemm_f32_kernel<2, false>, gemm_f32_kernel<2, true>},
+                                       {gemm_f32_kernel<4, false>, gemm_f32_kernel<4, true>}};
+  const GemmKernel kernel = bf16 ? gemm_bf16_kernel_for(FR) : f32[FR == 4 ? 2 : (FR == 2 ? 1 : 0)][vec ? 1 : 0];
+  MFM_LAUNCH_TIMED(kernel, dim3(total), dim3(256), 0, stream, g);
+  MFM_LAUNCH_CHECK(bf16 ? "gemm_bf16_kernel" : "gemm_f32_kernel");
+  return MFM_OK;
+}
+
+// Host-side launch of one group (count <= MFM_GEMM_MAXP).
+int gemm_group_launch(const MfmGemmDesc* descs, int count, hipStream_t stream, const ZeroSpans* zs, const MseEpi* mse,
+                      int mse_count, int precision, const GemmEpiSet* epis) {
+  MFM_REQUIRE(count >= 1 && count <= MFM_GEMM_MAXP, "gemm group: count %d out of range", count);
+  GemmGroup g;
+  memset(&g, 0, sizeof(g));
+  g.count = count;
+  MFM_REQUIRE(mse_count >= 0 && mse_count <= 3 && mse_count <= count && (mse_count == 0 || mse), "gemm group: bad mse epilogue count %d", mse_count);
+  g.mse_count = mse_count;
+  for (int i = 0; i < mse_count; ++i) {
+    MFM_REQUIRE(mse[i].x && !descs[i].accumulate && descs[i].batch == 1, "gemm group: mse epilogue %d needs a plain (non-accumulating, unbatched) product", i);
+    g.mse[i] = mse[i];
+  }
+  if (epis && epis->count > 0) {
+    MFM_REQUIRE(epis->count <= MFM_GEMM_NEPI && epis->count <= count && epis->epi, "gemm group: %d output transforms (max %d)", epis->count, MFM_GEMM_NEPI);
+    for (int i = 0; i < epis->count; ++i) {
+      const GemmEpi& e = epis->epi[i];
+      MFM_REQUIRE(e.kind >= 0 && e.kind <= 3 && (e.kind == 0 || e.kind == 2 || e.aux), "gemm group: bad output transform %d", i);
+      MFM_REQUIRE(e.kind == 0 || (!descs[i].accumulate && descs[i].split_k <= 1 && descs[i].batch == 1),
+                  "gemm group: output transform %d needs a plain (non-accumulating, unbatched) product", i);
+      g.epi[i] = e;
+    }
+    g.epi_count = epis->count; g.epi_train = epis->train; g.epi_seed = epis->seed; g.epi_tick = epis->tick;
+  }
+  if (zs) {
+    for (int i = 0; i < MFM_GEMM_ZSPANS; ++i) {
+      if (zs->n[i] <= 0) continue;
+      MFM_REQUIRE((zs->n[i] & 3) == 0 && (((uintptr_t)zs->ptr[i]) & 15) == 0, "gemm group: zero span %d not 16-byte shaped", i);
+      g.zero_ptr[i] = zs->ptr[i]; g.zero_n[i] = zs->n[i];
+    }
+  }
+  int rc, FR, total;
+  bool vec, bf16;
+  for (int i = 0; i < count; ++i)
+    if ((rc = gemm_check_problem(descs[i], i, precision, i < mse_count)) != MFM_OK) return rc;
+  if ((rc = gemm_plan_group(descs, count, device_cus(), precision, mse_count, g, FR, vec, bf16, total)) != MFM_OK) return rc;
+  return gemm_dispatch(g, bf16, FR, vec, total, stream);
 }
 
 }  // namespace mfm
 
-extern "C" int mfm_gemm_grouped_f32(const MfmGemmDesc* descs, int count, void* stream) {
+// the two precisions' entry points: `name` is the caller's, for its error texts
+static int gemm_grouped_entry(const char* name, const MfmGemmDesc* descs, int count, void* stream, int precision) {
   if (!descs || count <= 0) {
-    mfm::set_error("mfm_gemm_grouped_f32: no problems");
+    mfm::set_error("%s: no problems", name);
     return MFM_ERR_ARG;
   }
   for (int i = 0; i < count; ++i)       // (the library uses the reserved bytes internally: a caller's garbage there would be a device pointer)
     if (descs[i].reserved_[0] != 0 || descs[i].reserved_[1] != 0) {
-      mfm::set_error("mfm_gemm_grouped_f32: problem %d has non-zero reserved_ fields (zero the struct before filling it)", i);
+      mfm::set_error("%s: problem %d has non-zero reserved_ fields (zero the struct before filling it)", name, i);
       return MFM_ERR_ARG;
     }
   int done = 0;
   while (done < count) {
     int n = count - done;
     if (n > MFM_GEMM_MAXP) n = MFM_GEMM_MAXP;
-    int rc = mfm::gemm_group_launch(descs + done, n, (hipStream_t)stream);
+    int rc = mfm::gemm_group_launch(descs + done, n, (hipStream_t)stream, nullptr, nullptr, 0, precision);
     if (rc != MFM_OK) return rc;
     done += n;
   }
   return MFM_OK;
+}
+
+extern "C" int mfm_gemm_grouped_f32(const MfmGemmDesc* descs, int count, void* stream) {
+  return gemm_grouped_entry("mfm_gemm_grouped_f32", descs, count, stream, 0);
+}
+
+extern "C" int mfm_gemm_grouped_bf16(const MfmGemmDesc* descs, int count, void* stream) {
+  return gemm_grouped_entry("mfm_gemm_grouped_bf16", descs, count, stream, 1);
 }
 
 extern "C" int mfm_device_cus(void) { return mfm::device_cus(); }
 
-extern "C" int mfm_gemm_grouped_bf16(const MfmGemmDesc* descs, int count, void* stream) {
-  if (!descs || count <= 0) {
-    mfm::set_error("mfm_gemm_grouped_bf16: no problems");
-    return MFM_ERR_ARG;
-  }
-  for (int i = 0; i < count; ++i)
-    if (descs[i].reserved_[0] != 0 || descs[i].reserved_[1] != 0) {
-      mfm::set_error("mfm_gemm_grouped_bf16: problem %d has non-zero reserved_ fields (zero the struct before filling it)", i);
-      return MFM_ERR_ARG;
-    }
-  int done = 0;
-  while (done < count) {
-    int n = count - done;
-    if (n > MFM_GEMM_MAXP) n = MFM_GEMM_MAXP;
-    int rc = mfm::gemm_group_launch(descs + done, n, (hipStream_t)stream, nullptr, nullptr, 0, 1);
-    if (rc != MFM_OK) return rc;
-    done += n;
-  }
-  return MFM_OK;
-}

@@ -39,29 +39,10 @@ __global__ __launch_bounds__(256, (FR == 1) ? 4 : 2) void gemm_bf16_kernel(const
   const int bi = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // ---- locate problem / tile (wave-uniform); XCD-aware tile order as in gemm.hip
-  int pi = 0;
-  const int bid = blockIdx.x;
-#pragma unroll
-  for (int i = 1; i < MFM_GEMM_MAXP; ++i) pi += (bid >= g.begins[i]) ? 1 : 0;
-  const GemmProblem& P = g.p[pi];
-  const MfmGemmDesc& d = P.d;
-  int local = bid - P.block_begin;
-  {
-    constexpr int NX = 8;
-    const int nb = ((pi + 1 < g.count) ? g.begins[pi + 1] : (int)gridDim.x) - P.block_begin;
-    const int x = local % NX, j = local / NX;
-    const int per = nb / NX, rem = nb % NX;
-    local = x * per + (x < rem ? x : rem) + j;
-  }
-  const int tn = local % P.tiles_n; local /= P.tiles_n;
-  const int tm = local % P.tiles_m; local /= P.tiles_m;
-  const int z = local % d.batch;
-  const int split = local / d.batch;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int kbeg = split * P.k_per_split;
-  const int kend = min(d.k, kbeg + P.k_per_split);
-  if (kbeg >= kend && split > 0) return;
+  const GemmTile t = gemm_locate(g, BM, BN);
+  const MfmGemmDesc& d = g.p[t.pi].d;
+  const int pi = t.pi, z = t.z, m0 = t.m0, n0 = t.n0, kbeg = t.kbeg, kend = t.kend;
+  if (kbeg >= kend && t.split > 0) return;
 
   // a_bf16: the A operand is a bf16-RESIDENT buffer (saved hidden states / gate gradients of a bf16 plan): element size 2,
   // no rounding pass -- the 16-byte loads go to the LDS image as they are (wave-uniform per problem)
@@ -69,13 +50,12 @@ __global__ __launch_bounds__(256, (FR == 1) ? 4 : 2) void gemm_bf16_kernel(const
   const float* __restrict__ A = a16 ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(d.a) + (int64_t)z * d.a_sz)
                                     : d.a + (int64_t)z * d.a_sz;
   const float* __restrict__ Bm = d.b + (int64_t)z * d.b_sz;
-  const bool a_mcontig = (d.a_sm == 1 && d.a_sk != 1);
-  const bool b_ncontig = (d.b_sn == 1 && d.b_sk != 1);
+  const bool a_mcontig = gemm_operand_form(d.a_sm, d.a_sk) == GEMM_ROW_CONTIG;
+  const bool b_ncontig = gemm_operand_form(d.b_sn, d.b_sk) == GEMM_ROW_CONTIG;
   const int a_sm = (int)d.a_sm, a_sk = (int)d.a_sk, b_sk = (int)d.b_sk, b_sn = (int)d.b_sn;
-  // (bf16: rounded up to whole dwords -- the range check is per dword, an odd element count would zero the last element)
-  const int a_bytes = a16 ? ((((d.m - 1) * a_sm + (max(d.k, 1) - 1) * a_sk + 1) * 2 + 3) & ~3)
-                          : ((d.m - 1) * a_sm + (max(d.k, 1) - 1) * a_sk + 1) * 4;
-  const int b_bytes = ((max(d.k, 1) - 1) * b_sk + (max(d.n_valid, 1) - 1) * b_sn + 1) * 4;
+  // extents and every `off * 4` below are 32-bit ints: the host refuses operands whose span in BYTES does not fit one
+  const int a_bytes = gemm_operand_bytes(d.m, d.k, a_sm, a_sk, a16 ? 2 : 4);
+  const int b_bytes = gemm_operand_bytes(d.k, d.n_valid, b_sk, b_sn, 4);
   const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t bres = __builtin_amdgcn_make_buffer_rsrc((void*)Bm, 0, b_bytes, 0x00020000);
   const int klast = max(kend - 1, 0);
@@ -197,26 +177,11 @@ __global__ __launch_bounds__(256, (FR == 1) ? 4 : 2) void gemm_bf16_kernel(const
 
   // squared-error epilogue: the targets of this thread's outputs are requested before the K loop
   const bool do_mse = (FR <= 2) && pi < g.mse_count;          // wave-uniform
-  const MseEpi& me = g.mse[do_mse ? pi : 0];
   constexpr int TF = (FR <= 2) ? FR : 1;
   float tgt[TF][TF][4];
-  if constexpr (FR <= 2) if (do_mse) {
-#pragma unroll
-    for (int fm = 0; fm < FR; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < FR; ++fn)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = min(m0 + wm * 16 * FR + fm * 16 + q * 4 + r, d.m - 1);
-          const int col = min(n0 + wn * 16 * FR + fn * 16 + bi, max(d.n_valid - 1, 0));
-          tgt[fm][fn][r] = me.x[(int64_t)row * me.ldx + col];
-        }
-  }
+  gemm_mse_targets<FR, TF>(g.mse[do_mse ? pi : 0], do_mse, d, t, wm, wn, bi, q, tgt);
   f32x4 acc[FR][FR];
-#pragma unroll
-  for (int i = 0; i < FR; ++i)
-#pragma unroll
-    for (int j = 0; j < FR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  gemm_clear_acc<FR>(acc);
 
   const int nkt = (kend - kbeg + BKB - 1) / BKB;
   load_tiles(kbeg);
@@ -247,15 +212,11 @@ __global__ __launch_bounds__(256, (FR == 1) ? 4 : 2) void gemm_bf16_kernel(const
     lds_barrier();
   }
 
-  gemm_epilogue<FR, TF>(g, d, pi, z, split, m0, n0, wm, wn, bi, q, tid, lane, wave, acc, tgt, do_mse);
+  gemm_epilogue<FR, TF>(g, d, t, wm, wn, bi, q, tid, lane, wave, acc, tgt, do_mse);
 }
 
-int gemm_bf16_launch_kernel(const GemmGroup& g, int FR, int total, hipStream_t stream) {
-  if (FR == 4) MFM_LAUNCH_TIMED((gemm_bf16_kernel<4>), dim3(total), dim3(256), 0, stream, g);
-  else if (FR == 2) MFM_LAUNCH_TIMED((gemm_bf16_kernel<2>), dim3(total), dim3(256), 0, stream, g);
-  else MFM_LAUNCH_TIMED((gemm_bf16_kernel<1>), dim3(total), dim3(256), 0, stream, g);
-  MFM_LAUNCH_CHECK("gemm_bf16_kernel");
-  return MFM_OK;
+GemmKernel gemm_bf16_kernel_for(int FR) {
+  return FR == 4 ? gemm_bf16_kernel<4> : (FR == 2 ? gemm_bf16_kernel<2> : gemm_bf16_kernel<1>);
 }
 
 }  // namespace mfm

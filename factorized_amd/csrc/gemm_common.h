@@ -1,10 +1,36 @@
-// Shared between the fp32 (gemm.hip) and bf16-operand (gemm_bf16.hip) grouped GEMM kernels: the problem table
-// that travels in the kernel-argument segment and the common epilogue (bias, alpha, pad columns, atomics for
-// split-K / accumulating problems, squared-error epilogue, zero-fill spans).
+// Shared between the fp32 (gemm.hip) and bf16-operand (gemm_bf16.hip) grouped GEMM kernels and, as far as it applies, the
+// small-row weight-gradient kernel (gemm_tn.hip): the problem table that travels in the kernel-argument segment, the rules
+// that host and kernels must state alike (an operand's form and extent, which workgroup computes which tile) and the
+// common epilogue (bias, alpha, pad columns, atomics for split-K / accumulating problems, squared-error epilogue,
+// zero-fill spans).
 #pragma once
 #include "internal.h"
 
 namespace mfm {
+
+// ---------------------------------------------------------------- operand form and extent: one statement for host and kernels
+// How an operand lies in memory, seen from a thread's 4-element load group: unit-stride along k (x, h, W of a forward
+// product), unit-stride along its rows (m for a, n for b: both operands of a weight-gradient product), or neither.  The
+// first two are fetched 16 bytes at a time; one odd operand puts its whole group on the dword loads of the fp32 kernel.
+enum GemmForm { GEMM_K_CONTIG, GEMM_ROW_CONTIG, GEMM_ODD };
+__host__ __device__ inline GemmForm gemm_operand_form(const int64_t s_row, const int64_t s_k) {
+  return (s_k == 1) ? GEMM_K_CONTIG : (s_row == 1 ? GEMM_ROW_CONTIG : GEMM_ODD);
+}
+
+// Elements from the first to the last element of one batch member of a rows x cols operand, and the same in bytes: the
+// extent of the kernels' bounds-checked buffer descriptors, which end at the last addressable element (a 16-byte group
+// that runs past it reads zeros).  An empty axis counts as one element.  2-byte elements (bf16-resident operands) are
+// rounded up to whole dwords: the range check is per dword, an odd element count would zero the last element.  The kernels
+// instantiate it with the 32-bit ints of their offsets, the host with int64_t to refuse what those cannot hold.
+template <typename I>
+__host__ __device__ inline I gemm_operand_elems(const I rows, const I cols, const I s_row, const I s_col) {
+  return ((rows > 1 ? rows : 1) - 1) * s_row + ((cols > 1 ? cols : 1) - 1) * s_col + 1;
+}
+template <typename I>
+__host__ __device__ inline I gemm_operand_bytes(const I rows, const I cols, const I s_row, const I s_col, const int elem_bytes) {
+  const I e = gemm_operand_elems(rows, cols, s_row, s_col);
+  return (elem_bytes == 2) ? ((e * 2 + 3) & ~(I)3) : e * 4;
+}
 
 #define MFM_GEMM_NEPI 4     // problems per launch that may carry an output transform (always the first ones)
 
@@ -31,15 +57,95 @@ struct GemmGroup {
   unsigned long long epi_seed;
   const unsigned long long* epi_tick;
 };
+__host__ __device__ inline int gemm_problem_batch(const GemmProblem& P) { return P.d.batch; }
+__host__ __device__ inline int gemm_problem_k(const GemmProblem& P) { return P.d.k; }
 
+// Host: begins[i] holds the workgroup count of problem i on entry and its first workgroup on return, as does
+// p[i].block_begin; the entries past `count` are INT_MAX, which no workgroup id reaches.  Returns the grid size.
+template <typename Group>
+static inline int gemm_assign_blocks(Group& g) {
+  constexpr int MAXP = sizeof(g.begins) / sizeof(g.begins[0]);
+  int total = 0;
+  for (int i = 0; i < g.count; ++i) {
+    const int blocks = g.begins[i];
+    g.p[i].block_begin = g.begins[i] = total;
+    total += blocks;
+  }
+  for (int i = g.count; i < MAXP; ++i) g.begins[i] = 0x7fffffff;
+  return total;
+}
+
+// Which tile of which problem a workgroup computes (wave-uniform).  Group is a problem table with p[], begins[] and
+// count whose problems carry tiles_m, tiles_n, block_begin, k_per_split and answer gemm_problem_batch / gemm_problem_k.
+// The logical order inside a problem is (split, z, tm, tn), tn fastest; kbeg >= kend marks a K range with nothing in it.
+struct GemmTile { int pi, tm, tn, z, split, m0, n0, kbeg, kend; };
+template <typename Group>
+__device__ __forceinline__ GemmTile gemm_locate(const Group& g, const int BM, const int BN) {
+  constexpr int MAXP = sizeof(g.begins) / sizeof(g.begins[0]);
+  GemmTile t;
+  t.pi = 0;
+  const int bid = blockIdx.x;
+#pragma unroll
+  for (int i = 1; i < MAXP; ++i) t.pi += (bid >= g.begins[i]) ? 1 : 0;
+  const auto& P = g.p[t.pi];
+  int local = bid - P.block_begin;
+  {
+    // Workgroups are dealt to the 8 XCDs round-robin by id, and each XCD has its own L2.  Tiles that share
+    // an operand panel (same m-tile across n, same n-tile across m / gates) are neighbours in the LOGICAL
+    // order, so inside every problem each XCD is given one contiguous run of logical tiles: a panel is then
+    // fetched from HBM once per XCD that needs it instead of once per tile (the LSTM weight-gradient launch
+    // read 37.7 MB for ~6 MB of operands before this, the small-row one 45 MB for ~8 MB), while every XCD still
+    // gets an equal share of every problem (a whole-launch remap left the XCDs with the long-K problems as stragglers).
+    constexpr int NX = 8;
+    const int nb = ((t.pi + 1 < g.count) ? g.begins[t.pi + 1] : (int)gridDim.x) - P.block_begin;
+    const int x = local % NX, j = local / NX;
+    const int per = nb / NX, rem = nb % NX;
+    local = x * per + (x < rem ? x : rem) + j;
+  }
+  const int batch = gemm_problem_batch(P);
+  t.tn = local % P.tiles_n; local /= P.tiles_n;
+  t.tm = local % P.tiles_m; local /= P.tiles_m;
+  t.z = local % batch;
+  t.split = local / batch;
+  t.m0 = t.tm * BM; t.n0 = t.tn * BN;
+  t.kbeg = t.split * P.k_per_split;
+  t.kend = min(gemm_problem_k(P), t.kbeg + P.k_per_split);
+  return t;
+}
+
+// The squared-error targets of this thread's outputs (clamped into x: the epilogue uses only those inside), requested
+// ahead of the K loop; and the accumulator clear.
+template <int FR, int TF>
+__device__ __forceinline__ void gemm_mse_targets(const MseEpi& me, const bool do_mse, const MfmGemmDesc& d, const GemmTile& t,
+                                                 const int wm, const int wn, const int bi, const int q, float (&tgt)[TF][TF][4]) {
+  if constexpr (FR <= 2) if (do_mse) {
+#pragma unroll
+    for (int fm = 0; fm < FR; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < FR; ++fn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = min(t.m0 + wm * 16 * FR + fm * 16 + q * 4 + r, d.m - 1);
+          const int col = min(t.n0 + wn * 16 * FR + fn * 16 + bi, max(d.n_valid - 1, 0));
+          tgt[fm][fn][r] = me.x[(int64_t)row * me.ldx + col];
+        }
+  }
+}
+template <int FR>
+__device__ __forceinline__ void gemm_clear_acc(f32x4 (&acc)[FR][FR]) {
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int j = 0; j < FR; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
 
 // Epilogue of one workgroup tile.  acc[fm][fn] follows the 16x16 MFMA accumulator map (row = 4*(lane>>4) + r,
 // col = lane & 15), identical for the f32 and bf16 instructions.
 template <int FR, int TF>
-__device__ __forceinline__ void gemm_epilogue(const GemmGroup& g, const MfmGemmDesc& d, const int pi, const int z,
-                                              const int split, const int m0, const int n0, const int wm, const int wn,
+__device__ __forceinline__ void gemm_epilogue(const GemmGroup& g, const MfmGemmDesc& d, const GemmTile& t, const int wm, const int wn,
                                               const int bi, const int q, const int tid, const int lane, const int wave,
                                               f32x4 (&acc)[FR][FR], float (&tgt)[TF][TF][4], const bool do_mse) {
+  const int pi = t.pi, z = t.z, split = t.split, m0 = t.m0, n0 = t.n0;
   const MseEpi& me = g.mse[do_mse ? pi : 0];
   float* __restrict__ C = d.c ? d.c + (int64_t)z * d.c_sz : nullptr;
   float* __restrict__ C2 = d.c2 ? d.c2 + (int64_t)z * d.c_sz : nullptr;
@@ -126,8 +232,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmGroup& g, const MfmGemmD
   }
 }
 
-// gemm_bf16.hip
-int gemm_bf16_launch_kernel(const GemmGroup& g, int FR, int total, hipStream_t stream);
+// gemm_bf16.hip: the bf16-operand kernel with 32 FR x 32 FR tiles (FR = 1, 2, 4)
+typedef void (*GemmKernel)(const GemmGroup);
+GemmKernel gemm_bf16_kernel_for(int FR);
 constexpr int BKB = 64;   // K depth of one LDS stage of the bf16 kernel: two 32-deep MFMA k-steps
 
 }  // namespace mfm

@@ -34,6 +34,8 @@ struct TnProblem {
   float alpha;
 };
 struct TnGroup { TnProblem p[MFM_TN_MAXP]; int begins[MFM_TN_MAXP]; int count; };
+__device__ inline int gemm_problem_batch(const TnProblem& P) { return P.batch; }
+__device__ inline int gemm_problem_k(const TnProblem& P) { return P.k; }
 
 // TN_KC rows per chunk (80 / 160 / 320): 16-byte loads per thread and operand = TN_KC / 32
 template <int TN_KC>
@@ -47,42 +49,22 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const TnGroup g) {
   const int bi = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
 
-  int pi = 0;
-  const int bid = blockIdx.x;
-#pragma unroll
-  for (int i = 1; i < MFM_TN_MAXP; ++i) pi += (bid >= g.begins[i]) ? 1 : 0;
-  const TnProblem& P = g.p[pi];
-  const TnProblem& d = P;
-  int local = bid - P.block_begin;
-  {
-    // workgroups go to the 8 XCDs round-robin by id and every XCD has its own L2: give each XCD one contiguous run of a
-    // problem's logical (chunk, tile) order, as gemm.hip does, so that the tiles sharing an operand slice meet in one L2
-    // (without it the launch pulled 45 MB through the fabric for ~8 MB of operands)
-    constexpr int NX = 8;
-    const int nb = ((pi + 1 < g.count) ? g.begins[pi + 1] : (int)gridDim.x) - P.block_begin;
-    const int x = local % NX, j = local / NX;
-    const int per = nb / NX, rem = nb % NX;
-    local = x * per + (x < rem ? x : rem) + j;
-  }
-  const int tn = local % P.tiles_n; local /= P.tiles_n;
-  const int tm = local % P.tiles_m; local /= P.tiles_m;
-  const int z = local % d.batch;
-  const int split = local / d.batch;
-  const int m0 = tm * TN_T, n0 = tn * TN_T;
-  const int kbeg = split * P.k_per_split;
-  const int klen = min(d.k - kbeg, P.k_per_split);          // 1 .. TN_KC rows of this chunk
+  const GemmTile t = gemm_locate(g, TN_T, TN_T);          // (the logical order is (chunk, z, tile))
+  const TnProblem& d = g.p[t.pi];
+  const int tn = t.tn, z = t.z, m0 = t.m0, n0 = t.n0, kbeg = t.kbeg;
+  const int klen = min(d.k - kbeg, d.k_per_split);          // 1 .. TN_KC rows of this chunk
 
   const float* A = d.a + (int64_t)z * d.a_sz;
   const float* __restrict__ Bm = d.b + (int64_t)z * d.b_sz;
   const int a_sk = (int)d.a_sk, b_sk = (int)d.b_sk;
   // descriptors end at the last valid element: a 16-byte group that runs past it (or past its row's valid columns)
-  // returns zeros / neighbours' values for the excess elements, which only reach outputs that are never stored
+  // returns zeros / neighbours' values for the excess elements, which only reach outputs that are never stored.  That is
+  // the grouped kernels' extent with the strides this kernel fixes, a_sm = b_sn = 1.
   // a_bf16 (bf16-resident plans: the decoders' dA buffers): A holds __bf16 elements, addressed by the same element strides
   const bool a16 = d.a_bf16 != 0;
   if (a16) A = reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(d.a) + (int64_t)z * d.a_sz);
-  const int a_elems = (d.m - 1) + (d.k - 1) * a_sk + 1;
-  const int a_bytes = a16 ? ((a_elems * 2 + 3) & ~3) : a_elems * 4;
-  const int b_bytes = ((max(d.n_valid, 1) - 1) + (d.k - 1) * b_sk + 1) * 4;
+  const int a_bytes = gemm_operand_bytes(d.m, d.k, 1, a_sk, a16 ? 2 : 4);
+  const int b_bytes = gemm_operand_bytes(d.k, d.n_valid, b_sk, 1, 4);
   const __amdgpu_buffer_rsrc_t ares = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t bres = __builtin_amdgcn_make_buffer_rsrc((void*)Bm, 0, b_bytes, 0x00020000);
 
@@ -200,7 +182,6 @@ int gemm_tn_launch(const MfmGemmDesc* descs, int count, int max_rows, bool c_is_
   TnGroup g;
   memset(&g, 0, sizeof(g));
   g.count = count;
-  int total = 0;
   for (int i = 0; i < count; ++i) {
     const MfmGemmDesc& s = descs[i];
     TnProblem& P = g.p[i];
@@ -215,11 +196,9 @@ int gemm_tn_launch(const MfmGemmDesc* descs, int count, int max_rows, bool c_is_
     const int kps = round_up(cdiv(s.k, split), 4);
     split = cdiv(s.k, kps);
     P.k_per_split = kps;
-    P.block_begin = total;
-    g.begins[i] = total;
-    total += P.tiles_m * P.tiles_n * s.batch * split;
+    g.begins[i] = P.tiles_m * P.tiles_n * s.batch * split;
   }
-  for (int i = count; i < MFM_TN_MAXP; ++i) g.begins[i] = 0x7fffffff;
+  const int total = gemm_assign_blocks(g);
   constexpr size_t lds = (size_t)2 * KC * TN_T * sizeof(float);
   static_assert(lds <= 64 * 1024, "gemm tn: beyond the default LDS limit");
   MFM_LAUNCH_TIMED(gemm_tn_kernel<KC>, dim3(total), dim3(256), lds, stream, g);
