@@ -234,6 +234,12 @@ _SIGS = {
     "mfm_impute_missing_tile_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "mfm_impute_missing": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p), C.c_void_p,
                                      C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_void_p]),
+    "mfm_predict_missing_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                                         C.c_int64]),
+    "mfm_predict_missing_tile_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
+    "mfm_predict_missing": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p]),
     "mfm_p2p_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "mfm_p2p_handle_bytes": (C.c_int, []),
     "mfm_p2p_export": (C.c_int, [C.c_void_p, C.c_void_p]),

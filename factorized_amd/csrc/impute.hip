@@ -26,27 +26,6 @@
 
 namespace mfm {
 
-#define IMP_CASES INFER_DEC
-#define IMP_ENC (2 * IMP_CASES)
-#define IMP_CASE_PTRS 22     // per case: 6 of the encoder -> z_m, 6 of the encoder -> zy, 4 of z{m}_to_f{m}, 6 of decoder_m
-#define IMP_NPARAM (IMP_CASES * IMP_CASE_PTRS + 8)
-
-struct ImpEnc {
-  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
-  const float* w; const float* b;              // fc1
-  float* z;                                    // this chunk's rows [n, h]
-  int block_begin;
-};
-struct ImpEncodeDev { ImpEnc d[IMP_ENC]; int count, T, n, maxw; };
-
-// out_c [T * n, ld_c] <- rows [n0, n0 + n) of x [T, N, D], columns s0 .. s0 + len0 - 1 then s1 .. up to k_c in all; [k_c, ld_c): zeros
-struct ImpGather {
-  const float* x; float* out[IMP_CASES];
-  int s0[IMP_CASES], len0[IMP_CASES], s1[IMP_CASES], k[IMP_CASES], ld[IMP_CASES];
-  int64_t N, n0;
-  int n, T, D;
-};
-
 __global__ __launch_bounds__(256) void impute_gather_kernel(const ImpGather G) {
   const int c = blockIdx.y;
   const int ld = G.ld[c], k = G.k[c], s0 = G.s0[c], len0 = G.len0[c], s1 = G.s1[c];
@@ -76,14 +55,7 @@ __global__ __launch_bounds__(1024) void impute_encode_kernel(const ImpEncodeDev 
 }
 
 // ---------------------------------------------------------------- host
-// the sizes of a call, from the 12 the caller passes: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim
-struct ImpSizes {
-  int z[IMP_CASES], zy, fm[IMP_CASES], fy, dm[IMP_CASES], od, D;
-  int din[IMP_CASES], ld[IMP_CASES];           // the observed pair of case m: its width, and the row length of its gathered copy
-  int cs[IMP_CASES], nc;                       // the cases asked for, ascending
-};
-
-static bool imp_sizes(const int32_t* sz, int cases, ImpSizes& S) {
+bool imp_sizes(const int32_t* sz, int cases, ImpSizes& S) {
   for (int i = 0; i < 12; ++i)
     if (sz[i] < 1) return false;
   if (cases != 1 && cases != 2 && cases != 4 && cases != 7) return false;
@@ -118,7 +90,7 @@ static const int kImpEnc[IMP_ENC] = {8, 8, 2, 8, 20, 8};     // the canonical si
 // the launch(es) of one chunk of n rows (infer_launch_tuple_or_each); P.d holds the encoders of the cases asked for, two per
 // case; m0: the case when it is one
 template <int R>
-static int imp_encode_launch(ImpEncodeDev& P, int m0, int threads, size_t lds_bytes, hipStream_t stream) {
+static int imp_encode_launch(const char* who, ImpEncodeDev& P, int m0, int threads, size_t lds_bytes, hipStream_t stream) {
   const int ne = P.count;
   bool canon = true;
   for (int i = 0; i < ne; ++i) canon = canon && P.d[i].seq.hk4 == kImpEnc[ne == IMP_ENC ? i : 2 * m0 + i];
@@ -127,8 +99,36 @@ static int imp_encode_launch(ImpEncodeDev& P, int m0, int threads, size_t lds_by
   else if (canon && m0 == 0) kernel = impute_encode_kernel<R, 8, 8, 0, 0, 0, 0>;
   else if (canon && m0 == 1) kernel = impute_encode_kernel<R, 2, 8, 0, 0, 0, 0>;
   else if (canon) kernel = impute_encode_kernel<R, 20, 8, 0, 0, 0, 0>;
-  return infer_launch_tuple_or_each<R>("impute missing", "impute_encode_kernel", P, kernel,
+  return infer_launch_tuple_or_each<R>(who, "impute_encode_kernel", P, kernel,
                                        [](auto kk) { return impute_encode_kernel<R, decltype(kk)::value, 0, 0, 0, 0, 0>; }, threads, lds_bytes, stream);
+}
+
+// the same with the encoders -> z_m alone, one per case: the three of the canonical sizes in one launch, anything else (one case
+// among them) one launch per LSTM of the per-size instantiation
+template <int R>
+static int imp_encode_launch_z(const char* who, ImpEncodeDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
+  bool canon = P.count == IMP_CASES;
+  for (int i = 0; canon && i < IMP_CASES; ++i) canon = P.d[i].seq.hk4 == kImpEnc[2 * i];
+  return infer_launch_tuple_or_each<R>(who, "impute_encode_kernel", P, canon ? impute_encode_kernel<R, 8, 2, 20, 0, 0, 0> : nullptr,
+                                       [](auto kk) { return impute_encode_kernel<R, decltype(kk)::value, 0, 0, 0, 0, 0>; }, threads, lds_bytes, stream);
+}
+
+int impute_encode_launch(const char* who, ImpEncodeDev& P, bool pairs, int m0, int R, int threads, size_t lds_bytes, hipStream_t stream) {
+  if (pairs) return (R == 1) ? imp_encode_launch<1>(who, P, m0, threads, lds_bytes, stream) : imp_encode_launch<4>(who, P, m0, threads, lds_bytes, stream);
+  return (R == 1) ? imp_encode_launch_z<1>(who, P, threads, lds_bytes, stream) : imp_encode_launch_z<4>(who, P, threads, lds_bytes, stream);
+}
+
+void imp_gather_case(ImpGather& G, int c, int m, const ImpSizes& S, float* out) {
+  G.out[c] = out;
+  G.k[c] = S.din[m]; G.ld[c] = S.ld[m];
+  G.s0[c] = m == 0 ? S.dm[0] : 0; G.len0[c] = m == 1 ? S.dm[0] : S.din[m]; G.s1[c] = S.dm[0] + S.dm[1];
+}
+
+int impute_gather_launch(const ImpGather& G, int nc, hipStream_t stream) {
+  const int gblocks = (int)std::min<int64_t>(((int64_t)G.T * G.n * (G.D + 4) + 255) / 256, 4 * device_cus());
+  impute_gather_kernel<<<dim3(gblocks, nc), dim3(256), 0, stream>>>(G);
+  MFM_LAUNCH_CHECK("impute_gather_kernel");
+  return MFM_OK;
 }
 
 static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const float* const* prm, const float* x, float* ws,
@@ -205,9 +205,7 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
     Dd.seq.hs = w0; w0 += (int64_t)rows * T * Dd.seq.Hp;
     for (int l = 0; l < 2; ++l) { Dd.w[l] = p[12 + 2 * l]; Dd.b[l] = p[13 + 2 * l]; }
     Dd.zs = S.z[m]; Dd.fm = S.fm[m];
-    G.out[c] = w0; w0 += (int64_t)rows * T * S.ld[m];
-    G.k[c] = S.din[m]; G.ld[c] = S.ld[m];
-    G.s0[c] = m == 0 ? S.dm[0] : 0; G.len0[c] = m == 1 ? S.dm[0] : S.din[m]; G.s1[c] = S.dm[0] + S.dm[1];
+    imp_gather_case(G, c, m, S, w0); w0 += (int64_t)rows * T * S.ld[m];
   }
   for (int l = 0; l < 4; ++l) { PD.wy[l] = prm[IMP_CASES * IMP_CASE_PTRS + 2 * l]; PD.by[l] = prm[IMP_CASES * IMP_CASE_PTRS + 2 * l + 1]; }
   PE.count = 2 * S.nc; PE.T = T; PE.maxw = enc_maxw;
@@ -217,9 +215,7 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
     const int n = (int)std::min<int64_t>(rows, N - n0);
     const bool whole = n == N;           // one chunk: the T * N rows of an output are one matrix
     G.n0 = n0; G.n = n;
-    const int gblocks = (int)std::min<int64_t>(((int64_t)T * n * (S.D + 4) + 255) / 256, 4 * device_cus());
-    impute_gather_kernel<<<dim3(gblocks, S.nc), dim3(256), 0, stream>>>(G);
-    MFM_LAUNCH_CHECK("impute_gather_kernel");
+    if ((rc = impute_gather_launch(G, S.nc, stream)) != MFM_OK) return rc;
     // gates_e[t][i][g][u] = pair_e[t][i] . W_ih[g h + u] + b_ih + b_hh; pad units u >= h exact zeros.  The gathered pair of a
     // chunk is one [T * n, ld] matrix whatever the chunk
     rc = gemm_group_each(PE.count, stream, [&](int e, MfmGemmDesc& d) {
@@ -234,7 +230,7 @@ static int impute_missing(int T, int64_t N, const int32_t* sz, int cases, const 
       PD.d[c].zm = zbuf[c][0]; PD.d[c].zy = zbuf[c][1];
       PD.d[c].y_hat = out[2 * m + 1] + n0 * S.od;
     }
-    rc = (Re == 1) ? imp_encode_launch<1>(PE, S.cs[0], enc_threads, enc_lds, stream) : imp_encode_launch<4>(PE, S.cs[0], enc_threads, enc_lds, stream);
+    rc = impute_encode_launch(who, PE, true, S.cs[0], Re, enc_threads, enc_lds, stream);
     if (rc != MFM_OK) return rc;
     rc = decode_factors_launch(who, PD, Rd, dec_threads, dec_lds, stream);
     if (rc != MFM_OK) return rc;

@@ -173,6 +173,45 @@ int decode_factors_prepare(const char* who, int T, int64_t N, const int32_t* sz,
 // z: the chunk's first rows of zl, za, zv, zy; y_hat: the chunk's.  The recurrence launch alone: h_t is left in P.d[m].seq.hs [T, n, Hp]
 int decode_factors_chunk(const char* who, DecLaunch& L, const float* const* z, float* y_hat, int n, hipStream_t stream);
 
+// ---------------------------------------------------------------- the surrogate encoders of an observed pair (impute.hip; missing.hip launches them too)
+#define IMP_CASES INFER_DEC
+#define IMP_ENC (2 * IMP_CASES)
+#define IMP_CASE_PTRS 22     // per case: 6 of the encoder -> z_m, 6 of the encoder -> zy, 4 of z{m}_to_f{m}, 6 of decoder_m
+#define IMP_NPARAM (IMP_CASES * IMP_CASE_PTRS + 8)
+
+struct ImpEnc {
+  SeqDev seq;                                  // gates (the x-projections, read only), w_hh, h, Hp, hk4
+  const float* w; const float* b;              // fc1
+  float* z;                                    // this chunk's rows [n, h]
+  int block_begin;
+};
+struct ImpEncodeDev { ImpEnc d[IMP_ENC]; int count, T, n, maxw; };
+
+// out_c [T * n, ld_c] <- rows [n0, n0 + n) of x [T, N, D], columns s0 .. s0 + len0 - 1 then s1 .. up to k_c in all; [k_c, ld_c): zeros
+struct ImpGather {
+  const float* x; float* out[IMP_CASES];
+  int s0[IMP_CASES], len0[IMP_CASES], s1[IMP_CASES], k[IMP_CASES], ld[IMP_CASES];
+  int64_t N, n0;
+  int n, T, D;
+};
+
+// the sizes of a call, from the 12 the caller passes: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim
+struct ImpSizes {
+  int z[IMP_CASES], zy, fm[IMP_CASES], fy, dm[IMP_CASES], od, D;
+  int din[IMP_CASES], ld[IMP_CASES];           // the observed pair of case m: its width, and the row length of its gathered copy
+  int cs[IMP_CASES], nc;                       // the cases asked for, ascending
+};
+// false: a size below 1, or cases not one of 1, 2, 4, 7
+bool imp_sizes(const int32_t* sz, int cases, ImpSizes& S);
+// slot c of G (out / k / ld / s0 / len0 / s1) for the observed pair of case m, copied to `out`
+void imp_gather_case(ImpGather& G, int c, int m, const ImpSizes& S, float* out);
+// impute_gather_kernel over the nc slots of G (x, N, n0, n, T, D set).  The kernel stays in impute.hip alone
+int impute_gather_launch(const ImpGather& G, int nc, hipStream_t stream);
+// impute_encode_kernel on one chunk of P.n rows in tiles of R (1 or 4) rows; P.d[0 .. P.count) filled but for block_begin.  pairs:
+// P.d holds the encoders -> z_m and -> zy of every case asked for, two per case (canonical 32 / 8 / 80 and 32); else one per case, the
+// encoder -> z_m alone.  m0: the case when it is one.  The kernel's instantiations stay in impute.hip alone
+int impute_encode_launch(const char* who, ImpEncodeDev& P, bool pairs, int m0, int R, int threads, size_t lds_bytes, hipStream_t stream);
+
 // ---------------------------------------------------------------- host: sizes
 static int64_t gen_rows(int64_t N, int64_t max_rows) { return (max_rows > 0 && max_rows < N) ? max_rows : N; }
 static int64_t hp_of(int64_t h) { return (h + 15) / 16 * 16; }

@@ -12,7 +12,9 @@ autograd ops here, with independent LSTMs / Linears sharing launches (`seq_group
 There is no fused one-call plan for these classes ("pure re-wiring of existing ops").
 
 `MFM_missing.impute` is the exception: surrogate inference (a missing modality and the label from the other two) as one call
-of the library, `mfm_impute_missing` (csrc/impute.hip).
+of the library, `mfm_impute_missing` (csrc/impute.hip).  So is `predict_missing` of MFM_missing, seq2seq and basic_missing: the
+missing-modality test protocol (per missing case the label, the error of the rebuilt modality and the label loss) as one call,
+`mfm_predict_missing` (csrc/missing.hip).
 """
 import collections
 import ctypes as C
@@ -193,16 +195,185 @@ def _wb(lin):
     return [lin._parameters["weight"], lin._parameters["bias"]]
 
 
-class MFM_missing(_Base):
+Missing = collections.namedtuple("Missing", ["y_hat", "gen", "disc"])
+
+
+class _MissingProtocol:
+    """`predict_missing` of the three classes of the missing-modality family: one call of mfm_predict_missing (csrc/missing.hip).
+    A class names its family (`_MIS_FAMILY`: 0 MFM_missing, 1 seq2seq, 2 basic_missing) and gives `_missing_sizes()`,
+    `_missing_params(cases)` and `_missing_composed(x, m)`."""
+
+    MISSING_MAX_ROWS = 1024      # default row cap of predict_missing(): the x-projections of at most this many rows are alive at once
+    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
+    _CASES = ("l", "a", "v")
+    _PAIR = {"l": "av", "a": "lv", "v": "la"}       # the observed pair of each case
+    _LOSS = {"l1": 0, "ce": 1}
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_impute_bufs", None)          # (device workspaces and native pointer tables: rebuilt on the next call)
+        state.pop("_missing_bufs", None)
+        return state
+
+    def _pair_copy(self, x, missing):
+        """a COPY of the observed pair, never a column slice of x: the projection GEMM masks the 16-byte fetches that pass a row's
+        K range by multiplying with zero, and on a slice those fetches meet the missing modality's columns (csrc/impute.hip)"""
+        d_l, d_a = self.d_l, self.d_a
+        if missing == "l":
+            return x[:, :, d_l:].contiguous()
+        if missing == "v":
+            return x[:, :, :d_l + d_a].contiguous()
+        return torch.cat([x[:, :, :d_l], x[:, :, d_l + d_a:]], dim=2)
+
+    def _missing_columns(self, x, missing):
+        lo = {"l": 0, "a": self.d_l, "v": self.d_l + self.d_a}[missing]
+        return x[:, :, lo:lo + {"l": self.d_l, "a": self.d_a, "v": self.d_v}[missing]]
+
+    def _missing_hidden(self, sz):
+        """the widest hidden size the family's recurrences run, from the 12 sizes"""
+        fam = self._MIS_FAMILY
+        if fam == 0:
+            return max(max(sz[0:4]), sz[7] + max(sz[4:7]))
+        return max(max(sz[0:3]), max(sz[4:7])) if fam == 1 else sz[3]
+
+    def _missing_fused(self, x, y, cases, params, loss_kind, cap):
+        """mfm_predict_missing on the module's own tensors; MfmUnsupported when the entry refuses the sizes"""
+        T, N, _ = x.shape
+        L = _lib.lib()
+        fam = self._MIS_FAMILY
+        name = type(self).__name__
+        bits = sum(1 << self._CASES.index(m) for m in cases)
+        cache = self.__dict__.setdefault("_missing_bufs", {})
+        key = (T, N, bits, y is not None, cap, x.device)
+        st = cache.get(key)
+        if st is False:
+            raise _lib.MfmUnsupported("%s.predict_missing: mfm_predict_missing refused this shape" % name)
+        if st is None:
+            sz = self._missing_sizes()
+            sizes = (C.c_int32 * 12)(*sz)
+            nws = int(L.mfm_predict_missing_workspace_floats(T, N, sizes, fam, bits, int(y is not None), cap))
+            f32 = dict(dtype=torch.float32, device=x.device)
+            each = len(cases) == 3
+            i0 = self._CASES.index(cases[0])
+            y_hat = gen = disc = None
+            if fam != 1:
+                y_hat = torch.empty((3, N, sz[11]) if each else (N, sz[11]), **f32)
+                disc = torch.empty(3, **f32) if y is not None else None
+            if fam != 2:
+                gen = torch.empty(3, **f32)
+            ptrs = [None if t is None else t.data_ptr() for t in (y_hat, gen, disc)]
+            out = Missing(y_hat, gen if gen is None or each else gen[i0], disc if disc is None or each else disc[i0])
+            st = (torch.empty(max(nws, 4), **f32), (y_hat, gen, disc), out, sizes, ptrs, (C.c_void_p * 74)())
+        ws, _, out, sizes, ptrs, pptr = st
+        for i, p in enumerate(params):
+            pptr[i] = None if p is None else p.data_ptr()
+        rc = L.mfm_predict_missing(T, N, sizes, fam, bits, loss_kind, pptr, C.c_void_p(x.data_ptr()),
+                                   None if y is None else C.c_void_p(y.data_ptr()), C.c_void_p(ws.data_ptr()), ptrs[0], ptrs[1], ptrs[2],
+                                   cap, C.c_void_p(torch._C._cuda_getCurrentRawStream(x.device.index)))
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            # a hidden size beyond the on-chip recurrence is a property of the model: remembered.  The LDS limit also depends on the
+            # tile rows, hence on N and max_rows: that refusal is remembered for this shape alone (no buffers are kept for it)
+            self._missing_refused = self._missing_hidden(self._missing_sizes()) > self.MAX_RESIDENT_H
+            if not self._missing_refused:
+                cache[key] = False
+            raise _lib.MfmUnsupported("%s.predict_missing: %s" % (name, L.mfm_last_error().decode()))
+        _lib.check(rc, "mfm_predict_missing")
+        cache[key] = st
+        return out
+
+    def _missing_call(self, x, y, missing, loss, max_rows):
+        name = type(self).__name__ + ".predict_missing"
+        fam = self._MIS_FAMILY
+        if missing not in ("l", "a", "v", "each"):
+            raise ValueError("%s: missing must be 'l', 'a', 'v' or 'each', not %r" % (name, missing))
+        if loss not in self._LOSS:
+            raise ValueError("%s: loss must be 'l1' or 'ce', not %r" % (name, loss))
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.MfmError("%s: parameters are on %s; move the model to the GPU first (no CPU fallback)" % (name, dev))
+        D = self.d_l + self.d_a + self.d_v
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise _lib.MfmError("%s: x must be a CUDA tensor [T, N, %d]; got %s" % (name, D, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        M._require_cuda(x, name)
+        if x.device != dev:
+            raise _lib.MfmError("%s: x lives on %s, the model on %s" % (name, x.device, dev))
+        if x.shape[2] != D:
+            raise _lib.MfmError("%s: x has %d features per time step, the model's input_dims sum to %d" % (name, x.shape[2], D))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise _lib.MfmError("%s: empty split %s" % (name, tuple(x.shape)))
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("%s: max_rows must be at least 1, not %r" % (name, max_rows))
+        N = x.shape[1]
+        if y is not None:
+            od = self._missing_sizes()[11]
+            if not torch.is_tensor(y) or y.device != dev:
+                raise _lib.MfmError("%s: labels must be a tensor on %s; got %s" % (name, dev, y.device if torch.is_tensor(y) else type(y)))
+            if loss == "l1":
+                if not y.is_floating_point() or tuple(y.shape) != (N, od):
+                    raise _lib.MfmError("%s: loss 'l1' takes float labels [%d, %d]; got %s %s" % (name, N, od, y.dtype, tuple(y.shape)))
+                if not (y.dtype == torch.float32 and y.is_contiguous()):
+                    y = y.contiguous().float()
+            else:
+                if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+                    raise _lib.MfmError("%s: loss 'ce' takes int64 class indices [%d]; got %s %s" % (name, N, y.dtype, tuple(y.shape)))
+                y = y.contiguous()
+        cap = self.MISSING_MAX_ROWS if max_rows is None else int(max_rows)
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        cases = self._CASES if missing == "each" else (missing,)
+        with torch.no_grad():
+            if not getattr(self, "_missing_refused", False):
+                params = self._missing_params(cases)
+                if all(p is None or (p.dtype == torch.float32 and p.device == dev and p.is_contiguous()) for p in params):
+                    try:
+                        return self._missing_fused(x, y, cases, params, self._LOSS[loss], cap)
+                    except _lib.MfmUnsupported:
+                        pass
+            # the composition of the module's own granular operations on a copy of the observed pair, then torch reductions
+            F = torch.nn.functional
+            y_hats, gens, discs = [], [], []
+            for m in cases:
+                x_hat, y_hat = self._missing_composed(x, m)
+                if fam != 2:
+                    gens.append(F.mse_loss(x_hat, self._missing_columns(x, m)))
+                if fam != 1:
+                    y_hats.append(y_hat)
+                    if y is not None:
+                        discs.append(F.l1_loss(y_hat, y) if loss == "l1" else F.cross_entropy(y_hat, y))
+            pick = (lambda v: torch.stack(v) if v else None) if missing == "each" else (lambda v: v[0] if v else None)
+            return Missing(pick(y_hats), pick(gens), pick(discs))
+
+
+_MISSING_DOC = """x [T, N, D] (columns d_l | d_a | d_v), missing in "l" / "a" / "v" / "each" -> Missing(y_hat, gen, disc): the
+        missing-modality test protocol of this class in one call of mfm_predict_missing (csrc/missing.hip) -- per missing case
+        the label predicted from the other two modalities, the error of the rebuilt modality and the label loss; what the class
+        does not have is None.  missing="each": the three cases in the order l, a, v in shared launches, y_hat [3, N, output_dim],
+        gen and disc [3] device floats; one case: y_hat [N, output_dim], gen and disc 0-dim device tensors.
+
+        Always the deterministic eval computation (dropout the identity), `self.training` left as found, without autograd.  THE
+        COLUMNS OF THE MISSING MODALITY ARE NEVER READ by an encoder: they reach the squared error of `gen` alone, as its target.
+        y_hat and disc of a case do not depend on them (NaN there is legal and leaves their bits alone); gen does, by definition.
+        loss="l1" takes float labels [N, output_dim], loss="ce" int64 class indices [N]; disc is their mean label loss, None without
+        y.  The split is walked in chunks of at most `max_rows` rows (default MISSING_MAX_ROWS).  Workspace and outputs are kept on
+        the module (outside state_dict(), dropped when pickled) per (T, N, case set, labels or not, max_rows) and REUSED: after the
+        first call for a shape nothing is allocated and nothing synchronises (legal inside a stream capture), and the returned
+        tensors are overwritten by the next call for the same shape -- clone what must survive it.  "each" gives the bits of the
+        three single calls as long as both run on the same tile rows (include/mfm_hip.h, mfm_predict_missing_tile_rows).  A device x
+        that is not contiguous float32 is converted.  Sizes the entry refuses (a hidden size above 128, LDS beyond a CU's) take the
+        composition of the module's own granular operations on a COPY of the observed pair, followed by torch reductions; the
+        refusal is remembered.  So does a model with a parameter that is not a contiguous float32 tensor on x's device.  Argument
+        errors (shape, device, labels, max_rows < 1: MfmError; unknown `missing` / `loss`: ValueError) are raised before anything is
+        launched.  A CPU model or input raises MfmError: there is no CPU fallback."""
+
+
+class MFM_missing(_MissingProtocol, _Base):
     """reference mfm_model.py:766-898: MFM plus six surrogate encoders that predict a modality's (and z_y's) code
     from the other two modalities; forward returns the four decodings (all present / no l / no a / no v).
     `impute(x, missing)`: the no-<missing> decoding's reconstruction of that modality and its label from the other two
     modalities alone, as one call of the library."""
 
     IMPUTE_MAX_ROWS = 1024       # default row cap of impute(): the x-projections of at most this many rows are alive at once
-    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
-    _CASES = ("l", "a", "v")
-    _PAIR = {"l": "av", "a": "lv", "v": "la"}       # the observed pair of each case
+    _MIS_FAMILY = 0
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(MFM_missing, self).__init__(config)
@@ -262,12 +433,7 @@ class MFM_missing(_Base):
         decoded_nov = decode(zl, za, zv_nov, zy_nov)
         return decoded, decoded_nol, decoded_noa, decoded_nov, mmd_loss, missing_loss
 
-    # ------------------------------------------------------------------ surrogate inference
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop("_impute_bufs", None)          # (device workspaces and native pointer tables: rebuilt on the next call)
-        return state
-
+    # ------------------------------------------------------------------ surrogate inference (__getstate__: _MissingProtocol)
     def _impute_params(self, cases):
         """the 74 tensors of mfm_impute_missing's parameter table (include/mfm_hip.h); None for the cases not asked for"""
         mods = self._modules
@@ -401,9 +567,23 @@ class MFM_missing(_Base):
                 return {m: self._impute_composed(x, m) for m in cases}
             return self._impute_composed(x, missing)
 
+    # ------------------------------------------------------------------ the missing-modality test protocol
+    _missing_params = _impute_params       # (the 74 pointers of mfm_impute_missing unchanged)
+    _missing_sizes = _impute_sizes
+    _missing_composed = _impute_composed
 
-class seq2seq(_Base):
+    def predict_missing(self, x, y=None, *, missing="each", loss="l1", max_rows=None):
+        return self._missing_call(x, y, missing, loss, max_rows)
+    predict_missing.__doc__ = """y_hat = decoded_no<m>[3] of forward(), gen = F.mse_loss(decoded_no<m>[index of m], x_m), disc the label loss of
+        y_hat -- the pipeline of impute() with the decoder's fc1 fused into the squared error: no x_hat is written.
+
+        """ + _MISSING_DOC
+
+
+class seq2seq(_MissingProtocol, _Base):
     """reference mfm_model.py:900-960: reconstruct each modality from the other two (no multimodal factor)."""
+
+    _MIS_FAMILY = 1
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(seq2seq, self).__init__(config)
@@ -431,9 +611,46 @@ class seq2seq(_Base):
         x_l_hat, x_a_hat, x_v_hat = M.decoder_group([(fl, self.decoder_l), (fa, self.decoder_a), (fv, self.decoder_v)], t)
         return [x_l_hat], [x_a_hat], [x_v_hat], mmd_loss
 
+    # ------------------------------------------------------------------ the missing-modality test protocol
+    def _missing_params(self, cases):
+        """the table of mfm_predict_missing for family 1 (include/mfm_hip.h); None where the family or the case set has nothing"""
+        mods = self._modules
+        out = []
+        for m in self._CASES:
+            if m not in cases:
+                out += [None] * 22
+                continue
+            out += _lstm_fc(mods["encoder_%s_to_%s" % (self._PAIR[m], m)]) + [None] * 6
+            out += _wb(mods["z%s_to_f%s_fc1" % (m, m)]) + _wb(mods["z%s_to_f%s_fc2" % (m, m)]) + _lstm_fc(mods["decoder_" + m])
+        return out + [None] * 8
 
-class basic_missing(_Base):
+    def _missing_sizes(self):
+        """zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim; 1 for what the class does not have"""
+        shp = [tuple(self._modules[n]._parameters["weight"].shape) for n in ("zl_to_fl_fc1", "za_to_fa_fc1", "zv_to_fv_fc1")]
+        return tuple(s[1] for s in shp) + (1,) + tuple(s[0] for s in shp) + (1, self.d_l, self.d_a, self.d_v, 1)
+
+    def _missing_composed(self, x, missing):
+        """(x_hat, None) of ONE case as the composition of this module's own sub-modules; the dropout modules are left out (eval)"""
+        relu = torch.relu
+        zm, = _encode([(self._pair_copy(x, missing), getattr(self, "encoder_%s_to_%s" % (self._PAIR[missing], missing)))])
+        tag = "z%s_to_f%s" % (missing, missing)
+        h1, = M.linear_group([(zm, getattr(self, tag + "_fc1"))])
+        fm, = M.linear_group([(relu(h1), getattr(self, tag + "_fc2"))])
+        x_hat, = M.decoder_group([(relu(fm), getattr(self, "decoder_" + missing))], x.shape[0])
+        return x_hat, None
+
+    def predict_missing(self, x, *, missing="each", max_rows=None):
+        return self._missing_call(x, None, missing, "l1", max_rows)
+    predict_missing.__doc__ = """gen = F.mse_loss(x_m_hat, x_m), x_m_hat = decoder_m(relu(fc2(relu(fc1(encoder_<pair>_to_<m>(pair))))), T); the class has
+        no label path: y_hat and disc are None.
+
+        """ + _MISSING_DOC
+
+
+class basic_missing(_MissingProtocol, _Base):
     """reference mfm_model.py:962-1017: predict the label from two modalities, one small head per missing modality."""
+
+    _MIS_FAMILY = 2
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(basic_missing, self).__init__(config)
@@ -459,3 +676,36 @@ class basic_missing(_Base):
         h = [getattr(self, t_ + "_dropout")(torch.relu(v)) for t_, v in zip(tags, h)]
         y_hat_nol, y_hat_noa, y_hat_nov = M.linear_group([(v, getattr(self, t_ + "_fc2")) for t_, v in zip(tags, h)])
         return y_hat_nol, y_hat_noa, y_hat_nov, mmd_loss
+
+    # ------------------------------------------------------------------ the missing-modality test protocol
+    def _missing_params(self, cases):
+        """the table of mfm_predict_missing for family 2 (include/mfm_hip.h); None where the family or the case set has nothing"""
+        mods = self._modules
+        out = []
+        for m in self._CASES:
+            if m not in cases:
+                out += [None] * 22
+                continue
+            tag = "zy_no%s_to_y" % m
+            out += [None] * 6 + _lstm_fc(mods["encoder_%s_to_y" % self._PAIR[m]]) + _wb(mods[tag + "_fc1"]) + _wb(mods[tag + "_fc2"]) + [None] * 6
+        return out + [None] * 8
+
+    def _missing_sizes(self):
+        """zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim; 1 for what the class does not have"""
+        fy, zy = self._modules["zy_nol_to_y_fc1"]._parameters["weight"].shape
+        return (1, 1, 1, zy, 1, 1, 1, fy, self.d_l, self.d_a, self.d_v, self._modules["zy_nol_to_y_fc2"]._parameters["weight"].shape[0])
+
+    def _missing_composed(self, x, missing):
+        """(None, y_hat) of ONE case as the composition of this module's own sub-modules; the dropout modules are left out (eval)"""
+        zy, = _encode([(self._pair_copy(x, missing), getattr(self, "encoder_%s_to_y" % self._PAIR[missing]))])
+        tag = "zy_no%s_to_y" % missing
+        h1, = M.linear_group([(zy, getattr(self, tag + "_fc1"))])
+        y_hat, = M.linear_group([(torch.relu(h1), getattr(self, tag + "_fc2"))])
+        return None, y_hat
+
+    def predict_missing(self, x, y=None, *, missing="each", loss="l1", max_rows=None):
+        return self._missing_call(x, y, missing, loss, max_rows)
+    predict_missing.__doc__ = """y_hat = zy_no<m>_to_y_fc2(relu(zy_no<m>_to_y_fc1(encoder_<pair>_to_y(pair)))) and disc, its label loss; the class has no decoder:
+        gen is None.
+
+        """ + _MISSING_DOC

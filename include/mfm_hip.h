@@ -895,6 +895,54 @@ int mfm_impute_missing(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, 
                        const float* x, float* workspace, float* const* out /*host, 6*/, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The missing-modality test protocol (csrc/missing.hip; the `predict` / `score` blocks of the reference's train_mfm_missing,
+ * seq2seq and basic_missing loops, reference mfm_model.py:766-1017): per missing case m the error of the rebuilt modality, the
+ * label prediction and its label loss, for the three classes of the missing-modality family, in the pattern of
+ * mfm_impute_missing and mfm_predict_zeros_klef -- fp32, dropout the identity, no MfmPlan, no x_hat written.
+ *   family 0, MFM_missing    y_hat_m = decoded_no<m>[3] and x_hat_m = decoded_no<m>[index of m] as mfm_impute_missing computes them;
+ *                            gen_m = mean((x_hat_m - x_m)^2), disc_m = the mean label loss of y_hat_m
+ *   family 1, seq2seq        x_hat_m = decoder_m(relu(z<m>_to_f<m>_fc2(relu(z<m>_to_f<m>_fc1(encoder_<pair>_to_<m>(pair))))), T),
+ *                            gen_m = mean((x_hat_m - x_m)^2); no label path: y, y_hat and disc are not looked at
+ *   family 2, basic_missing  y_hat_m = zy_no<m>_to_y_fc2(relu(zy_no<m>_to_y_fc1(encoder_<pair>_to_y(pair)))), disc_m; no decoder:
+ *                            gen is not looked at
+ * pair = cat of the two observed modalities' columns of x.  THE COLUMNS OF m REACH THE SQUARED ERROR ALONE, as its target: no
+ * encoder, y_hat_m or disc_m depends on them, and family 2 never reads them.  Per row chunk: the gather of the observed pairs
+ * and the grouped x-projection GEMM of mfm_impute_missing; the encoder recurrences (families 0, 1: those of mfm_impute_missing;
+ * family 2: ONE launch of (case, row tile) workgroups that go on to the encoder's fc1 and the case's head and write y_hat); the
+ * decoder recurrences storing h_t (family 0: the launch of mfm_impute_missing; family 1: ONE launch of (case, row tile)
+ * workgroups without the fy half); the decoders' fc1 fused with the squared error, one partial per workgroup; one workgroup that
+ * adds the partials and the label loss in fp64 in a fixed order -- no float atomics.
+ *   sizes, cases  as mfm_impute_missing; a size the family does not have (family 1: zy, fy, output_dim; family 2: z_m, f_m) may be
+ *            any positive value
+ *   loss_kind 0: L1 against float labels y [N, output_dim]; 1: cross entropy against int64 class indices y [N] (8-byte aligned)
+ *   params   host array of 74 DEVICE pointers laid out as mfm_impute_missing's.  Family 0: all of them.  Family 1, per case at
+ *            22 * m: 0-5 the encoder -> z_m, 12-15 z<m>_to_f<m> fc1 weight, bias, fc2 weight, bias, 16-21 decoder_m (h = f_m).
+ *            Family 2, per case at 22 * m: 6-11 the encoder -> zy (av_to_y / lv_to_y / la_to_y), 12-15 zy_no<m>_to_y fc1 weight,
+ *            bias, fc2 weight, bias.  Slots a family does not have, and the 22 of a case not asked for, are not read and may be null
+ *   y        labels of the whole split, or null: no label loss (then disc must be null too)
+ *   y_hat    cases = 7: [3, N, output_dim] in the order l, a, v; one case: [N, output_dim]
+ *   gen, disc  3 floats each whatever the cases, case m's at index m, written behind the last chunk; with one case the other two
+ *            entries are overwritten with values that mean nothing
+ *   workspace mfm_predict_missing_workspace_floats(T, N, sizes, family, cases, with_labels, max_rows) floats, 16-byte aligned,
+ *            contents arbitrary: per case what mfm_impute_missing keeps of it for the family's launches, then one float per
+ *            squared-error workgroup of a chunk, six fp64 accumulators and 4 floats (for family 0 never less than
+ *            mfm_impute_missing_workspace_floats)
+ * mfm_predict_missing_tile_rows: host only; rows per workgroup of the encoders' launch (tile_rows[0]) and of the decoders'
+ * ([1]; 0 for family 2, which has none): 1 below six workgroups per CU over the launch, else 4.  The encoders' launch counts two
+ * LSTMs per case for family 0, one for families 1 and 2.  Results are bit-identical from call to call; y_hat also across row
+ * caps that keep the tile rows (gen and disc then differ in the grouping of the fp64 sums alone).
+ * Nothing outside the workspace and the three outputs is written.  Any N >= 1 (< 2^24), T >= 1.  Sizes the on-chip recurrence does
+ * not cover (a hidden size > 128, or more LDS than a CU has) return MFM_ERR_UNSUPPORTED with the size in the error text and
+ * enqueue nothing: compose the granular entries instead.  Bad arguments return MFM_ERR_ARG and enqueue nothing.  Stream-ordered,
+ * no host synchronisation, legal inside a stream capture. */
+int64_t mfm_predict_missing_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t family, int32_t cases,
+                                             int32_t with_labels, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_missing_tile_rows(int64_t N, int32_t family, int32_t cases, int64_t max_rows, int32_t* tile_rows /*host, 2*/);
+int mfm_predict_missing(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t family, int32_t cases, int32_t loss_kind,
+                        const float* const* params /*host, 74*/, const float* x, const void* y /*null: no label loss*/,
+                        float* workspace, float* y_hat, float* gen, float* disc, int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
