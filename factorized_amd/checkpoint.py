@@ -54,6 +54,14 @@ host, and the snapshot is a per-tensor clone of `state_dict()` refreshed with `t
 are the same and the path is always correct.  The two paths may alternate on one instance: state and snapshot move with it
 (that hand-over reads the state back, i.e. synchronises, once).
 
+Inside a stream capture such a module takes a third form, so that `evaluate -> scheduler.step -> best.update` of the composed
+classes that return a device loss (`M_B`, `M_D`) is one graph.  A torch-path `update` with a device metric on a module whose
+tensors live on one GPU leaves the state block and per-tensor snapshot buffers beside the model (one small upload; make that
+call outside the capture first, else `_lib.MfmError`).  The captured `update` applies the same fp32 rule with torch operations
+on them -- the comparison, one conditional copy per tensor, the bookkeeping -- and returns the 0-d int32 `taken` word;
+`last_path` is "tensors".  Replays move the block; `value`, `calls`, `epoch`, `taken`, `restore()` and `state_dict()` read it
+back, and an `update` outside the capture goes on from it on the torch path and uploads the result again.
+
 `state_dict()` / `load_state_dict()` carry the mode, `value`, `calls`, `epoch` and the snapshot under the model's own parameter
 names, so a KeepBest survives a checkpoint of the run on either path.
 
@@ -102,6 +110,11 @@ class KeepBest:
         self._mfm_taken = None           # its taken word (a 0-d view: what update returns)
         self._mfm_flat = None            # snapshot buffer with the engine's layout
         self._mfm_key = None             # (engine, layout) the buffers were last validated against
+        # tensor form (any other module on one GPU, see the module doc): the state block again, the snapshot per tensor
+        self._td_state = None            # int32[MFM_KEEP_STATE_WORDS] beside the model, in step with the host form after every
+        self._td_snap = None             # torch-path update; name -> tensor, the buffers `_snap` names once a snapshot was taken
+        self._td_fresh = False           # the block holds the host form's values
+        self._td_live = False            # a captured update was recorded: replays move the block, host reads read it back
 
     # ------------------------------------------------------------------ copies
     def __getstate__(self):
@@ -109,6 +122,10 @@ class KeepBest:
         state["_mfm_ticket"] = None          # (never shared with a copy: each instance draws its own tickets)
         state["_mfm_taken"] = None
         state["_mfm_key"] = None             # (an engine does not travel; re-validated on the next call)
+        if self._td_live:                    # (a copy has no graph that moves its block: it goes on from the values read back)
+            host = dict(zip(("_value", "_calls", "_best_call", "_taken"), _flat.unpack_words(self._td_state.cpu(), _STATE)))
+            state.update(host, _snap=self._td_snap if host["_best_call"] >= 0 else None)
+        state.update(_td_state=None, _td_snap=None, _td_fresh=False, _td_live=False)
         return state
 
     def __setstate__(self, state):
@@ -164,6 +181,62 @@ class KeepBest:
         """the device state into the host fields (synchronises); the device form stays authoritative"""
         self._value, self._calls, self._best_call, self._taken = _flat.unpack_words(self._mfm_state.cpu(), _STATE)
 
+    # ------------------------------------------------------------------ the tensor form: a captured update of any GPU module
+    def _td_read_back(self):
+        """what the replays of a captured update left in the block into the host form (synchronises); the replays may go on"""
+        if not self._td_live:
+            return
+        self._value, self._calls, self._best_call, self._taken = _flat.unpack_words(self._td_state.cpu(), _STATE)
+        self._snap = self._td_snap if self._best_call >= 0 else None
+
+    def _td_device(self):
+        """the one GPU every tensor of the model's state_dict lives on, else None"""
+        devs = {t.device for t in self.model.state_dict().values()}
+        dev = next(iter(devs)) if len(devs) == 1 else None
+        return dev if dev is not None and dev.type == "cuda" else None
+
+    def _td_upload(self, dev):
+        """the host form into the block beside the model (outside a capture, behind a torch-path update)"""
+        sd = self.model.state_dict()
+        snap = self._snap if self._snap is not None else self._td_snap
+        if (snap is None or list(snap) != list(sd)
+                or any(a.shape != b.shape or a.device != b.device or a.dtype != b.dtype for a, b in zip(snap.values(), sd.values()))):
+            snap = OrderedDict((k, t.detach().clone()) for k, t in sd.items())      # (buffers alone: no snapshot was taken yet)
+        self._td_snap = snap
+        values = (self._value, self._calls, self._best_call, self._taken)
+        host = _flat.pack_words(_lib.MFM_KEEP_STATE_WORDS, [(w, kind, v) for (w, kind), v in zip(_STATE, values)])
+        if self._td_state is None or self._td_state.device != dev:
+            self._td_state = host.to(dev)
+        else:
+            self._td_state.copy_(host)
+        self._td_fresh = True
+
+    def _update_tensors(self, metric):
+        """update() inside a stream capture for a module off the flat path: the rule, the conditional copies and the bookkeeping
+        as torch operations on the block and the snapshot buffers a torch-path update left beside the model"""
+        sd = self.model.state_dict()
+        snap = self._td_snap
+        if (not self._td_fresh or self._td_state is None or snap is None or list(snap) != list(sd)
+                or any(a.shape != b.shape or a.device != b.device or a.dtype != b.dtype for a, b in zip(snap.values(), sd.values()))):
+            raise _lib.MfmError("KeepBest.update: inside a stream capture a model off the flat path needs the state block and the "
+                                "snapshot buffers that an update with a device metric sets up; make that call outside the "
+                                "stream capture first")
+        st = self._td_state
+        with torch.no_grad():
+            v = metric.detach().to(device=st.device, dtype=torch.float32).reshape(())
+            best = st[_W_VALUE:_W_VALUE + 1].view(torch.float32)[0]             # (0-d views of the block's words)
+            calls, best_call, taken = st[_W_CALLS], st[_W_BEST_CALL], st[_W_TAKEN]
+            take = v <= best if self.mode == "min" else v >= best          # (False for a NaN)
+            for dst, src in zip(snap.values(), sd.values()):
+                dst.copy_(torch.where(take, src.detach(), dst))
+            best.copy_(torch.where(take, v, best))
+            best_call.copy_(torch.where(take, calls, best_call))
+            taken.copy_(take.to(torch.int32))
+            calls.add_(1)
+        self._td_live = True
+        self.last_path = "tensors"
+        return st[_W_TAKEN]
+
     def _to_host(self):
         """state and snapshot into the torch-path form (synchronises; the first torch-path call after flat ones)"""
         if not self._on_device:
@@ -189,7 +262,11 @@ class KeepBest:
         call took a snapshot (flat path: a view of device state, no synchronisation until it is read)."""
         eng = self._flat_engine()
         if eng is None:
+            if _flat.capturing() and isinstance(metric, torch.Tensor) and metric.is_cuda and metric.numel() == 1:
+                return self._update_tensors(metric)
             return self._update_torch(metric)
+        self._td_read_back()
+        self._td_fresh = self._td_live = False
         dev = eng.params.device
         keep, host = _flat.metric_arg(metric, dev, "KeepBest.update", "the model's device")      # (keep: alive over the launch)
         ptr, scalar = (keep.data_ptr(), 0.0) if keep is not None else (None, _fp32(host))
@@ -202,23 +279,31 @@ class KeepBest:
 
     def _update_torch(self, metric):
         self._to_host()
+        self._td_read_back()
         v = _fp32(metric)
         best = self._value
         take = v <= best if self.mode == "min" else v >= best          # (False for a NaN)
         if take:
             sd = self.model.state_dict()
             src = [t.detach() for t in sd.values()]
-            snap = self._snap
+            snap = self._snap if self._snap is not None else self._td_snap      # (the buffers a captured update writes, if any)
             if (snap is not None and list(snap) == list(sd)
                     and all(a.shape == b.shape and a.device == b.device and a.dtype == b.dtype for a, b in zip(snap.values(), src))):
                 with torch.no_grad():
                     torch._foreach_copy_(list(snap.values()), src)
+                self._snap = snap
             else:
                 self._snap = OrderedDict((k, t.clone()) for k, t in zip(sd, src))
             self._value, self._best_call = v, self._calls
         self._taken = 1 if take else 0
         self._calls += 1
         self.last_path = "torch"
+        # a device metric on a GPU module (or a block that a captured update already moves): keep the tensor form in step
+        self._td_fresh = False
+        if self._td_live or (isinstance(metric, torch.Tensor) and metric.is_cuda):
+            dev = self._td_device()
+            if dev is not None:
+                self._td_upload(dev)
         return torch.tensor(self._taken, dtype=torch.int32)
 
     # ------------------------------------------------------------------ restore
@@ -246,6 +331,7 @@ class KeepBest:
     def _host(self):
         if self._on_device:
             self._read_back()
+        self._td_read_back()
         return self
 
     @property
@@ -299,3 +385,4 @@ class KeepBest:
         self._taken = int(sd.get("taken", 0))
         self._snap = snap
         self._on_device = False          # (the next flat call uploads state and snapshot)
+        self._td_fresh = self._td_live = False

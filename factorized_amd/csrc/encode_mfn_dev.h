@@ -11,7 +11,8 @@
 // Host, shared by all four: the two size parsers (emfn_sizes, the 17 of mfm_encode_mfn; mfn_sizes, the MFN_SIZES of the other
 // three), the refusals (mfn_check_covered), the sizing of the two launches (emfn_chain_check / emfn_chain_fill) and the launches
 // themselves (emfn_att_launch, emfn_mem_launch, emfn_chain_launch), the workspace parts behind the x-projections (mfn_ws), the
-// MFN's three LSTMs of a call (MfnLstm, mfn_lstms_fill) and a chunk's grouped projection GEMM (mfn_xproj_chunk).
+// MFN's three LSTMs of a call (mfn_lstms_fill); a chunk's grouped projection GEMM (MfnLstm, mfn_xproj_chunk) is in infer_dev.h,
+// where ablation.hip drives it too.
 // At the end of the file: the launch in front of the chain as mfm_encode_mfn runs it -- the six recurrences (encoder l, a, v with
 // their heads, the MFN's LSTMs with their cell-state records) in one launch, encode_mfn_seq_kernel, its workspace parts and its
 // launcher; encode_mfn_front.h walks them chunk by chunk for mfm_encode_mfn and mfm_objective_mfn.  Nothing above that section
@@ -553,11 +554,7 @@ static MfnWs mfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, int cases) {
 // the first column of modality m in a row of x
 static int mfn_col(const EmfnSizes& S, int m) { return m == 0 ? 0 : (m == 1 ? S.d[0] : S.d[0] + S.d[1]); }
 
-// one LSTM of a call as the host walks it: where the caller's kernel argument keeps its SeqDev and (an MFN LSTM) its last hidden
-// states -- the entries' *One structs differ --, and the d columns of x from col on that it projects
-struct MfnLstm { SeqDev* seq; float** h_last; int col, d; };
-
-// the MFN's lstm l, a, v of a call, L[0 .. 3) with seq / h_last set by the caller: the cells from their twelve offsets, their
+// the MFN's lstm l, a, v (MfnLstm: infer_dev.h) of a call, L[0 .. 3) with seq / h_last set by the caller: the cells from their twelve offsets, their
 // projections from `gates` on, their c records (A.cs) and last hidden states (Mm.hl) and the chain's buffers from `rest` on in
 // the order of mfn_ws; returns the end of those parts
 static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64_t T, int64_t rows, int cases, const float* params,
@@ -575,18 +572,6 @@ static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64
   C.A.g1p = rest; rest += W.g1p;
   C.A.g2p = rest; rest += W.g2p;
   return rest;
-}
-
-// the x-projections of a chunk, rows [n0, n0 + n) of the split x [T, N, D], as ONE grouped GEMM: gates_e[t][i][g][u] =
-// x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh, pad units u >= h exact zeros.  One chunk: the T * N rows of x are one matrix and
-// an LSTM one problem; else one problem per LSTM and step
-static int mfn_xproj_chunk(int count, const MfnLstm* L, const float* x, int T, int64_t N, int D, int64_t n0, int n, hipStream_t stream) {
-  const bool whole = n == N;
-  return gemm_group_each(count * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
-    const int e = p % count, t = p / count;
-    const SeqDev& s = *L[e].seq;
-    xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + L[e].col, D, L[e].d, whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
-  });
 }
 
 // ---------------------------------------------------------------- the six recurrences (mfm_encode_mfn; mfm_objective_mfn launches them too)

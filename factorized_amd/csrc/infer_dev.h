@@ -338,6 +338,22 @@ static void xproj_desc(MfmGemmDesc& d, const SeqDev& s, const float* a, int64_t 
   d.alpha = 1.0f;
 }
 
+// one LSTM of a call as the host walks it: where the caller's kernel argument keeps its SeqDev and (an MFN LSTM) its last hidden
+// states -- the entries' *One structs differ --, and the d columns of x from col on that it projects
+struct MfnLstm { SeqDev* seq; float** h_last; int col, d; };
+
+// the x-projections of a chunk, rows [n0, n0 + n) of the split x [T, N, D], as ONE grouped GEMM: gates_e[t][i][g][u] =
+// x_e[t][n0 + i] . W_ih[g h + u] + b_ih + b_hh, pad units u >= h exact zeros.  One chunk: the T * N rows of x are one matrix and
+// an LSTM one problem; else one problem per LSTM and step
+static int mfn_xproj_chunk(int count, const MfnLstm* L, const float* x, int T, int64_t N, int D, int64_t n0, int n, hipStream_t stream) {
+  const bool whole = n == N;
+  return gemm_group_each(count * (whole ? 1 : T), stream, [&](int p, MfmGemmDesc& d) {
+    const int e = p % count, t = p / count;
+    const SeqDev& s = *L[e].seq;
+    xproj_desc(d, s, x + ((int64_t)t * N + n0) * D + L[e].col, D, L[e].d, whole ? T * n : n, s.gates + (int64_t)t * n * 4 * s.Hp);
+  });
+}
+
 // fc1 of decoder s over its stored h: c [m, dm] = hs [m, Hp] . w^T + b, `batch` times a_sz / c_sz apart
 static void dec_fc1_desc(MfmGemmDesc& d, const SeqDev& s, const float* hs, const float* w, const float* b, float* c, int dm, int m,
                          int batch = 1, int64_t a_sz = 0, int64_t c_sz = 0) {

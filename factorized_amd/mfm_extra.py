@@ -14,7 +14,7 @@ There is no fused one-call plan for these classes ("pure
 `MFM_missing.impute` is the exception: surrogate inference (a missing modality and the label from the other two) as one call
 of the library, `mfm_impute_missing` (csrc/impute.hip).  So is `predict_missing` of MFM_missing, seq2seq and basic_missing: the
 missing-modality test protocol (per missing case the label, the error of the rebuilt modality and the label loss) as one call,
-`mfm_predict_missing` (csrc/missing.hip).
+`mfm_predict_missing` (csrc/missing.hip); and `predict` / `evaluate` of M_B and M_D, `mfm_predict_ablation` (csrc/ablation.hip).
 """
 import collections
 import ctypes as C
@@ -73,6 +73,182 @@ def _encode(pairs):
     return out
 
 
+Ablation = collections.namedtuple("Ablation", ["y_hat", "gen", "disc"])
+
+
+class _AblationProtocol:
+    """`predict` / `evaluate` of the ablations whose three own-modality encoders meet at the label head: one call of
+    mfm_predict_ablation (csrc/ablation.hip).  A class names its family (`_ABL_FAMILY`: 0 M_B, 1 M_D) and gives `_ablation_head()`,
+    the tensors of its label head."""
+
+    ABLATION_MAX_ROWS = 1024     # default row cap: the x-projections of at most this many rows are alive at once
+    MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
+    _MODS = ("l", "a", "v")
+    _LOSS = {"l1": 0, "ce": 1}
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_ablation_bufs", None)        # (device workspaces and native pointer tables: rebuilt on the next call)
+        return state
+
+    def _ablation_sizes(self):
+        """zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim, read off the parameters; 1 for what the class does not have"""
+        shp = [tuple(self._modules["z%s_to_f%s_fc1" % (m, m)]._parameters["weight"].shape) for m in self._MODS]
+        head = self._ablation_head()
+        fy = head[0].shape[0] if len(head) == 4 else 1
+        return tuple(s[1] for s in shp) + (1,) + tuple(s[0] for s in shp) + (fy, self.d_l, self.d_a, self.d_v, head[-2].shape[0])
+
+    def _ablation_params(self, gen):
+        """the 52 tensors of mfm_predict_ablation's parameter table (include/mfm_hip.h); None where nothing is read"""
+        mods = self._modules
+        out = []
+        for m in self._MODS:
+            out += _lstm_fc(mods["encoder_" + m]) + _wb(mods["z%s_to_f%s_fc1" % (m, m)]) + _wb(mods["z%s_to_f%s_fc2" % (m, m)])
+            out += _lstm_fc(mods["decoder_" + m]) if gen else [None] * 6
+        head = self._ablation_head()
+        return out + head + [None] * (4 - len(head))
+
+    def _ablation_composed(self, x, gen):
+        """(y_hat, [x_hat_l, x_hat_a, x_hat_v] or None) as the composition of this module's own sub-modules (the granular HIP
+        operations); the dropout modules are left out (eval)"""
+        relu = torch.relu
+        mods = self._modules
+        zs = _encode([(xm, mods["encoder_" + m]) for m, xm in zip(self._MODS, self._split(x))])
+        h1 = M.linear_group([(z, mods["z%s_to_f%s_fc1" % (m, m)]) for m, z in zip(self._MODS, zs)])
+        fs = [relu(v) for v in M.linear_group([(relu(v), mods["z%s_to_f%s_fc2" % (m, m)]) for m, v in zip(self._MODS, h1)])]
+        cat = torch.cat(fs, dim=1)
+        if self._ABL_FAMILY == 0:
+            y1, = M.linear_group([(cat, self.fy_to_y_fc1)])
+            y_hat, = M.linear_group([(relu(y1), self.fy_to_y_fc2)])
+        else:
+            y_hat, = M.linear_group([(cat, self.fs_to_y)])
+        x_hat = M.decoder_group([(f, mods["decoder_" + m]) for m, f in zip(self._MODS, fs)], x.shape[0]) if gen else None
+        return y_hat, x_hat
+
+    def _ablation_fused(self, x, y, gen, params, loss_kind, cap):
+        """mfm_predict_ablation on the module's own tensors; MfmUnsupported when the entry refuses the sizes"""
+        T, N, _ = x.shape
+        L = _lib.lib()
+        fam = self._ABL_FAMILY
+        name = type(self).__name__
+        cache = self.__dict__.setdefault("_ablation_bufs", {})
+        key = (T, N, gen, y is not None, cap, x.device)
+        st = cache.get(key)
+        if st is False:
+            raise _lib.MfmUnsupported("%s.predict: mfm_predict_ablation refused this shape" % name)
+        if st is None:
+            sz = self._ablation_sizes()
+            sizes = (C.c_int32 * 12)(*sz)
+            nws = int(L.mfm_predict_ablation_workspace_floats(T, N, sizes, fam, int(gen), int(y is not None), cap))
+            f32 = dict(dtype=torch.float32, device=x.device)
+            out = Ablation(torch.empty((N, sz[11]), **f32), torch.empty(3, **f32) if gen else None,
+                           torch.empty((), **f32) if y is not None else None)
+            ptrs = [None if t is None else t.data_ptr() for t in out]
+            st = (torch.empty(max(nws, 4), **f32), out, sizes, ptrs, (C.c_void_p * 52)())
+        ws, out, sizes, ptrs, pptr = st
+        for i, p in enumerate(params):
+            pptr[i] = None if p is None else p.data_ptr()
+        rc = L.mfm_predict_ablation(T, N, sizes, fam, loss_kind, int(gen), pptr, C.c_void_p(x.data_ptr()),
+                                    None if y is None else C.c_void_p(y.data_ptr()), C.c_void_p(ws.data_ptr()), ptrs[0], ptrs[1], ptrs[2],
+                                    cap, C.c_void_p(torch._C._cuda_getCurrentRawStream(x.device.index)))
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            # a hidden size beyond the on-chip recurrence is a property of the model: remembered (an encoder's for every call, a
+            # decoder's for the calls with gen).  The LDS limit also depends on the tile rows, hence on N and max_rows: that
+            # refusal is remembered for this shape alone (no buffers are kept for it)
+            sz = self._ablation_sizes()
+            wide = self.__dict__.setdefault("_ablation_refused", set())
+            if max(sz[0:3]) > self.MAX_RESIDENT_H:
+                wide.update((False, True))
+            elif gen and max(sz[4:7]) > self.MAX_RESIDENT_H:
+                wide.add(True)
+            else:
+                cache[key] = False
+            raise _lib.MfmUnsupported("%s.predict: %s" % (name, L.mfm_last_error().decode()))
+        _lib.check(rc, "mfm_predict_ablation")
+        cache[key] = st
+        return out
+
+    def _ablation_call(self, what, x, y, loss, gen, max_rows):
+        name = "%s.%s" % (type(self).__name__, what)
+        if loss not in self._LOSS:
+            raise ValueError("%s: loss must be 'l1' or 'ce', not %r" % (name, loss))
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.MfmError("%s: parameters are on %s; move the model to the GPU first (no CPU fallback)" % (name, dev))
+        D = self.d_l + self.d_a + self.d_v
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise _lib.MfmError("%s: x must be a CUDA tensor [T, N, %d]; got %s" % (name, D, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        M._require_cuda(x, name)
+        if x.device != dev:
+            raise _lib.MfmError("%s: x lives on %s, the model on %s" % (name, x.device, dev))
+        if x.shape[2] != D:
+            raise _lib.MfmError("%s: x has %d features per time step, the model's input_dims sum to %d" % (name, x.shape[2], D))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise _lib.MfmError("%s: empty split %s" % (name, tuple(x.shape)))
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("%s: max_rows must be at least 1, not %r" % (name, max_rows))
+        N = x.shape[1]
+        if y is not None:
+            od = self._ablation_sizes()[11]
+            if not torch.is_tensor(y) or y.device != dev:
+                raise _lib.MfmError("%s: labels must be a tensor on %s; got %s" % (name, dev, y.device if torch.is_tensor(y) else type(y)))
+            if loss == "l1":
+                if not y.is_floating_point() or tuple(y.shape) != (N, od):
+                    raise _lib.MfmError("%s: loss 'l1' takes float labels [%d, %d]; got %s %s" % (name, N, od, y.dtype, tuple(y.shape)))
+                if not (y.dtype == torch.float32 and y.is_contiguous()):
+                    y = y.contiguous().float()
+            else:
+                if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+                    raise _lib.MfmError("%s: loss 'ce' takes int64 class indices [%d]; got %s %s" % (name, N, y.dtype, tuple(y.shape)))
+                y = y.contiguous()
+        cap = self.ABLATION_MAX_ROWS if max_rows is None else int(max_rows)
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.contiguous().float()
+        gen = bool(gen) and self._ABL_FAMILY == 0
+        with torch.no_grad():
+            if gen not in self.__dict__.get("_ablation_refused", ()):
+                params = self._ablation_params(gen)
+                if all(p is None or (p.dtype == torch.float32 and p.device == dev and p.is_contiguous()) for p in params):
+                    try:
+                        return self._ablation_fused(x, y, gen, params, self._LOSS[loss], cap)
+                    except _lib.MfmUnsupported:
+                        pass
+            # the composition of the module's own granular operations, then torch reductions
+            F = torch.nn.functional
+            y_hat, x_hat = self._ablation_composed(x, gen)
+            gens = torch.stack([F.mse_loss(xh, xm) for xh, xm in zip(x_hat, self._split(x))]) if gen else None
+            disc = None if y is None else (F.l1_loss(y_hat, y) if loss == "l1" else F.cross_entropy(y_hat, y))
+            return Ablation(y_hat, gens, disc)
+
+    def predict(self, x, y=None, *, loss="l1", gen=True, max_rows=None):
+        """x [T, N, D] (columns d_l | d_a | d_v) -> Ablation(y_hat [N, output_dim], gen, disc): what the `predict` block of the
+        reference's train_mfm_ablation reports, in one call of mfm_predict_ablation (csrc/ablation.hip).  gen: [3] device floats,
+        F.mse_loss(x_m_hat, x_m) in the order l, a, v -- None with gen=False and for a class without decoders (M_D accepts
+        gen=True and returns None); disc: the mean label loss of y_hat as a 0-dim device tensor, None without y.  y_hat and disc
+        have the same bits with and without gen.
+
+        Always the deterministic eval computation (dropout the identity), `self.training` left as found, without autograd.
+        loss="l1" takes float labels [N, output_dim], loss="ce" int64 class indices [N].  The split is walked in chunks of at most
+        `max_rows` rows (default ABLATION_MAX_ROWS).  Workspace and outputs are kept on the module (outside state_dict(), dropped
+        when pickled) per (T, N, gen, labels or not, max_rows, device) and REUSED: after the first call for a shape nothing is
+        allocated and nothing synchronises (legal inside a stream capture), and the returned tensors are overwritten by the next
+        call for the same shape -- clone what must survive it.  A device x that is not contiguous float32 is converted.  Sizes
+        the entry refuses (a hidden size above 128, LDS beyond a CU's) take the composition of the module's own granular
+        operations, followed by torch reductions; the refusal is remembered (per model for a hidden size above 128, per shape
+        otherwise).  So does a model with a parameter that is not a contiguous float32 tensor on x's device.  Argument errors
+        (shape, device, labels, an empty split, max_rows < 1: MfmError; unknown `loss`: ValueError) are raised before anything is
+        launched.  A CPU model or input raises MfmError: there is no CPU fallback."""
+        return self._ablation_call("predict", x, y, loss, gen, max_rows)
+
+    def evaluate(self, x, y, *, loss="l1", max_rows=None):
+        """the mean label loss of the split as a 0-dim device float -- the label path only, `predict(x, y, gen=False).disc` bit for
+        bit: no decoder runs, nothing comes back to the host, so `evaluate -> lr_scheduler.ReduceLROnPlateau.step ->
+        checkpoint.KeepBest.update` can be one captured graph.  The contract of predict()."""
+        if y is None:
+            raise _lib.MfmError("%s.evaluate: labels are required" % type(self).__name__)
+        return self._ablation_call("evaluate", x, y, loss, False, max_rows).disc
+
+
 class M_A(_Base):
     """reference mfm_model.py:201-266: one early-fusion encoder for z_l, MFN for z_y, all decoders fed [f_y, f_l]."""
 
@@ -103,8 +279,11 @@ class M_A(_Base):
         return [x_l_hat, x_a_hat, x_v_hat, self._classify(fy)], mmd_loss, 0.0
 
 
-class M_B(_Base):
-    """reference mfm_model.py:268-335: modality-specific factors only; the classifier reads [f_l, f_a, f_v]."""
+class M_B(_AblationProtocol, _Base):
+    """reference mfm_model.py:268-335: modality-specific factors only; the classifier reads [f_l, f_a, f_v].
+    `predict(x, y)` / `evaluate(x, y)`: y_hat, the reconstruction errors and the label loss as one call of the library."""
+
+    _ABL_FAMILY = 0
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(M_B, self).__init__(config)
@@ -131,6 +310,9 @@ class M_B(_Base):
         x_l_hat, x_a_hat, x_v_hat = M.decoder_group([(fl, self.decoder_l), (fa, self.decoder_a), (fv, self.decoder_v)], t)
         y_hat = self._classify(torch.cat([fl, fa, fv], dim=1))
         return [x_l_hat, x_a_hat, x_v_hat, y_hat], mmd_loss, 0.0
+
+    def _ablation_head(self):
+        return _wb(self._modules["fy_to_y_fc1"]) + _wb(self._modules["fy_to_y_fc2"])
 
 
 class M_C(_Base):
@@ -159,8 +341,11 @@ class M_C(_Base):
         return [x_l_hat, x_a_hat, x_v_hat, self._classify(fy)], mmd_loss, 0.0
 
 
-class M_D(_Base):
-    """reference mfm_model.py:389-467: purely discriminative (no decoders; `decoded` carries the inputs back)."""
+class M_D(_AblationProtocol, _Base):
+    """reference mfm_model.py:389-467: purely discriminative (no decoders; `decoded` carries the inputs back).
+    `predict(x, y)` / `evaluate(x, y)`: y_hat and the label loss as one call of the library; gen is None."""
+
+    _ABL_FAMILY = 1
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(M_D, self).__init__(config)
@@ -180,6 +365,9 @@ class M_D(_Base):
         fl, fa, fv = self._z_to_f_many([("zl_to_fl", zl), ("za_to_fa", za), ("zv_to_fv", zv)])
         y_hat = self.fs_to_y(torch.cat([fl, fa, fv], dim=1))
         return [x_l, x_a, x_v, y_hat], 0.0, 0.0
+
+    def _ablation_head(self):
+        return _wb(self._modules["fs_to_y"])
 
 
 Imputed = collections.namedtuple("Imputed", ["x_hat", "y_hat"])

@@ -943,6 +943,63 @@ int mfm_predict_missing(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/,
                         float* workspace, float* y_hat, float* gen, float* disc, int64_t max_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction of the ablations M_B and M_D (csrc/ablation.hip; the `evaluate` / `predict` blocks of the reference's
+ * train_mfm_ablation, reference mfm_mosi.py:640-767, mfm_model.py:317-343 and :445-467): the label prediction, its label loss
+ * and (M_B) the three reconstruction errors, in the pattern of mfm_predict_missing -- fp32, dropout the identity, no MfmPlan, no
+ * training workspace, no x_hat written.  Both classes run three independent own-modality encoders that meet at the label head:
+ *   family 0, M_B   z_m = encoder_m(x_m), f_m = relu(z<m>_to_f<m>_fc2(relu(z<m>_to_f<m>_fc1(z_m)))) for m in l, a, v;
+ *                   y_hat = fy_to_y_fc2(relu(fy_to_y_fc1([f_l | f_a | f_v]))); gen_m = mean((decoder_m(f_m, T) - x_m)^2)
+ *   family 1, M_D   the same three encoders and z -> f MLPs; y_hat = fs_to_y([f_l | f_a | f_v]); no decoders: gen must be null and
+ *                   with_gen 0
+ * Per row chunk: the three input projections as one grouped GEMM on the column ranges of x; ONE launch of (encoder m, row tile)
+ * workgroups, each of which runs its recurrence, the encoder's fc1 and the z -> f MLP on chip, stores its f_m rows into the
+ * workspace and draws an arrival ticket for its row tile -- the workgroup that draws the last of a tile's three tickets reads
+ * the tile's f rows, runs the label head, writes the tile's rows of y_hat and, with labels, one loss contribution per row; the
+ * last tile of a chunk to finish adds the chunk's contributions in fp64 in a fixed order.  No workgroup waits for another, every
+ * ticket word is 0 again when the call ends (a captured graph can be replayed), z_m is never written.  With gen: ONE launch of
+ * (decoder m, row tile) workgroups storing h_t (h = f_m), the decoders' fc1 fused with the squared error, one partial per
+ * workgroup, and one workgroup that adds the partials in fp64 in a fixed order -- no float atomics anywhere.
+ *   sizes    host, 12, the layout of mfm_predict_missing: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim; zy is unused, fy
+ *            is the classifier's hidden width (M_B; unused for M_D); an unused entry may be any positive value.  x [T, N, D]
+ *            time-major and contiguous (4-byte aligned: any contiguous view)
+ *   loss_kind 0: L1 against float labels y [N, output_dim]; 1: cross entropy against int64 class indices y [N] (8-byte aligned)
+ *   with_gen 1: gen is computed (family 0 alone) and must not be null; 0: gen must be null, no decoder runs
+ *   params   host array of 52 DEVICE pointers to the module's own tensors (torch layouts, contiguous fp32; the LSTM weights
+ *            16-byte aligned, the rest 4), per modality m = l, a, v at 16 * m: 0-5 encoder_m: lstm weight_ih, weight_hh, bias_ih,
+ *            bias_hh, fc1 weight, bias; 6-9 z<m>_to_f<m> fc1 weight, bias, fc2 weight, bias; 10-15 decoder_m alike the encoder
+ *            (h = f_m) -- not read, and may be null, when with_gen is 0 or family is 1.  Then at 48, M_B: fy_to_y_fc1 weight, bias,
+ *            fy_to_y_fc2 weight, bias; M_D: fs_to_y weight, bias, and 50-51 are not read
+ *   y        labels of the whole split, or null: no label loss (then disc must be null too)
+ *   y_hat    [N, output_dim];  gen  3 floats in the order l, a, v;  disc  1 float, the mean over the WHOLE split whatever the
+ *            chunking; gen and disc are written behind the last chunk
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_predict_ablation_workspace_floats(T, N, sizes, family, with_gen, with_labels, max_rows) floats, 16-byte aligned,
+ *            contents arbitrary; with rows = min(N, max_rows), in this order: rows * T * 4 * (round_up(zl, 16) + round_up(za, 16)
+ *            + round_up(zv, 16)) for the x-projections; round_up(rows * (fl + fa + fv), 4) for the f rows; with gen rows * T *
+ *            (round_up(fl, 16) + round_up(fa, 16) + round_up(fv, 16)) for the stored h, one float per squared-error workgroup of
+ *            a chunk (the sum over m of ceil(T * rows / 64) * ceil(d_m / 64), rounded up to 4) and 12 for six fp64 accumulators;
+ *            with labels round_up(rows, 4) loss contributions; round_up(rows, 4) ticket words; and 4 floats for the fp64 running
+ *            sum of the loss and the chunk's ticket word
+ * mfm_predict_ablation_tile_rows: host only; rows per workgroup of the encoders' launch (tile_rows[0]) and of the decoders'
+ * ([1]; 0 without gen): 1 below six workgroups per CU over the launch, else 4; both launches count three LSTMs.  Results are
+ * bit-identical from call to call; y_hat also across row caps that keep the tile rows (gen and disc then differ in the grouping
+ * of the fp64 sums alone); y_hat and disc have the same bits with and without gen.
+ * Nothing outside the workspace and the three outputs is written.  Any N >= 1 (< 2^24), T >= 1.  Sizes the on-chip recurrence does
+ * not cover (a z_m > 128, an f_m > 128 with gen, more LDS than a CU has, or a label head whose input row fl + fa + fv and
+ * activations do not fit the LDS) return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue nothing: compose the
+ * granular entries instead.  Bad arguments (T or N < 1, N >= 2^24, a null pointer, y without disc or disc without y, gen without
+ * with_gen or with_gen without gen, either of them for family 1, max_rows < 0, a family outside {0, 1}) return MFM_ERR_ARG and
+ * enqueue nothing.  Stream-ordered, no host synchronisation, no allocation; legal inside a stream capture on the one given
+ * stream (no forked branches). */
+int64_t mfm_predict_ablation_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t family, int32_t with_gen,
+                                              int32_t with_labels, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_ablation_tile_rows(int64_t N, int32_t family, int32_t with_gen, int64_t max_rows, int32_t* tile_rows /*host, 2*/);
+int mfm_predict_ablation(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t family, int32_t loss_kind, int32_t with_gen,
+                         const float* const* params /*host, 52*/, const float* x, const void* y /*null: no label loss*/,
+                         float* workspace, float* y_hat, float* gen /*3, or null*/, float* disc /*1, or null*/, int64_t max_rows,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached
