@@ -12,7 +12,7 @@
 //      runs the label head, writes the tile's rows of y_hat and, with labels, one loss contribution per row, and puts the ticket
 //      word back to 0.  z_m never leaves the chip.  The last tile of the chunk to finish (a second ticket, per chunk) adds the
 //      chunk's contributions in a fixed order in fp64 onto the running sum and, behind the last chunk, writes the mean;
-//   3. with gen: ablation_decode_kernel, workgroup (decoder m, row tile) stages its f_m rows and runs the decoder form of the
+//   3. with gen: ablation_decode_kernel (ablation_dec_dev.h), workgroup (decoder m, row tile) stages its f_m rows and runs the decoder form of the
 //      recurrence with h = f_m, storing h_t alone; fc1_sqerr_kernel (objective.hip) over the stored h against x, one partial per
 //      workgroup; zeros_finish_kernel (zeros.hip) adds the partials in fp64 in a fixed order.
 // Nobody waits or spins: a workgroup draws its ticket and either leaves or goes on, so the launch does not depend on which
@@ -21,11 +21,10 @@
 // last ticket, so y_hat is bit-identical for every chunking within one tile-row form.  Launches 2 and 3 follow the launch rules
 // of infer_dev.h: the per-block switch for the canonical size tuple only, else one launch per LSTM -- the tickets then meet across
 // the three launches, which are stream-ordered.
-#include "infer_dev.h"
+#include "ablation_dec_dev.h"
 
 namespace mfm {
 
-#define ABL_MODS 3
 #define ABL_FAMILIES 2
 #define ABL_MOD_PTRS 16      // per modality: 6 of encoder_m, 4 of z<m>_to_f<m>, 6 of decoder_m
 #define ABL_NPARAM (ABL_MODS * ABL_MOD_PTRS + 4)
@@ -145,41 +144,9 @@ __global__ __launch_bounds__(256) void ablation_zero_kernel(int* words, const in
   if (i < n) words[i] = 0;
 }
 
-// decode_plain_kernel (missing.hip) behind its two dense layers: the embedding f_m is read where launch 2 left it
-struct AblDec {
-  SeqDev seq;                                  // w_ih, w_hh, b_ih, b_hh, h = f_m, Hp, hk4, is_dec; hs: this chunk's [T, n, Hp]
-  int col, block_begin;                        // the first column of f_m in a row of the f block
-};
-struct AblDecDev { AblDec d[ABL_MODS]; const float* f; int count, T, n, ftot, seq_floats; };
-
-template <int R, int K0, int K1, int K2>
-__global__ __launch_bounds__(1024) void ablation_decode_kernel(const AblDecDev P) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, bid = blockIdx.x;
-  MFM_SEQ_BLOCK_LSTM(P, bid, di)
-  const AblDec& D = P.d[di];
-  const int tile = bid - D.block_begin, b0 = tile * R;
-  const int h = D.seq.h;
-  // behind everything the recurrence uses: the embedding must survive its weight staging.  [R][h]: the recurrence's h_init
-  float* emb = lds + P.seq_floats;
-  for (int e = tid; e < h * R; e += blockDim.x) {
-    const int r = e / h, k = e - r * h;
-    emb[e] = (b0 + r < P.n) ? P.f[(int64_t)(b0 + r) * P.ftot + D.col + k] : 0.0f;
-  }
-  lds_barrier();
-  // the tile as a batch of its own: row r of the embedding in LDS is row r of the recurrence, and of this tile's part of hs
-  SeqDev d = D.seq;
-  d.h_init = emb; d.ld_init = h;
-  d.hs = D.seq.hs + (int64_t)b0 * D.seq.Hp;
-  const int rows = min(R, P.n - b0);
-  const int64_t hs_step = (int64_t)P.n * D.seq.Hp;
-  MFM_TUPLE3((small_fwd_body<KQ, R, false, false, false, true>(d, P.T, rows, 0, lds, nullptr, 0u, 0,
-                                                                HoCtl{nullptr, nullptr, nullptr, 5000000ll, 1u}, hs_step)))
-}
-
 // ---------------------------------------------------------------- host
-static const int kAblEnc[ABL_MODS] = {8, 2, 20};          // the canonical sizes: the encoders h = zl / za / zv = 32 / 8 / 80 ...
-static const int kAblDec[ABL_MODS] = {22, 2, 2};          // ... the decoders h = fl / fa / fv = 88 / 8 / 8
+static const int kAblEnc[ABL_MODS] = {8, 2, 20};          // the canonical sizes: the encoders h = zl / za / zv = 32 / 8 / 80 (the decoders'
+                                                          // h = fl / fa / fv = 88 / 8 / 8: hk4 22 / 2 / 2 where their launch is named)
 
 template <int R>
 static int abl_encode_launch(const char* who, AblEncDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
@@ -187,14 +154,6 @@ static int abl_encode_launch(const char* who, AblEncDev& P, int threads, size_t 
   for (int i = 0; i < ABL_MODS; ++i) canon = canon && P.d[i].seq.hk4 == kAblEnc[i];
   return infer_launch_tuple_or_each<R>(who, "ablation_encode_kernel", P, canon ? ablation_encode_kernel<R, 8, 2, 20> : nullptr,
                                        [](auto kk) { return ablation_encode_kernel<R, decltype(kk)::value, 0, 0>; }, threads, lds_bytes, stream);
-}
-
-template <int R>
-static int abl_decode_launch(const char* who, AblDecDev& P, int threads, size_t lds_bytes, hipStream_t stream) {
-  bool canon = true;
-  for (int i = 0; i < ABL_MODS; ++i) canon = canon && P.d[i].seq.hk4 == kAblDec[i];
-  return infer_launch_tuple_or_each<R>(who, "ablation_decode_kernel", P, canon ? ablation_decode_kernel<R, 22, 2, 2> : nullptr,
-                                       [](auto kk) { return ablation_decode_kernel<R, decltype(kk)::value, 0, 0>; }, threads, lds_bytes, stream);
 }
 
 struct AblSizes { int z[ABL_MODS], fm[ABL_MODS], dm[ABL_MODS], fy, od, D, ftot; };
@@ -379,7 +338,7 @@ static int predict_ablation(int T, int64_t N, const int32_t* sz, int family, int
     if (rc != MFM_OK) return rc;
     if (!with_gen) continue;
     PD.n = n;
-    rc = (Rd == 1) ? abl_decode_launch<1>(who, PD, dec_threads, dec_lds, stream) : abl_decode_launch<4>(who, PD, dec_threads, dec_lds, stream);
+    rc = (Rd == 1) ? abl_decode_launch<1, 22, 2, 2>(who, PD, dec_threads, dec_lds, stream) : abl_decode_launch<4, 22, 2, 2>(who, PD, dec_threads, dec_lds, stream);
     if (rc != MFM_OK) return rc;
     if ((rc = fc1_sqerr_chunk(Sq, x, n0, n, part, Q.part, Q.npart, stream)) != MFM_OK) return rc;
     Q.n = n; Q.first = n0 == 0; Q.last = n0 + n == N;

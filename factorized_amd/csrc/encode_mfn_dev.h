@@ -5,10 +5,11 @@
 // i) of the zeroed-modality protocol, case major (mfm_predict_zeros_mfn): modality c's cell states and last hidden state come from
 // the ONE row the MFN's LSTM c computes on zero input (cz / hz), the other two modalities' from the real records.  Only the gather
 // differs; the arithmetic of a row is the same code.  zeros_mfn.hip alone instantiates ZC = true.
-// Template parameter TAIL of the memory recurrence (off by default; predict_mfn.hip alone turns it on, with ZC = false): zy stays
-// in LDS and the same workgroup goes on with zy_to_fy and the classifier, writes the row of y_hat and, with labels, the row's
-// loss contribution (EmfnTailDev); the other instantiations do not see any of it.
-// Host, shared by all four: the two size parsers (emfn_sizes, the 17 of mfm_encode_mfn; mfn_sizes, the MFN_SIZES of the other
+// Template parameter TAIL of the memory recurrence (off by default; predict_mfn.hip and ablation_mfn.hip turn it on, with ZC =
+// false): zy stays in LDS and the same workgroup goes on with zy_to_fy and the classifier, writes the row of y_hat and, with
+// labels, the row's loss contribution (EmfnTailDev); the other instantiations do not see any of it.  EMB (with TAIL;
+// ablation_mfn.hip alone): the workgroup also stores the row's fy, which it holds in LDS behind zy_to_fy_fc2, for the decoders.
+// Host, shared by all four (and by ablation_mfn.hip, whose parameters are separate tensors: the *_ptrs forms): the two size parsers (emfn_sizes, the 17 of mfm_encode_mfn; mfn_sizes, the MFN_SIZES of the other
 // three), the refusals (mfn_check_covered), the sizing of the two launches (emfn_chain_check / emfn_chain_fill) and the launches
 // themselves (emfn_att_launch, emfn_mem_launch, emfn_chain_launch), the workspace parts behind the x-projections (mfn_ws), the
 // MFN's three LSTMs of a call (mfn_lstms_fill); a chunk's grouped projection GEMM (MfnLstm, mfn_xproj_chunk) is in infer_dev.h,
@@ -231,6 +232,7 @@ struct EmfnTailDev : EmfnMemDev {
   float* loss;                                 // the result (null: no loss)
   double inv;                                  // 1 / (N od) (L1) or 1 / N (CE) over the WHOLE split
   int fy, od, loss_kind, tailw, first, last;   // tailw: floats of one tail activation in LDS; first / last chunk of the call
+  float* emb; int embw;                        // EMB: the chunk's embedding block [n, embw]; the row's fy goes to its columns [0, fy)
 };
 
 // one layer of the tail on LDS vectors, 8 lanes per output as the head: out[o] = (relu)(b[o] + sum_k W[o][k] in[k])
@@ -249,9 +251,10 @@ __device__ __forceinline__ void emfn_tail_layer(const float* __restrict__ W, con
 
 // The thread roles, the operand layout (lane q of a group owns the contiguous slice [32 q, 32 q + 32) of the reduction) and the
 // two barriers per step are those of mfn_mem_fwd_kernel (mfn_mem.hip); nothing of a step is stored
-template <int MAXT, bool ZC, bool TAIL = false>
+template <int MAXT, bool ZC, bool TAIL = false, bool EMB = false>
 __global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const std::conditional_t<TAIL, EmfnTailDev, EmfnMemDev> P) {
   static_assert(!(TAIL && ZC), "the label tail runs on the chunk's own rows");
+  static_assert(!EMB || TAIL, "fy exists in the label tail alone");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int T = P.T, n = P.n, M = P.M, H1 = P.H1, H2 = P.H2, QA = P.QA, QB = P.QB, MP = P.MP, HP = P.HP;
   float* memb = lds;                 // [2][MP]
@@ -356,6 +359,9 @@ __global__ __launch_bounds__(MAXT) void encode_mfn_mem_kernel(const std::conditi
     emfn_tail_layer(P.wz[0], P.bz[0], KT, P.zy, vec, act0, false, tid);
     emfn_tail_layer(P.wt[0], P.bt[0], P.zy, fy, act0, act1, true, tid);
     emfn_tail_layer(P.wt[1], P.bt[1], fy, fy, act1, act0, true, tid);
+    if constexpr (EMB) {      // fy, the label factor, for the decoders behind this launch (act0 is next written two barriers on)
+      for (int o = tid; o < fy; o += blockDim.x) P.emb[(int64_t)row * P.embw + o] = act0[o];
+    }
     emfn_tail_layer(P.wt[2], P.bt[2], fy, fy, act0, act1, true, tid);
     emfn_tail_layer(P.wt[3], P.bt[3], fy, od, act1, act0, false, tid);
     for (int o = tid; o < od; o += blockDim.x) P.y_hat[(int64_t)row * od + o] = act0[o];
@@ -489,24 +495,33 @@ static int emfn_chain_check(const char* who, const EmfnSizes& S, int64_t pairs, 
   return MFM_OK;
 }
 
-// sizes and parameters of the two launches: att, the sixteen offsets of the MFN's attention and gamma networks; zyo, those of
-// the label head(s).  The caller sets the records (A.cs / cz, Mm.hl / hz), the chain's buffers (chat, g1p, g2p) and Mm.oz
-static void emfn_chain_fill(EmfnChain& C, const EmfnSizes& S, int T, const float* params, const int64_t* att, const int64_t* zyo, int nheads) {
+// sizes and parameters of the two launches: att, the sixteen tensors of the MFN's attention and gamma networks; zyo, those of
+// the label head(s), weight and bias each.  The caller sets the records (A.cs / cz, Mm.hl / hz), the chain's buffers (chat, g1p,
+// g2p) and Mm.oz
+static void emfn_chain_fill_ptrs(EmfnChain& C, const EmfnSizes& S, int T, const float* const* att, const float* const* zyo, int nheads) {
   EmfnAttDev& A = C.A;
   EmfnMemDev& Mm = C.Mm;
   const int tot = S.hm[0] + S.hm[1] + S.hm[2], KC = 2 * tot;
-  // att1_fc1, att1_fc2, att2_fc1, att2_fc2, then gamma1_fc1 and gamma2_fc1 (offsets 8 and 12 of the MFN's sixteen)
+  // att1_fc1, att1_fc2, att2_fc1, att2_fc2, then gamma1_fc1 and gamma2_fc1 (tensors 8 and 12 of the MFN's sixteen)
   static const int att_off[6] = {0, 2, 4, 6, 8, 12};
-  for (int l = 0; l < 6; ++l) { A.w[l] = params + att[att_off[l]]; A.b[l] = params + att[att_off[l] + 1]; }
+  for (int l = 0; l < 6; ++l) { A.w[l] = att[att_off[l]]; A.b[l] = att[att_off[l] + 1]; }
   for (int m = 0; m < 3; ++m) { A.hm[m] = S.hm[m]; A.Hpm[m] = round_up(S.hm[m], 16); Mm.hn[m] = S.hm[m]; }
   A.T = T; A.tot = tot; A.KC = KC; A.KCp = round_up(KC, 16); A.h1 = S.h1; A.h2 = S.h2; A.hbp = round_up(std::max(S.h1, S.h2), 16);
   A.M = S.M; A.H1 = S.H1; A.H2 = S.H2;
   Mm.w1m = A.w[4] + KC; Mm.w2m = A.w[5] + KC; Mm.ldw = KC + S.M;
-  Mm.w1b = params + att[10]; Mm.b1b = params + att[11];
-  Mm.w2b = params + att[14]; Mm.b2b = params + att[15];
-  for (int hd = 0; hd < nheads; ++hd) { Mm.wz[hd] = params + zyo[2 * hd]; Mm.bz[hd] = params + zyo[2 * hd + 1]; }
+  Mm.w1b = att[10]; Mm.b1b = att[11];
+  Mm.w2b = att[14]; Mm.b2b = att[15];
+  for (int hd = 0; hd < nheads; ++hd) { Mm.wz[hd] = zyo[2 * hd]; Mm.bz[hd] = zyo[2 * hd + 1]; }
   Mm.T = T; Mm.M = S.M; Mm.H1 = S.H1; Mm.H2 = S.H2; Mm.tot = tot; Mm.zy = S.zy;
   Mm.nheads = nheads;
+}
+// the same from element offsets into one flat parameter buffer
+static void emfn_chain_fill(EmfnChain& C, const EmfnSizes& S, int T, const float* params, const int64_t* att, const int64_t* zyo, int nheads) {
+  const float* ap[16];
+  const float* zp[4];
+  for (int i = 0; i < 16; ++i) ap[i] = params + att[i];
+  for (int i = 0; i < 2 * nheads; ++i) zp[i] = params + zyo[i];
+  emfn_chain_fill_ptrs(C, S, T, ap, zp, nheads);
 }
 
 // the attention chain on a chunk of n rows (ZC: the 3 n rows (case, row)); the memory recurrence reads what it leaves
@@ -525,11 +540,11 @@ static int emfn_att_launch(EmfnChain& C, int T, int n, hipStream_t stream) {
 }
 
 // the memory recurrence on the rows the attention chain was launched on; Mm: C.Mm, or (TAIL) the caller's copy of it with the tail
-template <bool ZC, bool TAIL = false>
+template <bool ZC, bool TAIL = false, bool EMB = false>
 static int emfn_mem_launch(const EmfnChain& C, const std::conditional_t<TAIL, EmfnTailDev, EmfnMemDev>& Mm, hipStream_t stream) {
   if (C.mem_threads <= 512)
-    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC, TAIL>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
-  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC, TAIL>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+    return seq_launch_kernel(encode_mfn_mem_kernel<512, ZC, TAIL, EMB>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
+  return seq_launch_kernel(encode_mfn_mem_kernel<1024, ZC, TAIL, EMB>, "encode_mfn_mem_kernel", dim3(Mm.n), dim3(C.mem_threads), C.mem_lds, stream, nullptr, Mm);
 }
 
 // the two launches on a chunk of n rows (ZC: the 3 n rows (case, row) behind them)
@@ -554,15 +569,15 @@ static MfnWs mfn_ws(const EmfnSizes& S, int64_t T, int64_t rows, int cases) {
 // the first column of modality m in a row of x
 static int mfn_col(const EmfnSizes& S, int m) { return m == 0 ? 0 : (m == 1 ? S.d[0] : S.d[0] + S.d[1]); }
 
-// the MFN's lstm l, a, v (MfnLstm: infer_dev.h) of a call, L[0 .. 3) with seq / h_last set by the caller: the cells from their twelve offsets, their
+// the MFN's lstm l, a, v (MfnLstm: infer_dev.h) of a call, L[0 .. 3) with seq / h_last set by the caller: the cells from their twelve tensors, their
 // projections from `gates` on, their c records (A.cs) and last hidden states (Mm.hl) and the chain's buffers from `rest` on in
 // the order of mfn_ws; returns the end of those parts
-static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64_t T, int64_t rows, int cases, const float* params,
-                             const int64_t* cells, float* gates, float* rest) {
+static float* mfn_lstms_fill_ptrs(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64_t T, int64_t rows, int cases, const float* const* cells,
+                                  float* gates, float* rest) {
   const MfnWs W = mfn_ws(S, T, rows, cases);
   for (int m = 0; m < 3; ++m) {
-    const int64_t* o = cells + 4 * m;
-    seq_fill(*L[m].seq, params + o[0], params + o[1], params + o[2], params + o[3], S.hm[m], 0);
+    const float* const* o = cells + 4 * m;
+    seq_fill(*L[m].seq, o[0], o[1], o[2], o[3], S.hm[m], 0);
     L[m].seq->gates = gates; gates += rows * T * 4 * hp_of(S.hm[m]);
     L[m].col = mfn_col(S, m); L[m].d = S.d[m];
   }
@@ -572,6 +587,13 @@ static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64
   C.A.g1p = rest; rest += W.g1p;
   C.A.g2p = rest; rest += W.g2p;
   return rest;
+}
+// the same from twelve element offsets into one flat parameter buffer
+static float* mfn_lstms_fill(MfnLstm* L, EmfnChain& C, const EmfnSizes& S, int64_t T, int64_t rows, int cases, const float* params,
+                             const int64_t* cells, float* gates, float* rest) {
+  const float* cp[12];
+  for (int i = 0; i < 12; ++i) cp[i] = params + cells[i];
+  return mfn_lstms_fill_ptrs(L, C, S, T, rows, cases, cp, gates, rest);
 }
 
 // ---------------------------------------------------------------- the six recurrences (mfm_encode_mfn; mfm_objective_mfn launches them too)

@@ -14,7 +14,11 @@ There is no fused one-call plan for these classes ("pure
 `MFM_missing.impute` is the exception: surrogate inference (a missing modality and the label from the other two) as one call
 of the library, `mfm_impute_missing` (csrc/impute.hip).  So is `predict_missing` of MFM_missing, seq2seq and basic_missing: the
 missing-modality test protocol (per missing case the label, the error of the rebuilt modality and the label loss) as one call,
-`mfm_predict_missing` (csrc/missing.hip); and `predict` / `evaluate` of M_B and M_D, `mfm_predict_ablation` (csrc/ablation.hip).
+`mfm_predict_missing` (csrc/missing.hip); and `predict` / `evaluate` of the four ablations -- what the `evaluate` / `predict` blocks
+of the reference's train_mfm_ablation report --: M_B and M_D through `mfm_predict_ablation` (csrc/ablation.hip), M_A and M_C, whose
+label factor comes from the Memory Fusion Network, through `mfm_predict_ablation_mfn` (csrc/ablation_mfn.hip).  One mixin,
+`_AblationProtocol`, carries the protocol; `_AblationMfnProtocol` gives the MFN pair its parameter table, sizes, entry call and
+composed fallback.
 """
 import collections
 import ctypes as C
@@ -77,14 +81,20 @@ Ablation = collections.namedtuple("Ablation", ["y_hat", "gen", "disc"])
 
 
 class _AblationProtocol:
-    """`predict` / `evaluate` of the ablations whose three own-modality encoders meet at the label head: one call of
-    mfm_predict_ablation (csrc/ablation.hip).  A class names its family (`_ABL_FAMILY`: 0 M_B, 1 M_D) and gives `_ablation_head()`,
-    the tensors of its label head."""
+    """`predict` / `evaluate` of the ablations: argument checks, the buffer cache, the remembered refusals and the composed
+    fallback around one call of the class's library entry.  As it stands it serves the ablations whose three own-modality
+    encoders meet at the label head, mfm_predict_ablation (csrc/ablation.hip): a class names its family (`_ABL_FAMILY`: 0 M_B,
+    1 M_D) and gives `_ablation_head()`, the tensors of its label head.  `_AblationMfnProtocol` replaces what is the entry's own:
+    `_ablation_sizes`, `_ablation_params`, `_ablation_composed`, `_ablation_ws_floats`, `_ablation_entry`, `_ablation_wide`."""
 
     ABLATION_MAX_ROWS = 1024     # default row cap: the x-projections of at most this many rows are alive at once
     MAX_RESIDENT_H = 128         # widest LSTM of the on-chip recurrences (csrc/lstm_seq_dev.h, MFM_SEQ_MAX_RESIDENT_H)
     _MODS = ("l", "a", "v")
     _LOSS = {"l1": 0, "ce": 1}
+    _ABL_ENTRY = "mfm_predict_ablation"
+    _ABL_NPARAM = 52             # pointers of the entry's parameter table
+    _ABL_OD = 11                 # where output_dim stands among the entry's sizes
+    _ABL_HAS_GEN = True          # the class has decoders
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -125,46 +135,55 @@ class _AblationProtocol:
         x_hat = M.decoder_group([(f, mods["decoder_" + m]) for m, f in zip(self._MODS, fs)], x.shape[0]) if gen else None
         return y_hat, x_hat
 
+    def _ablation_ws_floats(self, L, T, N, sizes, gen, labels, cap):
+        return L.mfm_predict_ablation_workspace_floats(T, N, sizes, self._ABL_FAMILY, int(gen), int(labels), cap)
+
+    def _ablation_entry(self, L, T, N, sizes, loss_kind, gen, pptr, x, y, ws, ptrs, cap, stream):
+        return L.mfm_predict_ablation(T, N, sizes, self._ABL_FAMILY, loss_kind, int(gen), pptr, x, y, ws, ptrs[0], ptrs[1], ptrs[2], cap, stream)
+
+    def _ablation_wide(self, sz, gen):
+        """the values of `gen` for which a refusal is a property of the model (a hidden size beyond the on-chip recurrence: an
+        encoder's for every call, a decoder's for the calls with gen); empty: of this shape alone"""
+        if max(sz[0:3]) > self.MAX_RESIDENT_H:
+            return (False, True)
+        return (True,) if gen and max(sz[4:7]) > self.MAX_RESIDENT_H else ()
+
     def _ablation_fused(self, x, y, gen, params, loss_kind, cap):
-        """mfm_predict_ablation on the module's own tensors; MfmUnsupported when the entry refuses the sizes"""
+        """the class's entry on the module's own tensors; MfmUnsupported when the entry refuses the sizes"""
         T, N, _ = x.shape
         L = _lib.lib()
-        fam = self._ABL_FAMILY
         name = type(self).__name__
         cache = self.__dict__.setdefault("_ablation_bufs", {})
         key = (T, N, gen, y is not None, cap, x.device)
         st = cache.get(key)
         if st is False:
-            raise _lib.MfmUnsupported("%s.predict: mfm_predict_ablation refused this shape" % name)
+            raise _lib.MfmUnsupported("%s.predict: %s refused this shape" % (name, self._ABL_ENTRY))
         if st is None:
             sz = self._ablation_sizes()
-            sizes = (C.c_int32 * 12)(*sz)
-            nws = int(L.mfm_predict_ablation_workspace_floats(T, N, sizes, fam, int(gen), int(y is not None), cap))
+            sizes = (C.c_int32 * len(sz))(*sz)
+            nws = int(self._ablation_ws_floats(L, T, N, sizes, gen, y is not None, cap))
             f32 = dict(dtype=torch.float32, device=x.device)
-            out = Ablation(torch.empty((N, sz[11]), **f32), torch.empty(3, **f32) if gen else None,
+            out = Ablation(torch.empty((N, sz[self._ABL_OD]), **f32), torch.empty(3, **f32) if gen else None,
                            torch.empty((), **f32) if y is not None else None)
             ptrs = [None if t is None else t.data_ptr() for t in out]
-            st = (torch.empty(max(nws, 4), **f32), out, sizes, ptrs, (C.c_void_p * 52)())
+            st = (torch.empty(max(nws, 4), **f32), out, sizes, ptrs, (C.c_void_p * self._ABL_NPARAM)())
         ws, out, sizes, ptrs, pptr = st
         for i, p in enumerate(params):
             pptr[i] = None if p is None else p.data_ptr()
-        rc = L.mfm_predict_ablation(T, N, sizes, fam, loss_kind, int(gen), pptr, C.c_void_p(x.data_ptr()),
-                                    None if y is None else C.c_void_p(y.data_ptr()), C.c_void_p(ws.data_ptr()), ptrs[0], ptrs[1], ptrs[2],
-                                    cap, C.c_void_p(torch._C._cuda_getCurrentRawStream(x.device.index)))
+        rc = self._ablation_entry(L, T, N, sizes, loss_kind, gen, pptr, C.c_void_p(x.data_ptr()),
+                                  None if y is None else C.c_void_p(y.data_ptr()), C.c_void_p(ws.data_ptr()), ptrs, cap,
+                                  C.c_void_p(torch._C._cuda_getCurrentRawStream(x.device.index)))
         if rc == _lib.MFM_ERR_UNSUPPORTED:
-            # a hidden size beyond the on-chip recurrence is a property of the model: remembered (an encoder's for every call, a
-            # decoder's for the calls with gen).  The LDS limit also depends on the tile rows, hence on N and max_rows: that
-            # refusal is remembered for this shape alone (no buffers are kept for it)
-            sz = self._ablation_sizes()
-            wide = self.__dict__.setdefault("_ablation_refused", set())
-            if max(sz[0:3]) > self.MAX_RESIDENT_H:
-                wide.update((False, True))
-            elif gen and max(sz[4:7]) > self.MAX_RESIDENT_H:
-                wide.add(True)
+            # a hidden size beyond the on-chip recurrence is a property of the model: remembered (`_ablation_wide`).  The LDS
+            # limit also depends on the tile rows, hence on N and max_rows: that refusal is remembered for this shape alone (no
+            # buffers are kept for it)
+            wide = self._ablation_wide(self._ablation_sizes(), gen)
+            if wide:
+                self.__dict__.setdefault("_ablation_refused", set()).update(wide)
             else:
                 cache[key] = False
             raise _lib.MfmUnsupported("%s.predict: %s" % (name, L.mfm_last_error().decode()))
-        _lib.check(rc, "mfm_predict_ablation")
+        _lib.check(rc, self._ABL_ENTRY)
         cache[key] = st
         return out
 
@@ -189,7 +208,7 @@ class _AblationProtocol:
             raise _lib.MfmError("%s: max_rows must be at least 1, not %r" % (name, max_rows))
         N = x.shape[1]
         if y is not None:
-            od = self._ablation_sizes()[11]
+            od = self._ablation_sizes()[self._ABL_OD]
             if not torch.is_tensor(y) or y.device != dev:
                 raise _lib.MfmError("%s: labels must be a tensor on %s; got %s" % (name, dev, y.device if torch.is_tensor(y) else type(y)))
             if loss == "l1":
@@ -204,7 +223,7 @@ class _AblationProtocol:
         cap = self.ABLATION_MAX_ROWS if max_rows is None else int(max_rows)
         if not (x.dtype == torch.float32 and x.is_contiguous()):
             x = x.contiguous().float()
-        gen = bool(gen) and self._ABL_FAMILY == 0
+        gen = bool(gen) and self._ABL_HAS_GEN
         with torch.no_grad():
             if gen not in self.__dict__.get("_ablation_refused", ()):
                 params = self._ablation_params(gen)
@@ -222,7 +241,8 @@ class _AblationProtocol:
 
     def predict(self, x, y=None, *, loss="l1", gen=True, max_rows=None):
         """x [T, N, D] (columns d_l | d_a | d_v) -> Ablation(y_hat [N, output_dim], gen, disc): what the `predict` block of the
-        reference's train_mfm_ablation reports, in one call of mfm_predict_ablation (csrc/ablation.hip).  gen: [3] device floats,
+        reference's train_mfm_ablation reports, in one call of the library (M_B, M_D: mfm_predict_ablation, csrc/ablation.hip;
+        M_A, M_C: mfm_predict_ablation_mfn, csrc/ablation_mfn.hip).  gen: [3] device floats,
         F.mse_loss(x_m_hat, x_m) in the order l, a, v -- None with gen=False and for a class without decoders (M_D accepts
         gen=True and returns None); disc: the mean label loss of y_hat as a 0-dim device tensor, None without y.  y_hat and disc
         have the same bits with and without gen.
@@ -233,9 +253,9 @@ class _AblationProtocol:
         when pickled) per (T, N, gen, labels or not, max_rows, device) and REUSED: after the first call for a shape nothing is
         allocated and nothing synchronises (legal inside a stream capture), and the returned tensors are overwritten by the next
         call for the same shape -- clone what must survive it.  A device x that is not contiguous float32 is converted.  Sizes
-        the entry refuses (a hidden size above 128, LDS beyond a CU's) take the composition of the module's own granular
-        operations, followed by torch reductions; the refusal is remembered (per model for a hidden size above 128, per shape
-        otherwise).  So does a model with a parameter that is not a contiguous float32 tensor on x's device.  Argument errors
+        the entry refuses (a hidden size above 128 -- for M_A / M_C an `h_dims` entry or, with gen, the decoders' fy + fl / fy --,
+        LDS beyond a CU's) take the composition of the module's own granular operations in eval mode without the MMD, followed
+        by torch reductions; the refusal is remembered (per model for a hidden size above 128, per shape otherwise).  So does a model with a parameter that is not a contiguous float32 tensor on x's device.  Argument errors
         (shape, device, labels, an empty split, max_rows < 1: MfmError; unknown `loss`: ValueError) are raised before anything is
         launched.  A CPU model or input raises MfmError: there is no CPU fallback."""
         return self._ablation_call("predict", x, y, loss, gen, max_rows)
@@ -249,8 +269,99 @@ class _AblationProtocol:
         return self._ablation_call("evaluate", x, y, loss, False, max_rows).disc
 
 
-class M_A(_Base):
-    """reference mfm_model.py:201-266: one early-fusion encoder for z_l, MFN for z_y, all decoders fed [f_y, f_l]."""
+class _AblationMfnProtocol(_AblationProtocol):
+    """the protocol for the ablations whose label factor comes from the Memory Fusion Network: one call of
+    mfm_predict_ablation_mfn (csrc/ablation_mfn.hip).  `_ABL_FAMILY`: 0 M_A (encoder_l over all of x, decoders on [fy | fl]),
+    1 M_C (decoders on fy)."""
+
+    _ABL_ENTRY = "mfm_predict_ablation_mfn"
+    _ABL_NPARAM = 66
+    _ABL_OD = 21
+    _MFN_LINEARS = ("att1_fc1", "att1_fc2", "att2_fc1", "att2_fc2", "gamma1_fc1", "gamma1_fc2", "gamma2_fc1", "gamma2_fc2")
+    _TAIL_LINEARS = ("last_to_zy_fc1", "zy_to_fy_fc1", "zy_to_fy_fc2", "fy_to_y_fc1", "fy_to_y_fc2")
+
+    def _ablation_sizes(self):
+        """the 23 sizes of mfm_predict_zeros_mfn's layout, read off the parameters; 1 for what the class does not have (za, zv,
+        fa, fv; M_C: zl, fl too), heads 0.  Entry 22, the loss kind, is set per call"""
+        mods = self._modules
+        mfn = mods["mfn_encoder"]._modules
+        w = lambda mod: tuple(mod._parameters["weight"].shape)
+        hm = [mfn["lstm_" + m]._parameters["weight_hh"].shape[1] for m in self._MODS]
+        fl, zl = w(mods["zl_to_fl_fc1"]) if self._ABL_FAMILY == 0 else (1, 1)
+        fy, zy = w(mods["zy_to_fy_fc1"])
+        return (self.d_l, self.d_a, self.d_v, zl, 1, 1, zy, hm[0], hm[1], hm[2], w(mfn["att2_fc2"])[0], w(mfn["att1_fc1"])[1] // sum(hm),
+                w(mfn["att1_fc1"])[0], w(mfn["att2_fc1"])[0], w(mfn["gamma1_fc1"])[0], w(mfn["gamma2_fc1"])[0], 0,
+                fl, 1, 1, fy, w(mods["fy_to_y_fc2"])[0], 0)
+
+    def _ablation_params(self, gen):
+        """the 66 tensors of mfm_predict_ablation_mfn's parameter table (include/mfm_hip.h); None where nothing is read"""
+        mods = self._modules
+        mfn = mods["mfn_encoder"]._modules
+        out = []
+        for m in self._MODS:
+            lp = mfn["lstm_" + m]._parameters
+            out += [lp["weight_ih"], lp["weight_hh"], lp["bias_ih"], lp["bias_hh"]]
+        for n in self._MFN_LINEARS:
+            out += _wb(mfn[n])
+        for n in self._TAIL_LINEARS:
+            out += _wb(mods[n])
+        for m in self._MODS:
+            out += _lstm_fc(mods["decoder_" + m]) if gen else [None] * 6
+        if gen and self._ABL_FAMILY == 0:
+            return out + _lstm_fc(mods["encoder_l"]) + _wb(mods["zl_to_fl_fc1"]) + _wb(mods["zl_to_fl_fc2"])
+        return out + [None] * 10
+
+    def _ablation_composed(self, x, gen):
+        """(y_hat, [x_hat_l, x_hat_a, x_hat_v] or None) as the composition of this module's own sub-modules (the granular HIP
+        operations) in eval mode: the dropout modules and the MMD are left out; the MFN, whose forward applies its own dropout
+        modules, runs in eval mode and is put back as found"""
+        relu = torch.relu
+        mods = self._modules
+        mfn = mods["mfn_encoder"]
+        was = [mod.training for mod in mfn.modules()]
+        mfn.eval()
+        try:
+            last = mfn.forward(x)
+        finally:
+            for mod, t in zip(mfn.modules(), was):
+                mod.training = t
+        zy, = M.linear_group([(last, mods["last_to_zy_fc1"])])
+        h1, = M.linear_group([(zy, mods["zy_to_fy_fc1"])])
+        fy, = M.linear_group([(relu(h1), mods["zy_to_fy_fc2"])])
+        fy = relu(fy)
+        y1, = M.linear_group([(fy, mods["fy_to_y_fc1"])])
+        y_hat, = M.linear_group([(relu(y1), mods["fy_to_y_fc2"])])
+        if not gen:
+            return y_hat, None
+        emb = fy
+        if self._ABL_FAMILY == 0:
+            zl, = _encode([(x, mods["encoder_l"])])
+            h1, = M.linear_group([(zl, mods["zl_to_fl_fc1"])])
+            fl, = M.linear_group([(relu(h1), mods["zl_to_fl_fc2"])])
+            emb = torch.cat([fy, relu(fl)], dim=1)
+        return y_hat, M.decoder_group([(emb, mods["decoder_" + m]) for m in self._MODS], x.shape[0])
+
+    def _ablation_ws_floats(self, L, T, N, sizes, gen, labels, cap):
+        return L.mfm_predict_ablation_mfn_workspace_floats(T, N, sizes, self._ABL_FAMILY, int(gen), int(labels), cap)
+
+    def _ablation_entry(self, L, T, N, sizes, loss_kind, gen, pptr, x, y, ws, ptrs, cap, stream):
+        sizes[22] = loss_kind
+        return L.mfm_predict_ablation_mfn(T, N, sizes, self._ABL_FAMILY, int(gen), pptr, x, y, ws, ptrs[0], ptrs[1], ptrs[2], cap, stream)
+
+    def _ablation_wide(self, sz, gen):
+        """an `h_dims` entry above 128 refuses every call; encoder_l's zl (M_A) or the decoders' fy + fl / fy the calls with gen"""
+        if max(sz[7:10]) > self.MAX_RESIDENT_H:
+            return (False, True)
+        wdec = sz[20] + sz[17] if self._ABL_FAMILY == 0 else sz[20]
+        wenc = sz[3] if self._ABL_FAMILY == 0 else 1
+        return (True,) if gen and max(wdec, wenc) > self.MAX_RESIDENT_H else ()
+
+
+class M_A(_AblationMfnProtocol, _Base):
+    """reference mfm_model.py:201-266: one early-fusion encoder for z_l, MFN for z_y, all decoders fed [f_y, f_l].
+    `predict(x, y)` / `evaluate(x, y)`: y_hat, the reconstruction errors and the label loss as one call of the library."""
+
+    _ABL_FAMILY = 0
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(M_A, self).__init__(config)
@@ -315,8 +426,11 @@ class M_B(_AblationProtocol, _Base):
         return _wb(self._modules["fy_to_y_fc1"]) + _wb(self._modules["fy_to_y_fc2"])
 
 
-class M_C(_Base):
-    """reference mfm_model.py:337-387: the multimodal factor only (MFN -> z_y -> f_y feeds every decoder)."""
+class M_C(_AblationMfnProtocol, _Base):
+    """reference mfm_model.py:337-387: the multimodal factor only (MFN -> z_y -> f_y feeds every decoder).
+    `predict(x, y)` / `evaluate(x, y)`: y_hat, the reconstruction errors and the label loss as one call of the library."""
+
+    _ABL_FAMILY = 1
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(M_C, self).__init__(config)
@@ -346,6 +460,7 @@ class M_D(_AblationProtocol, _Base):
     `predict(x, y)` / `evaluate(x, y)`: y_hat and the label loss as one call of the library; gen is None."""
 
     _ABL_FAMILY = 1
+    _ABL_HAS_GEN = False
 
     def __init__(self, config, NN1Config, NN2Config, gamma1Config, gamma2Config, outConfig):
         super(M_D, self).__init__(config)

@@ -1000,6 +1000,80 @@ int mfm_predict_ablation(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction of the ablations M_A and M_C (csrc/ablation_mfn.hip; the same `evaluate` / `predict` blocks of the reference's
+ * train_mfm_ablation, reference mfm_model.py:201-266 and :337-387): the two ablations whose label factor comes from the Memory
+ * Fusion Network, under the contract of mfm_predict_ablation -- fp32, dropout the identity, no MfmPlan, no training workspace, no
+ * x_hat written, no MMD:
+ *   family 0, M_A   zy = last_to_zy_fc1(MFN(x)), fy = relu(zy_to_fy_fc2(relu(zy_to_fy_fc1(zy)))), y_hat = fy_to_y_fc2(relu(fy_to_y_fc1(fy)))
+ *                   as mfm_predict_mfn computes them; zl = encoder_l(x) over ALL D columns of x, fl = relu(zl_to_fl_fc2(relu(
+ *                   zl_to_fl_fc1(zl)))); gen_m = mean((decoder_m([fy | fl], T) - x_m)^2) for m in l, a, v
+ *   family 1, M_C   the same label path; gen_m = mean((decoder_m(fy, T) - x_m)^2)
+ * Per row chunk of n rows, on the one stream given: ONE grouped fp32 GEMM for the input projections (the MFN's three LSTMs on
+ * their column ranges, and with gen family 0's encoder_l on all of x); ONE launch of (LSTM, row tile) workgroups -- an MFN LSTM
+ * stores its cell states and last hidden state, encoder_l goes on with its fc1 and the zl -> fl MLP on chip and stores its fl
+ * rows into columns [fy, fy + fl) of the chunk's embedding block [n, fy + fl] in the workspace (zl is never written); the
+ * attention chain of mfm_encode_mfn; the memory recurrence with the label tail of mfm_predict_mfn (y_hat, one loss contribution
+ * per row, the chunk's arrival ticket: the workgroup that draws the last ticket of a chunk adds the contributions in fp64 in a
+ * fixed order and puts the ticket word back to 0), which with gen also stores the row's fy into columns [0, fy) of the
+ * embedding block; with gen ONE launch of (decoder m, row tile) workgroups that all stage the same embedding rows and store
+ * h_t, the decoders' fc1 fused with the squared error, one partial per workgroup, and one workgroup that adds the partials in
+ * fp64 in a fixed order.  No workgroup waits for another, the loss ticket is the only ticket, no float atomics touch a result.
+ * With with_gen 0 encoder_l, its projection and the decoders do not run and their parameters are not read.
+ *   sizes    host, 23: the layout of mfm_predict_zeros_mfn (d_l, d_a, d_v; zl, za, zv; zy; h_l, h_a, h_v; memsize; windowsize; the
+ *            hidden widths of att1, att2, gamma1, gamma2; heads; fl, fa, fv, fy, output_dim, loss_kind).  Entries a family does not
+ *            have may be any positive value: za, zv, fa, fv, and for M_C also zl and fl; heads must be 0 or 1 and is unused.
+ *            loss_kind 0: L1 against float labels y [N, output_dim]; 1: cross entropy against int64 class indices y [N]
+ *   with_gen 1: gen is computed and must not be null; 0: gen must be null, neither encoder_l nor a decoder runs
+ *   params   host array of 66 DEVICE pointers to the module's own tensors (torch layouts, contiguous fp32; the LSTM weights
+ *            16-byte aligned, the rest 4).  0-37, the 38 of mfm_predict_mfn in its offset order: per MFN LSTM l, a, v weight_ih,
+ *            weight_hh, bias_ih, bias_hh (12); weight and bias of att1_fc1, att1_fc2, att2_fc1, att2_fc2, gamma1_fc1, gamma1_fc2,
+ *            gamma2_fc1, gamma2_fc2 (16); of last_to_zy_fc1 (2); of zy_to_fy_fc1, zy_to_fy_fc2, fy_to_y_fc1, fy_to_y_fc2 (8).
+ *            38-55: decoder_l, decoder_a, decoder_v, each lstm weight_ih, weight_hh, bias_ih, bias_hh, fc1 weight, bias (hidden size
+ *            fy + fl for M_A, fy for M_C) -- not read, and may be null, when with_gen is 0.  56-65: encoder_l lstm weight_ih (over
+ *            all D columns), weight_hh, bias_ih, bias_hh, fc1 weight, bias, then zl_to_fl fc1 weight, bias, fc2 weight, bias -- not
+ *            read, and may be null, when with_gen is 0 or family is 1
+ *   x        [T, N, D] time-major and contiguous, D = d_l + d_a + d_v, 4-byte aligned: any contiguous view; read only
+ *   y        labels of the whole split, or null: no label loss (then disc must be null too)
+ *   y_hat    [N, output_dim];  gen  3 floats in the order l, a, v;  disc  1 float, the mean over the WHOLE split whatever the
+ *            chunking; gen and disc are written behind the last chunk
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_predict_ablation_mfn_workspace_floats(T, N, sizes, family, with_gen, with_labels, max_rows) floats, 16-byte
+ *            aligned, contents arbitrary.  With rows = min(N, max_rows), Hp(h) = round_up(h, 16), up4(v) = round_up(v, 4),
+ *            w = fy + fl (M_A) or fy (M_C), in this order:
+ *              rows * T * 4 * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                   the MFN's x-projections
+ *            + rows * T * 4 * Hp(zl)                          (M_A with gen)                  encoder_l's x-projection
+ *            + rows * T * (Hp(h_l) + Hp(h_a) + Hp(h_v))                                       the MFN LSTMs' cell states
+ *            + up4(rows * h_l) + up4(rows * h_a) + up4(rows * h_v)                            their last hidden states
+ *            + up4(rows * T * memsize) + up4(rows * T * gamma1) + up4(rows * T * gamma2)      cHat, the gamma partials
+ *            + up4(rows * w)                                                                  the embedding block
+ *            + 3 * rows * T * Hp(w)                           (with gen)                      the decoders' stored h
+ *            + up4(sum over m of ceil(T * rows / 64) * ceil(d_m / 64))   (with gen)           the squared-error partials
+ *            + 12                                             (with gen)                      six fp64 accumulators
+ *            + up4(rows)                                      (with labels)                   one loss contribution per chunk row
+ *            + 4                                                                              the fp64 running sum, the ticket word, a pad
+ *            It does not grow with N beyond the row cap.  With labels the call clears the ticket word itself (a memset on the
+ *            stream) and leaves it at 0: it is the third of the last four floats.
+ * mfm_predict_ablation_mfn_tile_rows: host only; rows per workgroup of the recurrence launch (tile_rows[0]) and of the decoders'
+ * ([1]; 0 without gen): 1 below six workgroups per CU over a launch of three LSTMs, else 4.  The recurrence launch counts the
+ * MFN's three LSTMs alone, with and without gen: y_hat and disc have the same bits with and without gen.  Results are
+ * bit-identical from call to call; y_hat also across row caps that keep the tile rows (gen and disc then differ in the grouping
+ * of the fp64 sums alone).
+ * Nothing outside the workspace and the three outputs is written.  MFM_ERR_UNSUPPORTED with the size in the error text, nothing
+ * enqueued: what mfm_predict_mfn refuses (an h_dims entry above 128, a windowsize other than 2, attention widths beyond the LDS,
+ * memsize or gamma widths beyond the register-resident memory recurrence, a label tail beyond the LDS); with gen zl > 128 (M_A),
+ * a decoder width fy + fl (M_A) or fy (M_C) above 128, or more LDS than a CU has: compose the granular entries instead.  Bad
+ * arguments (T or N < 1, N >= 2^24, a size below 1, a null pointer, y without disc or disc without y, gen without with_gen or
+ * with_gen without gen, max_rows < 0, a family outside {0, 1}) return MFM_ERR_ARG and enqueue nothing.  Stream-ordered, no host
+ * synchronisation, no allocation; legal inside a stream capture on the one given stream (no forked branches). */
+int64_t mfm_predict_ablation_mfn_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, int32_t family, int32_t with_gen,
+                                                  int32_t with_labels, int64_t max_rows); /* host only; 0 for bad sizes */
+int mfm_predict_ablation_mfn_tile_rows(int64_t N, int32_t family, int32_t with_gen, int64_t max_rows, int32_t* tile_rows /*host, 2*/);
+int mfm_predict_ablation_mfn(int32_t T, int64_t N, const int32_t* sizes /*host, 23*/, int32_t family, int32_t with_gen,
+                             const float* const* params /*host, 66*/, const float* x, const void* y /*null: no label loss*/,
+                             float* workspace, float* y_hat, float* gen /*3, or null*/, float* disc /*1, or null*/, int64_t max_rows,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (the reference has no multi-GPU
  * path): in-place fp32 sum of one flat buffer over all ranks of one node, ONE kernel launch on the
  * caller's stream, no host synchronisation.  Ranks are one process per GPU; every rank owns an uncached

@@ -1,17 +1,19 @@
-"""What `evaluate` and `predict` of a split cost for the ablations M_B and M_D (the per-epoch validation loss and the final
-prediction of the reference's train_mfm_ablation) on the plan-free entry and the way the package offered before (fp32), per call:
+"""What `evaluate` and `predict` of a split cost for the ablations M_A, M_B, M_C and M_D (the per-epoch validation loss and the
+final prediction of the reference's train_mfm_ablation) on the plan-free entry (M_B, M_D: mfm_predict_ablation; M_A, M_C:
+mfm_predict_ablation_mfn) and the way the package offered before (fp32), per call:
 
     ref_eval     the class's eval forward() under no_grad, then F.l1_loss on y_hat
     new_eval     model.evaluate(X, y)
     graph_eval   the same call replayed as one captured graph
-    ref_pred     the eval forward(), then F.l1_loss and (M_B) the three F.mse_loss
+    ref_pred     the eval forward(), then F.l1_loss and (the classes with decoders) the three F.mse_loss
     new_pred     model.predict(X, y)
     graph_pred   the same call replayed as one captured graph
 
 at T = 20 and N = 32 (the training batch), 229 (the MOSI validation split) and 1024, with the peak device memory of either way
 (beyond the parameters and the split, which both need).  It sets no threshold; it records.
 
-    python scripts/bench_ablation.py --out profiles/ablation_times.txt
+    python scripts/bench_ablation.py --classes M_B,M_D --out profiles/ablation_times.txt
+    python scripts/bench_ablation.py --classes M_A,M_C --out profiles/ablation_mfn_times.txt
 
 Every time is a host clock around `--calls` calls that end in a device synchronise, after `--warmup` calls of the same form; the
 forms alternate within a round and the median over the rounds is reported with the spread (max - min of the rounds).
@@ -26,15 +28,18 @@ from factorized_amd import mfm_model as M  # noqa: E402
 
 FORMS = ["ref_eval", "new_eval", "graph_eval", "ref_pred", "new_pred", "graph_pred"]
 BASE = {"new_eval": "ref_eval", "graph_eval": "ref_eval", "new_pred": "ref_pred", "graph_pred": "ref_pred"}
-CLASSES = ["M_B", "M_D"]
+HAS_GEN = {"M_A": True, "M_B": True, "M_C": True, "M_D": False}
 SHAPES = [(32, 20), (229, 20), (1024, 20)]
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--classes", default="M_A,M_B,M_C,M_D", help="comma-separated classes to time")
 ap.add_argument("--out", help="write the record to this file")
 args = ap.parse_args()
+CLASSES = args.classes.split(",")
+assert CLASSES and all(c in HAS_GEN for c in CLASSES), "--classes takes names out of %s" % sorted(HAS_GEN)
 
 need_gpu("bench_ablation.py")
 med_all = {}
@@ -53,7 +58,7 @@ for name in CLASSES:
         def ref_pred():
             with torch.no_grad():
                 out = model.forward(X)[0]
-                gen = torch.stack([F.mse_loss(out[i], real[i]) for i in range(3)]) if name == "M_B" else None
+                gen = torch.stack([F.mse_loss(out[i], real[i]) for i in range(3)]) if HAS_GEN[name] else None
                 return out[3], gen, F.l1_loss(out[3], y)
 
         def new_eval():
@@ -96,4 +101,4 @@ for name in CLASSES:
             m, base = med_all[(name, N, f)], med_all[(name, N, BASE[f])]
             say("%s N=%d T=%d  %s / %s = %.3f   (%.4f vs %.4f ms; spreads %.4f, %.4f)"
                 % (name, N, T, f, BASE[f], m[0] / base[0], m[0], base[0], m[1], base[1]))
-write_out(args.out, "scripts/bench_ablation.py --calls %d --warmup %d --rounds %d: M_B, M_D, fp32" % (args.calls, args.warmup, args.rounds))
+write_out(args.out, "scripts/bench_ablation.py --calls %d --warmup %d --rounds %d: %s, fp32" % (args.calls, args.warmup, args.rounds, ", ".join(CLASSES)))
