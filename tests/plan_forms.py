@@ -57,9 +57,10 @@ WEIGHT_SEED = 77
 BATCH_SEED = 21
 
 
-def klef_case(name):
+def klef_case(name, rates=None):
+    """`rates`: dropout probabilities per site (the *_dropout keys of the config) for the train-mode dropout tests; None: none"""
     over, B, T, want, stepwise = KLEF[name]
-    cfgs = configs.canonical_configs(dropout=False, **over)
+    cfgs = configs.canonical_configs(dropout=rates is not None, **dict(over, **(rates or {})))
     cfg = cfgs[0]
     loss_kind = cfg.get("loss", "l1")
     x, y = synth.make_batch(cfg["input_dims"], B, T, seed=BATCH_SEED, output_dim=cfg["output_dim"],
