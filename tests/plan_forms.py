@@ -15,6 +15,13 @@ What the row kernels' conditions make of the wished-for edges (plan_build.hip, t
  * zl = 40, za = 8, zv = 80 (128 wide, a first stage of exactly 1024 forward items) is therefore the first config PAST the edge:
    "past_edge_resident" (staged kernels, panel in LDS, every LSTM resident); "past_edge" adds the step-by-step encoder (132).
  * the row kernels take four workgroups per row while 4 * B <= compute units, i.e. up to B = 64: one workgroup per row is B = 65.
+
+Group (h), sizes off the multiple of 4: ONE layer whose reduction length K is no multiple of 4 takes the whole plan off the row
+kernels and off the MFMA products (plan_build.hip: the blocks that set mfma and row_path), so the staged quad kernels run their
+scalar branch (latent.hip: (op.K & 3) != 0, or an odd w_off without a panel); the LSTMs with h % 4 != 0 stage their recurrent
+weights through the LDS panel, take the general form of the decoder's step-0 product and get no forward weight images
+(lstm_seq_small_dev.h, lstm_seq_small.hip).  OFF4's LSTMs are 18, 7, 33, 58 wide (encoders, the early-fusion one last) and
+37, 15, 30 (decoders): every residue of h mod 4 in both roles.
 """
 import numpy as np
 
@@ -23,6 +30,8 @@ from factorized_amd import configs, synth
 ROW_EDGE = dict(zl_size=36, za_size=8, zv_size=80, fy_size=8, fl_size=120)
 WIDE = dict(zl_size=156, fl_size=256, za_size=16, fa_size=32)          # test_wide_hidden_sizes_match_oracle's sizes
 NOPANEL = dict(row_path=False, wpanel=0, mfma=False)
+OFF4 = dict(input_dims=[37, 3, 11], zl_size=18, za_size=7, zv_size=33, zy_size=21, fy_size=10, fl_size=27, fa_size=5, fv_size=20)
+QUAD = dict(row_path=False, mfma=False)                               # staged kernels, quad (VALU) products
 
 # id -> (config overrides, B, T, want, stepwise hidden sizes)
 KLEF = {
@@ -46,12 +55,35 @@ KLEF = {
     # (f) the widest output head
     "od64_l1_b5": (dict(output_dim=64), 5, 2, dict(row_path=True, nch=4), []),
     "od64_ce_b5": (dict(output_dim=64, loss="ce"), 5, 2, dict(row_path=True, nch=4), []),
+    # (h) sizes off the multiple of 4: staged quad kernels on their scalar branch, LSTMs of every residue of h mod 4
+    "off4_b5": (OFF4, 5, 3, dict(QUAD, rows_per_wg=4), []),
+    "off4_b65": (OFF4, 65, 2, QUAD, []),                               # past B = 64: role and fold launches out of reach
+    "off4_b257": (OFF4, 257, 2, QUAD, []),                             # the first batch at which every size takes the staged kernels
+    "off4_b513": (OFF4, 513, 2, QUAD, []),                             # the first on the MFMA recurrences (SEQ_MFMA): 1 to 3 pad units
+    "off4_ce_b5": (dict(OFF4, output_dim=7, loss="ce"), 5, 2, dict(QUAD, rows_per_wg=4), []),
+    "off4_h127_b5": (dict(zl_size=127, za_size=9, zv_size=78, zy_size=30, fy_size=10, fl_size=117, fa_size=6, fv_size=61), 5, 2,
+                     NOPANEL, [214]),                                  # encoder and decoder 127 wide: the widest resident; the
+                                                                       # heads on 214 columns leave no room for a panel
+    "off4_nopanel_b65": (dict(zl_size=157, fl_size=255, za_size=17, fa_size=33), 65, 2, NOPANEL, [157, 254, 271]),
 }
-PANEL = ("past_edge_resident_b5", "past_edge_b5", "halved_panel_b65")        # wpanel > 0 is asserted for these
+OFF4_GROUP = tuple(n for n in KLEF if n.startswith("off4_"))                 # none may take the row path or the MFMA products
+PANEL = ("past_edge_resident_b5", "past_edge_b5", "halved_panel_b65",        # wpanel > 0 is asserted for these
+         "off4_b5", "off4_b65", "off4_b257", "off4_b513", "off4_ce_b5")
+SEQ_MFMA = ("off4_b513",)                                                    # every resident LSTM on the fp32 MFMA recurrences
 
-# (g) MFM_KL at the resident limit of the MFN LSTMs: a cStar row of 768 columns, and one wide LSTM beside two of 4
-MFN = {"mfn_h128x3_b5": [128, 128, 128], "mfn_h128_4_4_b5": [128, 4, 4]}
-MFN_B, MFN_T = 5, 3
+# id -> (overrides of test_gpu_mfn_plan.ODD_MFN, widths of the four attention nets, B, T)
+ATT = (36, 20, 28, 44)
+MFN_OFF4 = dict(OFF4, h_dims=[37, 5, 18], memsize=21)
+MFN = {
+    # (g) MFM_KL at the resident limit of the MFN LSTMs: a cStar row of 768 columns, and one wide LSTM beside two of 4
+    "mfn_h128x3_b5": (dict(h_dims=[128, 128, 128]), ATT, 5, 3),
+    "mfn_h128_4_4_b5": (dict(h_dims=[128, 4, 4]), ATT, 5, 3),
+    # (h) MFM_KL and MFM off the multiple of 4: MFN LSTMs, memory and attention nets of every residue too
+    "mfn_off4_b5": (MFN_OFF4, (35, 19, 27, 43), 5, 3),
+    "mfn_off4_b65": (MFN_OFF4, (35, 19, 27, 43), 65, 2),
+}
+MFN_RESIDENT = ("mfn_h128x3_b5", "mfn_h128_4_4_b5")
+MFN_OFF4_GROUP = ("mfn_off4_b5", "mfn_off4_b65")
 
 WEIGHT_SEED = 77
 BATCH_SEED = 21
@@ -70,10 +102,11 @@ def klef_case(name, rates=None):
 
 def mfn_case(name):
     from tests.test_gpu_mfn_plan import ODD_MFN
-    cfgs = configs.canonical_configs(dropout=False, **dict(ODD_MFN, h_dims=MFN[name]))
-    cfgs[1]["shapes"], cfgs[2]["shapes"], cfgs[3]["shapes"], cfgs[4]["shapes"] = 36, 20, 28, 44
-    x, y = synth.make_batch(cfgs[0]["input_dims"], MFN_B, MFN_T, seed=23)
-    return dict(name=name, cfgs=cfgs, cfg=cfgs[0], B=MFN_B, T=MFN_T, x=x, y=y)
+    over, att, B, T = MFN[name]
+    cfgs = configs.canonical_configs(dropout=False, **dict(ODD_MFN, **over))
+    cfgs[1]["shapes"], cfgs[2]["shapes"], cfgs[3]["shapes"], cfgs[4]["shapes"] = att
+    x, y = synth.make_batch(cfgs[0]["input_dims"], B, T, seed=23)
+    return dict(name=name, cfgs=cfgs, cfg=cfgs[0], B=B, T=T, x=x, y=y)
 
 
 def expected_rows(B, rec_size, wpanel, cus, budget=150 * 1024):

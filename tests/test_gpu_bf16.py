@@ -169,9 +169,11 @@ def _emulate_bwd(gates, cs, Wb, T, B, h, dh_ext_all=None, dh_last=None, W0b=None
 
 SEQ_SHAPES = [(8, 5, 1, 3), (8, 5, 32, 20), (24, 7, 33, 4), (32, 300, 32, 20), (80, 20, 17, 6),
               (104, 9, 16, 5), (120, 325, 32, 20), (20, 6, 5, 1), (128, 4, 3, 2), (36, 10, 40, 3), (120, 30, 300, 8)]
+OFF4_ENC = [(18, 7, 5, 3), (37, 11, 33, 4)]          # h off the multiple of 4: partly filled quads of the packed fragments
+OFF4_DEC = [(15, 5, 1), (37, 33, 4)]
 
 
-@pytest.mark.parametrize("h,d,B,T", SEQ_SHAPES)
+@pytest.mark.parametrize("h,d,B,T", SEQ_SHAPES + OFF4_ENC)
 def test_bf16_lstm_seq_encoder_fwd_bwd(eng, h, d, B, T):
     rs = np.random.RandomState(h * 7 + B)
     k = 1.0 / np.sqrt(h)
@@ -205,7 +207,7 @@ def test_bf16_lstm_seq_encoder_fwd_bwd(eng, h, d, B, T):
     assert np.all(dA[:, :, :, h:] == 0.0)
 
 
-@pytest.mark.parametrize("h,B,T", [(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7), (104, 200, 6)])
+@pytest.mark.parametrize("h,B,T", [(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7), (104, 200, 6)] + OFF4_DEC)
 def test_bf16_lstm_seq_decoder_fwd_bwd(eng, h, B, T):
     rs = np.random.RandomState(h + B + T)
     k = 1.0 / np.sqrt(h)
@@ -250,7 +252,7 @@ def b2n(t):
     return t.float().cpu().numpy().astype(np.float64)
 
 
-@pytest.mark.parametrize("h,d,B,T", [(8, 5, 32, 20), (24, 7, 33, 4), (32, 300, 32, 20), (80, 20, 17, 6), (120, 325, 40, 5), (36, 10, 300, 3)])
+@pytest.mark.parametrize("h,d,B,T", [(8, 5, 32, 20), (24, 7, 33, 4), (32, 300, 32, 20), (80, 20, 17, 6), (120, 325, 40, 5), (36, 10, 300, 3)] + OFF4_ENC)
 def test_bf16_resident_encoder_fwd_bwd(eng, h, d, B, T):
     """store_bf16: the x-projection is READ as bf16, activated gates / h are WRITTEN as bf16 (c stays fp32), h_{T-1} also
     as fp32; BPTT reads the bf16 gates and leaves dA as bf16 in place.  Reference: the emulation fed with exactly the
@@ -286,7 +288,7 @@ def test_bf16_resident_encoder_fwd_bwd(eng, h, d, B, T):
     assert np.all(dA[:, :, :, h:] == 0.0)
 
 
-@pytest.mark.parametrize("h,B,T", [(24, 32, 20), (104, 32, 20), (24, 5, 1), (112, 33, 7), (104, 200, 6)])
+@pytest.mark.parametrize("h,B,T", [(24, 32, 20), (104, 32, 20), (24, 5, 1), (112, 33, 7), (104, 200, 6)] + OFF4_DEC)
 def test_bf16_resident_decoder_fwd_bwd(eng, h, B, T):
     """decoders: hs (the fc1 operand) bf16, and in the BPTT the per-step external gradient dh_ext [T,B,Hp] is a bf16
     buffer (written by the fc1-backward GEMM with c_bf16); d h_init stays fp32"""
@@ -447,7 +449,7 @@ def test_bf16_lstm_seq_four_in_one_launch_matches_single_launches(eng):
         assert torch.equal(h0, h1) and torch.equal(c0, c1) and torch.equal(g0, g1)
 
 
-@pytest.mark.parametrize("h,is_dec", [(120, False), (104, True), (24, True), (36, False), (8, False)])
+@pytest.mark.parametrize("h,is_dec", [(120, False), (104, True), (24, True), (36, False), (8, False), (37, True), (18, False)])
 def test_bf16_packed_weight_fragments_equal_in_kernel_gather(eng, h, is_dec):
     """mfm_lstm_pack_bf16 (what the plan runs once per step) must hand the recurrences exactly the fragments they
     would gather themselves: forward and backward results bit-identical with and without the pack."""
@@ -653,6 +655,43 @@ def test_bf16_forward_and_gradients_near_fp32_reference(name, seq_policy):
     assert worst_c[1] > 0.995, worst_c
     # not accidentally the fp32 path
     assert worst_g[1] > 1e-5
+
+
+@pytest.mark.parametrize("seq_policy", ["all-bf16", "default"], indirect=True)
+def test_bf16_step_off_multiple_of_4_near_fp32_oracle(seq_policy):
+    """The whole bf16 step on tests/plan_forms.OFF4 (LSTMs of 18, 7, 33, 58 and 37, 15, 30; B = 33, T = 7), on the bf16
+    recurrences with bf16-resident activations and on the default policy of this batch.  No golden: the fp32 oracle is the
+    reference, as it is for the gradients of every other case.  Loss terms within the 1e-3 of
+    test_bf16_forward_and_gradients_near_fp32_reference, every gradient within its bound 2 cond(n) + 1.5e-2."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from tests.plan_forms import OFF4
+    B, T = 33, 7
+    cfgs = configs.canonical_configs(dropout=False, **OFF4)
+    cfg = cfgs[0]
+    e, w = _bf16_engine(cfgs)
+    xn, yn = synth.make_batch(cfg["input_dims"], B, T, seed=7)
+    x, y = torch.from_numpy(xn), torch.from_numpy(yn)
+    torch.set_num_threads(4)
+    m = O.build("kl_ef", cfgs)
+    O.load_numpy_weights(m, w)
+    m.train()
+    terms = O.loss_terms(m, x, y, cfg, "l1")
+    xd, yd = x.cuda(), y.cuda()
+    out = e.forward(xd, yd, train=True, want_xhat=False)
+    ld = e.loss_dict(out["losses"])
+    worst_l = 0.0
+    for k in ("disc", "gen", "reg", "loss"):
+        ref = float(terms[k].detach())
+        print("off4 bf16 %s %s: got %.9g ref %.9g" % (seq_policy, k, ld[k], ref))
+        worst_l = max(worst_l, abs(ld[k] - ref) / max(abs(ref), 1e-3))
+    cases.report("bf16_loss_terms_rel_off4_b33_t7_%s" % seq_policy, worst_l)
+    assert worst_l < 1e-3, (ld, worst_l)
+    cond, ref = _conditioning(cfgs, w, x, y, cfg, "l1")
+    e.backward(xd, yd, stage=0)
+    worst_g, _, _, worst_ratio = _check_bf16_gradients(e.grad_views(), ref, cond, "off4_b33_t7_%s" % seq_policy)
+    print("off4 bf16 %s worst gradient: %s %.3e, rel / bound %s %.3f" % ((seq_policy,) + worst_g + worst_ratio))
+    assert worst_g[1] > 1e-5          # not accidentally the fp32 path
 
 
 @pytest.mark.parametrize("name", ["klef_b32_t20", "klef_you_b32_t50", "klef_b33_t7"])

@@ -181,7 +181,9 @@ def _pad_gates(g, h, Hp):
 
 
 SEQ_SHAPES = [(8, 5, 1, 3), (8, 5, 32, 20), (24, 7, 33, 4), (32, 300, 32, 20), (80, 20, 17, 6),
-              (104, 9, 16, 5), (120, 325, 32, 20), (20, 6, 5, 1), (128, 4, 3, 2), (36, 10, 40, 3)]
+              (104, 9, 16, 5), (120, 325, 32, 20), (20, 6, 5, 1), (128, 4, 3, 2), (36, 10, 40, 3),
+              # h off the multiple of 4, every residue: recurrent weights staged through the LDS panel, 1 to 3 pad units below Hp
+              (5, 3, 3, 2), (18, 7, 5, 3), (37, 11, 33, 4), (127, 9, 17, 2)]
 
 
 @pytest.fixture(params=["mfma", "small", "small:1", "small:2", "small:4", "stepwise", "small:1:ks8"])
@@ -209,6 +211,10 @@ def seq_path(request, monkeypatch):
 # from an inf / exact-0 exponential) at two shapes only, against the float64 recurrence; bounds stay TOL
 ENC_SCALED = [(32, 20, 5, 3), (128, 4, 3, 2)]
 DEC_SCALED = [(32, 5, 3), (128, 3, 2)]
+
+
+# the last four: h off the multiple of 4 (the general form of the step-0 product d h_init = dA_0 W_ih, no forward weight images)
+DEC_SHAPES = [(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7), (15, 5, 1), (30, 19, 3), (37, 33, 4), (127, 3, 2)]
 
 
 def _with_scale(shapes, scaled):
@@ -258,7 +264,7 @@ def test_lstm_seq_encoder_fwd_bwd(eng, seq_path, h, d, B, T, scale):
     assert rel_err(dW_hh, cell.weight_hh.grad.numpy()) < TOL
 
 
-@pytest.mark.parametrize("h,B,T,scale", _with_scale([(24, 32, 20), (104, 32, 20), (24, 5, 1), (40, 19, 3), (112, 33, 7)], DEC_SCALED))
+@pytest.mark.parametrize("h,B,T,scale", _with_scale(DEC_SHAPES, DEC_SCALED))
 def test_lstm_seq_decoder_fwd_bwd(eng, seq_path, h, B, T, scale):
     rs = np.random.RandomState(h + B + T)
     k = 1.0 / np.sqrt(h)
@@ -307,10 +313,19 @@ def test_lstm_seq_four_in_one_launch(eng, seq_path):
     """The 4 encoders of the canonical model share one launch; results must equal solo launches (to rounding:
     a solo launch of an uncommon size takes the generic 4-row tile whose k-order of partial sums differs
     from the 1-row tile of the shared launch)."""
+    _four_in_one_launch(eng, (32, 8, 80, 120))
+
+
+def test_lstm_seq_four_in_one_launch_off_multiple_of_4(eng, seq_path):
+    """the same with the four encoder widths of tests/plan_forms.OFF4: every residue of h mod 4 in one launch"""
+    _four_in_one_launch(eng, (18, 7, 33, 58))
+
+
+def _four_in_one_launch(eng, widths):
     rs = np.random.RandomState(0)
     T, B = 20, 32
     keep, solo, descs = [], [], []
-    for h in (32, 8, 80, 120):
+    for h in widths:
         Hp = (h + 15) // 16 * 16
         k = 1.0 / np.sqrt(h)
         w = dev(rs.uniform(-k, k, size=(4 * h, h)))
@@ -376,7 +391,8 @@ def test_adam_matches_torch(eng):
 
 
 # ---------------------------------------------------------------------------------- MFN memory recurrence
-@pytest.mark.parametrize("T,B,M,H1,H2", [(20, 32, 64, 128, 128), (7, 5, 24, 40, 72), (1, 3, 64, 128, 128), (9, 19, 100, 100, 60)])
+@pytest.mark.parametrize("T,B,M,H1,H2", [(20, 32, 64, 128, 128), (7, 5, 24, 40, 72), (1, 3, 64, 128, 128), (9, 19, 100, 100, 60),
+                                          (3, 5, 21, 35, 43)])
 def test_mfn_memory_recurrence(eng, T, B, M, H1, H2):
     """mfm_mfn_mem_fwd/bwd against the step-by-step statement of reference mfm_model.py:177-181 in torch
     (float64 on the CPU): last memory and every input / weight gradient."""

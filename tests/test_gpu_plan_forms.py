@@ -8,7 +8,12 @@ tenth of the tolerance on the same inputs (tests/test_plan_forms_host.py).  Tole
 
 (d) of the matrix -- rows halved under a staged panel -- needs no exotic size: 2 * 8 records of the canonical 1180 floats plus
 the 22264-float panel already exceed the 150 KB budget, so every staged plan between B = 65 and 1024 halves 8 -> 4; the entry
-here grows the panel (fl = 176) until they halve twice."""
+here grows the panel (fl = 176) until they halve twice.
+
+(h) of the matrix -- sizes off the multiple of 4 -- holds hidden, latent and factor widths of every residue mod 4: one layer
+with K % 4 != 0 turns the row kernels and the MFMA products off for the whole plan (asserted for the group), and LSTMs with
+h % 4 != 0 take the panel-staged recurrent weights and the decoders' forms without forward weight images.  The same sizes run
+as MFM_KL and MFM plans with MFN LSTMs, memory and attention nets off the multiple of 4 (test_mfn_off4_matches_oracle)."""
 import os
 
 import numpy as np
@@ -66,6 +71,14 @@ def _check_numbers(key, e, m, cs, loss_kind="l1"):
         assert np.max(np.abs(pv[n].cpu().numpy() - p.detach().numpy())) < 0.1 * 3e-3, n
 
 
+def _layer_ks(cfg):
+    """reduction lengths of the latent stack's layers that the sizes of group (h) move: the z -> f MLPs, the classifier, and the
+    heads on the encoders' last hidden states"""
+    z = [cfg["zl_size"], cfg["za_size"], cfg["zv_size"], cfg["zy_size"]]
+    f = [cfg["fl_size"], cfg["fa_size"], cfg["fv_size"], cfg["fy_size"]]
+    return z + f + [sum(z[:3])]
+
+
 @pytest.mark.parametrize("name", list(PF.KLEF))
 def test_klef_form_matches_oracle(name):
     if not torch.cuda.is_available():
@@ -84,6 +97,13 @@ def test_klef_form_matches_oracle(name):
         assert form[k] == v, (k, form[k], v, form)
     if name in PF.PANEL:
         assert form["wpanel"] > 0, form
+    if name in PF.OFF4_GROUP:
+        # what the group is there for: no row path, no MFMA products, and at least one layer the quad kernels must take scalar
+        assert not form["row_path"] and not form["mfma"], form
+        assert any(k % 4 for k in _layer_ks(cs["cfg"])), name
+        assert any(s["h"] % 4 for s in seq if not s["stepwise"]), seq
+    if name in PF.OFF4_GROUP:
+        assert all(s["mfma"] == (name in PF.SEQ_MFMA) for s in seq if not s["stepwise"]), seq
     assert sorted(s["h"] for s in seq if s["stepwise"]) == sorted(cs["stepwise"]), seq
     assert len(seq) == 7 and all(s["stepwise"] == (s["h"] > 128) for s in seq)
     if "nch" in want:
@@ -120,7 +140,7 @@ def test_output_dim_65_is_refused_at_plan_creation():
     assert torch.equal(e.params, before) and not e.grads.any()
 
 
-@pytest.mark.parametrize("name", list(PF.MFN))
+@pytest.mark.parametrize("name", list(PF.MFN_RESIDENT))
 def test_mfn_resident_limit_matches_oracle(name):
     """MFM_KL with MFN LSTMs at the resident limit (h = 128): cStar rows of 768 columns (twelve per lane in the attention
     softmax) and one 128-wide LSTM beside two of 4, through test_gpu_mfn_plan's engine / oracle helpers."""
@@ -128,7 +148,7 @@ def test_mfn_resident_limit_matches_oracle(name):
         pytest.skip("no GPU")
     from tests.test_gpu_mfn_plan import _engine, _oracle
     cs = PF.mfn_case(name)
-    B, T, hd = cs["B"], cs["T"], PF.MFN[name]
+    B, T, hd = cs["B"], cs["T"], cs["cfg"]["h_dims"]
     e, w = _engine(cs["cfgs"], "kl")
     form, seq = e.latent_form(T, B), e.seq_form(T, B)
     print(name, form, [(s["h"], s["stepwise"]) for s in seq])
@@ -137,3 +157,31 @@ def test_mfn_resident_limit_matches_oracle(name):
     assert form["row_path"] and form["nch"] == (4 if 4 * B <= _lib.lib().mfm_device_cus() else 1), form
     assert e.mfn_buffers(T, B)["cstar"].shape == (T * B, 2 * sum(hd))
     _check_numbers(name, e, _oracle("kl", cs["cfgs"], w), cs)
+
+
+@pytest.mark.parametrize("variant", ["kl", "mmd"])
+@pytest.mark.parametrize("name", list(PF.MFN_OFF4_GROUP))
+def test_mfn_off4_matches_oracle(name, variant):
+    """MFM_KL and MFM with every width off the multiple of 4: OFF4's latents and factors, MFN LSTMs of 37, 5 and 18, a memory of 21
+    and attention nets of 35, 19, 27 and 43 (mfn_att.hip, mfn_mem.hip and the staged latent kernels' scalar branch in one plan).
+    MFM's Gaussian sample is injected on both sides, as test_gpu_mfn_plan does."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from tests.test_gpu_mfn_plan import _engine, _oracle
+    cs = PF.mfn_case(name)
+    cfg, B, T = cs["cfg"], cs["B"], cs["T"]
+    e, w = _engine(cs["cfgs"], variant)
+    gauss = None
+    if variant == "mmd":
+        gl = cfg["zl_size"] + cfg["za_size"] + cfg["zv_size"] + cfg["zy_size"]
+        gauss = torch.from_numpy(np.random.RandomState(5).normal(size=(B, gl)).astype(np.float32))
+        e.gauss = gauss.cuda()
+    form, seq = e.latent_form(T, B), e.seq_form(T, B)
+    print(name, variant, form, [(s["h"], s["stepwise"]) for s in seq])
+    assert not form["row_path"] and not form["mfma"] and form["wpanel"] > 0, form
+    assert len(seq) == 9 and [s["h"] for s in seq] == [18, 7, 33, 37, 5, 18, 37, 15, 30], seq
+    assert not any(s["stepwise"] for s in seq), seq
+    bufs = e.mfn_buffers(T, B)
+    assert bufs["cstar"].shape == (T * B, 2 * sum(cfg["h_dims"])) and bufs["chat"].shape == (T * B, 21)
+    assert (bufs["h1"].shape[1], bufs["h2"].shape[1]) == (35, 19)
+    _check_numbers("%s_%s" % (name, variant), e, _oracle(variant, cs["cfgs"], w, gauss), cs)

@@ -53,4 +53,6 @@ def test_klef_oracle_has_headroom(name):
 
 @pytest.mark.parametrize("name", list(PF.MFN))
 def test_mfn_oracle_has_headroom(name):
+    """MFM_KL only: the MFM plans of the same sizes (tests/test_gpu_plan_forms.py) draw their Gaussian sample per run, so the
+    fp32 and the float64 oracle would not see the same one"""
     _headroom("kl", PF.mfn_case(name), 1234)          # the weights of test_gpu_mfn_plan._engine
