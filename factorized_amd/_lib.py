@@ -246,6 +246,12 @@ _SIGS = {
     "mfm_predict_ablation": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int64, C.c_void_p]),
+    "mfm_train_ablation_d_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
+    "mfm_train_ablation_d_mask_offset": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int64]),
+    "mfm_train_ablation_d_tile_rows": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
+    "mfm_train_ablation_d": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                       C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mfm_predict_ablation_mfn_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                                               C.c_int32, C.c_int64]),
     "mfm_predict_ablation_mfn_tile_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),

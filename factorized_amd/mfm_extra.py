@@ -9,7 +9,9 @@ Same constructors (six dicts), sub-module / parameter names (`state_dict()` keys
 tests/test_module_surface.py) and forward contracts.  They are re-wirings of the blocks `mfm_model.py` already runs on
 libmfm_hip.so -- `encoderLSTM`, `decoderLSTM`, `MFN`, `HipLinear`, `loss_MMD` -- so they are COMPOSED from those
 autograd ops here, with independent LSTMs / Linears sharing launches (`seq_group`, `decoder_group`, `linear_group`).
-There is no fused one-call plan for these classes ("pure re-wiring of existing ops").
+There is no fused one-call plan for these classes ("pure re-wiring of existing ops"); the one training
+entry so far is `M_D.loss_and_grad`: the label loss and every parameter's gradient as one call of `mfm_train_ablation_d`
+(csrc/train_ablation.hip), without autograd.
 
 `MFM_missing.impute` is the exception: surrogate inference (a missing modality and the label from the other two) as one call
 of the library, `mfm_impute_missing` (csrc/impute.hip).  So is `predict_missing` of MFM_missing, seq2seq and basic_missing: the
@@ -99,7 +101,56 @@ class _AblationProtocol:
     def __getstate__(self):
         state = dict(self.__dict__)
         state.pop("_ablation_bufs", None)        # (device workspaces and native pointer tables: rebuilt on the next call)
+        state.pop("_train_bufs", None)           # (those of M_D.loss_and_grad, and which of them the latest call used)
+        state.pop("_train_last", None)
         return state
+
+    def _ablation_check_x(self, name, x, dev, max_rows, cuda):
+        """the checks of a split x [T, N, D] and a row cap against a model on `dev`; cuda: x must be a device tensor"""
+        D = self.d_l + self.d_a + self.d_v
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise _lib.MfmError("%s: x must be a %stensor [T, N, %d]; got %s" % (name, "CUDA " if cuda else "", D, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+        if cuda:
+            M._require_cuda(x, name)
+        if x.device != dev:
+            raise _lib.MfmError("%s: x lives on %s, the model on %s" % (name, x.device, dev))
+        if x.shape[2] != D:
+            raise _lib.MfmError("%s: x has %d features per time step, the model's input_dims sum to %d" % (name, x.shape[2], D))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise _lib.MfmError("%s: empty split %s" % (name, tuple(x.shape)))
+        if max_rows is not None and int(max_rows) < 1:
+            raise _lib.MfmError("%s: max_rows must be at least 1, not %r" % (name, max_rows))
+
+    def _entry_cache(self, attr, key, who):
+        """(the buffer cache `attr` of an entry, its state for `key` or None); MfmUnsupported where a refusal is remembered for it"""
+        cache = self.__dict__.setdefault(attr, {})
+        st = cache.get(key)
+        if st is False:
+            raise _lib.MfmUnsupported("%s refused this shape" % who)
+        return cache, st
+
+    def _entry_refused(self, cache, key, attr, wide):
+        """remember a refusal: `wide` (what a property of the model refuses, not empty) joins the set `attr` on the model; else the
+        refusal belongs to this shape alone and no buffers are kept for it"""
+        if wide:
+            self.__dict__.setdefault(attr, set()).update(wide)
+        else:
+            cache[key] = False
+
+    def _ablation_labels(self, name, y, N, loss, dev):
+        """the labels of a split of N rows as the entries take them (float32 [N, output_dim] or int64 [N], contiguous on dev)"""
+        od = self._ablation_sizes()[self._ABL_OD]
+        if not torch.is_tensor(y) or y.device != dev:
+            raise _lib.MfmError("%s: labels must be a tensor on %s; got %s" % (name, dev, y.device if torch.is_tensor(y) else type(y)))
+        if loss == "l1":
+            if not y.is_floating_point() or tuple(y.shape) != (N, od):
+                raise _lib.MfmError("%s: loss 'l1' takes float labels [%d, %d]; got %s %s" % (name, N, od, y.dtype, tuple(y.shape)))
+            if not (y.dtype == torch.float32 and y.is_contiguous()):
+                y = y.contiguous().float()
+            return y
+        if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+            raise _lib.MfmError("%s: loss 'ce' takes int64 class indices [%d]; got %s %s" % (name, N, y.dtype, tuple(y.shape)))
+        return y.contiguous()
 
     def _ablation_sizes(self):
         """zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim, read off the parameters; 1 for what the class does not have"""
@@ -153,11 +204,8 @@ class _AblationProtocol:
         T, N, _ = x.shape
         L = _lib.lib()
         name = type(self).__name__
-        cache = self.__dict__.setdefault("_ablation_bufs", {})
         key = (T, N, gen, y is not None, cap, x.device)
-        st = cache.get(key)
-        if st is False:
-            raise _lib.MfmUnsupported("%s.predict: %s refused this shape" % (name, self._ABL_ENTRY))
+        cache, st = self._entry_cache("_ablation_bufs", key, "%s.predict: %s" % (name, self._ABL_ENTRY))
         if st is None:
             sz = self._ablation_sizes()
             sizes = (C.c_int32 * len(sz))(*sz)
@@ -177,11 +225,7 @@ class _AblationProtocol:
             # a hidden size beyond the on-chip recurrence is a property of the model: remembered (`_ablation_wide`).  The LDS
             # limit also depends on the tile rows, hence on N and max_rows: that refusal is remembered for this shape alone (no
             # buffers are kept for it)
-            wide = self._ablation_wide(self._ablation_sizes(), gen)
-            if wide:
-                self.__dict__.setdefault("_ablation_refused", set()).update(wide)
-            else:
-                cache[key] = False
+            self._entry_refused(cache, key, "_ablation_refused", self._ablation_wide(self._ablation_sizes(), gen))
             raise _lib.MfmUnsupported("%s.predict: %s" % (name, L.mfm_last_error().decode()))
         _lib.check(rc, self._ABL_ENTRY)
         cache[key] = st
@@ -194,32 +238,10 @@ class _AblationProtocol:
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise _lib.MfmError("%s: parameters are on %s; move the model to the GPU first (no CPU fallback)" % (name, dev))
-        D = self.d_l + self.d_a + self.d_v
-        if not torch.is_tensor(x) or x.dim() != 3:
-            raise _lib.MfmError("%s: x must be a CUDA tensor [T, N, %d]; got %s" % (name, D, tuple(x.shape) if torch.is_tensor(x) else type(x)))
-        M._require_cuda(x, name)
-        if x.device != dev:
-            raise _lib.MfmError("%s: x lives on %s, the model on %s" % (name, x.device, dev))
-        if x.shape[2] != D:
-            raise _lib.MfmError("%s: x has %d features per time step, the model's input_dims sum to %d" % (name, x.shape[2], D))
-        if x.shape[0] < 1 or x.shape[1] < 1:
-            raise _lib.MfmError("%s: empty split %s" % (name, tuple(x.shape)))
-        if max_rows is not None and int(max_rows) < 1:
-            raise _lib.MfmError("%s: max_rows must be at least 1, not %r" % (name, max_rows))
+        self._ablation_check_x(name, x, dev, max_rows, cuda=True)
         N = x.shape[1]
         if y is not None:
-            od = self._ablation_sizes()[self._ABL_OD]
-            if not torch.is_tensor(y) or y.device != dev:
-                raise _lib.MfmError("%s: labels must be a tensor on %s; got %s" % (name, dev, y.device if torch.is_tensor(y) else type(y)))
-            if loss == "l1":
-                if not y.is_floating_point() or tuple(y.shape) != (N, od):
-                    raise _lib.MfmError("%s: loss 'l1' takes float labels [%d, %d]; got %s %s" % (name, N, od, y.dtype, tuple(y.shape)))
-                if not (y.dtype == torch.float32 and y.is_contiguous()):
-                    y = y.contiguous().float()
-            else:
-                if y.dtype != torch.int64 or tuple(y.shape) != (N,):
-                    raise _lib.MfmError("%s: loss 'ce' takes int64 class indices [%d]; got %s %s" % (name, N, y.dtype, tuple(y.shape)))
-                y = y.contiguous()
+            y = self._ablation_labels(name, y, N, loss, dev)
         cap = self.ABLATION_MAX_ROWS if max_rows is None else int(max_rows)
         if not (x.dtype == torch.float32 and x.is_contiguous()):
             x = x.contiguous().float()
@@ -483,6 +505,171 @@ class M_D(_AblationProtocol, _Base):
 
     def _ablation_head(self):
         return _wb(self._modules["fs_to_y"])
+
+    # ------------------------------------------------------------------ one training step without the optimizer
+    TRAIN_MAX_ROWS = 1024        # default row cap of loss_and_grad(): the BPTT record of at most this many rows is alive at once
+    dropout_seed = None          # seed of loss_and_grad()'s dropout masks; None: torch.initial_seed() at the first call
+    last_y_hat = None            # y_hat [N, output_dim] of the latest loss_and_grad() (the call's own buffer on the one-call path)
+
+    def _train_params(self):
+        """the 32 tensors of mfm_train_ablation_d's parameter table (include/mfm_hip.h)"""
+        mods = self._modules
+        out = []
+        for m in self._MODS:
+            out += _lstm_fc(mods["encoder_" + m]) + _wb(mods["z%s_to_f%s_fc1" % (m, m)]) + _wb(mods["z%s_to_f%s_fc2" % (m, m)])
+        return out + _wb(mods["fs_to_y"])
+
+    def _train_drop(self):
+        """the dropout probability of the three z -> f sites as the modules stand (0: eval mode, or p = 0)"""
+        drops = [self._modules["z%s_to_f%s_dropout" % (m, m)] for m in self._MODS]
+        return [float(d.p) if d.training else 0.0 for d in drops]
+
+    def _forward_torch(self, x):
+        """y_hat of forward() in plain torch operations on the module's own parameters: the path of a model that is not on the GPU"""
+        F = torch.nn.functional
+        mods = self._modules
+        fs = []
+        for m, xm in zip(self._MODS, self._split(x.float())):
+            enc = mods["encoder_" + m]
+            cell = enc._modules["lstm"]
+            h = c = xm.new_zeros(xm.shape[1], cell.hidden_size)
+            for t in range(xm.shape[0]):
+                h, c = cell(xm[t], (h, c))
+            z = F.linear(h, enc.fc1.weight, enc.fc1.bias)
+            tag = "z%s_to_f%s" % (m, m)
+            fc1, fc2 = mods[tag + "_fc1"], mods[tag + "_fc2"]
+            h1 = mods[tag + "_dropout"](torch.relu(F.linear(z, fc1.weight, fc1.bias)))
+            fs.append(torch.relu(F.linear(h1, fc2.weight, fc2.bias)))
+        return F.linear(torch.cat(fs, dim=1), self.fs_to_y.weight, self.fs_to_y.bias)
+
+    def _train_composed(self, x, y, loss):
+        F = torch.nn.functional
+        with torch.enable_grad():
+            y_hat = self.forward(x)[0][3] if x.is_cuda else self._forward_torch(x)
+            out = F.l1_loss(y_hat, y) if loss == "l1" else F.cross_entropy(y_hat, y)
+            out.backward()
+        self.last_y_hat = y_hat.detach()
+        self._train_last = None
+        return out.detach()
+
+    def _train_fused(self, x, y, params, loss_kind, cap):
+        """mfm_train_ablation_d on the module's own tensors and their .grad; MfmUnsupported when the entry refuses the sizes, or
+        a gradient that is there already is not a contiguous float32 tensor on x's device"""
+        T, N, _ = x.shape
+        L = _lib.lib()
+        dev = x.device
+        key = (T, N, cap, dev)
+        cache, st = self._entry_cache("_train_bufs", key, "M_D.loss_and_grad: mfm_train_ablation_d")
+        sz = self._ablation_sizes()
+        if st is None:
+            sizes = (C.c_int32 * 12)(*sz)
+            nws = int(L.mfm_train_ablation_d_workspace_floats(T, N, sizes, cap))
+            f32 = dict(dtype=torch.float32, device=dev)
+            st = (torch.empty(max(nws, 4), **f32), torch.empty((N, sz[11]), **f32), torch.empty((), **f32), sizes,
+                  (C.c_void_p * 32)(), (C.c_void_p * 32)(), (C.c_float * 3)(), torch.zeros(1, dtype=torch.int64, device=dev))
+        ws, y_hat, out, sizes, pptr, gptr, pdrop, tick = st
+        # .grad as torch keeps it: left alone where requires_grad is false, created where it is None, added to where it exists
+        live = [p for p in params if p.requires_grad]
+        have = [p.grad is not None for p in live]
+        if not all(g is None or (g.dtype == torch.float32 and g.device == dev and g.is_contiguous() and g.shape == p.shape)
+                   for p, g in ((p, p.grad) for p in live)):
+            raise _lib.MfmUnsupported("M_D.loss_and_grad: a .grad is not a contiguous float32 tensor on %s" % dev)
+        accumulate = any(have)
+        made = []
+        for p in live:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p) if accumulate else torch.empty_like(p)
+                made.append(p)
+        for i, p in enumerate(params):
+            pptr[i] = p.data_ptr()
+            gptr[i] = p.grad.data_ptr() if p.requires_grad else None
+        drop = self._train_drop()
+        pdrop[:] = drop
+        train = any(p > 0.0 for p in drop)
+        if self.dropout_seed is None:
+            self.dropout_seed = torch.initial_seed() & 0xFFFFFFFFFFFF
+        call = self.__dict__.get("_train_calls", 0)
+        tickp = None
+        if train and torch.cuda.is_current_stream_capturing():
+            # a replayed graph re-runs this call with the same host seed and call number: add a device word that the graph
+            # itself advances, so every replay draws new masks
+            tick.add_(0x1E3779B97F4A7C15)
+            tickp = C.c_void_p(tick.data_ptr())
+        rc = L.mfm_train_ablation_d(T, N, sizes, loss_kind, int(train), pdrop, int(self.dropout_seed), call, tickp, pptr, gptr,
+                                    int(accumulate), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                    C.c_void_p(y_hat.data_ptr()), C.c_void_p(out.data_ptr()), cap,
+                                    C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index)))
+        if rc != 0:
+            for p in made:
+                p.grad = None
+        if rc == _lib.MFM_ERR_UNSUPPORTED:
+            # a z or f size beyond the on-chip bound is a property of the model: remembered for every call; else for this shape
+            self._entry_refused(cache, key, "_train_refused", ("sizes",) if max(sz[0:3] + sz[4:7]) > self.MAX_RESIDENT_H else ())
+            raise _lib.MfmUnsupported("M_D.loss_and_grad: %s" % L.mfm_last_error().decode())
+        _lib.check(rc, "mfm_train_ablation_d")
+        self._train_calls = call + 1
+        cache[key] = st
+        self._train_last = key
+        self.last_y_hat = y_hat
+        return out
+
+    def last_dropout_masks(self):
+        """the dropout scales of the latest loss_and_grad(), read out of its workspace at the offset the library names
+        (mfm_train_ablation_d_mask_offset): per site l, a, v a view [n, f_m] of 0 / 1 / (1 - p), n the rows of the call's last
+        chunk -- None for a site that drew nothing (eval mode or p = 0).  None altogether when there is nothing to read: before
+        the first call, after a call that took the composed path, or once the buffers were dropped (a pickled copy)"""
+        key = self.__dict__.get("_train_last")
+        st = self.__dict__.get("_train_bufs", {}).get(key) if key is not None else None
+        if not st:
+            return None
+        T, N, cap, _ = key
+        ws, sizes, pdrop = st[0], st[3], st[6]
+        rows = min(N, cap) if cap > 0 else N
+        off = int(_lib.lib().mfm_train_ablation_d_mask_offset(T, N, sizes, cap))
+        n = N - (N - 1) // rows * rows
+        out = []
+        for f, p in zip(sizes[4:7], pdrop):
+            out.append(ws[off:off + n * f].view(n, f) if p > 0.0 else None)
+            off += rows * f
+        return out
+
+    def loss_and_grad(self, x, y, *, loss="l1", max_rows=None):
+        """x [T, N, D] (columns d_l | d_a | d_v), labels y -> the mean label loss of y_hat = forward(x)[0][3] as a 0-dim float
+        tensor on the model's device, with the gradient of that loss left in every parameter's .grad: the `train` block of the
+        reference's train_mfm_ablation minus the optimizer, in one call of the library (mfm_train_ablation_d,
+        csrc/train_ablation.hip: five launches per row chunk, no autograd graph).  loss="l1" takes float labels
+        [N, output_dim], loss="ce" int64 class indices [N].  .grad as torch keeps it: created where it is None, added to where it
+        exists (zero_grad(set_to_none=...) and accumulation over several calls both work), left alone where requires_grad is
+        false.  Any optimizer then steps.  `self.training` is honoured: in train mode the three dropout sites draw the library's
+        counter-based masks from `dropout_seed` (per model; None: torch.initial_seed() at the first call) and the number of
+        calls so far -- `last_dropout_masks()` reads them back --, in eval mode dropout is the identity.  `last_y_hat` holds y_hat.
+
+        The split is walked in chunks of at most `max_rows` rows (default TRAIN_MAX_ROWS) whose gradients add up in chunk order.
+        Workspace, y_hat and the loss are kept on the module (outside state_dict(), dropped when pickled) per (T, N, max_rows,
+        device) and REUSED: after the first call for a shape nothing is allocated (but a .grad that is None) and nothing
+        synchronises -- legal inside a stream capture --, and the returned tensor is overwritten by the next call for the same
+        shape.  Loss and gradients are bit-identical from call to call.  Sizes the entry refuses (a z or f size above 128), a
+        model, input or .grad that is not contiguous float32 on the GPU (a CPU model among them) take the composed path
+        instead -- forward() (plain torch on the CPU), the torch loss, .backward() -- with the same result; inside a stream
+        capture that raises MfmError.  Argument errors (shapes, devices, labels, max_rows < 1: MfmError; unknown `loss`:
+        ValueError) are raised before anything is launched."""
+        name = "M_D.loss_and_grad"
+        if loss not in self._LOSS:
+            raise ValueError("%s: loss must be 'l1' or 'ce', not %r" % (name, loss))
+        dev = next(self.parameters()).device
+        self._ablation_check_x(name, x, dev, max_rows, cuda=False)
+        y = self._ablation_labels(name, y, x.shape[1], loss, dev)
+        cap = self.TRAIN_MAX_ROWS if max_rows is None else int(max_rows)
+        if dev.type == "cuda" and x.dtype == torch.float32 and not self.__dict__.get("_train_refused", False):
+            params = self._train_params()
+            if all(p.dtype == torch.float32 and p.device == dev and p.is_contiguous() for p in params):
+                try:
+                    return self._train_fused(x.contiguous(), y, params, self._LOSS[loss], cap)
+                except _lib.MfmUnsupported:
+                    pass
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _lib.MfmError("%s: this model, input or shape takes the composed autograd path, which cannot run inside a stream capture" % name)
+        return self._train_composed(x, y, loss)
 
 
 Imputed = collections.namedtuple("Imputed", ["x_hat", "y_hat"])

@@ -178,7 +178,14 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if self._fallback is None or self._fallback_ids != ids:
             old = self._fallback
             groups = [dict(params=ps, **{k: g[k] for k in self._hyper}) for g, ps in rest]
-            self._fallback = self._inner_cls(groups, foreach=self.defaults["foreach"])
+            # (capturable=True reaches the inner optimizer of device tensors too: a composed module's step -- M_D.loss_and_grad
+            # then step() -- can be captured into a graph like a fused model's.  Its fresh state then keeps the step counts on
+            # the device.  A "fallback" state saved by a plain optimizer still loads: torch's load_state_dict takes the saved
+            # groups, capturable=False among them, so such a state steps eagerly as it did and cannot be captured)
+            flags = {}
+            if self.defaults.get("capturable") and all(p.is_cuda for _, ps in rest for p in ps):
+                flags["capturable"] = True
+            self._fallback = self._inner_cls(groups, foreach=self.defaults["foreach"], **flags)
             self._fallback._mfm_inner = True        # (steps on behalf of this class: not a foreign optimizer)
             self._fallback_ids = ids
             self._inner_rebuilt(rest, old)

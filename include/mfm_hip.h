@@ -1000,6 +1000,71 @@ int mfm_predict_ablation(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * One training step of the ablation M_D without the optimizer (csrc/train_ablation.hip; the `train` block of the reference's
+ * train_mfm_ablation, reference mfm_mosi.py:640-767, for mfm_model.py:389-467): the mean label loss of the split and its gradient
+ * with respect to all 32 parameter tensors, fp32 throughout, no MfmPlan.  The class is purely discriminative:
+ *   z_m = encoder_m.fc1(h_T,m), f_m = relu(z<m>_to_f<m>_fc2(drop_m(relu(z<m>_to_f<m>_fc1(z_m))))) for m in l, a, v;
+ *   y_hat = fs_to_y([f_l | f_a | f_v]); loss = L1 or cross entropy of y_hat, the mean over all N rows
+ * Per row chunk, in this order on the one given stream: (1) the three input projections x_m W_ih^T + b_ih + b_hh as one grouped
+ * fp32 GEMM into gate records; (2) one forward recurrence launch for the three encoders, the BPTT record (gates, hs, cs) kept;
+ * (3) one launch of the head kernel over row tiles: a workgroup goes from h_T through the ten linears to y_hat (stored) and the
+ * row's loss contribution and straight back to d h_T,m (stored), and stores ONE partial of the ten weight / bias gradients; the
+ * workgroup that draws the launch's last arrival ticket adds the partials tile by tile in a fixed order and stores or adds the
+ * gradients, adds the loss contributions in fp64 in a fixed order onto the running sum, writes the mean behind the last chunk and
+ * puts the ticket word back to 0 -- no float atomic touches a result, no workgroup waits for another; (4) one BPTT launch for
+ * the three encoders with dh_ext = the stored d h_T,m; (5) one grouped GEMM, unsplit along K, for dW_ih, dW_hh (skipped when
+ * T == 1: nothing feeds W_hh, and a stored gradient is cleared with a memset node instead) and both bias gradients of the three
+ * encoders.  dx is not computed.  A chunk of a longer split (max_rows < N) is first copied out of x as one [T n, D] matrix (a
+ * 2-D copy node).  Loss, y_hat and gradients are bit-identical from call to call for a given (T, N, max_rows).
+ *   sizes    host, 12, the layout of mfm_predict_ablation: zl, za, zv, zy, fl, fa, fv, fy, d_l, d_a, d_v, output_dim; zy and fy are
+ *            unused and may be any positive value.  x [T, N, D] time-major and contiguous (4-byte aligned: any contiguous view)
+ *   loss_kind 0: L1 against float labels y [N, output_dim]; 1: cross entropy against int64 class indices y [N] (8-byte aligned).
+ *            The indices must lie in [0, output_dim): the labels are device data and are not checked; an index outside the
+ *            range is clamped to the nearest class (so that nothing outside the row is read) and loss and gradients are then
+ *            those of that class, without an error
+ *   train, p_drop, seed, call, tick  dropout of the three z -> f MLPs: with train != 0 and p_drop[m] > 0 (host, 3 floats in [0, 1))
+ *            element (row, column) of site m is kept when rng_uniform(seed + 0x9E3779B97F4A7C15 * call + *tick, (m << 40) + row *
+ *            f_m + column) >= p_drop[m] (csrc/common.h; row counts through the WHOLE split) and scaled by 1 / (1 - p_drop[m]); tick
+ *            is an optional device word (8-byte aligned; null: 0) that a captured graph can advance between replays.  With
+ *            train == 0 or p_drop[m] == 0 the site is the identity and draws nothing
+ *   params   host array of 32 DEVICE pointers to the module's own tensors (torch layouts, contiguous fp32; the LSTM weights
+ *            16-byte aligned, the rest 4), per modality m = l, a, v at 10 * m: 0-3 encoder_m.lstm weight_ih, weight_hh, bias_ih,
+ *            bias_hh; 4-5 encoder_m.fc1 weight, bias; 6-9 z<m>_to_f<m> fc1 weight, bias, fc2 weight, bias.  Then 30-31: fs_to_y
+ *            weight, bias
+ *   grads    host array of 32 DEVICE pointers (4-byte aligned) in the order of params, each the size of its parameter; null: the
+ *            parameter is frozen, its products are skipped and nothing is written for it
+ *   accumulate 0: the gradients are stored; 1: added to what grads holds.  Either way the chunks of one call add up in chunk order
+ *   y_hat    [N, output_dim];  loss  1 float, written behind the last chunk
+ *   max_rows row cap: chunks of at most max_rows rows (0: one chunk) that share the workspace
+ *   workspace mfm_train_ablation_d_workspace_floats(T, N, sizes, max_rows) floats, 16-byte aligned, contents arbitrary; with rows =
+ *            min(N, max_rows), Hp(h) = round_up(h, 16) and up4 = round_up(., 4), in this order: with rows < N up4(T * rows * D) for
+ *            the chunk's copy of x; rows * T * 4 * (Hp(zl) + Hp(za) + Hp(zv)) gate records, each LSTM's [T, n, 4, Hp] for a chunk
+ *            of n rows; rows * T * (Hp(zl) + Hp(za) + Hp(zv)) hidden states and as many cell states; up4(rows * zl) + up4(rows *
+ *            za) + up4(rows * zv) for d h_T; the DROPOUT SCALES of the last chunk, up4(rows * (fl + fa + fv)): site m begins at
+ *            rows * (the f sizes in front of it) and holds [n, f_m] row-major floats, 0 or 1 / (1 - p) -- written for the sites
+ *            that draw, left alone otherwise; one partial of round_up(sum over the ten linears of out * in + out, 4) floats per
+ *            workgroup, ceil(rows / tile rows) of them; up4(rows) loss contributions; up4(rows * T) ones (the bias gradients'
+ *            right-hand side); and 4 floats for the fp64 running sum of the loss and the ticket word
+ * mfm_train_ablation_d_mask_offset: host only; the first float of the dropout scales in that workspace (0 for bad sizes).
+ * mfm_train_ablation_d_tile_rows: host only; rows per workgroup of the head kernel (tile_rows[0]), chosen as
+ * mfm_predict_ablation_tile_rows chooses them: 1 while three workgroups per row stay below six per CU, else 4.
+ * Nothing outside the workspace, y_hat, loss and the non-null gradients is written.  Any N >= 1 (< 2^24), T >= 1.  Sizes that do
+ * not fit on chip -- a z_m or an f_m above 128 (MFM_SEQ_MAX_RESIDENT_H of the recurrences and the head's bound), or a head row
+ * whose output_dim does not fit the LDS beside the rest -- return MFM_ERR_UNSUPPORTED with the size in the error text and enqueue
+ * nothing: compose the granular entries instead.  Bad arguments (T or N < 1, N >= 2^24, a null pointer other than tick and the
+ * entries of grads, a misaligned one, max_rows < 0, an unknown loss_kind, accumulate or train outside {0, 1}, a p_drop outside
+ * [0, 1)) return MFM_ERR_ARG and enqueue nothing.  Stream-ordered, no host synchronisation, no allocation; legal inside a stream
+ * capture on the one given stream (no forked branches). */
+int64_t mfm_train_ablation_d_workspace_floats(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int64_t max_rows); /* host only; 0 for bad sizes */
+int64_t mfm_train_ablation_d_mask_offset(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int64_t max_rows); /* host only */
+int mfm_train_ablation_d_tile_rows(int64_t N, int64_t max_rows, int32_t* tile_rows /*host, 1*/);
+int mfm_train_ablation_d(int32_t T, int64_t N, const int32_t* sizes /*host, 12*/, int32_t loss_kind, int32_t train,
+                         const float* p_drop /*host, 3*/, uint64_t seed, uint64_t call, const uint64_t* tick /*device, or null*/,
+                         const float* const* params /*host, 32*/, float* const* grads /*host, 32; null entries: frozen*/,
+                         int32_t accumulate, const float* x, const void* y, float* workspace, float* y_hat, float* loss,
+                         int64_t max_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction of the ablations M_A and M_C (csrc/ablation_mfn.hip; the same `evaluate` / `predict` blocks of the reference's
  * train_mfm_ablation, reference mfm_model.py:201-266 and :337-387): the two ablations whose label factor comes from the Memory
  * Fusion Network, under the contract of mfm_predict_ablation -- fp32, dropout the identity, no MfmPlan, no training workspace, no
